@@ -36,6 +36,10 @@ Also in the line: `host_delivered` — W*H*spp over the wall time of rt_render
 with the reference's 10x10 tile grid (every tile copied out of the callback),
 and of rt_render_frame into a caller-owned host frame: what a binding of the
 reference receives, next to the device-resident `value`.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step computed
+(the resolved frame and its RGBA8 image) as DIR/<name>.npy, so that two builds
+can be compared output for output on the same inputs.
 """
 import argparse
 import importlib
@@ -84,9 +88,15 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group and run the strip gather as a collective even with "
                          "ONE rank (proves librccl + an f64 device gather on a one-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the resolved frame and its RGBA8 "
+                         "image) as DIR/<name>.npy, under 64 MB in all (a fixed, seeded pixel sample when larger)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.pmc_child:
         args.steps, args.warmup, args.no_cpu_baseline, args.pmc, args.no_host_delivery = 1, 1, True, "none", True
+        args.dump_outputs = None
     return args
 
 
@@ -313,6 +323,31 @@ def host_delivery(rt, scene, session, reps=5):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 << 20     # under 64 MB with the .npy headers
+DUMP_SAMPLE_SEED = 20240601       # fixed: the same pixels are sampled in every run and every build
+
+
+def dump_outputs(out_dir, frame, rgba):
+    """What a caller of the timed path receives from its last step: the resolved [H, W, 3] f64 frame and the
+    [H, W, 4] RGBA8 image (as float32).  Written whole when both fit DUMP_BUDGET_BYTES; otherwise the same fixed,
+    seeded sample of pixels from both, with their row-major indices in pixel_index.npy.  Returns {name: shape}."""
+    import numpy as np
+    frame = frame.detach().cpu().numpy().astype(np.float64)
+    rgba = rgba.detach().cpu().numpy().astype(np.float32)
+    H, W = frame.shape[:2]
+    arrays = {"frame": frame, "rgba8": rgba}
+    if frame.nbytes + rgba.nbytes > DUMP_BUDGET_BYTES:
+        per_pixel = 3 * 8 + 4 * 4 + 8          # frame + rgba8 + pixel_index
+        n = DUMP_BUDGET_BYTES // per_pixel
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H * W, size=n, replace=False))
+        arrays = {"frame": frame.reshape(-1, 3)[idx], "rgba8": rgba.reshape(-1, 4)[idx],
+                  "pixel_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -426,6 +461,7 @@ def main():
         step(world == 1 or k == args.steps - 1)
     fence()
     elapsed = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, frame, rgba) if args.dump_outputs and rank == 0 else None
     if dist is not None:
         red_dev = "cpu" if rehearsal else "cuda"
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -513,6 +549,8 @@ def main():
                 out["roofline"]["traffic_frac_of_hbm_peak"] = round(traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
         else:
             out["roofline"]["counters_unavailable"] = why_not
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
         t_host = time.time()
         if world == 1 and dist is None and not args.no_host_delivery:
             out["host_delivered"] = host_delivery(rt, scene, session)
