@@ -44,7 +44,7 @@ def lib():
             import torch  # noqa: F401
         except ImportError:
             pass
-        _lib = abi.bind(C.CDLL(LIB_PATH), abi.PROTOTYPES)
+        _lib = abi.bind(abi.bind(C.CDLL(LIB_PATH), abi.PROTOTYPES), abi.DEV_PROTOTYPES)
         if _lib.rt_abi_version() != abi.ABI_VERSION:
             raise ImportError("ABI version mismatch: library %d, binding %d"
                               % (_lib.rt_abi_version(), abi.ABI_VERSION))
@@ -55,7 +55,7 @@ def load_library(path):
     """Another build of the same ABI (e.g. build/libracer_tracer_amd_exact.so, the tests' exact-arithmetic
     build) next to the default one: pass the result as Scene(..., library=...)."""
     lib()  # the default library (and torch's HIP runtime) first
-    other = abi.bind(C.CDLL(path), abi.PROTOTYPES)
+    other = abi.bind(abi.bind(C.CDLL(path), abi.PROTOTYPES), abi.DEV_PROTOTYPES)
     if other.rt_abi_version() != abi.ABI_VERSION:
         raise ImportError("ABI version mismatch in %s" % path)
     return other
@@ -71,6 +71,15 @@ def _strerror(code):
 def check(code, what, library=None):
     if code != abi.RT_OK:
         raise RtError(code, what, (library or lib()).rt_last_error_message().decode())
+
+
+def classify(desc):
+    """rtdev_scene_classify: the kernel selection rule of rt_scene_create_ex on a description, without a device
+    -> dict of abi.CLASSIFY_FIELDS."""
+    d = desc.desc if hasattr(desc, "desc") else desc
+    out = (C.c_int32 * len(abi.CLASSIFY_FIELDS))()
+    check(lib().rtdev_scene_classify(C.byref(d), out), "rtdev_scene_classify")
+    return dict(zip(abi.CLASSIFY_FIELDS, out))
 
 
 def device_count():
@@ -181,6 +190,14 @@ class Scene:
             cancel_ptr = C.cast(cancel, C.POINTER(C.c_int)) if cancel is not None else None
             check(self._lib.rt_render(self._h, C.byref(camera), C.byref(params), cb, None, cancel_ptr), "rt_render", self._lib)
         return tiles
+
+    def variant(self):
+        """rtdev_scene_variant: which trace kernel rt_scene_create_ex chose -> dict of abi.VARIANT_FIELDS."""
+        out = (C.c_int32 * len(abi.VARIANT_FIELDS))()
+        rc = self._lib.rtdev_scene_variant(self._h, out, len(out))
+        if rc != abi.RT_OK:
+            raise RtError(rc, "rtdev_scene_variant", "")
+        return dict(zip(abi.VARIANT_FIELDS, out))
 
     def last_stats(self):
         st = abi.RtRenderStats()

@@ -149,6 +149,16 @@ PROTOTYPES = {
 }
 
 
+# Internal exports of the library for the tests (csrc/rt_scene.h; not in rt_abi.h, not covered by ABI_VERSION)
+VARIANT_FIELDS = ("kernel", "prims_class", "textured", "specular", "use_bvh", "exact", "bvh_nodes_in_lds", "has_moving",
+                  "perlin_in_lds", "static_lds", "dyn_lds", "dyn_lds_lens", "blocks_per_cu", "blocks_per_cu_lens")
+CLASSIFY_FIELDS = ("prims_class", "textured", "specular", "has_moving")
+DEV_PROTOTYPES = {
+    "rtdev_scene_variant": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
+    "rtdev_scene_classify": (C.c_int, [C.POINTER(RtSceneDesc), C.POINTER(C.c_int32)]),
+}
+
+
 def bind(lib, prototypes):
     """Attach restype/argtypes; raises AttributeError if a symbol is missing."""
     for name, (res, args) in prototypes.items():

@@ -27,6 +27,7 @@
                                                        int strip_rows, int strip_count, int strip_index, int samples,     \
                                                        hipStream_t stream);                                               \
     extern "C" int rtdev_pool_blocks_per_cu##SUFFIX(int prims_class, int textured, int specular, int bvh, size_t dyn_lds); \
+    extern "C" int rtdev_pool_static_lds##SUFFIX(int prims_class, int textured, int specular, int bvh);                 \
     extern "C" hipError_t rtdev_launch_trace_pool##SUFFIX(const rtdev::TraceArgs *args, int prims_class, int textured,    \
                                                           int specular, int bvh, unsigned blocks, hipStream_t stream);    \
     extern "C" hipError_t rtdev_launch_resolve_chunks##SUFFIX(const double *partial, double *out, int width, int height,  \
@@ -103,6 +104,32 @@ int validate_desc(const RtSceneDesc *d) {
     if (d->background.kind != RT_BG_SKY && d->background.kind != RT_BG_SOLID)
         return fail(RT_ERR_INVALID_ARGUMENT, "unknown background kind");
     return RT_OK;
+}
+
+// Which trace-kernel instantiation a (validated) description needs: the primitive class (rtdev::PRIMS_*: untransformed rects
+// only, untransformed spheres only, anything), whether some material reads a texture that is not a plain SolidColor (a
+// Dielectric reads none), whether some material is Metal or Dielectric, and whether a MovingSphere is present.
+struct Selection {
+    int prims_class, textured, specular, has_moving;
+};
+Selection select_variant(const RtSceneDesc *d) {
+    Selection sel{0, 0, 0, 0};
+    bool only_rects = true, only_spheres = true;
+    for (int i = 0; i < d->n_primitives; ++i) {
+        const RtPrimitive &p = d->primitives[i];
+        const bool wrapped = (p.flags & (RT_PRIM_HAS_ROTATE_Y | RT_PRIM_HAS_TRANSLATE)) != 0;
+        const bool is_rect = p.kind == RT_PRIM_XY_RECT || p.kind == RT_PRIM_XZ_RECT || p.kind == RT_PRIM_YZ_RECT;
+        if (wrapped || !is_rect) only_rects = false;
+        if (wrapped || p.kind != RT_PRIM_SPHERE) only_spheres = false;
+        if (p.kind == RT_PRIM_MOVING_SPHERE) sel.has_moving = 1;
+    }
+    sel.prims_class = only_rects ? 0 : (only_spheres ? 1 : 2);
+    for (int i = 0; i < d->n_materials; ++i) {
+        const RtMaterial &m = d->materials[i];
+        if (m.kind == RT_MAT_METAL || m.kind == RT_MAT_DIELECTRIC) sel.specular = 1;
+        if (m.kind != RT_MAT_DIELECTRIC && d->textures[m.texture].kind != RT_TEX_SOLID_COLOR) sel.textured = 1;
+    }
+    return sel;
 }
 
 bool texture_reads_uv(const RtSceneDesc *d, int ti) {
@@ -356,6 +383,13 @@ int rtapi::enqueue_render(RtScene *s, const RtCamera *camera, const RtRenderPara
                                     a.strip_index, p->samples, stream));
         RT_HIP(hipEventRecord(s->ev_resolved, stream));
     } else {
+        // A block must fit one CU's LDS: the primitive table of the linear loop, the textures, the Perlin gradients, the lens
+        // samples and the ray times all come on top of the kernel's static LDS (rt_device_types.h: pool_lds_layout).  A launch
+        // that does not fit is refused here, before anything is enqueued; the lens part depends on the camera.
+        const size_t lds = (size_t)s->pool_static_lds + (a.lens_lds ? s->pool_dyn_lds_lens : s->pool_dyn_lds);
+        if (lds > rtdev::kLdsPerCu || (a.lens_lds ? s->pool_blocks_per_cu_lens : s->pool_blocks_per_cu) < 1)
+            return fail(RT_ERR_UNSUPPORTED, a.lens_lds ? "the trace kernel's LDS (static + tables + lens samples) exceeds a CU's 160 KiB"
+                                                       : "the trace kernel's LDS (static + tables) exceeds a CU's 160 KiB");
         // Work items = 8x8 tiles x sample chunks.
         a.tiles_x = (a.cover_w / a.step_x + 7) / 8; // grid cells per row
         a.n_tiles = a.tiles_x * ((a.owned_rows + 7) / 8);
@@ -903,19 +937,11 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
         for (int k = 0; k < 256; ++k)
             if (d->perlins[i].perm_x[k] != k || d->perlins[i].perm_y[k] != k || d->perlins[i].perm_z[k] != k) s->perlin_identity = 0;
     }
-    bool only_rects = true, only_spheres = true;
-    for (const rtdev::Prim &q : prims) {
-        bool is_rect = q.kind == RT_PRIM_XY_RECT || q.kind == RT_PRIM_XZ_RECT || q.kind == RT_PRIM_YZ_RECT;
-        if (q.flags || !is_rect) only_rects = false;
-        if (q.flags || q.kind != RT_PRIM_SPHERE) only_spheres = false;
-    }
-    s->prims_class = only_rects ? 0 : (only_spheres ? 1 : 2);
-    for (const rtdev::Prim &q : prims)
-        if (q.kind == RT_PRIM_MOVING_SPHERE) s->has_moving = 1;
-    for (const rtdev::Material &q : materials) {
-        if (q.kind == RT_MAT_METAL || q.kind == RT_MAT_DIELECTRIC) s->specular = 1;
-        if (q.kind != RT_MAT_DIELECTRIC && q.tex_kind != RT_TEX_SOLID_COLOR) s->textured = 1;
-    }
+    const Selection sel = select_variant(d);
+    s->prims_class = sel.prims_class;
+    s->textured = sel.textured;
+    s->specular = sel.specular;
+    s->has_moving = sel.has_moving;
     // The linear loop costs ~35 VALU instructions per primitive with scalar loads and
     // no divergence; the BVH walk ~25 node visits plus leaf tests with per-lane loads.
     // They cross at a few dozen primitives (clown.yml, 23 spheres, is still linear).
@@ -954,11 +980,11 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
         // global memory, the node from LDS; `random`: 40 % of the walk for 5.8 tests against 26.5 nodes per
         // segment), so leaves of three beat leaves of four (66.1 -> 62.1 ms) — as long as the larger node array
         // does not cost the variant a block per CU (leaves of two: 70.6 ms with three blocks instead of four).
-        const size_t lds_other = (s->textured && d->n_perlins > 0 && s->perlin_identity ? sizeof(double) * 256 * 3 : 0) +
-                                 (s->has_moving ? rtdev::pool_time_lds_bytes(true) : 0);
         auto blocks_with = [&](const rtdev::BvhBuild &b) {
             const size_t bytes = b.nodes.size() * sizeof(rtdev::BvhNode);
-            return (s->exact ? rtdev_pool_blocks_per_cu_exact : rtdev_pool_blocks_per_cu)(s->prims_class, s->textured, s->specular, 1, (bytes <= 32 * 1024 ? bytes : 0) + lds_other);
+            const size_t dyn = rtdev::pool_lds_layout(true, s->textured, d->n_primitives, d->n_textures, bytes <= 32 * 1024 ? (int)b.nodes.size() : 0,
+                                                      d->n_perlins > 0 && s->perlin_identity, false, s->has_moving).bytes;
+            return (s->exact ? rtdev_pool_blocks_per_cu_exact : rtdev_pool_blocks_per_cu)(s->prims_class, s->textured, s->specular, 1, dyn);
         };
         // (more than 2048 primitives: at most four to a leaf, the node array cannot fit LDS — the direction-ordered copies are
         // wanted, built in the same pass)
@@ -1050,14 +1076,22 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
 #ifdef RT_DEVELOPER_KNOBS
     if (const char *k = getenv("RT_BVH_LDS")) s->bvh_nodes_in_lds = s->bvh_nodes_in_lds && atoi(k) != 0;
 #endif
-    // dynamic LDS of the variant: the BVH node array, or the primitive table of the linear-loop variants
-    const size_t dyn_lds = (s->use_bvh ? (s->bvh_nodes_in_lds ? (size_t)(s->n_bvh_nodes + 1) * sizeof(rtdev::BvhNode) : 0)
-                                       : (size_t)s->n_prims * sizeof(rtdev::Prim) + (s->textured ? (size_t)s->n_textures * sizeof(rtdev::Texture) : 0)) +
-                           (s->textured && s->n_perlins > 0 && s->perlin_identity ? sizeof(double) * 256 * 3 : 0) +
-                           (s->has_moving ? rtdev::pool_time_lds_bytes(s->use_bvh != 0) : 0);
-    s->pool_blocks_per_cu = (s->exact ? rtdev_pool_blocks_per_cu_exact : rtdev_pool_blocks_per_cu)(s->prims_class, s->textured, s->specular, s->use_bvh, dyn_lds);
-    s->pool_blocks_per_cu_lens = (s->exact ? rtdev_pool_blocks_per_cu_exact : rtdev_pool_blocks_per_cu)(s->prims_class, s->textured, s->specular, s->use_bvh,
-                                                          dyn_lds + rtdev::pool_lens_lds_bytes(s->use_bvh != 0));
+    // dynamic LDS of the variant (rt_device_types.h: pool_lds_layout) without and with the lens samples, and its static LDS:
+    // what enqueue_render checks against the CU's LDS before a launch.  The v1 kernel has no dynamic LDS.
+    if (!s->use_v1) {
+        auto dyn_lds = [&](bool lens) {
+            return rtdev::pool_lds_layout(s->use_bvh, s->textured, s->n_prims, s->n_textures, s->bvh_nodes_in_lds ? s->n_bvh_nodes + 1 : 0,
+                                          s->n_perlins > 0 && s->perlin_identity, lens, s->has_moving).bytes;
+        };
+        s->pool_dyn_lds = dyn_lds(false);
+        s->pool_dyn_lds_lens = dyn_lds(true);
+        s->pool_static_lds = (s->exact ? rtdev_pool_static_lds_exact : rtdev_pool_static_lds)(s->prims_class, s->textured, s->specular, s->use_bvh);
+        if (s->pool_static_lds < 0) return fail(RT_ERR_HIP, "hipFuncGetAttributes of the trace kernel failed");
+        s->pool_blocks_per_cu = (s->exact ? rtdev_pool_blocks_per_cu_exact : rtdev_pool_blocks_per_cu)(s->prims_class, s->textured, s->specular, s->use_bvh,
+                                                                                                     s->pool_dyn_lds);
+        s->pool_blocks_per_cu_lens = (s->exact ? rtdev_pool_blocks_per_cu_exact : rtdev_pool_blocks_per_cu)(s->prims_class, s->textured, s->specular,
+                                                                                                          s->use_bvh, s->pool_dyn_lds_lens);
+    }
 #ifdef RT_DEVELOPER_KNOBS // occupancy experiments
     if (const char *k = getenv("RT_POOL_BLOCKS_PER_CU"))
         if (atoi(k) > 0) s->pool_blocks_per_cu = s->pool_blocks_per_cu_lens = atoi(k);
@@ -1094,10 +1128,14 @@ int rt_scene_create_ex(const RtSceneDesc *d, int device, const RtSceneOptions *o
 
 int rt_render_frame_device(RtScene *s, const RtCamera *camera, const RtRenderParams *p, double *out_dev,
                            void *hip_stream) {
-    if (!s || !out_dev) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out is NULL");
-    int rc = check_params(camera, p);
-    if (rc != RT_OK) return rc;
-    return enqueue_render(s, camera, p, out_dev, (hipStream_t)hip_stream, 0, Cancel());
+    try { // nothing may unwind through the C ABI (the error messages are std::strings)
+        if (!s || !out_dev) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out is NULL");
+        int rc = check_params(camera, p);
+        if (rc != RT_OK) return rc;
+        return enqueue_render(s, camera, p, out_dev, (hipStream_t)hip_stream, 0, Cancel());
+    } catch (...) {
+        return RT_ERR_OUT_OF_MEMORY;
+    }
 }
 
 int rt_post_rgba8_device(RtScene *s, const RtToneMap *tm, const double *rgb_device, size_t n_pixels,
@@ -1109,8 +1147,8 @@ int rt_post_rgba8_device(RtScene *s, const RtToneMap *tm, const double *rgb_devi
     return RT_OK;
 }
 
-int rt_render_frame_rgba8(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtToneMap *tm,
-                          uint8_t *out_rgba) {
+namespace {
+int render_frame_rgba8(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtToneMap *tm, uint8_t *out_rgba) {
     if (!s || !tm || !out_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "scene/tone_map/out is NULL");
     int rc = check_params(camera, p);
     if (rc != RT_OK) return rc;
@@ -1126,6 +1164,43 @@ int rt_render_frame_rgba8(RtScene *s, const RtCamera *camera, const RtRenderPara
     if (rc != RT_OK) return rc;
     RT_HIP(hipStreamSynchronize(s->stream));
     RT_HIP(hipMemcpy(out_rgba, s->rgba.ptr, px * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+} // namespace
+
+int rt_render_frame_rgba8(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtToneMap *tm,
+                          uint8_t *out_rgba) {
+    try { // nothing may unwind through the C ABI (the error messages are std::strings)
+        return render_frame_rgba8(s, camera, p, tm, out_rgba);
+    } catch (...) {
+        return RT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+int rtdev_scene_classify(const RtSceneDesc *d, int32_t out[4]) {
+    if (!out) return RT_ERR_INVALID_ARGUMENT;
+    try { // (validate_desc's messages are std::strings)
+        int rc = validate_desc(d);
+        if (rc != RT_OK) return rc;
+        const Selection sel = select_variant(d);
+        out[0] = sel.prims_class;
+        out[1] = sel.textured;
+        out[2] = sel.specular;
+        out[3] = sel.has_moving;
+        return RT_OK;
+    } catch (...) {
+        return RT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+int rtdev_scene_variant(const RtScene *s, int32_t *out, int32_t n_out) {
+    if (!s || (!out && n_out > 0) || n_out < 0) return RT_ERR_INVALID_ARGUMENT; // (no message: nothing here may allocate)
+    const int32_t v[RTDEV_VARIANT_FIELDS] = {
+        s->use_v1 ? 1 : 0, s->prims_class, s->textured, s->specular, s->use_bvh, s->exact ? 1 : 0, s->bvh_nodes_in_lds ? 1 : 0,
+        s->has_moving, (s->textured && s->n_perlins > 0 && s->perlin_identity) ? 1 : 0,
+        s->use_v1 ? 0 : s->pool_static_lds, s->use_v1 ? 0 : (int32_t)s->pool_dyn_lds, s->use_v1 ? 0 : (int32_t)s->pool_dyn_lds_lens,
+        s->pool_blocks_per_cu, s->pool_blocks_per_cu_lens};
+    for (int32_t k = 0; k < n_out && k < RTDEV_VARIANT_FIELDS; ++k) out[k] = v[k];
     return RT_OK;
 }
 

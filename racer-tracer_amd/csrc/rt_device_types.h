@@ -247,4 +247,30 @@ struct TraceArgs {
     int32_t dbg[4];        // developer knobs (env RT_DBG0..3), 0 in production
 };
 
+// The dynamic LDS of a pooled trace-kernel block, in the order k_trace_pool_f64 lays it out (rt_trace_pool_kernel.hip):
+//   [BVH nodes (bvh_lds_nodes of them) | primitive table + the texture table of the TEXTURED variants]
+//   [Perlin gradients of the first table (TEXTURED, identity permutations)] [lens samples (aperture > 0)]
+//   [ray times (a MovingSphere)]
+// The one statement of that bill on the host: the launch, the occupancy of the grid and the check that a block fits
+// a CU (rt_api.hip: enqueue_render) all read it.
+struct PoolLdsLayout {
+    size_t perlin_at, lens_at, time_at, bytes;
+};
+inline PoolLdsLayout pool_lds_layout(bool bvh, bool textured, int n_prims, int n_textures, int bvh_lds_nodes, bool perlin_in_lds,
+                                     bool lens, bool time) {
+    PoolLdsLayout l;
+    size_t at = bvh ? (size_t)bvh_lds_nodes * sizeof(BvhNode)
+                    : (size_t)n_prims * sizeof(Prim) + (textured ? (size_t)n_textures * sizeof(Texture) : 0);
+    l.perlin_at = at;
+    if (textured && perlin_in_lds) at += sizeof(double) * 256 * 3;
+    l.lens_at = at;
+    if (lens) at += pool_lens_lds_bytes(bvh);
+    l.time_at = at;
+    if (time) at += pool_time_lds_bytes(bvh);
+    l.bytes = at;
+    return l;
+}
+// LDS of one CU (MI355X: 160 KiB), what a block's static + dynamic LDS may not exceed
+constexpr size_t kLdsPerCu = 160 * 1024;
+
 } // namespace rtdev

@@ -106,6 +106,8 @@ struct RtScene {
     bool gather_staged = false; // RtSceneOptions.gather == RT_GATHER_STAGED (rt_multi.hip)
     int num_cus = 0, pool_blocks_per_cu = 1;
     int pool_blocks_per_cu_lens = 1; // ... when the camera has an aperture (its lens samples take dynamic LDS)
+    int pool_static_lds = 0;         // static LDS of the variant's kernel (hipFuncGetAttributes)
+    size_t pool_dyn_lds = 0, pool_dyn_lds_lens = 0; // its dynamic LDS without / with lens samples (rt_device_types.h: pool_lds_layout)
     rtapi::DevBuf<double> partial;       // [chunks][H][W][3] per-chunk sums
     rtapi::DevBuf<unsigned int> queue;   // one item counter per launch of a render call
     int last_chunks = 0;
@@ -131,6 +133,17 @@ struct RtScene {
     bool has_stats = false;
     int last_launches = 0;
 };
+
+// Internal exports for the tests (not part of rt_abi.h; the ABI version does not cover them).
+//   rtdev_scene_variant: what rt_scene_create_ex chose for a scene, RTDEV_VARIANT_FIELDS values in this order:
+//     kernel (0 pool, 1 v1), prims_class (rtdev::PRIMS_*), textured, specular, use_bvh, exact (RT_ARITH_REFERENCE kernels),
+//     bvh_nodes_in_lds, has_moving, perlin_in_lds, static LDS of the pool variant, its dynamic LDS without and with lens
+//     samples (bytes; 0 for v1), resident blocks per CU without and with lens samples.  Writes min(n_out, fields) values.
+//   rtdev_scene_classify: the selection rule of rt_scene_create_ex on a description alone (no device): prims_class, textured,
+//     specular, has_moving.  Returns the description's validation error, if any.
+#define RTDEV_VARIANT_FIELDS 14
+extern "C" int rtdev_scene_variant(const RtScene *s, int32_t *out, int32_t n_out);
+extern "C" int rtdev_scene_classify(const RtSceneDesc *d, int32_t out[4]);
 
 namespace rtapi {
 int check_params(const RtCamera *camera, const RtRenderParams *p);

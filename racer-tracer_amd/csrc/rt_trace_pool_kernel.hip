@@ -475,8 +475,8 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
     constexpr bool OVERLAP = BVH || PRIMS == PRIMS_ANY;
 #endif
     __shared__ WaveLds<TEXTURED, NBUF, OVERLAP> lds_all[4];
-    // Dynamic LDS of a block: [BVH nodes | primitive table + texture table][Perlin gradients]; the host sizes it
-    // (pool_dynamic_lds below) and says what is in it.
+    // Dynamic LDS of a block: [BVH nodes | primitive table + texture table][Perlin gradients][lens samples][ray times];
+    // the host sizes it (rt_device_types.h: pool_lds_layout, whose order the offsets below follow) and says what is in it.
     extern __shared__ __align__(16) unsigned char dyn_lds[];
     // The gradients of the first Perlin table (6 KB) are staged in LDS once per block when the
     // permutation tables are the identity (always, in the reference: noise.rs:121-130): the 56
@@ -1272,10 +1272,8 @@ namespace {
 // linear closest-hit loop, plus PRIMS_ANY x TEXTURED x SPECULAR with the BVH.
 template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH> struct PoolVariant {
     static void launch(const rtdev::TraceArgs &a, unsigned blocks, hipStream_t stream) {
-        const size_t dyn = (BVH ? (size_t)a.bvh_lds_nodes * sizeof(rtdev::BvhNode)
-                                : (size_t)a.n_prims * sizeof(rtdev::Prim) + (TEXTURED ? (size_t)a.n_textures * sizeof(rtdev::Texture) : 0)) +
-                           (TEXTURED && a.perlin_in_lds ? sizeof(double) * 256 * 3 : 0) +
-                           (a.lens_lds ? rtdev::pool_lens_lds_bytes(BVH) : 0) + (a.time_lds ? rtdev::pool_time_lds_bytes(BVH) : 0);
+        const size_t dyn = rtdev::pool_lds_layout(BVH, TEXTURED, a.n_prims, a.n_textures, a.bvh_lds_nodes, a.perlin_in_lds, a.lens_lds,
+                                                  a.time_lds).bytes;
         hipLaunchKernelGGL((RT_KNS::k_trace_pool_f64<PRIMS, TEXTURED, SPECULAR, BVH>), dim3(blocks), dim3(256), dyn, stream, a);
     }
     static int blocks_per_cu(size_t dyn_lds) {
@@ -1290,7 +1288,12 @@ template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH> struct PoolVariant 
             const size_t granules = (attr.sharedSizeBytes + dyn_lds + 1279) / 1280;
             if (granules > 0 && (int)(128 / granules) < n) n = (int)(128 / granules);
         }
-        return n < 1 ? 1 : n;
+        return n < 0 ? 0 : n; // 0: a block does not fit a CU (rt_api.hip: enqueue_render refuses the launch)
+    }
+    static int static_lds() {
+        hipFuncAttributes attr;
+        if (hipFuncGetAttributes(&attr, (const void *)RT_KNS::k_trace_pool_f64<PRIMS, TEXTURED, SPECULAR, BVH>) != hipSuccess) return -1;
+        return (int)attr.sharedSizeBytes;
     }
 };
 
@@ -1312,6 +1315,11 @@ template <class F> auto dispatch_variant(int prims_class, bool textured, bool sp
 extern "C" int RT_LAUNCHER(rtdev_pool_blocks_per_cu)(int prims_class, int textured, int specular, int bvh, size_t dyn_lds) {
     return dispatch_variant(prims_class, textured != 0, specular != 0, bvh != 0,
                             [dyn_lds](auto v) { return decltype(v)::blocks_per_cu(dyn_lds); });
+}
+
+// Static LDS of the variant's kernel (its WaveLds), -1 when the runtime cannot say.
+extern "C" int RT_LAUNCHER(rtdev_pool_static_lds)(int prims_class, int textured, int specular, int bvh) {
+    return dispatch_variant(prims_class, textured != 0, specular != 0, bvh != 0, [](auto v) { return decltype(v)::static_lds(); });
 }
 
 extern "C" hipError_t RT_LAUNCHER(rtdev_launch_trace_pool)(const rtdev::TraceArgs *args, int prims_class, int textured, int specular,

@@ -238,8 +238,8 @@ def test_multi_device_call_on_one_card(rt, orc, gpu):
 
 def test_multi_device_call_into_device_memory(rt, gpu):
     import torch
-    if not torch.cuda.is_available():
-        pytest.skip("torch sees no GPU (the library does): no way to allocate the device buffer for this test")
+    # a -m gpu run without a device torch can use is a failure, not a skip (the `gpu` fixture does the same)
+    assert torch.cuda.is_available(), "torch sees no GPU (the library does): no way to allocate the device buffer for this test"
     bundle, cam, _ = S.three_balls()
     w, h, spp = 160, 90, 8
     camera = S.camera_for(cam, w, h)
@@ -263,8 +263,8 @@ def test_staged_gather_runs_the_peer_copy_branch_on_one_card(rt, gpu):
     in place.  2 and 3 shares, strips of 8 and 5 rows, 131 rows (a short last strip), one staged share alone, a mix
     of staged and in-place shares: the output must equal the single-scene frame (cpu.rs:118-131 shards ONE frame)."""
     import torch
-    if not torch.cuda.is_available():
-        pytest.skip("torch sees no GPU (the library does): no way to allocate the device buffer for this test")
+    # a -m gpu run without a device torch can use is a failure, not a skip (the `gpu` fixture does the same)
+    assert torch.cuda.is_available(), "torch sees no GPU (the library does): no way to allocate the device buffer for this test"
     bundle, cam, _ = S.cornell_box_boxes()
     w, h, spp = 200, 131, 16
     camera = S.camera_for(cam, w, h)

@@ -38,8 +38,8 @@ def tone_map_sessions(host, tmp_path_factory):
 
 def test_device_post_equals_host_post_and_oracle(rt, host, orc, gpu, tmp_path_factory):
     import torch
-    if not torch.cuda.is_available():   # the device buffers of this test come from torch; the library itself needs none
-        pytest.skip("torch sees no GPU (the library does): no way to allocate the device buffers for this test")
+    # a -m gpu run without a device torch can use is a failure, not a skip (the `gpu` fixture does the same)
+    assert torch.cuda.is_available(), "torch sees no GPU (the library does): no way to allocate the device buffers for this test"
     sessions = tone_map_sessions(host, tmp_path_factory)
     rng = np.random.default_rng(11)
     rgb = np.concatenate([rng.random((4093, 3)) * 3.0,                       # ordinary range, above 1 included

@@ -9,27 +9,18 @@ with each other — with device-scope RELAXED accesses and one s_waitcnt instead
     returned (the atomic's own s_waitcnt vmcnt(0)),
   * the finished pixels are released at system scope (buffer_wbl2 sc0 sc1) before the tile is counted for its region.
 The reference hands tiles over through a channel (cpu.rs:64-70); this is that channel's memory order."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import kernel_asm
 
 
 @pytest.fixture(scope="module")
-def pool_kernel_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
+def pool_kernel_asm():
+    if kernel_asm.hipcc() is None:
         pytest.skip("no hipcc")
-    out = str(tmp_path_factory.mktemp("isa") / "pool.s")
-    cmd = [HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S",
-           os.path.join(ROOT, "racer-tracer_amd", "csrc", "rt_trace_pool_kernel.hip"), "-o", out]
-    run = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert run.returncode == 0, run.stderr[-2000:]
-    return open(out).read().split("\n")
+    return kernel_asm.asm_text("pool", "fast").split("\n")
 
 
 def function_body(lines, needle):

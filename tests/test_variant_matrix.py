@@ -1,0 +1,145 @@
+"""What keeps tests/test_gpu_variants.py honest, without a GPU:
+  * the inventory: the trace-kernel instantiations in the compiled code (both arithmetic flavours) are exactly the cases
+    the GPU module renders, and dispatch_variant can reach each of them;
+  * the selection rule (rt_api.hip: select_variant, exported as rtdev_scene_classify): every scene of the matrix selects
+    the form it is there for, and the edge descriptions select what the kernels expect;
+  * sensitivity: turning off the feature a scene is there to exercise changes the oracle's picture, so a GPU case would
+    fail if the kernel's arm for that feature were wrong."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import kernel_asm
+import scenes_py as S
+import test_gpu_variants as G
+import variant_scenes as V
+
+abi = S.abi
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# what dispatch_variant (rt_trace_pool_kernel.hip) and the v1 launcher (rt_trace_kernel.hip) can select: the BVH forms
+# exist for PRIMS_ANY only
+REACHABLE = {
+    "pool": {(p, t, s, 0) for p in (0, 1, 2) for t in (0, 1) for s in (0, 1)} | {(2, t, s, 1) for t in (0, 1) for s in (0, 1)},
+    "v1": {(p, t, s, 0) for p in (0, 1, 2) for t in (0, 1) for s in (0, 1)},
+}
+
+
+@pytest.fixture(scope="module")
+def hipcc():
+    if kernel_asm.hipcc() is None:
+        pytest.skip("no hipcc")
+
+
+@pytest.mark.parametrize("kernel", ["pool", "v1"])
+@pytest.mark.parametrize("flavour", ["fast", "exact"])
+def test_the_gpu_matrix_covers_every_compiled_instantiation(hipcc, kernel, flavour):
+    found = kernel_asm.inventory(kernel, flavour)
+    assert len(found) == {"pool": 16, "v1": 12}[kernel], sorted(found)
+    assert set(found) == REACHABLE[kernel]
+    assert set(found) == {form for k, fl, form in G.CASES if (k, fl) == (kernel, flavour)}
+
+
+def test_dispatch_sends_only_prims_any_to_the_bvh_forms():
+    src = open(os.path.join(ROOT, "racer-tracer_amd", "csrc", "rt_trace_pool_kernel.hip")).read()
+    body = src[src.index("auto dispatch_variant("):]
+    body = body[:body.index("#undef RT_PICK")]
+    assert re.search(r"if \(bvh\) return RT_PICK\(PRIMS_ANY, true\);", body)
+    assert len(re.findall(r"RT_PICK\(PRIMS_\w+, (?:true|false)\)", body)) == 4
+
+
+def test_static_lds_of_the_linear_forms(hipcc):
+    """The static LDS every linear-loop form adds to its dynamic tables (what the LDS bill of test_gpu_variants.py and
+    rt_api.hip's refusal are computed from): the RT_ARITH_FAST PRIMS_ANY forms keep two items in flight and the most."""
+    for flavour in ("fast", "exact"):
+        found = kernel_asm.inventory("pool", flavour)
+        for (p, t, s, b), lds in found.items():
+            assert 0 < lds < 32 * 1024, (flavour, p, t, s, b, lds)
+            if t:
+                assert lds >= found[(p, 0, s, b)]     # the textured WaveLds holds more
+        worst = max(found.values())
+        # the worst linear-loop bill the refusal still accepts: 640 primitives, a Perlin table, lens samples, ray times
+        assert worst + 640 * 192 + 6144 + 8192 + 4096 <= 160 * 1024
+
+
+# ---- the selection rule --------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("form", list(V.SPECS), ids=lambda f: "%s%s%s%s" % ("RSA"[f[0]], "t" * f[1], "s" * f[2], "-bvh" * f[3]))
+def test_each_matrix_scene_selects_its_form(rt, form):
+    bundle, _ = V.build(form)
+    got = rt.classify(bundle)
+    assert (got["prims_class"], got["textured"], got["specular"]) == form[:3]
+    assert got["has_moving"] == int(bool(V.SPECS[form].get("moving")))
+    assert bundle.desc.n_primitives <= 48 or form[3]   # (the linear forms would be picked by RT_HIT_AUTO too)
+
+
+def _classify(rt, prims, materials, textures, perlins=()):
+    return rt.classify(abi.SceneBundle(prims, materials, textures, abi.sky(), perlins=list(perlins)))
+
+
+def test_selection_rule_edges(rt):
+    solid = [abi.solid((0.5, 0.5, 0.5))]
+    lam = [abi.material(V.L, 0)]
+    noise = abi.RtTexture(abi.RT_TEX_NOISE, -1, -1, -1, 0, 2, abi.D3(1.0, 1.0, 1.0), 4.0)
+    # a Dielectric reads no texture, whatever index it carries
+    got = _classify(rt, [abi.sphere((0, 0, -2), 0.5, 1)], lam + [abi.material(V.D, 1, ior=1.5)], solid + [noise], [V.perlin(False)])
+    assert (got["prims_class"], got["textured"], got["specular"]) == (V.SPHERES, 0, 1)
+    # ... and a Lambertian that reads the same Noise is textured
+    got = _classify(rt, [abi.sphere((0, 0, -2), 0.5, 1)], lam + [abi.material(V.L, 1)], solid + [noise], [V.perlin(False)])
+    assert (got["textured"], got["specular"]) == (1, 0)
+    # a rect with flags is not a bare rect, a sphere with flags not a bare sphere
+    rect = abi.rect(abi.RT_PRIM_XY_RECT, -1, 1, -1, 1, -3, 0)
+    assert _classify(rt, [rect], lam, solid)["prims_class"] == V.RECTS
+    for flags in (abi.RT_PRIM_HAS_TRANSLATE, abi.RT_PRIM_HAS_ROTATE_Y, abi.RT_PRIM_HAS_ROTATE_Y | abi.RT_PRIM_HAS_TRANSLATE):
+        wrapped = abi.rect(abi.RT_PRIM_YZ_RECT, -1, 1, -1, 1, -3, 0)
+        wrapped.flags = flags
+        assert _classify(rt, [rect, wrapped], lam, solid)["prims_class"] == V.ANY, flags
+        sphere = abi.sphere((0, 0, -2), 0.5, 0)
+        sphere.flags = flags
+        assert _classify(rt, [sphere], lam, solid)["prims_class"] == V.ANY, flags
+    # flag bits the ABI does not define are not a wrapper
+    odd = abi.sphere((0, 0, -2), 0.5, 0)
+    odd.flags = 8
+    assert _classify(rt, [odd], lam, solid)["prims_class"] == V.SPHERES
+    # a lone Box, a lone MovingSphere, a rect next to a sphere
+    assert _classify(rt, [abi.box((0, 0, -3), (1, 1, -2), 0)], lam, solid) == dict(prims_class=V.ANY, textured=0, specular=0, has_moving=0)
+    got = _classify(rt, [abi.moving_sphere((0, 0, -2), (0, 1, -2), 0.5, 0)], lam, solid)
+    assert (got["prims_class"], got["has_moving"]) == (V.ANY, 1)
+    assert _classify(rt, [rect, abi.sphere((0, 0, -2), 0.5, 0)], lam, solid)["prims_class"] == V.ANY
+    # Metal alone is specular; a DiffuseLight with a Checkered texture is textured
+    assert _classify(rt, [rect], [abi.material(V.M, 0, fuzz=0.2)], solid)["specular"] == 1
+    checker = abi.RtTexture(abi.RT_TEX_CHECKERED, 0, 0, -1, -1, 0, abi.D3(0, 0, 0), 0.0)
+    assert _classify(rt, [rect], [abi.material(V.E, 1)], solid + [checker])["textured"] == 1
+
+
+def test_classify_refuses_what_scene_creation_refuses(rt):
+    solid = [abi.solid((0.5, 0.5, 0.5))]
+    inner = abi.RtTexture(abi.RT_TEX_CHECKERED, 0, 0, -1, -1, 0, abi.D3(0, 0, 0), 0.0)
+    outer = abi.RtTexture(abi.RT_TEX_CHECKERED, 0, 1, -1, -1, 0, abi.D3(0, 0, 0), 0.0)
+    bundle = abi.SceneBundle([abi.sphere((0, 0, -2), 0.5, 0)], [abi.material(V.L, 2)], solid + [inner, outer], abi.sky())
+    with pytest.raises(rt.RtError) as err:
+        rt.classify(bundle)
+    assert err.value.code == abi.RT_ERR_UNSUPPORTED
+    out = (C.c_int32 * 4)()
+    assert rt.lib().rtdev_scene_classify(None, out) == abi.RT_ERR_INVALID_ARGUMENT
+    assert rt.lib().rtdev_scene_variant(None, out, 4) == abi.RT_ERR_INVALID_ARGUMENT
+
+
+# ---- sensitivity -----------------------------------------------------------------------------------------------------------
+
+PROBES = [(form, key) for form, spec in V.SPECS.items() for key in spec["probes"]]
+
+
+@pytest.mark.parametrize("form,key", PROBES, ids=lambda x: str(x).replace(" ", ""))
+def test_each_scene_reaches_the_code_it_is_there_for(orc, form, key):
+    """Each swap must change at least 1 % of the pixels by more than 1e-2: the arm it turns off is on screen."""
+    params = abi.render_params(V.W, V.H, V.SPP, max_depth=V.DEPTH)
+    frames = []
+    for override in ({}, {key: V.SPECS[form]["probes"][key]}):
+        bundle, cam = V.build(form, **override)
+        frame, _ = orc.render(bundle.desc, S.camera_for(cam, V.W, V.H), params, use_bvh=V.oracle_use_bvh(bundle))
+        frames.append(frame)
+    changed = float((np.abs(frames[0] - frames[1]).max(axis=-1) > 1e-2).mean())
+    assert changed >= 0.01, (form, key, changed)
