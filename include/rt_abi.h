@@ -270,10 +270,16 @@ enum RtTraceKernel {
  *     ~1e-13 per channel; a scene that amplifies rounding (thousands of small mirrors: a bounce multiplies a
  *     direction error by distance / radius) can flip the odd hit, i.e. a few pixels in ten thousand beyond 1e-3.
  *     Scenes with boxes, wrappers, moving spheres or more than 48 primitives add their per-pixel sums in 64-bit fixed
- *     point (quantum: the scene's largest emission / background component x 2^-52 per sample — a pixel whose radiance
- *     is of that order, black for every purpose, comes out up to 4e-8 from the f64 sum's value), which makes the frame
- *     independent of how the GPU schedules the work; that needs a bound on a sample's radiance, so a scene with a
- *     colour above 1 (or below 0, or not finite) on a scattering material is rendered as RT_ARITH_REFERENCE.
+ *     point, which makes the frame independent of how the GPU schedules the work.  That needs a bound E on a sample's
+ *     radiance: the largest of 1, the emitted colours and the background's components, with every colour on a
+ *     scattering material in [0, 1].  A sample is rounded to a multiple of 2^(e-52), where 2^e is the power of two
+ *     above E (the next one when E is within 1e-6 below one) and e grows by one per halving that brings the longest
+ *     sample chunk (about spp / 16) to at most 2048 samples; a pixel whose radiance is of that order, black for every
+ *     purpose, comes out up to sqrt(2^(e-53)) from the f64 sum's value (4e-8 for E = 15).  Fixed-point sums are used
+ *     exactly when E < 2^30 and e <= 31, which keeps that error below 4.9e-4.  A scene without such a bound (a colour
+ *     above 1, below 0 or not finite on a scattering material, or E >= 2^30) is rendered as RT_ARITH_REFERENCE; a
+ *     render whose sample count would take e past 31 (a bound near 2^30 and more than about 32 768 spp) returns
+ *     RT_ERR_UNSUPPORTED — create the scene with RT_ARITH_REFERENCE to render it.
  *   RT_ARITH_REFERENCE: the reference's own operations (IEEE divisions, sqrt + three divisions, no contraction);
  *     holds the 1e-3 per-channel tolerance on such scenes too; ~25 % slower.  Same kernels, same draws, same
  *     closest-hit rule: only the last bits of the arithmetic differ. */

@@ -82,6 +82,24 @@ def classify(desc):
     return dict(zip(abi.CLASSIFY_FIELDS, out))
 
 
+def radiance_bound(desc):
+    """rtdev_scene_radiance_bound: the bound on a finished sample's radiance that rt_scene_create_ex gives a description
+    (what sizes the fixed-point sums), or 0.0: the scene has none and keeps f64 sums.  No device needed."""
+    d = desc.desc if hasattr(desc, "desc") else desc
+    out = C.c_double(0.0)
+    check(lib().rtdev_scene_radiance_bound(C.byref(d), C.byref(out)), "rtdev_scene_radiance_bound")
+    return out.value
+
+
+def sum_exponent(bound, samples):
+    """rtdev_sum_exponent: the exponent e of the fixed-point sums (sum_scale = 2^(52 - e)) of a render of `samples` samples
+    per pixel under a radiance bound, or 0: f64 sums.  Raises RtError (RT_ERR_UNSUPPORTED) where such a render is refused.
+    No device needed."""
+    e = C.c_int32(0)
+    check(lib().rtdev_sum_exponent(float(bound), int(samples), C.byref(e)), "rtdev_sum_exponent")
+    return e.value
+
+
 def device_count():
     return lib().rt_device_count()
 

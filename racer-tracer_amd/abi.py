@@ -156,6 +156,8 @@ CLASSIFY_FIELDS = ("prims_class", "textured", "specular", "has_moving")
 DEV_PROTOTYPES = {
     "rtdev_scene_variant": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "rtdev_scene_classify": (C.c_int, [C.POINTER(RtSceneDesc), C.POINTER(C.c_int32)]),
+    "rtdev_scene_radiance_bound": (C.c_int, [C.POINTER(RtSceneDesc), C.POINTER(C.c_double)]),
+    "rtdev_sum_exponent": (C.c_int, [C.c_double, C.c_int32, C.POINTER(C.c_int32)]),
 }
 
 

@@ -132,6 +132,72 @@ Selection select_variant(const RtSceneDesc *d) {
     return sel;
 }
 
+// THE ERROR BUDGET OF THE FIXED-POINT SUMS (rt_device_types.h: sum_scale).  A sample's radiance T is rounded to a multiple
+// of 2^(e-52): an ABSOLUTE error of at most 2^(e-53) per sample, hence in the pixel's mean.  The frame holds sqrt(mean),
+// and |sqrt(a) - sqrt(b)| <= sqrt(|a - b|): a pixel of radiance near 0 comes out up to sqrt(2^(e-53)) from the f64 sum's
+// value.  The 1e-3 per channel that RT_ARITH_FAST promises (rt_abi.h) therefore allows e <= 31 (4.9e-4, half the
+// tolerance; e = 33 would be 9.8e-4, all of it).  A bound below 2^30 gives e <= 31 for chunks of up to 2048 samples; a
+// scene whose bound is larger has none (RT_ARITH_REFERENCE copy, f64 sums), and a render whose longer chunks would push e
+// past 31 is refused.
+constexpr double kSumsBoundCap = 0x1p30;
+constexpr int kSumsMaxExponent = 31;
+
+// What a finished sample can be at most (RtScene.radiance_bound): the product of its path's attenuations times what the
+// path ran into.  Attenuations are texture values (lambertian.rs:36, metal.rs:40) or 1 (dialectric.rs:26) — a
+// SolidColor's colour, a Noise colour times 0.5 (1 + sin) <= the colour, an image texel <= 1 — so with every such colour
+// in [0, 1] the bound is the largest of 1 (renderer.rs:48-55: white at depth 0), the emitted colours
+// (diffuse_light.rs:33-35) and the background's.  A colour outside [0, 1] on a scattering material, or anything
+// negative or not finite, leaves the scene without a bound (0): the pooled kernel then keeps f64 sums.  So does a bound
+// of kSumsBoundCap or more (sum_exponent below: the error budget of the fixed-point sums).
+double scene_radiance_bound(const RtSceneDesc *d) {
+    bool bounded = true;
+    double bound = 1.0;
+    auto colours_of = [&](int ti, double &hi, double &lo) { // over the texture and, for a Checkered, its two sides
+        auto one = [&](const RtTexture &t) {
+            if (t.kind == RT_TEX_IMAGE) {
+                hi = std::max(hi, 1.0);
+                lo = std::min(lo, 0.0);
+                return;
+            }
+            if (t.kind == RT_TEX_CHECKERED) return;
+            for (int k = 0; k < 3; ++k) {
+                if (!std::isfinite(t.color[k])) bounded = false;
+                hi = std::max(hi, t.color[k]);
+                lo = std::min(lo, t.color[k]);
+            }
+        };
+        const RtTexture &t = d->textures[ti];
+        one(t);
+        if (t.kind == RT_TEX_CHECKERED) {
+            one(d->textures[t.tex_even]);
+            one(d->textures[t.tex_odd]);
+            // (a Checkered inside a Checkered is not evaluated further by the kernels: texture_value_deferred returns its colour field)
+            for (int side : {t.tex_even, t.tex_odd})
+                if (d->textures[side].kind == RT_TEX_CHECKERED)
+                    for (int k = 0; k < 3; ++k) {
+                        if (!std::isfinite(d->textures[side].color[k])) bounded = false;
+                        hi = std::max(hi, d->textures[side].color[k]);
+                        lo = std::min(lo, d->textures[side].color[k]);
+                    }
+        }
+    };
+    for (int i = 0; i < d->n_materials; ++i) {
+        const RtMaterial &m = d->materials[i];
+        if (m.kind == RT_MAT_DIELECTRIC) continue;
+        double hi = 0.0, lo = 0.0;
+        colours_of(m.texture, hi, lo);
+        if (lo < 0.0) bounded = false;
+        if (m.kind == RT_MAT_DIFFUSE_LIGHT) bound = std::max(bound, hi);
+        else if (hi > 1.0) bounded = false;
+    }
+    for (int k = 0; k < 3; ++k)
+        for (double c : {d->background.top[k], d->background.bottom[k]}) {
+            if (!std::isfinite(c) || c < 0.0) bounded = false;
+            bound = std::max(bound, c);
+        }
+    return bounded && std::isfinite(bound) && bound < kSumsBoundCap ? bound : 0.0;
+}
+
 bool texture_reads_uv(const RtSceneDesc *d, int ti) {
     const RtTexture &t = d->textures[ti];
     if (t.kind == RT_TEX_IMAGE) return true;
@@ -211,7 +277,32 @@ std::vector<int> chunk_plan(int samples) {
     return starts;
 }
 
-void fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtdev::TraceArgs &a) {
+// The exponent e of the fixed-point sums (sum_scale = 2^(52-e)) for a radiance bound and a sample count, or 0: f64 sums
+// (no bound, or one of kSumsBoundCap or more).  A sample's radiance is at most bound < 2^e, so T * 2^(52 - e) < 2^52 —
+// what the kernel's conversion can hold — and 2048 of them, the samples of the longest chunk (or the scale halves), stay
+// below 2^63.  RT_ERR_UNSUPPORTED: the halving would take e past the budget (kSumsMaxExponent).
+int sum_exponent(double bound, int samples, int *e_out) {
+    *e_out = 0;
+    if (samples <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "samples must be positive");
+    if (bound == 0.0 || !(bound < kSumsBoundCap)) return RT_OK; // (NaN and infinity included)
+    // every sample can be the white of an exhausted depth: scene_radiance_bound never returns less than 1
+    if (!(bound >= 1.0)) return fail(RT_ERR_INVALID_ARGUMENT, "a radiance bound is 0 or at least 1");
+    int e = 0;
+    // bound < 2^e, with room for the last bits a sample may exceed the bound by (a sky blend or a Noise factor an ulp
+    // above 1, twenty bounces deep): a bound within 1e-6 of the power of two takes the next one
+    if (frexp(bound, &e) > 1.0 - 1e-6) ++e;
+    const std::vector<int> plan = chunk_plan(samples);
+    int longest = 1;
+    for (size_t k = 0; k + 1 < plan.size(); ++k) longest = std::max(longest, plan[k + 1] - plan[k]);
+    for (; longest > 2048; longest = (longest + 1) / 2) ++e;
+    if (e > kSumsMaxExponent)
+        return fail(RT_ERR_UNSUPPORTED, "this many samples per pixel would coarsen the fixed-point sums of a scene this bright "
+                                        "beyond the 1e-3 tolerance: render it with RT_ARITH_REFERENCE");
+    *e_out = e;
+    return RT_OK;
+}
+
+int fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtdev::TraceArgs &a) {
     memset(&a, 0, sizeof a);
     a.prims = s->prims.ptr;
     a.textures = s->textures.ptr;
@@ -292,18 +383,12 @@ void fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtd
     for (int g = 0; g < 3; ++g) a.rect_end[g] = s->rect_end[g];
     a.sphere_end = s->sphere_end;
     a.box_end = s->box_end;
-    // Fixed-point sums (rt_device_types.h: sum_scale): a sample's radiance is at most radiance_bound < 2^e, so
-    // T * 2^(52 - e) < 2^52 — what the kernel's conversion can hold — and 2048 of them, the samples of the longest chunk
-    // (or the scale halves), stay below 2^63.
-    if (!s->exact && !s->use_v1 && s->radiance_bound > 0.0) {
+    // Fixed-point sums (rt_device_types.h: sum_scale; the variants that keep two items in flight: any primitive kind, BVH)
+    if (!s->exact && !s->use_v1 && (s->use_bvh || s->prims_class == 2)) {
         int e = 0;
-        // radiance_bound < 2^e, with room for the last bits a sample may exceed the bound by (a sky blend or a Noise factor
-        // an ulp above 1, twenty bounces deep): a bound within 1e-6 of the power of two takes the next one
-        if (frexp(s->radiance_bound, &e) > 1.0 - 1e-6) ++e;
-        const std::vector<int> plan = chunk_plan(p->samples);
-        int longest = 1;
-        for (size_t k = 0; k + 1 < plan.size(); ++k) longest = std::max(longest, plan[k + 1] - plan[k]);
-        for (; longest > 2048; longest = (longest + 1) / 2) ++e;
+        const int rc = sum_exponent(s->radiance_bound, p->samples, &e);
+        if (rc != RT_OK) return rc;
+        if (e == 0) return fail(RT_ERR_UNSUPPORTED, "a scene without a radiance bound needs the f64 sums of RT_ARITH_REFERENCE"); // (scene_create)
         a.sum_scale = ldexp(1.0, 52 - e);
         a.sum_unscale = ldexp(1.0, e - 52);
     }
@@ -314,6 +399,7 @@ void fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtd
         if (const char *v = getenv(name)) a.dbg[k] = atoi(v);
     }
 #endif
+    return RT_OK;
 }
 
 } // namespace
@@ -360,7 +446,8 @@ int rtapi::enqueue_render(RtScene *s, const RtCamera *camera, const RtRenderPara
     RT_HIP(hipSetDevice(s->device));
     size_t n = (size_t)p->width * (size_t)p->height * 3;
     rtdev::TraceArgs a;
-    fill_args(s, camera, p, a);
+    int rc = fill_args(s, camera, p, a);
+    if (rc != RT_OK) return rc;
     if (batch <= 0 || batch > p->samples) batch = p->samples;
     int launches = 0;
     if (s->use_v1) {
@@ -847,60 +934,7 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
         }
     }
     for (rtdev::Prim &q : prims) q.mat = materials[(size_t)q.material]; // the only device copy of a material
-    // What a finished sample can be at most (RtScene.radiance_bound): the product of its path's attenuations times what the
-    // path ran into.  Attenuations are texture values (lambertian.rs:36, metal.rs:40) or 1 (dialectric.rs:26) — a
-    // SolidColor's colour, a Noise colour times 0.5 (1 + sin) <= the colour, an image texel <= 1 — so with every such colour
-    // in [0, 1] the bound is the largest of 1 (renderer.rs:48-55: white at depth 0), the emitted colours
-    // (diffuse_light.rs:33-35) and the background's.  A colour outside [0, 1] on a scattering material, or anything
-    // negative or not finite, leaves the scene without a bound (0): the pooled kernel then keeps f64 sums.
-    {
-        bool bounded = true;
-        double bound = 1.0;
-        auto colours_of = [&](int ti, double &hi, double &lo) { // over the texture and, for a Checkered, its two sides
-            auto one = [&](const RtTexture &t) {
-                if (t.kind == RT_TEX_IMAGE) {
-                    hi = std::max(hi, 1.0);
-                    lo = std::min(lo, 0.0);
-                    return;
-                }
-                if (t.kind == RT_TEX_CHECKERED) return;
-                for (int k = 0; k < 3; ++k) {
-                    if (!std::isfinite(t.color[k])) bounded = false;
-                    hi = std::max(hi, t.color[k]);
-                    lo = std::min(lo, t.color[k]);
-                }
-            };
-            const RtTexture &t = d->textures[ti];
-            one(t);
-            if (t.kind == RT_TEX_CHECKERED) {
-                one(d->textures[t.tex_even]);
-                one(d->textures[t.tex_odd]);
-                // (a Checkered inside a Checkered is not evaluated further by the kernels: texture_value_deferred returns its colour field)
-                for (int side : {t.tex_even, t.tex_odd})
-                    if (d->textures[side].kind == RT_TEX_CHECKERED)
-                        for (int k = 0; k < 3; ++k) {
-                            if (!std::isfinite(d->textures[side].color[k])) bounded = false;
-                            hi = std::max(hi, d->textures[side].color[k]);
-                            lo = std::min(lo, d->textures[side].color[k]);
-                        }
-            }
-        };
-        for (int i = 0; i < d->n_materials; ++i) {
-            const RtMaterial &m = d->materials[i];
-            if (m.kind == RT_MAT_DIELECTRIC) continue;
-            double hi = 0.0, lo = 0.0;
-            colours_of(m.texture, hi, lo);
-            if (lo < 0.0) bounded = false;
-            if (m.kind == RT_MAT_DIFFUSE_LIGHT) bound = std::max(bound, hi);
-            else if (hi > 1.0) bounded = false;
-        }
-        for (int k = 0; k < 3; ++k)
-            for (double c : {d->background.top[k], d->background.bottom[k]}) {
-                if (!std::isfinite(c) || c < 0.0) bounded = false;
-                bound = std::max(bound, c);
-            }
-        s->radiance_bound = bounded && std::isfinite(bound) && bound < 0x1p40 ? bound : 0.0;
-    }
+    s->radiance_bound = scene_radiance_bound(d);
     std::vector<rtdev::Image> images((size_t)d->n_images);
     s->image_pixels.assign((size_t)d->n_images, nullptr);
     for (int i = 0; i < d->n_images; ++i) {
@@ -1188,6 +1222,30 @@ int rtdev_scene_classify(const RtSceneDesc *d, int32_t out[4]) {
         out[2] = sel.specular;
         out[3] = sel.has_moving;
         return RT_OK;
+    } catch (...) {
+        return RT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+int rtdev_scene_radiance_bound(const RtSceneDesc *d, double *bound) {
+    if (!bound) return RT_ERR_INVALID_ARGUMENT;
+    try {
+        int rc = validate_desc(d);
+        if (rc != RT_OK) return rc;
+        *bound = scene_radiance_bound(d);
+        return RT_OK;
+    } catch (...) {
+        return RT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+int rtdev_sum_exponent(double bound, int32_t samples, int32_t *e) {
+    if (!e) return RT_ERR_INVALID_ARGUMENT;
+    try { // (chunk_plan allocates, fail's messages are std::strings)
+        int k = 0;
+        const int rc = sum_exponent(bound, samples, &k);
+        *e = k;
+        return rc;
     } catch (...) {
         return RT_ERR_OUT_OF_MEMORY;
     }

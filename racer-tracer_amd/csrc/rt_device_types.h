@@ -238,8 +238,11 @@ struct TraceArgs {
     // samples of a chunk, so the 64-bit sums cannot overflow), and the item's sum is that integer, rounded once, times
     // sum_unscale = 2^-k.  Integer sums do not depend on the order of their terms, which is what lets a wave start its next
     // item while the last paths of the previous one are still in flight without the frame depending on scheduling.  The
-    // price is an ABSOLUTE quantum of E 2^-52 per sample where a double has a relative one: a pixel whose radiance is of
-    // that order — black, for every purpose — comes out up to sqrt(E 2^-53) (4e-8 for E = 16) from the f64 sum's value.
+    // price is an ABSOLUTE quantum of 2^-k per sample where a double has a relative one: a pixel whose radiance is of that
+    // order — black, for every purpose — comes out up to sqrt(2^-(k+1)) (4e-8 for E = 15: k = 48) from the f64 sum's
+    // value.  So the host uses these sums only while that stays within half the 1e-3 tolerance: k = 52 - e with
+    // E < 2^30 and e <= 31 (rt_api.hip: sum_exponent; 4.9e-4).  A brighter scene is rendered by the RT_ARITH_REFERENCE
+    // copy, and a render whose chunks would take e past 31 is refused (RT_ERR_UNSUPPORTED).
     // The other variants, and every RT_ARITH_REFERENCE kernel, add doubles in the order the samples finish, one item at a time.
     double sum_scale, sum_unscale;
     int32_t time_lds;  // the scene has a MovingSphere: the ray times of the batches sit behind the lens samples in dynamic LDS

@@ -141,9 +141,16 @@ struct RtScene {
 //     samples (bytes; 0 for v1), resident blocks per CU without and with lens samples.  Writes min(n_out, fields) values.
 //   rtdev_scene_classify: the selection rule of rt_scene_create_ex on a description alone (no device): prims_class, textured,
 //     specular, has_moving.  Returns the description's validation error, if any.
+//   rtdev_scene_radiance_bound: the bound on a finished sample's radiance that rt_scene_create_ex gives a description
+//     (RtScene.radiance_bound), or 0: none (f64 sums).  Returns the description's validation error, if any.
+//   rtdev_sum_exponent: the exponent e of the fixed-point sums (TraceArgs.sum_scale = 2^(52-e)) that a render of `samples`
+//     samples per pixel gets from a radiance bound, or e = 0: f64 sums; RT_ERR_UNSUPPORTED where the render is refused
+//     (rt_api.hip: sum_exponent).
 #define RTDEV_VARIANT_FIELDS 14
 extern "C" int rtdev_scene_variant(const RtScene *s, int32_t *out, int32_t n_out);
 extern "C" int rtdev_scene_classify(const RtSceneDesc *d, int32_t out[4]);
+extern "C" int rtdev_scene_radiance_bound(const RtSceneDesc *d, double *bound);
+extern "C" int rtdev_sum_exponent(double bound, int32_t samples, int32_t *e);
 
 namespace rtapi {
 int check_params(const RtCamera *camera, const RtRenderParams *p);

@@ -178,11 +178,12 @@ def with_light(bundle, emission):
     return S.abi.SceneBundle(list(bundle.primitives), list(bundle.materials), textures, S.abi.solid_background((0.0, 0.0, 0.0)))
 
 
-@pytest.mark.parametrize("emission", [16.0, 15.99999999, 1.0, 1e13])
+@pytest.mark.parametrize("emission", [16.0, 15.99999999, 1.0, 2.0 ** 30 * (1 - 1e-15), 2.0 ** 30, 1e13])
 def test_radiance_bounds_at_the_edges(rt, gpu, emission):
     """The scale of the fixed-point sums comes from the scene's largest emission: a bound that IS a power of two, one a hair
-    below it (the exponent keeps a margin), the smallest one (1: the white of an exhausted depth), and one beyond 2^40 —
-    where the scene takes the f64 sums of the reference copy.  Against that copy the radiance agrees to the quantum."""
+    below it (the exponent keeps a margin), the smallest one (1: the white of an exhausted depth), one a hair below the cap
+    of 2^30 (the coarsest scale, e = 31), and the cap and beyond — where the scene takes the f64 sums of the reference
+    copy.  Against that copy the radiance agrees to the quantum."""
     bundle, cam, _ = S.cornell_box_boxes()
     lit = with_light(bundle, emission)
     w, h, spp = 96, 54, 16
@@ -196,7 +197,7 @@ def test_radiance_bounds_at_the_edges(rt, gpu, emission):
         finally:
             scene.close()
     assert np.isfinite(frames[0]).all() and frames[0].max() > 0.0
-    if emission > 2.0 ** 40:
+    if emission >= 2.0 ** 30:
         assert np.array_equal(frames[0], frames[1])
     else:
         assert np.abs(frames[0] ** 2 - frames[1] ** 2).max() < 1e-11 * max(1.0, emission)
