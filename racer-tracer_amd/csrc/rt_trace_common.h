@@ -216,13 +216,19 @@ __device__ __forceinline__ double sym53(uint32_t hi, uint32_t lo) {
 // The three coordinates of a random_in_unit_sphere candidate from ONE block (rt_rng.h, RT_RNG_SCATTER): coordinate j is
 // random_double_range(-1, 1) of the 42-bit uniform d_j = U_j * 2^-42, U_j = out[j] << 10 | (out[3] >> 10 j & 0x3FF).
 // D = 2 * (1 + U * 2^-42) is assembled from bits (exponent of [2, 4), mantissa U << 10) and -1 + 2 d = D - 3, exactly.
-__device__ __forceinline__ double sym42(uint32_t w, uint32_t t_at_10) { // t_at_10: the ten extra bits at bits 10..19
-    const uint32_t d_hi = 0x40000000u | (w >> 12);
-    const uint32_t d_lo = (w << 20) | t_at_10;
+// The words are placed with v_alignbit_b32 (hi:lo >> s, the low 32 bits): d_hi = 0x400:w >> 12 is one instruction where
+// a shift and an OR were two, and out[0]'s d_lo = w:(out[3] << 22) >> 12 two where a shift, an AND and a shift-OR were
+// three.  The bits are the same (tests/test_sampler_isa.py checks the formula against rt_rng.h's).
+__device__ __forceinline__ double sym42_bits(uint32_t d_lo, uint32_t w) {
+    const uint32_t d_hi = __builtin_amdgcn_alignbit(0x400u, w, 12);
     return __longlong_as_double((long long)(((unsigned long long)d_hi << 32) | d_lo)) - 3.0;
 }
+__device__ __forceinline__ double sym42(uint32_t w, uint32_t t_at_10) { // t_at_10: the ten extra bits at bits 10..19
+    return sym42_bits((w << 20) | t_at_10, w);
+}
 __device__ __forceinline__ d3 sphere_candidate(const u4 &b) {
-    return mk(sym42(b.a, (b.d << 10) & 0x000FFC00u), sym42(b.b, b.d & 0x000FFC00u), sym42(b.c, (b.d >> 10) & 0x000FFC00u));
+    return mk(sym42_bits(__builtin_amdgcn_alignbit(b.a, b.d << 22, 12), b.a), sym42(b.b, b.d & 0x000FFC00u),
+              sym42(b.c, (b.d >> 10) & 0x000FFC00u));
 }
 
 struct PathRng {

@@ -205,15 +205,19 @@ template <bool TEXTURED, int NBUF, bool OVERLAP> struct WaveLds {
 
 // vec3.rs:424-430 for every lane with `need`, evaluated by the whole wave.
 // Must be called by all 64 lanes (wave-uniform control flow).  Runs at most
-// `max_rounds` rounds: a lane whose request is still open afterwards returns
+// MAX_ROUNDS rounds: a lane whose request is still open afterwards returns
 // false and keeps `base` (its first untested candidate), so the search resumes
 // at the same stream position in the next call.
+// The round count is a template constant: two rounds (the plain variants) are unrolled into straight-line code.  The
+// first round writes `result` in EVERY lane (no lane holds a sample yet), so only the later rounds write it under the
+// mask of the lanes still searching — a masked write is a copy of the old value at the join (C3 -0.8 %).
+template <int MAX_ROUNDS>
 __device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t pixel, uint32_t sample, uint32_t seg,
                                                            uint32_t &base, uint32_t k0, uint32_t k1, int lane,
-                                                           Req4 *req, int max_rounds, d3 &result) {
+                                                           Req4 *req, d3 &result) {
     bool have = false;
     uint64_t pending = ballot(need);
-    for (int round = 0; round < max_rounds && pending != 0; ++round) {
+    for (int round = 0; round < MAX_ROUNDS && pending != 0; ++round) {
         const int n = __popcll(pending);
         // a round costs the whole wave ~70 instructions; past the first it only runs while enough requests are
         // open to be worth that (the others resume next iteration): C2 +2.2 %, C3 +0.3 % (thresholds 2..16 and one to
@@ -222,11 +226,13 @@ __device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t p
         // group size q = 2^lg, the largest power of two with n * q <= 64
         const int lg = n > 32 ? 0 : (n > 16 ? 1 : (n > 8 ? 2 : (n > 4 ? 3 : (n > 2 ? 4 : (n > 1 ? 5 : 6)))));
         if (lg == 0) { // more than 32 requests: one candidate each, so every lane tests its OWN (no LDS, no shuffle)
+            // `result` only means something to a lane that returns true: a lane that still needs a sample may take every
+            // candidate it looks at, rejected ones included, without a select; in the first round no lane has one yet,
+            // so every lane takes its candidate (no copy of the result under the lanes' mask)
+            const d3 p = sphere_candidate(philox4x32(pixel, sample, (seg << 8) | RT_RNG_SCATTER, base, k0, k1));
+            if (round == 0 || need) result = p;
             if (need) {
-                // `result` only means something to a lane that returns true: a lane that still needs a sample
-                // may take every candidate it looks at, rejected ones included, without a select
-                result = sphere_candidate(philox4x32(pixel, sample, (seg << 8) | RT_RNG_SCATTER, base, k0, k1));
-                if (len2(result) < 1.0) {
+                if (len2(p) < 1.0) {
                     need = false;
                     have = true;
                 } else {
@@ -252,7 +258,7 @@ __device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t p
         const bool got = mine != 0;
         const int src = got ? first + __ffsll((unsigned long long)mine) - 1 : lane;
         const double rx = shfl_d(p.x, src), ry = shfl_d(p.y, src), rz = shfl_d(p.z, src);
-        if (need) result = mk(rx, ry, rz); // (its own candidate's coordinates when it got none: see above)
+        if (round == 0 || need) result = mk(rx, ry, rz); // (its own candidate's coordinates when it got none: see above)
         if (got) {
             need = false;
             have = true;
@@ -1120,8 +1126,8 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         }
         RT_REGION(10); // Noise rounds
         d3 sph = mk(0.0, 0.0, 0.0); // (left uninitialised, three moves fewer per iteration cost the plain variants 16 bytes of scratch)
-        if (coop_random_in_unit_sphere(waiting, rng.pixel, rng.sample, seg, cand_base, A.seed_lo, A.seed_hi, lane,
-                                       L.scratch.req, (TEXTURED || SPECULAR) ? 4 : 2, sph)) {
+        if (coop_random_in_unit_sphere<(TEXTURED || SPECULAR) ? 4 : 2>(waiting, rng.pixel, rng.sample, seg, cand_base, A.seed_lo,
+                                                                       A.seed_hi, lane, L.scratch.req, sph)) {
             waiting = false;
             finish = true;
         }
