@@ -1,8 +1,10 @@
-// rt_api.hip — implementation of the C ABI declared in include/rt_abi.h.
+// rt_api.hip — implementation of the C ABI declared in include/rt_abi.h: scene creation, the render-buffer cache,
+// the device-output entry points and enqueue_render, which every render entry point goes through (the host-output
+// ones live in rt_deliver.hip and rt_multi.hip).
 //
-// Host code only (HIP runtime calls); the kernels live in
-// rt_trace_kernel.hip.  Nothing here falls back to a CPU renderer: without a
-// usable HIP device every entry point returns RT_ERR_NO_DEVICE.
+// Host code only (HIP runtime calls); the kernels live in rt_trace_kernel.hip (v1), rt_trace_pool_kernel.hip (pooled)
+// and rt_post_kernel.hip.  Nothing here falls back to a CPU renderer: without a usable HIP device every entry point
+// returns RT_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -10,8 +12,8 @@
 #include <algorithm>
 #include <cmath>
 #include <atomic>
+#include <memory>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 #include <thread>
@@ -19,31 +21,25 @@
 #include "rt_bvh.h"
 #include "rt_scene.h"
 
-// The trace kernels exist twice (rt_trace_common.h: ARITHMETIC): RT_ARITH_FAST, and RT_ARITH_REFERENCE behind *_exact.
-#define RT_DECLARE_LAUNCHERS(SUFFIX)                                                                                       \
-    extern "C" hipError_t rtdev_launch_trace##SUFFIX(const rtdev::TraceArgs *args, int prims_class, int textured,         \
-                                                     int specular, hipStream_t stream);                                   \
-    extern "C" hipError_t rtdev_launch_resolve##SUFFIX(const double *accum, double *out, int width, int height,           \
-                                                       int strip_rows, int strip_count, int strip_index, int samples,     \
-                                                       hipStream_t stream);                                               \
-    extern "C" int rtdev_pool_blocks_per_cu##SUFFIX(int prims_class, int textured, int specular, int bvh, size_t dyn_lds); \
-    extern "C" int rtdev_pool_static_lds##SUFFIX(int prims_class, int textured, int specular, int bvh);                 \
-    extern "C" hipError_t rtdev_launch_trace_pool##SUFFIX(const rtdev::TraceArgs *args, int prims_class, int textured,    \
-                                                          int specular, int bvh, unsigned blocks, hipStream_t stream);    \
-    extern "C" hipError_t rtdev_launch_resolve_chunks##SUFFIX(const double *partial, double *out, int width, int height,  \
-                                                              int n_chunks, int slice_rows, int strip_rows, int strip_count, \
-                                                              int strip_index, int step_x, int step_y, int cover_w,       \
-                                                              int cover_h, int out_col_step, int out_cols, int samples,   \
-                                                              hipStream_t stream);
-RT_DECLARE_LAUNCHERS()
-RT_DECLARE_LAUNCHERS(_exact)
 extern "C" hipError_t rtdev_launch_post_rgba8(const RtToneMap *tm, const double *rgb, size_t n_pixels, uint8_t *rgba,
                                               double *mapped, hipStream_t stream);
 
-thread_local std::string g_last_error;
+namespace {
+const rtapi::Launchers kFastLaunchers = {rtdev_launch_trace,      rtdev_launch_resolve,    rtdev_pool_blocks_per_cu,
+                                         rtdev_pool_static_lds,   rtdev_launch_trace_pool, rtdev_launch_resolve_chunks};
+const rtapi::Launchers kExactLaunchers = {rtdev_launch_trace_exact,      rtdev_launch_resolve_exact,
+                                          rtdev_pool_blocks_per_cu_exact, rtdev_pool_static_lds_exact,
+                                          rtdev_launch_trace_pool_exact,  rtdev_launch_resolve_chunks_exact};
 
-int rtapi::fail(int code, const std::string &msg) {
-    g_last_error = msg;
+thread_local char g_last_error[1024]; // a fixed buffer: setting it cannot throw (rtapi::guarded's handlers use it)
+} // namespace
+
+int rtapi::fail(int code, const char *msg) noexcept {
+    snprintf(g_last_error, sizeof g_last_error, "%s", msg);
+    return code;
+}
+int rtapi::fail_in(int code, const char *what, const char *msg) noexcept {
+    snprintf(g_last_error, sizeof g_last_error, "%s: %s", what, msg);
     return code;
 }
 using rtapi::Cancel;
@@ -302,19 +298,8 @@ int sum_exponent(double bound, int samples, int *e_out) {
     return RT_OK;
 }
 
-int fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtdev::TraceArgs &a) {
-    memset(&a, 0, sizeof a);
-    a.prims = s->prims.ptr;
-    a.textures = s->textures.ptr;
-    a.images = s->images.ptr;
-    a.perlins = s->perlins.ptr;
-    a.n_prims = s->n_prims;
-    a.n_materials = s->n_materials;
-    a.n_textures = s->n_textures;
-    a.n_images = s->n_images;
-    a.n_perlins = s->n_perlins;
-    a.perlin_identity = s->perlin_identity;
-    a.perlin_in_lds = s->textured && s->n_perlins > 0 && s->perlin_identity;
+// The render's pixel grid: sizes, samples, strips, the preview's coarser grid, the seed.
+void fill_grid(const RtRenderParams *p, rtdev::TraceArgs &a) {
     a.width = p->width;
     a.height = p->height;
     a.samples = p->samples;
@@ -351,6 +336,22 @@ int fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtde
     a.seed_hi = (uint32_t)(p->seed >> 32);
     a.inv_width_m1 = 1.0 / (double)(p->width - 1);
     a.inv_height_m1 = 1.0 / (double)(p->height - 1);
+}
+
+int fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtdev::TraceArgs &a) {
+    memset(&a, 0, sizeof a);
+    a.prims = s->prims.ptr;
+    a.textures = s->textures.ptr;
+    a.images = s->images.ptr;
+    a.perlins = s->perlins.ptr;
+    a.n_prims = s->n_prims;
+    a.n_materials = s->n_materials;
+    a.n_textures = s->n_textures;
+    a.n_images = s->n_images;
+    a.n_perlins = s->n_perlins;
+    a.perlin_identity = s->perlin_identity;
+    a.perlin_in_lds = s->textured && s->n_perlins > 0 && s->perlin_identity;
+    fill_grid(p, a);
     for (int k = 0; k < 3; ++k) {
         a.cam.origin[k] = c->origin[k];
         a.cam.ulc[k] = c->upper_left_corner[k];
@@ -365,8 +366,8 @@ int fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtde
     a.cam.time_a = c->time_a;
     a.cam.time_b = c->time_b;
     a.bg = s->bg;
-    a.accum = s->accum.ptr;
-    a.segments = s->segments.ptr;
+    a.accum = s->buf.accum.ptr;
+    a.segments = s->buf.segments.ptr;
     a.bvh_nodes = s->bvh_nodes.ptr;
     a.bvh_nodes_ordered = s->bvh_nodes_in_lds ? nullptr : s->bvh_nodes_ordered.ptr;
     a.bvh_prim_index = s->bvh_prim_index.ptr;
@@ -413,6 +414,24 @@ int rtapi::owned_rows_of(const RtRenderParams *p) {
     return owned_strips * p->strip_rows;
 }
 
+namespace {
+
+// The counters of a delivering launch over `n_tiles` item tiles (zero between launches: fresh ones must be cleared).
+int reserve_delivery_counters(RtScene *s, size_t n_tiles) {
+    rtapi::RenderBuffers &b = s->buf;
+    if (b.tile_done.count < n_tiles) {
+        RT_HIP(b.tile_done.alloc(n_tiles));
+        b.deliver_dirty = true;
+    }
+    if (b.region_done.count < (size_t)rtdev::RT_MAX_REGIONS) {
+        RT_HIP(b.region_done.alloc((size_t)rtdev::RT_MAX_REGIONS));
+        b.deliver_dirty = true;
+    }
+    return RT_OK;
+}
+
+} // namespace
+
 // What a pooled-kernel launch of these parameters needs in device memory, allocated now.  enqueue_render does the same
 // when it finds a buffer too small; a call over SEVERAL shares reserves for all of them before it launches the first
 // (rt_deliver.hip, rt_multi.hip): hipMalloc waits for the device's running kernels, so a share that allocated inside its
@@ -424,27 +443,186 @@ int rtapi::reserve_render_buffers(RtScene *s, const RtRenderParams *p, bool deli
     const int owned = p->scale > 1 ? p->height : owned_rows_of(p); // (the preview's grid is smaller: an upper bound)
     const size_t slice_elems = (size_t)p->width * (size_t)owned * 3;
     const size_t chunks = (size_t)chunk_plan(p->samples).size() - 1;
-    if (s->partial.count < slice_elems * chunks) RT_HIP(s->partial.alloc(slice_elems * chunks));
-    if (s->queue.count < 1) RT_HIP(s->queue.alloc(1));
-    if (delivering) {
-        const size_t n_tiles = (size_t)((p->width + 7) / 8) * (size_t)((owned + 7) / 8);
-        if (s->tile_done.count < n_tiles) {
-            RT_HIP(s->tile_done.alloc(n_tiles));
-            s->deliver_dirty = true;
-        }
-        if (s->region_done.count < (size_t)rtdev::RT_MAX_REGIONS) {
-            RT_HIP(s->region_done.alloc((size_t)rtdev::RT_MAX_REGIONS));
-            s->deliver_dirty = true;
-        }
-    }
+    if (s->buf.partial.count < slice_elems * chunks) RT_HIP(s->buf.partial.alloc(slice_elems * chunks));
+    if (s->buf.queue.count < 1) RT_HIP(s->buf.queue.alloc(1));
+    if (delivering) return reserve_delivery_counters(s, (size_t)((p->width + 7) / 8) * (size_t)((owned + 7) / 8));
     return RT_OK;
 }
+
+namespace {
+
+// The v1 kernel: sample batches into the accumulator, a synchronisation after each while a cancel hook is armed (so
+// that the next poll is meaningful), then the resolve pass into out_device.
+int enqueue_v1(RtScene *s, rtdev::TraceArgs &a, const RtRenderParams *p, double *out_device, hipStream_t stream, int batch,
+               const Cancel &cancel, int &launches) {
+    const size_t n = (size_t)p->width * (size_t)p->height * 3;
+    if (s->buf.accum.count < n) RT_HIP(s->buf.accum.alloc(n));
+    a.accum = s->buf.accum.ptr;
+    RT_HIP(hipMemsetAsync(s->buf.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
+    RT_HIP(hipEventRecord(s->buf.ev_begin, stream));
+    for (int b = 0; b < p->samples; b += batch) {
+        if (cancel.raised()) return RT_ERR_CANCEL_EVENT;
+        a.sample_begin = b;
+        a.sample_end = b + batch < p->samples ? b + batch : p->samples;
+        RT_HIP(s->kernels->trace(&a, s->prims_class, s->textured, s->specular, stream));
+        ++launches;
+        if (cancel.armed()) RT_HIP(hipStreamSynchronize(stream));
+    }
+    RT_HIP(hipEventRecord(s->buf.ev_traced, stream));
+    RT_HIP(s->kernels->resolve(s->buf.accum.ptr, out_device, p->width, p->height, a.strip_rows, a.strip_count, a.strip_index,
+                               p->samples, stream));
+    RT_HIP(hipEventRecord(s->buf.ev_resolved, stream));
+    return RT_OK;
+}
+
+// One launch of the pooled kernel: chunks [first_chunk, first_chunk + n_chunks) of every tile.
+struct Launch {
+    int first_chunk, n_chunks;
+};
+// Sample batches are cut on chunk boundaries (chunk_plan), so batching changes no sum.
+std::vector<Launch> plan_launches(const std::vector<int> &starts, int batch) {
+    const int total_chunks = (int)starts.size() - 1;
+    std::vector<Launch> plan;
+    for (int c = 0; c < total_chunks;) {
+        Launch l{c, 0};
+        while (c < total_chunks && (l.n_chunks == 0 || starts[(size_t)c] - starts[(size_t)l.first_chunk] < batch)) {
+            ++l.n_chunks;
+            ++c;
+        }
+        plan.push_back(l);
+    }
+    return plan;
+}
+
+// A delivering launch (rt_deliver.hip): its items queued region by region, its counters cleared where they must be.
+int setup_delivery(RtScene *s, rtdev::TraceArgs &a, const Delivery &delivery, int total_chunks, hipStream_t stream) {
+    if (delivery.regions.empty() || (int)delivery.regions.size() > rtdev::RT_MAX_REGIONS)
+        return fail(RT_ERR_INVALID_ARGUMENT, "bad region list");
+    rtapi::RenderBuffers &b = s->buf;
+    const int rc = reserve_delivery_counters(s, (size_t)a.n_tiles);
+    if (rc != RT_OK) return rc;
+    if (b.deliver_dirty) { // fresh buffers, or a launch that was cut short (cancel, error): counters back to zero
+        RT_HIP(hipMemsetAsync(b.tile_done.ptr, 0, b.tile_done.count * sizeof(unsigned int), stream));
+        RT_HIP(hipMemsetAsync(b.region_done.ptr, 0, b.region_done.count * sizeof(unsigned int), stream));
+    }
+    b.deliver_dirty = true; // until every region has been published (rt_deliver.hip clears it)
+    a.n_regions = (int)delivery.regions.size();
+    uint64_t at = 0;
+    for (int r = 0; r < a.n_regions; ++r) {
+        rtdev::Region reg = delivery.regions[(size_t)r];
+        if (reg.ntx <= 0 || reg.nty <= 0 || reg.tx0 < 0 || reg.ty0 < 0 || reg.tx0 + reg.ntx > a.tiles_x ||
+            (reg.ty0 + reg.nty) * a.tiles_x > a.n_tiles)
+            return fail(RT_ERR_INVALID_ARGUMENT, "region outside the tile grid");
+        reg.item_begin = (uint32_t)at;
+        at += (uint64_t)reg.ntx * (uint64_t)reg.nty * (uint64_t)total_chunks;
+        a.regions[r] = reg;
+    }
+    if (at != (uint64_t)a.n_tiles * (uint64_t)total_chunks) return fail(RT_ERR_INVALID_ARGUMENT, "the regions do not tile the grid");
+    a.deliver_out = delivery.out;
+    a.tile_done = b.tile_done.ptr;
+    a.region_done = b.region_done.ptr;
+    a.deliver_flags = b.host_flags;
+    a.deliver_serial = delivery.serial;
+    a.deliver_col_step = delivery.col_step;
+    a.deliver_cols = delivery.cols;
+    return RT_OK;
+}
+
+// A tree that lives in LDS is walked in ONE fixed child order: the order that suits the rays starting at this camera
+// (rt_bvh.h: order_bvh_for_origin).  Re-emitted when the camera has moved — microseconds for the few hundred nodes LDS
+// holds — and copied in stream order, i.e. behind whatever launch of this scene still walks the old array.
+int order_bvh_for_camera(RtScene *s, const RtCamera *camera, hipStream_t stream) {
+    if (!s->use_bvh || !s->bvh_nodes_in_lds || s->bvh_host.nodes.empty()) return RT_OK;
+    if (s->bvh_is_ordered && camera->origin[0] == s->bvh_ordered_for[0] && camera->origin[1] == s->bvh_ordered_for[1] &&
+        camera->origin[2] == s->bvh_ordered_for[2])
+        return RT_OK;
+    s->bvh_upload_slot ^= 1; // (two host copies in turn: the one a pending copy may still read is left alone)
+    std::vector<rtdev::BvhNode> &arr = s->bvh_ordered_nodes[s->bvh_upload_slot];
+    arr = rtdev::order_bvh_for_origin(s->bvh_host, camera->origin);
+    RT_HIP(hipMemcpyAsync(s->bvh_nodes.ptr, arr.data(), arr.size() * sizeof(rtdev::BvhNode), hipMemcpyHostToDevice, stream));
+    for (int k = 0; k < 3; ++k) s->bvh_ordered_for[k] = camera->origin[k];
+    s->bvh_is_ordered = true;
+    return RT_OK;
+}
+
+// The pooled kernel: work items = 8x8 tiles x sample chunks, one launch per batch of chunks, then — without a Delivery —
+// the resolve pass into out_device.
+int enqueue_pool(RtScene *s, rtdev::TraceArgs &a, const RtCamera *camera, const RtRenderParams *p, double *out_device,
+                 hipStream_t stream, int batch, const Cancel &cancel, const Delivery *delivery, int out_col_step,
+                 int out_cols, int &launches) {
+    // A block must fit one CU's LDS: the primitive table of the linear loop, the textures, the Perlin gradients, the lens
+    // samples and the ray times all come on top of the kernel's static LDS (rt_device_types.h: pool_lds_layout).  A launch
+    // that does not fit is refused here, before anything is enqueued; the lens part depends on the camera.
+    const size_t lds = (size_t)s->pool_static_lds + (a.lens_lds ? s->pool_dyn_lds_lens : s->pool_dyn_lds);
+    const int blocks_per_cu = a.lens_lds ? s->pool_blocks_per_cu_lens : s->pool_blocks_per_cu;
+    if (lds > rtdev::kLdsPerCu || blocks_per_cu < 1)
+        return fail(RT_ERR_UNSUPPORTED, a.lens_lds ? "the trace kernel's LDS (static + tables + lens samples) exceeds a CU's 160 KiB"
+                                                   : "the trace kernel's LDS (static + tables) exceeds a CU's 160 KiB");
+    a.tiles_x = (a.cover_w / a.step_x + 7) / 8; // grid cells per row
+    a.n_tiles = a.tiles_x * ((a.owned_rows + 7) / 8);
+    const std::vector<int> starts = chunk_plan(p->samples);
+    const int total_chunks = (int)starts.size() - 1;
+    for (int c = 0; c <= total_chunks; ++c) a.chunk_start[c] = starts[(size_t)c];
+    a.chunk_samples = starts[1] - starts[0];
+    a.total_chunks = total_chunks;
+    const std::vector<Launch> plan = plan_launches(starts, batch);
+    int rc = RT_OK;
+    if (delivery) { // one launch, finishing its own pixels
+        if (plan.size() != 1 || p->scale > 1) return fail(RT_ERR_UNSUPPORTED, "a delivering launch is one whole-frame launch");
+        if ((rc = setup_delivery(s, a, *delivery, total_chunks, stream)) != RT_OK) return rc;
+    }
+    rtapi::RenderBuffers &b = s->buf;
+    // a call whose caller polls a cancel hook: the waves read the scene's cancel word with every item they fetch
+    if (cancel.armed() || (delivery && delivery->cancellable)) {
+        b.host_flags[rtdev::RT_MAX_REGIONS] = 0u;
+        a.cancel_flag = b.host_flags + rtdev::RT_MAX_REGIONS;
+    }
+    // slices hold the launch's owned rows only (the kernel compacts rows: owned_rows, tile_py0)
+    a.slice_rows = a.owned_rows;
+    const size_t slice_elems = (size_t)p->width * (size_t)a.slice_rows * 3;
+    if (b.partial.count < slice_elems * (size_t)total_chunks) RT_HIP(b.partial.alloc(slice_elems * (size_t)total_chunks));
+    if (b.queue.count < plan.size()) RT_HIP(b.queue.alloc(plan.size()));
+    a.partial = b.partial.ptr;
+    RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
+#ifdef RT_PROFILE_REGIONS
+    RT_HIP(hipMemsetAsync(b.segments.ptr + rtdev::RT_STAT_WALL + 0, 0xff, sizeof(unsigned long long), stream)); // min slots
+    RT_HIP(hipMemsetAsync(b.segments.ptr + rtdev::RT_STAT_WALL + 2, 0xff, sizeof(unsigned long long), stream));
+#endif
+    RT_HIP(hipMemsetAsync(b.queue.ptr, 0, sizeof(unsigned int) * b.queue.count, stream));
+    if ((rc = order_bvh_for_camera(s, camera, stream)) != RT_OK) return rc;
+    RT_HIP(hipEventRecord(b.ev_begin, stream));
+    // a slice is only written for the pixels a launch covers; unowned rows are skipped by the resolve
+    int chunks_done = 0;
+    for (const Launch &l : plan) {
+        if (cancel.raised()) return RT_ERR_CANCEL_EVENT;
+        a.sample_begin = starts[(size_t)l.first_chunk];
+        a.sample_end = starts[(size_t)(l.first_chunk + l.n_chunks)];
+        a.n_chunks = l.n_chunks;
+        a.chunk_base = l.first_chunk;
+        a.n_items = (uint32_t)a.n_chunks * (uint32_t)a.n_tiles;
+        if ((uint64_t)a.n_chunks * (uint64_t)a.n_tiles >= 0x40000000ull) // the item counter's top bit is the cancel poison
+            return fail(RT_ERR_UNSUPPORTED, "more than 2^30 work items in one launch");
+        a.queue = b.queue.ptr + launches;
+        const unsigned blocks = std::min((unsigned)(s->num_cus * blocks_per_cu), (a.n_items + 3) / 4);
+        RT_HIP(s->kernels->trace_pool(&a, s->prims_class, s->textured, s->specular, s->use_bvh, blocks, stream));
+        chunks_done += a.n_chunks;
+        ++launches;
+    }
+    RT_HIP(hipEventRecord(b.ev_traced, stream));
+    if (!delivery)
+        RT_HIP(s->kernels->resolve_chunks(b.partial.ptr, out_device, p->width, p->height, chunks_done, a.slice_rows, a.strip_rows,
+                                          a.strip_count, a.strip_index, a.step_x, a.step_y, a.cover_w, a.cover_h, out_col_step,
+                                          out_cols, p->samples, stream));
+    RT_HIP(hipEventRecord(b.ev_resolved, stream));
+    return RT_OK;
+}
+
+} // namespace
 
 int rtapi::enqueue_render(RtScene *s, const RtCamera *camera, const RtRenderParams *p, double *out_device,
                           hipStream_t stream, int batch, const Cancel &cancel, const Delivery *delivery, int out_col_step,
                           int out_cols) {
     RT_HIP(hipSetDevice(s->device));
-    size_t n = (size_t)p->width * (size_t)p->height * 3;
     rtdev::TraceArgs a;
     int rc = fill_args(s, camera, p, a);
     if (rc != RT_OK) return rc;
@@ -453,149 +631,11 @@ int rtapi::enqueue_render(RtScene *s, const RtCamera *camera, const RtRenderPara
     if (s->use_v1) {
         if (p->scale > 1) return fail(RT_ERR_UNSUPPORTED, "the v1 kernel has no preview mode");
         if (delivery || out_cols > 1) return fail(RT_ERR_UNSUPPORTED, "the v1 kernel does not deliver its own pixels");
-        if (s->accum.count < n) RT_HIP(s->accum.alloc(n));
-        a.accum = s->accum.ptr;
-        RT_HIP(hipMemsetAsync(s->segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
-        RT_HIP(hipEventRecord(s->ev_begin, stream));
-        for (int b = 0; b < p->samples; b += batch) {
-            if (cancel.raised()) return RT_ERR_CANCEL_EVENT;
-            a.sample_begin = b;
-            a.sample_end = b + batch < p->samples ? b + batch : p->samples;
-            RT_HIP((s->exact ? rtdev_launch_trace_exact : rtdev_launch_trace)(&a, s->prims_class, s->textured, s->specular, stream));
-            ++launches;
-            if (cancel.armed()) RT_HIP(hipStreamSynchronize(stream)); // so the next poll is meaningful
-        }
-        RT_HIP(hipEventRecord(s->ev_traced, stream));
-        RT_HIP((s->exact ? rtdev_launch_resolve_exact : rtdev_launch_resolve)(s->accum.ptr, out_device, p->width, p->height, a.strip_rows, a.strip_count,
-                                    a.strip_index, p->samples, stream));
-        RT_HIP(hipEventRecord(s->ev_resolved, stream));
+        rc = enqueue_v1(s, a, p, out_device, stream, batch, cancel, launches);
     } else {
-        // A block must fit one CU's LDS: the primitive table of the linear loop, the textures, the Perlin gradients, the lens
-        // samples and the ray times all come on top of the kernel's static LDS (rt_device_types.h: pool_lds_layout).  A launch
-        // that does not fit is refused here, before anything is enqueued; the lens part depends on the camera.
-        const size_t lds = (size_t)s->pool_static_lds + (a.lens_lds ? s->pool_dyn_lds_lens : s->pool_dyn_lds);
-        if (lds > rtdev::kLdsPerCu || (a.lens_lds ? s->pool_blocks_per_cu_lens : s->pool_blocks_per_cu) < 1)
-            return fail(RT_ERR_UNSUPPORTED, a.lens_lds ? "the trace kernel's LDS (static + tables + lens samples) exceeds a CU's 160 KiB"
-                                                       : "the trace kernel's LDS (static + tables) exceeds a CU's 160 KiB");
-        // Work items = 8x8 tiles x sample chunks.
-        a.tiles_x = (a.cover_w / a.step_x + 7) / 8; // grid cells per row
-        a.n_tiles = a.tiles_x * ((a.owned_rows + 7) / 8);
-        // Sample chunks (chunk_plan above).  Sample batches are cut on chunk boundaries, so batching changes
-        // nothing either.
-        const std::vector<int> starts = chunk_plan(p->samples);
-        const int total_chunks = (int)starts.size() - 1;
-        for (int c = 0; c <= total_chunks; ++c) a.chunk_start[c] = starts[(size_t)c];
-        a.chunk_samples = starts[1] - starts[0];
-        a.total_chunks = total_chunks;
-        struct Launch {
-            int first_chunk, n_chunks;
-        };
-        std::vector<Launch> plan;
-        for (int c = 0; c < total_chunks;) {
-            Launch l{c, 0};
-            while (c < total_chunks && (l.n_chunks == 0 || starts[(size_t)c] - starts[(size_t)l.first_chunk] < batch)) {
-                ++l.n_chunks;
-                ++c;
-            }
-            plan.push_back(l);
-        }
-        if (delivery) { // one launch, its items queued region by region, finishing its own pixels
-            if (plan.size() != 1 || p->scale > 1) return fail(RT_ERR_UNSUPPORTED, "a delivering launch is one whole-frame launch");
-            if (delivery->regions.empty() || (int)delivery->regions.size() > rtdev::RT_MAX_REGIONS)
-                return fail(RT_ERR_INVALID_ARGUMENT, "bad region list");
-            if (s->tile_done.count < (size_t)a.n_tiles) {
-                RT_HIP(s->tile_done.alloc((size_t)a.n_tiles));
-                s->deliver_dirty = true;
-            }
-            if (s->region_done.count < (size_t)rtdev::RT_MAX_REGIONS) {
-                RT_HIP(s->region_done.alloc((size_t)rtdev::RT_MAX_REGIONS));
-                s->deliver_dirty = true;
-            }
-            if (s->deliver_dirty) { // fresh buffers, or a launch that was cut short (cancel, error): counters back to zero
-                RT_HIP(hipMemsetAsync(s->tile_done.ptr, 0, s->tile_done.count * sizeof(unsigned int), stream));
-                RT_HIP(hipMemsetAsync(s->region_done.ptr, 0, s->region_done.count * sizeof(unsigned int), stream));
-            }
-            s->deliver_dirty = true; // until every region has been published (rt_deliver.hip clears it)
-            a.n_regions = (int)delivery->regions.size();
-            uint64_t at = 0;
-            for (int r = 0; r < a.n_regions; ++r) {
-                rtdev::Region reg = delivery->regions[(size_t)r];
-                if (reg.ntx <= 0 || reg.nty <= 0 || reg.tx0 < 0 || reg.ty0 < 0 || reg.tx0 + reg.ntx > a.tiles_x ||
-                    (reg.ty0 + reg.nty) * a.tiles_x > a.n_tiles)
-                    return fail(RT_ERR_INVALID_ARGUMENT, "region outside the tile grid");
-                reg.item_begin = (uint32_t)at;
-                at += (uint64_t)reg.ntx * (uint64_t)reg.nty * (uint64_t)total_chunks;
-                a.regions[r] = reg;
-            }
-            if (at != (uint64_t)a.n_tiles * (uint64_t)total_chunks) return fail(RT_ERR_INVALID_ARGUMENT, "the regions do not tile the grid");
-            a.deliver_out = delivery->out;
-            a.tile_done = s->tile_done.ptr;
-            a.region_done = s->region_done.ptr;
-            a.deliver_flags = s->host_flags;
-            a.deliver_serial = delivery->serial;
-            a.deliver_col_step = delivery->col_step;
-            a.deliver_cols = delivery->cols;
-        }
-        // a call whose caller polls a cancel hook: the waves read the scene's cancel word with every item they fetch
-        if (cancel.armed() || (delivery && delivery->cancellable)) {
-            s->host_flags[rtdev::RT_MAX_REGIONS] = 0u;
-            a.cancel_flag = s->host_flags + rtdev::RT_MAX_REGIONS;
-        }
-        const int n_batches = (int)plan.size();
-        // slices hold the launch's owned rows only (the kernel compacts rows: owned_rows, tile_py0)
-        a.slice_rows = a.owned_rows;
-        const size_t slice_elems = (size_t)p->width * (size_t)a.slice_rows * 3;
-        if (s->partial.count < slice_elems * (size_t)total_chunks) RT_HIP(s->partial.alloc(slice_elems * (size_t)total_chunks));
-        if (s->queue.count < (size_t)n_batches) RT_HIP(s->queue.alloc((size_t)n_batches));
-        a.partial = s->partial.ptr;
-        RT_HIP(hipMemsetAsync(s->segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
-#ifdef RT_PROFILE_REGIONS
-        RT_HIP(hipMemsetAsync(s->segments.ptr + rtdev::RT_STAT_WALL + 0, 0xff, sizeof(unsigned long long), stream)); // min slots
-        RT_HIP(hipMemsetAsync(s->segments.ptr + rtdev::RT_STAT_WALL + 2, 0xff, sizeof(unsigned long long), stream));
-#endif
-        RT_HIP(hipMemsetAsync(s->queue.ptr, 0, sizeof(unsigned int) * s->queue.count, stream));
-        // A tree that lives in LDS is walked in ONE fixed child order: the order that suits the rays starting at this
-        // camera (rt_bvh.h: order_bvh_for_origin).  Re-emitted when the camera has moved — microseconds for the few hundred
-        // nodes LDS holds — and copied in stream order, i.e. behind whatever launch of this scene still walks the old array.
-        if (s->use_bvh && s->bvh_nodes_in_lds && !s->bvh_host.nodes.empty() &&
-            (!s->bvh_is_ordered || camera->origin[0] != s->bvh_ordered_for[0] || camera->origin[1] != s->bvh_ordered_for[1] ||
-             camera->origin[2] != s->bvh_ordered_for[2])) {
-            s->bvh_upload_slot ^= 1; // (two host copies in turn: the one a pending copy may still read is left alone)
-            std::vector<rtdev::BvhNode> &arr = s->bvh_ordered_nodes[s->bvh_upload_slot];
-            arr = rtdev::order_bvh_for_origin(s->bvh_host, camera->origin);
-            RT_HIP(hipMemcpyAsync(s->bvh_nodes.ptr, arr.data(), arr.size() * sizeof(rtdev::BvhNode), hipMemcpyHostToDevice, stream));
-            for (int k = 0; k < 3; ++k) s->bvh_ordered_for[k] = camera->origin[k];
-            s->bvh_is_ordered = true;
-        }
-        RT_HIP(hipEventRecord(s->ev_begin, stream));
-        // a slice is only written for the pixels a launch covers; unowned rows are skipped by the resolve
-        int chunks_done = 0;
-        for (const Launch &l : plan) {
-            if (cancel.raised()) return RT_ERR_CANCEL_EVENT;
-            a.sample_begin = starts[(size_t)l.first_chunk];
-            a.sample_end = starts[(size_t)(l.first_chunk + l.n_chunks)];
-            a.n_chunks = l.n_chunks;
-            a.chunk_base = l.first_chunk;
-            a.n_items = (uint32_t)a.n_chunks * (uint32_t)a.n_tiles;
-            if ((uint64_t)a.n_chunks * (uint64_t)a.n_tiles >= 0x40000000ull) // the item counter's top bit is the cancel poison
-                return fail(RT_ERR_UNSUPPORTED, "more than 2^30 work items in one launch");
-            a.queue = s->queue.ptr + launches;
-            unsigned blocks = (unsigned)(s->num_cus * (a.lens_lds ? s->pool_blocks_per_cu_lens : s->pool_blocks_per_cu));
-            unsigned needed = (a.n_items + 3) / 4;
-            if (blocks > needed) blocks = needed;
-            RT_HIP((s->exact ? rtdev_launch_trace_pool_exact : rtdev_launch_trace_pool)(&a, s->prims_class, s->textured, s->specular, s->use_bvh, blocks, stream));
-            chunks_done += a.n_chunks;
-            ++launches;
-        }
-        RT_HIP(hipEventRecord(s->ev_traced, stream));
-        if (!delivery)
-            RT_HIP((s->exact ? rtdev_launch_resolve_chunks_exact : rtdev_launch_resolve_chunks)(s->partial.ptr, out_device, p->width, p->height, chunks_done, a.slice_rows, a.strip_rows,
-                                               a.strip_count, a.strip_index, a.step_x, a.step_y, a.cover_w, a.cover_h,
-                                               out_col_step, out_cols, p->samples, stream));
-        RT_HIP(hipEventRecord(s->ev_resolved, stream));
-        s->last_chunks = chunks_done;
+        rc = enqueue_pool(s, a, camera, p, out_device, stream, batch, cancel, delivery, out_col_step, out_cols, launches);
     }
-    s->last_stream = stream;
+    if (rc != RT_OK) return rc;
     s->has_stats = true;
     s->last_launches = launches;
     return RT_OK;
@@ -633,20 +673,20 @@ int rtapi::wait_event(hipEvent_t ev, const Cancel &cancel) {
 //   the v1 kernel's launches and anything not yet started.
 int rtapi::poison_queue_begin(RtScene *s) {
     // 1. the cancel word in pinned memory, which every wave reads with its next item: a CPU store, lands at once
-    if (s->host_flags) {
-        reinterpret_cast<volatile unsigned int *>(s->host_flags)[rtdev::RT_MAX_REGIONS] = 1u;
+    if (s->buf.host_flags) {
+        reinterpret_cast<volatile unsigned int *>(s->buf.host_flags)[rtdev::RT_MAX_REGIONS] = 1u;
         std::atomic_thread_fence(std::memory_order_seq_cst);
     }
     // 2. the item counters themselves, for a launch that has not started yet or a caller without the word (the v1
     //    kernel's batches); this write is a small kernel of the runtime's and lands when it finds room
     RT_HIP(hipSetDevice(s->device));
-    RT_HIP(hipStreamWaitEvent(s->stream_ctl, s->ev_begin, 0));
+    RT_HIP(hipStreamWaitEvent(s->buf.stream_ctl, s->buf.ev_begin, 0));
     bool by_cp = true;
-    for (size_t i = 0; i < s->queue.count && by_cp; ++i)
-        by_cp = hipStreamWriteValue32(s->stream_ctl, s->queue.ptr + i, 0x80000000u, 0) == hipSuccess;
+    for (size_t i = 0; i < s->buf.queue.count && by_cp; ++i)
+        by_cp = hipStreamWriteValue32(s->buf.stream_ctl, s->buf.queue.ptr + i, 0x80000000u, 0) == hipSuccess;
     if (!by_cp) { // a runtime without stream memory operations: a fill kernel does it, once it finds room
         (void)hipGetLastError();
-        RT_HIP(hipMemsetD32Async((hipDeviceptr_t)s->queue.ptr, (int)0x80000000u, s->queue.count, s->stream_ctl));
+        RT_HIP(hipMemsetD32Async((hipDeviceptr_t)s->buf.queue.ptr, (int)0x80000000u, s->buf.queue.count, s->buf.stream_ctl));
     }
     return RT_OK;
 }
@@ -654,212 +694,56 @@ int rtapi::poison_queue_begin(RtScene *s) {
 int rtapi::poison_queue(RtScene *s) {
     const int rc = poison_queue_begin(s);
     if (rc != RT_OK) return rc;
-    RT_HIP(hipStreamSynchronize(s->stream_ctl));
+    RT_HIP(hipStreamSynchronize(s->buf.stream_ctl));
     return RT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- render-buffer cache
-// Everything a render call allocates on first use, kept per device across rt_scene_destroy / rt_scene_create.
-// Measured on 1 x MI355X at 1080p (tools/time_scene_create.py, profiles/r04_scene_create.txt): rt_scene_create itself
-// is 0.3 - 1.4 ms, but the first render of a new scene paid 3 ms of hipMalloc / hipHostMalloc (50 MB pinned frame,
-// slices, counters) and the destroy before it 1 - 4 ms of hipFree / hipHostFree — on every object event of the
-// reference's interactive loop.  At most two sets per device are kept (two scenes alive at a time is the pattern of
-// `rebuild, then drop the old one`); rt_release_cached_buffers gives the memory back.
+// Everything a render call allocates on first use (RenderBuffers), kept per device across rt_scene_destroy /
+// rt_scene_create.  Measured on 1 x MI355X at 1080p (tools/time_scene_create.py, profiles/r04_scene_create.txt):
+// rt_scene_create itself is 0.3 - 1.4 ms, but the first render of a new scene paid 3 ms of hipMalloc / hipHostMalloc
+// (50 MB pinned frame, slices, counters) and the destroy before it 1 - 4 ms of hipFree / hipHostFree — on every object
+// event of the reference's interactive loop.  At most two sets per device are kept (two scenes alive at a time is the
+// pattern of `rebuild, then drop the old one`); rt_release_cached_buffers gives the memory back.
 namespace {
-struct RenderBuffers {
-    int device = -1;
-    DevBuf<double> partial, accum, frame;
-    DevBuf<unsigned int> queue, tile_done, region_done;
-    DevBuf<uint8_t> rgba;
-    DevBuf<unsigned long long> segments;
-    double *host_frame = nullptr;
-    size_t host_frame_count = 0;
-    unsigned int *host_flags = nullptr;
-    uint32_t deliver_serial = 0; // the flags still hold the serials this scene published: the counter moves on
-    bool deliver_dirty = false;
-    hipStream_t stream = nullptr, stream_ctl = nullptr;
-    hipEvent_t ev_begin = nullptr, ev_traced = nullptr, ev_resolved = nullptr;
-    void free_all() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        partial.release();
-        accum.release();
-        frame.release();
-        queue.release();
-        tile_done.release();
-        region_done.release();
-        rgba.release();
-        segments.release();
-        if (host_frame) (void)hipHostFree(host_frame);
-        if (host_flags) (void)hipHostFree(host_flags);
-        if (ev_begin) (void)hipEventDestroy(ev_begin);
-        if (ev_traced) (void)hipEventDestroy(ev_traced);
-        if (ev_resolved) (void)hipEventDestroy(ev_resolved);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (stream_ctl) (void)hipStreamDestroy(stream_ctl);
-        device = -1;
-    }
+struct CachedSet {
+    int device;
+    rtapi::RenderBuffers buf;
 };
 std::mutex g_cache_mutex;
-std::vector<RenderBuffers> g_cache;
+std::vector<CachedSet> g_cache;
 const size_t kCachedSetsPerDevice = 2;
 
-template <class T> void move_buf(DevBuf<T> &to, DevBuf<T> &from) {
-    to.ptr = from.ptr;
-    to.count = from.count;
-    from.ptr = nullptr;
-    from.count = 0;
-}
-void move_render_buffers(RenderBuffers &b, RtScene *s, bool to_scene) {
-#define RT_MOVE(member) do { if (to_scene) move_buf(s->member, b.member); else move_buf(b.member, s->member); } while (0)
-    RT_MOVE(partial);
-    RT_MOVE(accum);
-    RT_MOVE(frame);
-    RT_MOVE(queue);
-    RT_MOVE(tile_done);
-    RT_MOVE(region_done);
-    RT_MOVE(rgba);
-    RT_MOVE(segments);
-#undef RT_MOVE
-#define RT_SWAP(member) do { if (to_scene) s->member = b.member; else b.member = s->member; } while (0)
-    RT_SWAP(host_frame);
-    RT_SWAP(host_frame_count);
-    RT_SWAP(host_flags);
-    RT_SWAP(deliver_serial);
-    RT_SWAP(deliver_dirty);
-    RT_SWAP(stream);
-    RT_SWAP(stream_ctl);
-    RT_SWAP(ev_begin);
-    RT_SWAP(ev_traced);
-    RT_SWAP(ev_resolved);
-#undef RT_SWAP
-    if (!to_scene) {
-        s->host_frame = nullptr;
-        s->host_frame_count = 0;
-        s->host_flags = nullptr;
-        s->stream = s->stream_ctl = nullptr;
-        s->ev_begin = s->ev_traced = s->ev_resolved = nullptr;
-    }
-}
-// rt_scene_destroy: the scene's render buffers go to the cache (or are freed when the device's slots are taken or the
-// scene never got as far as creating its streams)
+// rt_scene_destroy: the scene's render buffers go to the cache, or are freed when the device's slots are taken or the
+// scene never got as far as creating its streams.  Should the cache throw, they are still the scene's.
 void render_cache_put(RtScene *s) {
-    RenderBuffers b;
-    b.device = s->device;
-    move_render_buffers(b, s, false);
-    const bool complete = b.stream && b.stream_ctl && b.ev_begin && b.ev_traced && b.ev_resolved && b.host_flags && b.segments.ptr;
-    if (complete) {
+    if (s->buf.complete()) {
         std::lock_guard<std::mutex> lock(g_cache_mutex);
         size_t held = 0;
-        for (const RenderBuffers &c : g_cache) held += c.device == b.device;
+        for (const CachedSet &c : g_cache) held += c.device == s->device;
         if (held < kCachedSetsPerDevice) {
-            g_cache.push_back(b);
+            g_cache.push_back(CachedSet{s->device, s->buf});
+            s->buf = rtapi::RenderBuffers();
             return;
         }
     }
-    b.free_all();
+    s->buf.free_all(s->device);
 }
 // rt_scene_create: take over a cached set of this device (the one with the largest slices), if there is one
 bool render_cache_take(RtScene *s) {
-    RenderBuffers b;
-    {
-        std::lock_guard<std::mutex> lock(g_cache_mutex);
-        int best = -1;
-        for (size_t i = 0; i < g_cache.size(); ++i)
-            if (g_cache[i].device == s->device && (best < 0 || g_cache[i].partial.count > g_cache[(size_t)best].partial.count)) best = (int)i;
-        if (best < 0) return false;
-        b = g_cache[(size_t)best];
-        g_cache.erase(g_cache.begin() + best);
-    }
-    move_render_buffers(b, s, true);
+    std::lock_guard<std::mutex> lock(g_cache_mutex);
+    int best = -1;
+    for (size_t i = 0; i < g_cache.size(); ++i)
+        if (g_cache[i].device == s->device && (best < 0 || g_cache[i].buf.partial.count > g_cache[(size_t)best].buf.partial.count))
+            best = (int)i;
+    if (best < 0) return false;
+    s->buf = g_cache[(size_t)best].buf;
+    g_cache.erase(g_cache.begin() + best);
     return true;
 }
-} // namespace
 
-extern "C" {
-
-int rt_abi_version(void) { return RT_ABI_VERSION; }
-
-int rt_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-const char *rt_last_error_message(void) { return g_last_error.c_str(); }
-
-const char *rt_strerror(int code) {
-    switch (code) {
-    case RT_OK: return "Ok";
-    case RT_ERR_FAILED_TO_CREATE_WINDOW: return "Failed to create window";
-    case RT_ERR_FAILED_TO_UPDATE_WINDOW: return "Failed to update window";
-    case RT_ERR_CONFIGURATION: return "Config Error";
-    case RT_ERR_UNKNOWN_MATERIAL: return "Unknown Material";
-    case RT_ERR_FAILED_TO_ACQUIRE_LOCK: return "Failed to acquire lock";
-    case RT_ERR_EXIT_EVENT: return "Exit event";
-    case RT_ERR_CANCEL_EVENT: return "Cancel event";
-    case RT_ERR_IMAGE_SAVE: return "Image save error";
-    case RT_ERR_SCENE_LOAD: return "Scene failed to load";
-    case RT_ERR_ARGUMENT_PARSING: return "Argument parsing Error";
-    case RT_ERR_KEY: return "Key callback failed";
-    case RT_ERR_CREATE_LOG: return "Failed to create log";
-    case RT_ERR_RECEIVE: return "Failed to recieve data";
-    case RT_ERR_SEND: return "Failed to send data";
-    case RT_ERR_ACTION_PROTOCOL: return "Action protocol error";
-    case RT_ERR_BUS_WRITE: return "Failed to write data to bus";
-    case RT_ERR_BUS_READ: return "Failed to read data from bus";
-    case RT_ERR_BUS_UPDATE: return "Failed to update databus";
-    case RT_ERR_BUS_TIMEOUT: return "Bus timeout error";
-    case RT_ERR_NO_OBJECT_WITH_ID: return "No object with id";
-    case RT_ERR_FAILED_TO_OPEN_IMAGE: return "Failed to open image";
-    case RT_ERR_FAILED_TO_PARSE: return "Failed to parse into a vector";
-    case RT_ERR_NO_DEVICE: return "No usable HIP device";
-    case RT_ERR_HIP: return "HIP runtime error";
-    case RT_ERR_INVALID_ARGUMENT: return "Invalid argument";
-    case RT_ERR_UNSUPPORTED: return "Unsupported scene feature";
-    case RT_ERR_OUT_OF_MEMORY: return "Out of memory";
-    default: return "Unknown error";
-    }
-}
-
-void rt_scene_destroy(RtScene *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    if (s->stream_ctl) (void)hipStreamSynchronize(s->stream_ctl);
-    for (uint8_t *p : s->image_pixels)
-        if (p) (void)hipFree(p);
-    s->prims.release();
-    s->textures.release();
-    s->images.release();
-    s->perlins.release();
-    s->bvh_nodes.release();
-    s->bvh_nodes_ordered.release();
-    s->bvh_prim_index.release();
-    s->leaf_geo.release();
-    // what a render allocates — slices, frames, pinned memory, counters, streams, events — outlives the scene: the
-    // reference rebuilds its scene on every object event (main.rs:174-189), and the next rt_scene_create on this
-    // device takes these over instead of paying hipMalloc / hipHostMalloc again (render_cache below)
-    render_cache_put(s);
-    delete s;
-}
-
-void rt_release_cached_buffers(void) {
-    std::vector<RenderBuffers> all;
-    {
-        std::lock_guard<std::mutex> lock(g_cache_mutex);
-        all.swap(g_cache);
-    }
-    for (RenderBuffers &b : all) b.free_all();
-}
-
-int rt_scene_create(const RtSceneDesc *d, int device, RtScene **out) { return rt_scene_create_ex(d, device, nullptr, out); }
-
-namespace {
-int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options, RtScene **out) {
-    int rc = validate_desc(d);
-    if (rc != RT_OK) return rc;
-    RtSceneOptions opt;
+// ------------------------------------------------------------------------------------------------ scene creation
+int check_options(const RtSceneOptions *options, RtSceneOptions &opt) {
     memset(&opt, 0, sizeof opt);
     if (options) opt = *options;
     if (opt.closest_hit < RT_HIT_AUTO || opt.closest_hit > RT_HIT_BVH) return fail(RT_ERR_INVALID_ARGUMENT, "unknown closest_hit option");
@@ -868,21 +752,35 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
     if (opt.gather < RT_GATHER_AUTO || opt.gather > RT_GATHER_STAGED) return fail(RT_ERR_INVALID_ARGUMENT, "unknown gather option");
     for (int32_t r : opt._reserved)
         if (r != 0) return fail(RT_ERR_INVALID_ARGUMENT, "reserved option fields must be 0");
-    int n_dev = rt_device_count();
-    if (n_dev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device is visible to this process");
-    if (device < 0 || device >= n_dev) return fail(RT_ERR_INVALID_ARGUMENT, "device index out of range");
-    RT_HIP(hipSetDevice(device));
+    return RT_OK;
+}
 
-    RtScene *s = new (std::nothrow) RtScene();
-    if (!s) return fail(RT_ERR_OUT_OF_MEMORY, "host allocation failed");
-    s->device = device;
-    s->exact = opt.arithmetic == RT_ARITH_REFERENCE;
-    s->gather_staged = opt.gather == RT_GATHER_STAGED;
-    struct Guard { // destroy the half-built scene on any early return
-        RtScene *s;
-        ~Guard() { if (s) rt_scene_destroy(s); }
-    } guard{s};
-
+// The device records of the primitives, each carrying its material (the only device copy of a material).
+std::vector<rtdev::Prim> pack_prims(const RtSceneDesc *d) {
+    std::vector<rtdev::Material> materials((size_t)d->n_materials);
+    for (int i = 0; i < d->n_materials; ++i) {
+        const RtMaterial &m = d->materials[i];
+        rtdev::Material &q = materials[(size_t)i];
+        memset(&q, 0, sizeof q);
+        q.kind = m.kind;
+        q.texture = m.texture;
+        q.tex_kind = -1;
+        q.fuzz = m.fuzz;
+        q.ior = m.refraction_index;
+        if (m.kind == RT_MAT_DIELECTRIC) { // rt_device_types.h: the per-hit quotients, once
+            const double ior = m.refraction_index;
+            q.color[0] = 1.0 / ior;
+            const double front = (1.0 - q.color[0]) / (1.0 + q.color[0]), back = (1.0 - ior) / (1.0 + ior);
+            q.color[1] = front * front;
+            q.color[2] = back * back;
+        }
+        if (m.kind != RT_MAT_DIELECTRIC) {
+            const RtTexture &t = d->textures[m.texture];
+            q.tex_kind = t.kind;
+            q.needs_uv = texture_reads_uv(d, m.texture) ? 1 : 0;
+            for (int k = 0; k < 3; ++k) q.color[k] = t.color[k];
+        }
+    }
     std::vector<rtdev::Prim> prims((size_t)d->n_primitives);
     for (int i = 0; i < d->n_primitives; ++i) {
         const RtPrimitive &p = d->primitives[i];
@@ -908,34 +806,14 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
             q.rot_sin = p.time_a;
             q.rot_cos = 1.0 / (p.time_b - p.time_a);
         }
+        q.mat = materials[(size_t)q.material];
     }
-    std::vector<rtdev::Material> materials((size_t)d->n_materials);
-    for (int i = 0; i < d->n_materials; ++i) {
-        const RtMaterial &m = d->materials[i];
-        rtdev::Material &q = materials[(size_t)i];
-        memset(&q, 0, sizeof q);
-        q.kind = m.kind;
-        q.texture = m.texture;
-        q.tex_kind = -1;
-        q.fuzz = m.fuzz;
-        q.ior = m.refraction_index;
-        if (m.kind == RT_MAT_DIELECTRIC) { // rt_device_types.h: the per-hit quotients, once
-            const double ior = m.refraction_index;
-            q.color[0] = 1.0 / ior;
-            const double front = (1.0 - q.color[0]) / (1.0 + q.color[0]), back = (1.0 - ior) / (1.0 + ior);
-            q.color[1] = front * front;
-            q.color[2] = back * back;
-        }
-        if (m.kind != RT_MAT_DIELECTRIC) {
-            const RtTexture &t = d->textures[m.texture];
-            q.tex_kind = t.kind;
-            q.needs_uv = texture_reads_uv(d, m.texture) ? 1 : 0;
-            for (int k = 0; k < 3; ++k) q.color[k] = t.color[k];
-        }
-    }
-    for (rtdev::Prim &q : prims) q.mat = materials[(size_t)q.material]; // the only device copy of a material
-    s->radiance_bound = scene_radiance_bound(d);
-    std::vector<rtdev::Image> images((size_t)d->n_images);
+    return prims;
+}
+
+// The images' texels on the device (RtScene.image_pixels) and their device records.
+int upload_images(const RtSceneDesc *d, RtScene *s, std::vector<rtdev::Image> &images) {
+    images.assign((size_t)d->n_images, rtdev::Image());
     s->image_pixels.assign((size_t)d->n_images, nullptr);
     for (int i = 0; i < d->n_images; ++i) {
         size_t bytes = (size_t)d->images[i].width * (size_t)d->images[i].height * 4;
@@ -945,6 +823,11 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
         images[(size_t)i].width = d->images[i].width;
         images[(size_t)i].height = d->images[i].height;
     }
+    return RT_OK;
+}
+
+// The device records of the textures; an image texture embeds its image's record (rt_device_types.h).
+std::vector<rtdev::Texture> pack_textures(const RtSceneDesc *d, const std::vector<rtdev::Image> &images) {
     std::vector<rtdev::Texture> textures((size_t)d->n_textures);
     for (int i = 0; i < d->n_textures; ++i) {
         const RtTexture &t = d->textures[i];
@@ -958,19 +841,212 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
         q.depth = t.depth;
         for (int k = 0; k < 3; ++k) q.color[k] = t.color[k];
         q.scale = t.scale;
-        if (t.kind == RT_TEX_IMAGE) { // the device record of its image, embedded (rt_device_types.h)
+        if (t.kind == RT_TEX_IMAGE) {
             q.img.rgba = images[(size_t)t.image].rgba;
             q.img.width = images[(size_t)t.image].width;
             q.img.height = images[(size_t)t.image].height;
         }
     }
+    return textures;
+}
+
+// The Perlin tables as they are; `identity` is cleared when some permutation is not the identity.
+std::vector<rtdev::Perlin> pack_perlins(const RtSceneDesc *d, int &identity) {
     std::vector<rtdev::Perlin> perlins((size_t)d->n_perlins);
     for (int i = 0; i < d->n_perlins; ++i) {
         static_assert(sizeof(rtdev::Perlin) == sizeof(RtPerlin), "Perlin layouts must match");
         memcpy(&perlins[(size_t)i], &d->perlins[i], sizeof(RtPerlin));
         for (int k = 0; k < 256; ++k)
-            if (d->perlins[i].perm_x[k] != k || d->perlins[i].perm_y[k] != k || d->perlins[i].perm_z[k] != k) s->perlin_identity = 0;
+            if (d->perlins[i].perm_x[k] != k || d->perlins[i].perm_y[k] != k || d->perlins[i].perm_z[k] != k) identity = 0;
     }
+    return perlins;
+}
+
+// Linear loop: group the table (rt_device_types.h: rect_end, sphere_end, box_end); the order inside a group is kept.
+void group_linear_table(RtScene *s, std::vector<rtdev::Prim> &prims) {
+    std::vector<rtdev::Prim> sorted;
+    sorted.reserve(prims.size());
+    auto group_of = [](const rtdev::Prim &q) {
+        if (q.flags == 0 && q.kind == RT_PRIM_XY_RECT) return 0;
+        if (q.flags == 0 && q.kind == RT_PRIM_XZ_RECT) return 1;
+        if (q.flags == 0 && q.kind == RT_PRIM_YZ_RECT) return 2;
+        if (q.flags == 0 && q.kind == RT_PRIM_SPHERE) return 3;
+        if (q.kind == RT_PRIM_BOX) return 4; // bare or wrapped
+        return 5;
+    };
+    for (int g = 0; g < 6; ++g) {
+        for (const rtdev::Prim &q : prims)
+            if (group_of(q) == g) sorted.push_back(q);
+        if (g < 3) s->rect_end[g] = (int)sorted.size();
+        if (g == 3) s->sphere_end = (int)sorted.size();
+        if (g == 4) s->box_end = (int)sorted.size();
+    }
+    prims.swap(sorted);
+}
+
+constexpr size_t kBvhLdsBytes = 32 * 1024; // a node array up to this size is staged in dynamic LDS
+
+// Primitives per leaf.  A leaf primitive costs a lane four times what a node costs (its record comes from global memory,
+// the node from LDS; `random`: 40 % of the walk for 5.8 tests against 26.5 nodes per segment), so leaves of three beat
+// leaves of four (66.1 -> 62.1 ms) — as long as the larger node array does not cost the variant a block per CU (leaves of
+// two: 70.6 ms with three blocks instead of four).  A tree whose nodes stay in global memory, where a step is two dependent
+// loads and every node not visited counts, comes with the eight direction-ordered copies (rt_bvh.cpp; 8 x 32 B per node).
+rtdev::BvhBuild choose_bvh(const RtSceneDesc *d, const RtScene *s) {
+    auto blocks_with = [&](const rtdev::BvhBuild &b) {
+        const size_t bytes = b.nodes.size() * sizeof(rtdev::BvhNode);
+        const size_t dyn = rtdev::pool_lds_layout(true, s->textured, d->n_primitives, d->n_textures, bytes <= kBvhLdsBytes ? (int)b.nodes.size() : 0,
+                                                  d->n_perlins > 0 && s->perlin_identity, false, s->has_moving).bytes;
+        return s->kernels->pool_blocks_per_cu(s->prims_class, s->textured, s->specular, 1, dyn);
+    };
+    // (more than 2048 primitives: at most four to a leaf, the node array cannot fit LDS — the direction-ordered copies are
+    // wanted, built in the same pass)
+    const bool surely_large = d->n_primitives > 2048;
+    rtdev::BvhBuild bvh = rtdev::build_bvh(d->primitives, d->n_primitives, 4, surely_large);
+    int max_leaf = 0;
+#ifdef RT_DEVELOPER_KNOBS
+    if (const char *k = getenv("RT_BVH_LEAF")) max_leaf = atoi(k);
+#endif
+    if (max_leaf > 0) {
+        bvh = rtdev::build_bvh(d->primitives, d->n_primitives, max_leaf);
+    } else if (bvh.nodes.size() * sizeof(rtdev::BvhNode) <= kBvhLdsBytes) { // the nodes live in LDS
+        rtdev::BvhBuild three = rtdev::build_bvh(d->primitives, d->n_primitives, 3);
+        if (three.nodes.size() * sizeof(rtdev::BvhNode) <= kBvhLdsBytes && blocks_with(three) == blocks_with(bvh)) bvh = std::move(three);
+    }
+    bool ordered = true;
+#ifdef RT_DEVELOPER_KNOBS
+    if (const char *k = getenv("RT_BVH_ORDERED")) ordered = atoi(k) != 0;
+#endif
+    if (!ordered) bvh.ordered.clear();
+    else if (bvh.nodes.size() * sizeof(rtdev::BvhNode) > kBvhLdsBytes && bvh.ordered.empty())
+        bvh = rtdev::build_bvh(d->primitives, d->n_primitives, max_leaf > 0 ? max_leaf : 4, true);
+    return bvh;
+}
+
+// The compact records the walk tests leaves with (rt_device_types.h: LeafGeo), of a table in leaf order; the first
+// MovingSphere sets the scene-wide time interval.
+std::vector<rtdev::LeafGeo> leaf_geometry(RtScene *s, const std::vector<rtdev::Prim> &prims) {
+    std::vector<rtdev::LeafGeo> geo(prims.size());
+    bool have_interval = false;
+    for (size_t j = 0; j < prims.size(); ++j) {
+        const rtdev::Prim &q = prims[j];
+        rtdev::LeafGeo &g = geo[j];
+        memset(&g, 0, sizeof g);
+        g.tag = 1;
+        if (q.flags != 0 || (q.kind != RT_PRIM_SPHERE && q.kind != RT_PRIM_MOVING_SPHERE)) continue;
+        if (q.kind == RT_PRIM_MOVING_SPHERE) {
+            // a MovingSphere with time_a == time_b degenerates by itself in the reference (moving_sphere.rs:37-39:
+            // 0/0); its 1 / (time_b - time_a) = inf must not become the scene-wide interval, where it would turn
+            // the centre of every plain Sphere (dc = 0) into inf * 0 = NaN: it keeps the general path (tag 1)
+            if (!std::isfinite(q.rot_cos)) continue;
+            if (!have_interval) {
+                s->leaf_time_a = q.rot_sin;
+                s->leaf_inv_dt = q.rot_cos;
+                have_interval = true;
+            }
+            if (q.rot_sin != s->leaf_time_a || q.rot_cos != s->leaf_inv_dt) continue; // another interval: general path
+            for (int k = 0; k < 3; ++k) g.dc[k] = q.tr[k];
+        }
+        for (int k = 0; k < 3; ++k) g.c0[k] = q.p[k];
+        g.radius2 = q.radius2;
+        g.tag = 0;
+    }
+    return geo;
+}
+
+// The tree on the device; the primitive table is put in leaf order (a leaf is a contiguous run of records).
+int upload_bvh(RtScene *s, const rtdev::BvhBuild &bvh, std::vector<rtdev::Prim> &prims) {
+    const bool nodes_fit_lds = bvh.nodes.size() * sizeof(rtdev::BvhNode) <= kBvhLdsBytes;
+    int rc = RT_OK;
+    if (!nodes_fit_lds && !bvh.ordered.empty() && (rc = upload(s->bvh_nodes_ordered, bvh.ordered)) != RT_OK) return rc;
+    if ((rc = upload(s->bvh_nodes, bvh.nodes)) != RT_OK) return rc;
+    if (nodes_fit_lds) { // kept for the per-camera child order (enqueue_render: order_bvh_for_camera)
+        s->bvh_host.nodes = bvh.nodes;
+        for (int k = 0; k < 3; ++k) s->bvh_host.center[k] = bvh.center[k];
+    }
+    if ((rc = upload(s->bvh_prim_index, bvh.prim_index)) != RT_OK) return rc;
+    s->n_bvh_nodes = (int)bvh.nodes.size() - 1; // the array ends with the sentinel (rt_device_types.h: BvhNode)
+    for (int k = 0; k < 3; ++k) {
+        s->bvh_root_mn[k] = bvh.root_mn[k];
+        s->bvh_root_mx[k] = bvh.root_mx[k];
+        s->bvh_center[k] = bvh.center[k];
+    }
+    std::vector<rtdev::Prim> ordered(prims.size());
+    for (size_t j = 0; j < bvh.prim_index.size(); ++j) ordered[j] = prims[(size_t)bvh.prim_index[j]];
+    prims.swap(ordered);
+    return upload(s->leaf_geo, leaf_geometry(s, prims));
+}
+
+// The pooled variant's LDS bill — its dynamic LDS (rt_device_types.h: pool_lds_layout) without and with the lens
+// samples, and its static LDS: what enqueue_render checks against the CU's LDS before a launch — and its resident blocks
+// per CU.  The v1 kernel has no dynamic LDS.
+int size_pool(RtScene *s) {
+    RT_HIP(hipDeviceGetAttribute(&s->num_cus, hipDeviceAttributeMultiprocessorCount, s->device));
+    s->bvh_nodes_in_lds = s->use_bvh && (size_t)(s->n_bvh_nodes + 1) * sizeof(rtdev::BvhNode) <= kBvhLdsBytes;
+#ifdef RT_DEVELOPER_KNOBS
+    if (const char *k = getenv("RT_BVH_LDS")) s->bvh_nodes_in_lds = s->bvh_nodes_in_lds && atoi(k) != 0;
+#endif
+    if (!s->use_v1) {
+        auto dyn_lds = [&](bool lens) {
+            return rtdev::pool_lds_layout(s->use_bvh, s->textured, s->n_prims, s->n_textures, s->bvh_nodes_in_lds ? s->n_bvh_nodes + 1 : 0,
+                                          s->n_perlins > 0 && s->perlin_identity, lens, s->has_moving).bytes;
+        };
+        s->pool_dyn_lds = dyn_lds(false);
+        s->pool_dyn_lds_lens = dyn_lds(true);
+        s->pool_static_lds = s->kernels->pool_static_lds(s->prims_class, s->textured, s->specular, s->use_bvh);
+        if (s->pool_static_lds < 0) return fail(RT_ERR_HIP, "hipFuncGetAttributes of the trace kernel failed");
+        s->pool_blocks_per_cu = s->kernels->pool_blocks_per_cu(s->prims_class, s->textured, s->specular, s->use_bvh, s->pool_dyn_lds);
+        s->pool_blocks_per_cu_lens = s->kernels->pool_blocks_per_cu(s->prims_class, s->textured, s->specular, s->use_bvh, s->pool_dyn_lds_lens);
+    }
+#ifdef RT_DEVELOPER_KNOBS // occupancy experiments
+    if (const char *k = getenv("RT_POOL_BLOCKS_PER_CU"))
+        if (atoi(k) > 0) s->pool_blocks_per_cu = s->pool_blocks_per_cu_lens = atoi(k);
+#endif
+    return RT_OK;
+}
+
+// The scene's render buffers: a cached set of this device's, or a fresh one of what every render needs.
+int acquire_render_buffers(RtScene *s) {
+    rtapi::RenderBuffers &b = s->buf;
+    if (!render_cache_take(s)) { // nothing of this device's to take over: the first scene, or more than the cache holds
+        RT_HIP(b.segments.alloc(rtdev::RT_STAT_SLOTS)); // rt_device_types.h: RT_STAT_*
+        RT_HIP(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+        RT_HIP(hipEventCreate(&b.ev_begin));
+        RT_HIP(hipEventCreate(&b.ev_traced));
+        RT_HIP(hipEventCreate(&b.ev_resolved));
+        RT_HIP(hipHostMalloc((void **)&b.host_flags, (rtdev::RT_MAX_REGIONS + 1) * sizeof(unsigned int),
+                             hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
+        memset(b.host_flags, 0, (rtdev::RT_MAX_REGIONS + 1) * sizeof(unsigned int));
+        RT_HIP(hipStreamCreateWithFlags(&b.stream_ctl, hipStreamNonBlocking));
+    }
+    RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), b.stream));
+    return RT_OK;
+}
+
+int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options, RtScene **out) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    int rc = validate_desc(d);
+    if (rc != RT_OK) return rc;
+    RtSceneOptions opt;
+    if ((rc = check_options(options, opt)) != RT_OK) return rc;
+    int n_dev = rt_device_count();
+    if (n_dev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device is visible to this process");
+    if (device < 0 || device >= n_dev) return fail(RT_ERR_INVALID_ARGUMENT, "device index out of range");
+    RT_HIP(hipSetDevice(device));
+
+    RtScene *s = new RtScene(); // (std::bad_alloc: rtapi::guarded)
+    std::unique_ptr<RtScene, void (*)(RtScene *)> half_built(s, rt_scene_destroy); // destroyed on any early return
+    s->device = device;
+    s->exact = opt.arithmetic == RT_ARITH_REFERENCE;
+    s->gather_staged = opt.gather == RT_GATHER_STAGED;
+    s->use_v1 = opt.kernel == RT_KERNEL_V1;
+
+    std::vector<rtdev::Prim> prims = pack_prims(d);
+    s->radiance_bound = scene_radiance_bound(d);
+    std::vector<rtdev::Image> images;
+    if ((rc = upload_images(d, s, images)) != RT_OK) return rc;
+    const std::vector<rtdev::Texture> textures = pack_textures(d, images);
+    const std::vector<rtdev::Perlin> perlins = pack_perlins(d, s->perlin_identity);
     const Selection sel = select_variant(d);
     s->prims_class = sel.prims_class;
     s->textured = sel.textured;
@@ -985,110 +1061,14 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
     // The RT_ARITH_FAST copies of the pooled variants that keep two items in flight (any primitive kind, BVH:
     // rt_trace_pool_kernel.hip, OVERLAP) have fixed-point sums only: a scene without a radiance bound is rendered by their
     // RT_ARITH_REFERENCE copies (f64 sums, one item per wave at a time, the reference's own divisions: ~25 % slower).
-    if (s->radiance_bound == 0.0 && opt.kernel == RT_KERNEL_POOL && (s->use_bvh || s->prims_class == 2)) s->exact = true;
-    // the linear-loop variants keep the whole primitive table in LDS
-    if (!s->use_bvh && (size_t)d->n_primitives * sizeof(rtdev::Prim) > 120 * 1024)
-        return fail(RT_ERR_UNSUPPORTED, "RT_HIT_LINEAR: the primitive table does not fit in LDS");
-    if (!s->use_bvh) { // linear loop: group the table (rt_device_types.h: rect_end, sphere_end); the order inside a group is kept
-        std::vector<rtdev::Prim> sorted;
-        sorted.reserve(prims.size());
-        auto group_of = [](const rtdev::Prim &q) {
-            if (q.flags == 0 && q.kind == RT_PRIM_XY_RECT) return 0;
-            if (q.flags == 0 && q.kind == RT_PRIM_XZ_RECT) return 1;
-            if (q.flags == 0 && q.kind == RT_PRIM_YZ_RECT) return 2;
-            if (q.flags == 0 && q.kind == RT_PRIM_SPHERE) return 3;
-            if (q.kind == RT_PRIM_BOX) return 4; // bare or wrapped
-            return 5;
-        };
-        for (int g = 0; g < 6; ++g) {
-            for (const rtdev::Prim &q : prims)
-                if (group_of(q) == g) sorted.push_back(q);
-            if (g < 3) s->rect_end[g] = (int)sorted.size();
-            if (g == 3) s->sphere_end = (int)sorted.size();
-            if (g == 4) s->box_end = (int)sorted.size();
-        }
-        prims.swap(sorted);
-    }
+    if (s->radiance_bound == 0.0 && !s->use_v1 && (s->use_bvh || s->prims_class == 2)) s->exact = true;
+    s->kernels = s->exact ? &kExactLaunchers : &kFastLaunchers;
     if (s->use_bvh) {
-        // Primitives per leaf.  A leaf primitive costs a lane four times what a node costs (its record comes from
-        // global memory, the node from LDS; `random`: 40 % of the walk for 5.8 tests against 26.5 nodes per
-        // segment), so leaves of three beat leaves of four (66.1 -> 62.1 ms) — as long as the larger node array
-        // does not cost the variant a block per CU (leaves of two: 70.6 ms with three blocks instead of four).
-        auto blocks_with = [&](const rtdev::BvhBuild &b) {
-            const size_t bytes = b.nodes.size() * sizeof(rtdev::BvhNode);
-            const size_t dyn = rtdev::pool_lds_layout(true, s->textured, d->n_primitives, d->n_textures, bytes <= 32 * 1024 ? (int)b.nodes.size() : 0,
-                                                      d->n_perlins > 0 && s->perlin_identity, false, s->has_moving).bytes;
-            return (s->exact ? rtdev_pool_blocks_per_cu_exact : rtdev_pool_blocks_per_cu)(s->prims_class, s->textured, s->specular, 1, dyn);
-        };
-        // (more than 2048 primitives: at most four to a leaf, the node array cannot fit LDS — the direction-ordered copies are
-        // wanted, built in the same pass)
-        const bool surely_large = d->n_primitives > 2048;
-        rtdev::BvhBuild bvh = rtdev::build_bvh(d->primitives, d->n_primitives, 4, surely_large);
-        int max_leaf = 0;
-#ifdef RT_DEVELOPER_KNOBS
-        if (const char *k = getenv("RT_BVH_LEAF")) max_leaf = atoi(k);
-#endif
-        if (max_leaf > 0) {
-            bvh = rtdev::build_bvh(d->primitives, d->n_primitives, max_leaf);
-        } else if (bvh.nodes.size() * sizeof(rtdev::BvhNode) <= 32 * 1024) { // the nodes live in LDS
-            rtdev::BvhBuild three = rtdev::build_bvh(d->primitives, d->n_primitives, 3);
-            if (three.nodes.size() * sizeof(rtdev::BvhNode) <= 32 * 1024 && blocks_with(three) == blocks_with(bvh)) bvh = std::move(three);
-        }
-        if (bvh.nodes.size() * sizeof(rtdev::BvhNode) > 32 * 1024) {
-            // the nodes stay in global memory, where a step is two dependent loads and every node not visited counts: the
-            // eight direction-ordered copies (rt_bvh.cpp; 8 x 32 B per node)
-            bool ordered = true;
-#ifdef RT_DEVELOPER_KNOBS
-            if (const char *k = getenv("RT_BVH_ORDERED")) ordered = atoi(k) != 0;
-#endif
-            if (ordered) {
-                if (bvh.ordered.empty()) bvh = rtdev::build_bvh(d->primitives, d->n_primitives, max_leaf > 0 ? max_leaf : 4, true);
-                if ((rc = upload(s->bvh_nodes_ordered, bvh.ordered)) != RT_OK) return rc;
-            }
-        }
-        if ((rc = upload(s->bvh_nodes, bvh.nodes)) != RT_OK) return rc;
-        if (bvh.nodes.size() * sizeof(rtdev::BvhNode) <= 32 * 1024) { // the nodes live in LDS: kept for the per-camera child order (enqueue_render)
-            s->bvh_host.nodes = bvh.nodes;
-            for (int k = 0; k < 3; ++k) s->bvh_host.center[k] = bvh.center[k];
-        }
-        if ((rc = upload(s->bvh_prim_index, bvh.prim_index)) != RT_OK) return rc;
-        s->n_bvh_nodes = (int)bvh.nodes.size() - 1; // the array ends with the sentinel (rt_device_types.h: BvhNode)
-        for (int k = 0; k < 3; ++k) {
-            s->bvh_root_mn[k] = bvh.root_mn[k];
-            s->bvh_root_mx[k] = bvh.root_mx[k];
-            s->bvh_center[k] = bvh.center[k];
-        }
-        // the device table is stored in leaf order, so a leaf is a contiguous run of records
-        std::vector<rtdev::Prim> ordered(prims.size());
-        for (size_t j = 0; j < bvh.prim_index.size(); ++j) ordered[j] = prims[(size_t)bvh.prim_index[j]];
-        prims.swap(ordered);
-        // the compact records the walk tests leaves with; the first MovingSphere sets the scene-wide time interval
-        std::vector<rtdev::LeafGeo> geo(prims.size());
-        bool have_interval = false;
-        for (size_t j = 0; j < prims.size(); ++j) {
-            const rtdev::Prim &q = prims[j];
-            rtdev::LeafGeo &g = geo[j];
-            memset(&g, 0, sizeof g);
-            g.tag = 1;
-            if (q.flags != 0 || (q.kind != RT_PRIM_SPHERE && q.kind != RT_PRIM_MOVING_SPHERE)) continue;
-            if (q.kind == RT_PRIM_MOVING_SPHERE) {
-                // a MovingSphere with time_a == time_b degenerates by itself in the reference (moving_sphere.rs:37-39:
-                // 0/0); its 1 / (time_b - time_a) = inf must not become the scene-wide interval, where it would turn
-                // the centre of every plain Sphere (dc = 0) into inf * 0 = NaN: it keeps the general path (tag 1)
-                if (!std::isfinite(q.rot_cos)) continue;
-                if (!have_interval) {
-                    s->leaf_time_a = q.rot_sin;
-                    s->leaf_inv_dt = q.rot_cos;
-                    have_interval = true;
-                }
-                if (q.rot_sin != s->leaf_time_a || q.rot_cos != s->leaf_inv_dt) continue; // another interval: general path
-                for (int k = 0; k < 3; ++k) g.dc[k] = q.tr[k];
-            }
-            for (int k = 0; k < 3; ++k) g.c0[k] = q.p[k];
-            g.radius2 = q.radius2;
-            g.tag = 0;
-        }
-        if ((rc = upload(s->leaf_geo, geo)) != RT_OK) return rc;
+        if ((rc = upload_bvh(s, choose_bvh(d, s), prims)) != RT_OK) return rc;
+    } else { // the linear-loop variants keep the whole primitive table in LDS
+        if ((size_t)d->n_primitives * sizeof(rtdev::Prim) > 120 * 1024)
+            return fail(RT_ERR_UNSUPPORTED, "RT_HIT_LINEAR: the primitive table does not fit in LDS");
+        group_linear_table(s, prims);
     }
     if ((rc = upload(s->prims, prims)) != RT_OK) return rc;
     if ((rc = upload(s->textures, textures)) != RT_OK) return rc;
@@ -1104,84 +1084,22 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
         s->bg.top[k] = d->background.top[k];
         s->bg.bottom[k] = d->background.bottom[k];
     }
-    s->use_v1 = opt.kernel == RT_KERNEL_V1;
-    RT_HIP(hipDeviceGetAttribute(&s->num_cus, hipDeviceAttributeMultiprocessorCount, device));
-    s->bvh_nodes_in_lds = s->use_bvh && (size_t)(s->n_bvh_nodes + 1) * sizeof(rtdev::BvhNode) <= 32 * 1024;
-#ifdef RT_DEVELOPER_KNOBS
-    if (const char *k = getenv("RT_BVH_LDS")) s->bvh_nodes_in_lds = s->bvh_nodes_in_lds && atoi(k) != 0;
-#endif
-    // dynamic LDS of the variant (rt_device_types.h: pool_lds_layout) without and with the lens samples, and its static LDS:
-    // what enqueue_render checks against the CU's LDS before a launch.  The v1 kernel has no dynamic LDS.
-    if (!s->use_v1) {
-        auto dyn_lds = [&](bool lens) {
-            return rtdev::pool_lds_layout(s->use_bvh, s->textured, s->n_prims, s->n_textures, s->bvh_nodes_in_lds ? s->n_bvh_nodes + 1 : 0,
-                                          s->n_perlins > 0 && s->perlin_identity, lens, s->has_moving).bytes;
-        };
-        s->pool_dyn_lds = dyn_lds(false);
-        s->pool_dyn_lds_lens = dyn_lds(true);
-        s->pool_static_lds = (s->exact ? rtdev_pool_static_lds_exact : rtdev_pool_static_lds)(s->prims_class, s->textured, s->specular, s->use_bvh);
-        if (s->pool_static_lds < 0) return fail(RT_ERR_HIP, "hipFuncGetAttributes of the trace kernel failed");
-        s->pool_blocks_per_cu = (s->exact ? rtdev_pool_blocks_per_cu_exact : rtdev_pool_blocks_per_cu)(s->prims_class, s->textured, s->specular, s->use_bvh,
-                                                                                                     s->pool_dyn_lds);
-        s->pool_blocks_per_cu_lens = (s->exact ? rtdev_pool_blocks_per_cu_exact : rtdev_pool_blocks_per_cu)(s->prims_class, s->textured, s->specular,
-                                                                                                          s->use_bvh, s->pool_dyn_lds_lens);
-    }
-#ifdef RT_DEVELOPER_KNOBS // occupancy experiments
-    if (const char *k = getenv("RT_POOL_BLOCKS_PER_CU"))
-        if (atoi(k) > 0) s->pool_blocks_per_cu = s->pool_blocks_per_cu_lens = atoi(k);
-#endif
-    if (!render_cache_take(s)) { // nothing of this device's to take over: the first scene, or more than the cache holds
-        RT_HIP(s->segments.alloc(rtdev::RT_STAT_SLOTS)); // rt_device_types.h: RT_STAT_*
-        RT_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&s->ev_begin));
-        RT_HIP(hipEventCreate(&s->ev_traced));
-        RT_HIP(hipEventCreate(&s->ev_resolved));
-        RT_HIP(hipHostMalloc((void **)&s->host_flags, (rtdev::RT_MAX_REGIONS + 1) * sizeof(unsigned int),
-                             hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
-        memset(s->host_flags, 0, (rtdev::RT_MAX_REGIONS + 1) * sizeof(unsigned int));
-        RT_HIP(hipStreamCreateWithFlags(&s->stream_ctl, hipStreamNonBlocking));
-    }
-    RT_HIP(hipMemsetAsync(s->segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), s->stream));
-    guard.s = nullptr;
-    *out = s;
+    if ((rc = size_pool(s)) != RT_OK) return rc;
+    if ((rc = acquire_render_buffers(s)) != RT_OK) return rc;
+    *out = half_built.release();
     return RT_OK;
 }
-} // namespace
 
-int rt_scene_create_ex(const RtSceneDesc *d, int device, const RtSceneOptions *options, RtScene **out) {
-    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
-    *out = nullptr;
-    try { // nothing may unwind through the C ABI (std::vector / std::string / the BVH build allocate)
-        return scene_create(d, device, options, out);
-    } catch (const std::bad_alloc &) {
-        return fail(RT_ERR_OUT_OF_MEMORY, "host allocation failed while building the scene");
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string("scene build failed: ") + e.what());
-    }
-}
-
-int rt_render_frame_device(RtScene *s, const RtCamera *camera, const RtRenderParams *p, double *out_dev,
-                           void *hip_stream) {
-    try { // nothing may unwind through the C ABI (the error messages are std::strings)
-        if (!s || !out_dev) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out is NULL");
-        int rc = check_params(camera, p);
-        if (rc != RT_OK) return rc;
-        return enqueue_render(s, camera, p, out_dev, (hipStream_t)hip_stream, 0, Cancel());
-    } catch (...) {
-        return RT_ERR_OUT_OF_MEMORY;
-    }
-}
-
-int rt_post_rgba8_device(RtScene *s, const RtToneMap *tm, const double *rgb_device, size_t n_pixels,
-                         uint8_t *rgba_device, double *mapped_device, void *hip_stream) {
+// ------------------------------------------------------------------------------------------ device-output entry points
+int post_rgba8(RtScene *s, const RtToneMap *tm, const double *rgb_device, size_t n_pixels, uint8_t *rgba_device,
+               double *mapped_device, hipStream_t stream) {
     if (!s || !tm || !rgb_device || !rgba_device) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
     if (tm->kind < RT_TM_NONE || tm->kind > RT_TM_ACES) return fail(RT_ERR_INVALID_ARGUMENT, "unknown tone map kind");
     RT_HIP(hipSetDevice(s->device));
-    RT_HIP(rtdev_launch_post_rgba8(tm, rgb_device, n_pixels, rgba_device, mapped_device, (hipStream_t)hip_stream));
+    RT_HIP(rtdev_launch_post_rgba8(tm, rgb_device, n_pixels, rgba_device, mapped_device, stream));
     return RT_OK;
 }
 
-namespace {
 int render_frame_rgba8(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtToneMap *tm, uint8_t *out_rgba) {
     if (!s || !tm || !out_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "scene/tone_map/out is NULL");
     int rc = check_params(camera, p);
@@ -1189,90 +1107,30 @@ int render_frame_rgba8(RtScene *s, const RtCamera *camera, const RtRenderParams 
     if (p->strip_count > 1) // the packed frame is a whole picture; gather strips with rt_render_frame_device, then rt_post_rgba8_device
         return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_frame_rgba8 packs the whole frame: strip ownership is not supported here");
     RT_HIP(hipSetDevice(s->device));
+    rtapi::RenderBuffers &b = s->buf;
     const size_t px = (size_t)p->width * (size_t)p->height;
-    if (s->frame.count < px * 3) RT_HIP(s->frame.alloc(px * 3));
-    if (s->rgba.count < px * 4) RT_HIP(s->rgba.alloc(px * 4));
-    rc = enqueue_render(s, camera, p, s->frame.ptr, s->stream, 0, Cancel());
+    if (b.frame.count < px * 3) RT_HIP(b.frame.alloc(px * 3));
+    if (b.rgba.count < px * 4) RT_HIP(b.rgba.alloc(px * 4));
+    rc = enqueue_render(s, camera, p, b.frame.ptr, b.stream, 0, Cancel());
     if (rc != RT_OK) return rc;
-    rc = rt_post_rgba8_device(s, tm, s->frame.ptr, px, s->rgba.ptr, nullptr, s->stream);
+    rc = post_rgba8(s, tm, b.frame.ptr, px, b.rgba.ptr, nullptr, b.stream);
     if (rc != RT_OK) return rc;
-    RT_HIP(hipStreamSynchronize(s->stream));
-    RT_HIP(hipMemcpy(out_rgba, s->rgba.ptr, px * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-} // namespace
-
-int rt_render_frame_rgba8(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtToneMap *tm,
-                          uint8_t *out_rgba) {
-    try { // nothing may unwind through the C ABI (the error messages are std::strings)
-        return render_frame_rgba8(s, camera, p, tm, out_rgba);
-    } catch (...) {
-        return RT_ERR_OUT_OF_MEMORY;
-    }
-}
-
-int rtdev_scene_classify(const RtSceneDesc *d, int32_t out[4]) {
-    if (!out) return RT_ERR_INVALID_ARGUMENT;
-    try { // (validate_desc's messages are std::strings)
-        int rc = validate_desc(d);
-        if (rc != RT_OK) return rc;
-        const Selection sel = select_variant(d);
-        out[0] = sel.prims_class;
-        out[1] = sel.textured;
-        out[2] = sel.specular;
-        out[3] = sel.has_moving;
-        return RT_OK;
-    } catch (...) {
-        return RT_ERR_OUT_OF_MEMORY;
-    }
-}
-
-int rtdev_scene_radiance_bound(const RtSceneDesc *d, double *bound) {
-    if (!bound) return RT_ERR_INVALID_ARGUMENT;
-    try {
-        int rc = validate_desc(d);
-        if (rc != RT_OK) return rc;
-        *bound = scene_radiance_bound(d);
-        return RT_OK;
-    } catch (...) {
-        return RT_ERR_OUT_OF_MEMORY;
-    }
-}
-
-int rtdev_sum_exponent(double bound, int32_t samples, int32_t *e) {
-    if (!e) return RT_ERR_INVALID_ARGUMENT;
-    try { // (chunk_plan allocates, fail's messages are std::strings)
-        int k = 0;
-        const int rc = sum_exponent(bound, samples, &k);
-        *e = k;
-        return rc;
-    } catch (...) {
-        return RT_ERR_OUT_OF_MEMORY;
-    }
-}
-
-int rtdev_scene_variant(const RtScene *s, int32_t *out, int32_t n_out) {
-    if (!s || (!out && n_out > 0) || n_out < 0) return RT_ERR_INVALID_ARGUMENT; // (no message: nothing here may allocate)
-    const int32_t v[RTDEV_VARIANT_FIELDS] = {
-        s->use_v1 ? 1 : 0, s->prims_class, s->textured, s->specular, s->use_bvh, s->exact ? 1 : 0, s->bvh_nodes_in_lds ? 1 : 0,
-        s->has_moving, (s->textured && s->n_perlins > 0 && s->perlin_identity) ? 1 : 0,
-        s->use_v1 ? 0 : s->pool_static_lds, s->use_v1 ? 0 : (int32_t)s->pool_dyn_lds, s->use_v1 ? 0 : (int32_t)s->pool_dyn_lds_lens,
-        s->pool_blocks_per_cu, s->pool_blocks_per_cu_lens};
-    for (int32_t k = 0; k < n_out && k < RTDEV_VARIANT_FIELDS; ++k) out[k] = v[k];
+    RT_HIP(hipStreamSynchronize(b.stream));
+    RT_HIP(hipMemcpy(out_rgba, b.rgba.ptr, px * 4, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
-int rt_scene_last_stats(RtScene *s, RtRenderStats *out) {
+int last_stats(RtScene *s, RtRenderStats *out) {
     if (!s || !out) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out is NULL");
     memset(out, 0, sizeof *out);
     if (!s->has_stats) return RT_OK;
     RT_HIP(hipSetDevice(s->device));
-    RT_HIP(hipEventSynchronize(s->ev_resolved));
+    RT_HIP(hipEventSynchronize(s->buf.ev_resolved));
     float ms_trace = 0.f, ms_resolve = 0.f;
-    RT_HIP(hipEventElapsedTime(&ms_trace, s->ev_begin, s->ev_traced));
-    RT_HIP(hipEventElapsedTime(&ms_resolve, s->ev_traced, s->ev_resolved));
+    RT_HIP(hipEventElapsedTime(&ms_trace, s->buf.ev_begin, s->buf.ev_traced));
+    RT_HIP(hipEventElapsedTime(&ms_resolve, s->buf.ev_traced, s->buf.ev_resolved));
     unsigned long long counters[rtdev::RT_STAT_SLOTS]; // rt_device_types.h: RT_STAT_*
-    RT_HIP(hipMemcpy(counters, s->segments.ptr, sizeof counters, hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(counters, s->buf.segments.ptr, sizeof counters, hipMemcpyDeviceToHost));
     const unsigned long long segs = counters[rtdev::RT_STAT_SEGMENTS];
 #ifdef RT_PROFILE_REGIONS
     {
@@ -1318,6 +1176,172 @@ int rt_scene_last_stats(RtScene *s, RtRenderStats *out) {
     out->resolve_ms = ms_resolve;
     out->kernel_launches = s->last_launches;
     return RT_OK;
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------------- C entry points
+// Every one that returns a status runs its body through rtapi::guarded; the others cannot throw.
+extern "C" {
+
+int rt_abi_version(void) { return RT_ABI_VERSION; }
+
+int rt_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+const char *rt_last_error_message(void) { return g_last_error; }
+
+const char *rt_strerror(int code) {
+    switch (code) {
+    case RT_OK: return "Ok";
+    case RT_ERR_FAILED_TO_CREATE_WINDOW: return "Failed to create window";
+    case RT_ERR_FAILED_TO_UPDATE_WINDOW: return "Failed to update window";
+    case RT_ERR_CONFIGURATION: return "Config Error";
+    case RT_ERR_UNKNOWN_MATERIAL: return "Unknown Material";
+    case RT_ERR_FAILED_TO_ACQUIRE_LOCK: return "Failed to acquire lock";
+    case RT_ERR_EXIT_EVENT: return "Exit event";
+    case RT_ERR_CANCEL_EVENT: return "Cancel event";
+    case RT_ERR_IMAGE_SAVE: return "Image save error";
+    case RT_ERR_SCENE_LOAD: return "Scene failed to load";
+    case RT_ERR_ARGUMENT_PARSING: return "Argument parsing Error";
+    case RT_ERR_KEY: return "Key callback failed";
+    case RT_ERR_CREATE_LOG: return "Failed to create log";
+    case RT_ERR_RECEIVE: return "Failed to recieve data";
+    case RT_ERR_SEND: return "Failed to send data";
+    case RT_ERR_ACTION_PROTOCOL: return "Action protocol error";
+    case RT_ERR_BUS_WRITE: return "Failed to write data to bus";
+    case RT_ERR_BUS_READ: return "Failed to read data from bus";
+    case RT_ERR_BUS_UPDATE: return "Failed to update databus";
+    case RT_ERR_BUS_TIMEOUT: return "Bus timeout error";
+    case RT_ERR_NO_OBJECT_WITH_ID: return "No object with id";
+    case RT_ERR_FAILED_TO_OPEN_IMAGE: return "Failed to open image";
+    case RT_ERR_FAILED_TO_PARSE: return "Failed to parse into a vector";
+    case RT_ERR_NO_DEVICE: return "No usable HIP device";
+    case RT_ERR_HIP: return "HIP runtime error";
+    case RT_ERR_INVALID_ARGUMENT: return "Invalid argument";
+    case RT_ERR_UNSUPPORTED: return "Unsupported scene feature";
+    case RT_ERR_OUT_OF_MEMORY: return "Out of memory";
+    default: return "Unknown error";
+    }
+}
+
+void rt_scene_destroy(RtScene *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    if (s->buf.stream) (void)hipStreamSynchronize(s->buf.stream);
+    if (s->buf.stream_ctl) (void)hipStreamSynchronize(s->buf.stream_ctl);
+    for (uint8_t *p : s->image_pixels)
+        if (p) (void)hipFree(p);
+    s->prims.release();
+    s->textures.release();
+    s->images.release();
+    s->perlins.release();
+    s->bvh_nodes.release();
+    s->bvh_nodes_ordered.release();
+    s->bvh_prim_index.release();
+    s->leaf_geo.release();
+    // what a render allocates — slices, frames, pinned memory, counters, streams, events — outlives the scene: the
+    // reference rebuilds its scene on every object event (main.rs:174-189), and the next rt_scene_create on this
+    // device takes these over instead of paying hipMalloc / hipHostMalloc again (render_cache_put); should the cache
+    // throw, they are freed here
+    if (rtapi::guarded("rt_scene_destroy", [&] { render_cache_put(s); return RT_OK; }) != RT_OK) s->buf.free_all(s->device);
+    delete s;
+}
+
+void rt_release_cached_buffers(void) {
+    (void)rtapi::guarded("rt_release_cached_buffers", [] {
+        std::vector<CachedSet> all;
+        {
+            std::lock_guard<std::mutex> lock(g_cache_mutex);
+            all.swap(g_cache);
+        }
+        for (CachedSet &c : all) c.buf.free_all(c.device);
+        return RT_OK;
+    });
+}
+
+int rt_scene_create(const RtSceneDesc *d, int device, RtScene **out) {
+    return rtapi::guarded("rt_scene_create", [&] { return scene_create(d, device, nullptr, out); });
+}
+
+int rt_scene_create_ex(const RtSceneDesc *d, int device, const RtSceneOptions *options, RtScene **out) {
+    return rtapi::guarded("rt_scene_create_ex", [&] { return scene_create(d, device, options, out); });
+}
+
+int rt_render_frame_device(RtScene *s, const RtCamera *camera, const RtRenderParams *p, double *out_dev,
+                           void *hip_stream) {
+    return rtapi::guarded("rt_render_frame_device", [&] {
+        if (!s || !out_dev) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out is NULL");
+        int rc = check_params(camera, p);
+        if (rc != RT_OK) return rc;
+        return enqueue_render(s, camera, p, out_dev, (hipStream_t)hip_stream, 0, Cancel());
+    });
+}
+
+int rt_post_rgba8_device(RtScene *s, const RtToneMap *tm, const double *rgb_device, size_t n_pixels,
+                         uint8_t *rgba_device, double *mapped_device, void *hip_stream) {
+    return rtapi::guarded("rt_post_rgba8_device", [&] {
+        return post_rgba8(s, tm, rgb_device, n_pixels, rgba_device, mapped_device, (hipStream_t)hip_stream);
+    });
+}
+
+int rt_render_frame_rgba8(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtToneMap *tm,
+                          uint8_t *out_rgba) {
+    return rtapi::guarded("rt_render_frame_rgba8", [&] { return render_frame_rgba8(s, camera, p, tm, out_rgba); });
+}
+
+int rt_scene_last_stats(RtScene *s, RtRenderStats *out) {
+    return rtapi::guarded("rt_scene_last_stats", [&] { return last_stats(s, out); });
+}
+
+int rtdev_scene_classify(const RtSceneDesc *d, int32_t out[4]) {
+    return rtapi::guarded("rtdev_scene_classify", [&]() -> int {
+        if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+        int rc = validate_desc(d);
+        if (rc != RT_OK) return rc;
+        const Selection sel = select_variant(d);
+        out[0] = sel.prims_class;
+        out[1] = sel.textured;
+        out[2] = sel.specular;
+        out[3] = sel.has_moving;
+        return RT_OK;
+    });
+}
+
+int rtdev_scene_radiance_bound(const RtSceneDesc *d, double *bound) {
+    return rtapi::guarded("rtdev_scene_radiance_bound", [&]() -> int {
+        if (!bound) return fail(RT_ERR_INVALID_ARGUMENT, "bound is NULL");
+        int rc = validate_desc(d);
+        if (rc != RT_OK) return rc;
+        *bound = scene_radiance_bound(d);
+        return RT_OK;
+    });
+}
+
+int rtdev_sum_exponent(double bound, int32_t samples, int32_t *e) {
+    return rtapi::guarded("rtdev_sum_exponent", [&] {
+        if (!e) return fail(RT_ERR_INVALID_ARGUMENT, "e is NULL");
+        int k = 0;
+        const int rc = sum_exponent(bound, samples, &k);
+        *e = k;
+        return rc;
+    });
+}
+
+int rtdev_scene_variant(const RtScene *s, int32_t *out, int32_t n_out) {
+    return rtapi::guarded("rtdev_scene_variant", [&]() -> int {
+        if (!s || (!out && n_out > 0) || n_out < 0) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out is NULL or n_out is negative");
+        const int32_t v[RTDEV_VARIANT_FIELDS] = {
+            s->use_v1 ? 1 : 0, s->prims_class, s->textured, s->specular, s->use_bvh, s->exact ? 1 : 0, s->bvh_nodes_in_lds ? 1 : 0,
+            s->has_moving, (s->textured && s->n_perlins > 0 && s->perlin_identity) ? 1 : 0,
+            s->use_v1 ? 0 : s->pool_static_lds, s->use_v1 ? 0 : (int32_t)s->pool_dyn_lds, s->use_v1 ? 0 : (int32_t)s->pool_dyn_lds_lens,
+            s->pool_blocks_per_cu, s->pool_blocks_per_cu_lens};
+        for (int32_t k = 0; k < n_out && k < RTDEV_VARIANT_FIELDS; ++k) out[k] = v[k];
+        return RT_OK;
+    });
 }
 
 } // extern "C"

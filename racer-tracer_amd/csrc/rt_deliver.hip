@@ -45,21 +45,21 @@ struct Share {
 
 // Pinned frame + flags of the call live on shares[0]'s scene.
 int ensure_host_frame(RtScene *s, size_t doubles) {
-    if (s->host_frame_count >= doubles) return RT_OK;
+    if (s->buf.host_frame_count >= doubles) return RT_OK;
     RT_HIP(hipSetDevice(s->device));
-    if (s->host_frame) (void)hipHostFree(s->host_frame);
-    s->host_frame = nullptr;
-    s->host_frame_count = 0;
-    RT_HIP(hipHostMalloc((void **)&s->host_frame, doubles * sizeof(double),
+    if (s->buf.host_frame) (void)hipHostFree(s->buf.host_frame);
+    s->buf.host_frame = nullptr;
+    s->buf.host_frame_count = 0;
+    RT_HIP(hipHostMalloc((void **)&s->buf.host_frame, doubles * sizeof(double),
                          hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
-    s->host_frame_count = doubles;
+    s->buf.host_frame_count = doubles;
     return RT_OK;
 }
 
 // Blocks until region `r` of `sh` has been published.  RT_ERR_CANCEL_EVENT when the hook is raised first.
 int wait_region(Share &sh, int r, const Cancel &cancel) {
     RtScene *s = sh.scene;
-    const volatile unsigned int *flags = s->host_flags;
+    const volatile unsigned int *flags = s->buf.host_flags;
     const uint32_t serial = sh.delivery.serial;
     for (unsigned spins = 1;; ++spins) {
         if (flags[r] == serial) {
@@ -69,7 +69,7 @@ int wait_region(Share &sh, int r, const Cancel &cancel) {
         if (cancel.raised()) return RT_ERR_CANCEL_EVENT;
         if ((spins & 127u) == 0) { // has the launch ended (or failed) without publishing?
             (void)hipSetDevice(s->device);
-            const hipError_t e = hipEventQuery(s->ev_traced);
+            const hipError_t e = hipEventQuery(s->buf.ev_traced);
             if (e == hipSuccess) {
                 if (flags[r] == serial) continue;
                 return fail(RT_ERR_HIP, "the launch ended without publishing region " + std::to_string(r));
@@ -89,8 +89,8 @@ void abort_shares(std::vector<Share> &shares) {
     for (Share &sh : shares)
         if (sh.launched) {
             (void)hipSetDevice(sh.scene->device);
-            (void)hipStreamSynchronize(sh.scene->stream_ctl);
-            (void)hipStreamSynchronize(sh.scene->stream);
+            (void)hipStreamSynchronize(sh.scene->buf.stream_ctl);
+            (void)hipStreamSynchronize(sh.scene->buf.stream);
         }
     (void)hipGetLastError();
 }
@@ -99,43 +99,26 @@ int finish_shares(std::vector<Share> &shares) {
     int rc = RT_OK;
     for (Share &sh : shares) {
         if (!sh.launched) continue;
-        if (hipSetDevice(sh.scene->device) != hipSuccess || hipStreamSynchronize(sh.scene->stream) != hipSuccess) {
+        if (hipSetDevice(sh.scene->device) != hipSuccess || hipStreamSynchronize(sh.scene->buf.stream) != hipSuccess) {
             if (rc == RT_OK) rc = fail(RT_ERR_HIP, "stream synchronisation failed");
         } else {
-            sh.scene->deliver_dirty = false; // every region was published: the counters are back at zero
+            sh.scene->buf.deliver_dirty = false; // every region was published: the counters are back at zero
         }
     }
     return rc;
 }
 
-int check_scenes(RtScene *const *scenes, int n) {
-    if (!scenes || n <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "no scenes");
-    for (int i = 0; i < n; ++i)
-        if (!scenes[i]) return fail(RT_ERR_INVALID_ARGUMENT, "scenes[" + std::to_string(i) + "] is NULL");
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < i; ++j)
-            if (scenes[i] == scenes[j]) return fail(RT_ERR_INVALID_ARGUMENT, "the same RtScene is listed twice (create one per share)");
-    return RT_OK;
-}
-
 // shares[i].params: the caller's parameters for one scene, strips dealt out for several
 int make_shares(RtScene *const *scenes, int n, const RtRenderParams *p, int strip_rows, std::vector<Share> &shares) {
+    std::vector<RtRenderParams> params(1, *p);
     if (n > 1) {
-        if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "params->strip_* must be unset: the call assigns strips itself");
-        if (p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "the preview scale cannot be combined with strips");
-        if (strip_rows < 0) return fail(RT_ERR_INVALID_ARGUMENT, "strip_rows must not be negative");
-        if (strip_rows == 0) strip_rows = 8;
+        const int rc = rtapi::deal_strips(p, n, strip_rows, params);
+        if (rc != RT_OK) return rc;
     }
     shares.assign((size_t)n, Share());
     for (int i = 0; i < n; ++i) {
-        Share &sh = shares[(size_t)i];
-        sh.scene = scenes[i];
-        sh.params = *p;
-        if (n > 1) {
-            sh.params.strip_rows = strip_rows;
-            sh.params.strip_count = n;
-            sh.params.strip_index = i;
-        }
+        shares[(size_t)i].scene = scenes[i];
+        shares[(size_t)i].params = params[(size_t)i];
     }
     return RT_OK;
 }
@@ -152,9 +135,9 @@ int launch_shares(std::vector<Share> &shares, const RtCamera *camera, bool cance
         // strip lies below the image) has nothing to launch and nothing to wait for: it counts as published, and the
         // rows of the frame stay as they are — what the two-pass path does with n_items == 0.
         if (sh.delivery.regions.empty()) continue;
-        sh.delivery.serial = ++sh.scene->deliver_serial;
-        if (sh.delivery.serial == 0) sh.delivery.serial = ++sh.scene->deliver_serial; // 0 is the flags' idle value
-        const int rc = rtapi::enqueue_render(sh.scene, camera, &sh.params, nullptr, sh.scene->stream, 0, Cancel(), &sh.delivery);
+        sh.delivery.serial = ++sh.scene->buf.deliver_serial;
+        if (sh.delivery.serial == 0) sh.delivery.serial = ++sh.scene->buf.deliver_serial; // 0 is the flags' idle value
+        const int rc = rtapi::enqueue_render(sh.scene, camera, &sh.params, nullptr, sh.scene->buf.stream, 0, Cancel(), &sh.delivery);
         if (rc != RT_OK) return rc;
         sh.launched = true;
     }
@@ -196,7 +179,7 @@ int deliver_frame(RtScene *const *scenes, int n, const RtCamera *camera, const R
             reg.nty = (int)((long long)tile_rows * (b + 1) / bands) - reg.ty0;
             if (reg.nty > 0) sh.delivery.regions.push_back(reg);
         }
-        sh.delivery.out = scenes[0]->host_frame;
+        sh.delivery.out = scenes[0]->buf.host_frame;
         sh.delivery.col_step = p->width;
         sh.delivery.cols = 1;
         most_bands = (int)sh.delivery.regions.size() > most_bands ? (int)sh.delivery.regions.size() : most_bands;
@@ -217,7 +200,7 @@ int deliver_frame(RtScene *const *scenes, int n, const RtCamera *camera, const R
                 while (vr + run < vr_end && rtapi::owned_row_to_image_row(&sh.params, vr + run) == row + run) ++run;
                 if (row < p->height) {
                     const int rows = row + run <= p->height ? run : p->height - row;
-                    memcpy(out_rgb + (size_t)row * row_doubles, scenes[0]->host_frame + (size_t)row * row_doubles,
+                    memcpy(out_rgb + (size_t)row * row_doubles, scenes[0]->buf.host_frame + (size_t)row * row_doubles,
                            (size_t)rows * row_doubles * sizeof(double));
                 }
                 vr += run;
@@ -242,7 +225,7 @@ int deliver_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const R
     auto column_w = [&](int ws) { return ws == p->tiles_w - 1 ? p->width - width_step * ws : width_step; };
     rc = ensure_host_frame(scenes[0], (size_t)p->width * (size_t)p->height * 3);
     if (rc != RT_OK) return rc;
-    const double *frame = scenes[0]->host_frame;
+    const double *frame = scenes[0]->buf.host_frame;
     // One callback per tile of tile column `ws`, top to bottom.  The pinned frame holds column ws as
     // [height][w][3] behind the columns before it, so a tile is a contiguous run of it.
     auto emit_column = [&](int ws) {
@@ -294,7 +277,7 @@ int deliver_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const R
         const int tile_rows = (rtapi::owned_rows_of(&sh.params) + 7) / 8;
         if (tile_rows > 0) sh.delivery.regions = regions; // (none: the share owns no rows and is not launched)
         for (rtdev::Region &reg : sh.delivery.regions) reg.nty = tile_rows;
-        sh.delivery.out = scenes[0]->host_frame;
+        sh.delivery.out = scenes[0]->buf.host_frame;
         sh.delivery.col_step = width_step;
         sh.delivery.cols = p->tiles_w;
     }
@@ -332,7 +315,7 @@ int deliver_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const R
 int tiles_from_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p, RtTileCallback callback, void *user,
                      const Cancel &cancel) {
     const size_t n = (size_t)p->width * (size_t)p->height * 3;
-    if (s->frame.count < n) RT_HIP(s->frame.alloc(n));
+    if (s->buf.frame.count < n) RT_HIP(s->buf.frame.alloc(n));
     int rc = ensure_host_frame(s, n);
     if (rc != RT_OK) return rc;
     int batch = 0;
@@ -343,40 +326,40 @@ int tiles_from_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p
     }
     const int width_step = p->width / p->tiles_w, height_step = p->height / p->tiles_h;
     const bool column_layout = !s->use_v1 && width_step > 0 && p->tiles_w > 1; // written by the resolve pass itself
-    rc = rtapi::enqueue_render(s, camera, p, s->frame.ptr, s->stream, batch, cancel, nullptr, column_layout ? width_step : 0,
+    rc = rtapi::enqueue_render(s, camera, p, s->buf.frame.ptr, s->buf.stream, batch, cancel, nullptr, column_layout ? width_step : 0,
                                column_layout ? p->tiles_w : 1);
-    hipEvent_t copied = s->ev_resolved; // re-recorded behind the copy: rt_scene_last_stats reads ev_traced -> ev_resolved (+ the copy)
+    hipEvent_t copied = s->buf.ev_resolved; // re-recorded behind the copy: rt_scene_last_stats reads ev_traced -> ev_resolved (+ the copy)
     if (rc == RT_OK) {
-        hipError_t e = hipMemcpyAsync(s->host_frame, s->frame.ptr, n * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-        if (e == hipSuccess) e = hipEventRecord(copied, s->stream);
+        hipError_t e = hipMemcpyAsync(s->buf.host_frame, s->buf.frame.ptr, n * sizeof(double), hipMemcpyDeviceToHost, s->buf.stream);
+        if (e == hipSuccess) e = hipEventRecord(copied, s->buf.stream);
         if (e != hipSuccess) { // the kernels are in flight on the scene's buffers: drain before the error goes up
-            (void)hipStreamSynchronize(s->stream);
+            (void)hipStreamSynchronize(s->buf.stream);
             return fail(RT_ERR_HIP, std::string("tiles_from_frame: ") + hipGetErrorString(e));
         }
     }
     if (rc == RT_OK) rc = rtapi::wait_event(copied, cancel);
     if (rc == RT_ERR_CANCEL_EVENT) { // cpu.rs:55-62: return Ok, no tile written
         rc = s->use_v1 ? RT_OK : rtapi::poison_queue(s);
-        (void)hipStreamSynchronize(s->stream);
+        (void)hipStreamSynchronize(s->buf.stream);
         return rc;
     }
     if (rc != RT_OK) {
-        (void)hipStreamSynchronize(s->stream);
+        (void)hipStreamSynchronize(s->buf.stream);
         return rc;
     }
-    RT_HIP(hipStreamSynchronize(s->stream));
+    RT_HIP(hipStreamSynchronize(s->buf.stream));
     std::vector<double> column; // v1 / single-column grids: one column of the plain frame, repacked
     for (int ws = 0; ws < p->tiles_w; ++ws) {
         const int x = width_step * ws, w = ws == p->tiles_w - 1 ? p->width - x : width_step;
         const double *col;
         if (column_layout) {
-            col = s->host_frame + (size_t)p->height * (size_t)x * 3;
+            col = s->buf.host_frame + (size_t)p->height * (size_t)x * 3;
         } else if (w == p->width || w <= 0) {
-            col = s->host_frame; // (w == 0: an empty tile column — more tile columns than pixels — reads nothing)
+            col = s->buf.host_frame; // (w == 0: an empty tile column — more tile columns than pixels — reads nothing)
         } else {
             column.resize((size_t)w * (size_t)p->height * 3);
             for (int r = 0; r < p->height; ++r)
-                memcpy(&column[(size_t)r * w * 3], s->host_frame + ((size_t)r * p->width + x) * 3, (size_t)w * 3 * sizeof(double));
+                memcpy(&column[(size_t)r * w * 3], s->buf.host_frame + ((size_t)r * p->width + x) * 3, (size_t)w * 3 * sizeof(double));
             col = column.data();
         }
         for (int hs = 0; hs < p->tiles_h; ++hs) {
@@ -389,9 +372,30 @@ int tiles_from_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p
     return RT_OK;
 }
 
+// rt_render_frame where the delivering launch does not apply (the v1 kernel, the preview scale): resolve kernel + one copy
+int frame_two_pass(RtScene *s, const RtCamera *camera, const RtRenderParams *p, double *out_rgb) {
+    const size_t n = (size_t)p->width * (size_t)p->height * 3;
+    if (s->buf.frame.count < n) RT_HIP(s->buf.frame.alloc(n));
+    int rc = rtapi::enqueue_render(s, camera, p, s->buf.frame.ptr, s->buf.stream, 0, Cancel());
+    if (rc != RT_OK) {
+        (void)hipStreamSynchronize(s->buf.stream);
+        return rc;
+    }
+    RT_HIP(hipStreamSynchronize(s->buf.stream));
+    if (p->strip_count > 1) { // the owned rows only; the rest of out_rgb stays untouched
+        const size_t row_bytes = (size_t)p->width * 3 * sizeof(double);
+        for (int r = 0; r < p->height; ++r)
+            if ((r / p->strip_rows) % p->strip_count == p->strip_index)
+                RT_HIP(hipMemcpy(out_rgb + (size_t)r * p->width * 3, s->buf.frame.ptr + (size_t)r * p->width * 3, row_bytes, hipMemcpyDeviceToHost));
+    } else {
+        RT_HIP(hipMemcpy(out_rgb, s->buf.frame.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return RT_OK;
+}
+
 int render_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p, int strip_rows,
                  RtTileCallback callback, void *user, const Cancel &cancel) {
-    int rc = check_scenes(scenes, n);
+    int rc = rtapi::check_scenes(scenes, n);
     if (rc != RT_OK) return rc;
     if (!callback) return fail(RT_ERR_INVALID_ARGUMENT, "callback is NULL");
     rc = rtapi::check_params(camera, p);
@@ -408,45 +412,42 @@ int render_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const Rt
     return tiles_from_frame(scenes[0], camera, p, callback, user, cancel);
 }
 
-template <class F> int guarded(const char *what, F f) { // nothing may unwind through the C ABI
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(RT_ERR_OUT_OF_MEMORY, std::string(what) + ": host allocation failed");
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(what) + ": " + e.what());
-    }
+} // namespace
+
+int rtapi::check_scenes(RtScene *const *scenes, int n) {
+    if (!scenes || n <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "no scenes");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(RT_ERR_INVALID_ARGUMENT, "scenes[" + std::to_string(i) + "] is NULL");
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            if (scenes[i] == scenes[j]) return fail(RT_ERR_INVALID_ARGUMENT, "the same RtScene is listed twice (create one per share)");
+    return RT_OK;
 }
 
-} // namespace
+int rtapi::deal_strips(const RtRenderParams *p, int n, int &strip_rows, std::vector<RtRenderParams> &params) {
+    if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "params->strip_* must be unset: the call assigns strips itself");
+    if (p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "the preview scale cannot be combined with strips");
+    if (strip_rows < 0) return fail(RT_ERR_INVALID_ARGUMENT, "strip_rows must not be negative");
+    if (strip_rows == 0) strip_rows = 8;
+    params.assign((size_t)n, *p);
+    if (n > 1)
+        for (int i = 0; i < n; ++i) {
+            params[(size_t)i].strip_rows = strip_rows;
+            params[(size_t)i].strip_count = n;
+            params[(size_t)i].strip_index = i;
+        }
+    return RT_OK;
+}
 
 extern "C" {
 
 int rt_render_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p, double *out_rgb) {
-    if (!s || !out_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out is NULL");
-    int rc = rtapi::check_params(camera, p);
-    if (rc != RT_OK) return rc;
-    return guarded("rt_render_frame", [&]() -> int {
+    return rtapi::guarded("rt_render_frame", [&] {
+        if (!s || !out_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out is NULL");
+        int rc = rtapi::check_params(camera, p);
+        if (rc != RT_OK) return rc;
         RT_HIP(hipSetDevice(s->device));
-        if (s->use_v1 || p->scale > 1) { // two-pass path: resolve kernel + one copy
-            const size_t n = (size_t)p->width * (size_t)p->height * 3;
-            if (s->frame.count < n) RT_HIP(s->frame.alloc(n));
-            int rc2 = rtapi::enqueue_render(s, camera, p, s->frame.ptr, s->stream, 0, Cancel());
-            if (rc2 != RT_OK) {
-                (void)hipStreamSynchronize(s->stream);
-                return rc2;
-            }
-            RT_HIP(hipStreamSynchronize(s->stream));
-            if (p->strip_count > 1) { // the owned rows only; the rest of out_rgb stays untouched
-                const size_t row_bytes = (size_t)p->width * 3 * sizeof(double);
-                for (int r = 0; r < p->height; ++r)
-                    if ((r / p->strip_rows) % p->strip_count == p->strip_index)
-                        RT_HIP(hipMemcpy(out_rgb + (size_t)r * p->width * 3, s->frame.ptr + (size_t)r * p->width * 3, row_bytes, hipMemcpyDeviceToHost));
-            } else {
-                RT_HIP(hipMemcpy(out_rgb, s->frame.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
-            }
-            return RT_OK;
-        }
+        if (s->use_v1 || p->scale > 1) return frame_two_pass(s, camera, p, out_rgb);
         RtScene *scenes[1] = {s};
         return deliver_frame(scenes, 1, camera, p, 0, out_rgb);
     });
@@ -454,41 +455,37 @@ int rt_render_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p,
 
 int rt_render_frame_multi(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *params,
                           int strip_rows, double *out_rgb) {
-    int rc = check_scenes(scenes, n_scenes);
-    if (rc != RT_OK) return rc;
-    if (!out_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
-    rc = rtapi::check_params(camera, params);
-    if (rc != RT_OK) return rc;
-    if (params->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "params->strip_* must be unset: the call assigns strips itself");
-    if (params->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "the preview scale cannot be combined with strips");
-    for (int i = 0; i < n_scenes; ++i)
-        if (scenes[i]->use_v1) return fail(RT_ERR_UNSUPPORTED, "rt_render_frame_multi needs the pooled kernel");
-    return guarded("rt_render_frame_multi", [&] { return deliver_frame(scenes, n_scenes, camera, params, strip_rows, out_rgb); });
+    return rtapi::guarded("rt_render_frame_multi", [&] {
+        int rc = rtapi::check_scenes(scenes, n_scenes);
+        if (rc != RT_OK) return rc;
+        if (!out_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+        rc = rtapi::check_params(camera, params);
+        if (rc != RT_OK) return rc;
+        if (params->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "params->strip_* must be unset: the call assigns strips itself");
+        if (params->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "the preview scale cannot be combined with strips");
+        for (int i = 0; i < n_scenes; ++i)
+            if (scenes[i]->use_v1) return fail(RT_ERR_UNSUPPORTED, "rt_render_frame_multi needs the pooled kernel");
+        return deliver_frame(scenes, n_scenes, camera, params, strip_rows, out_rgb);
+    });
 }
 
 int rt_render(RtScene *s, const RtCamera *camera, const RtRenderParams *p, RtTileCallback callback, void *user,
               const volatile int *cancel) {
-    Cancel c;
-    c.flag = cancel;
     RtScene *scenes[1] = {s};
-    return guarded("rt_render", [&] { return render_tiles(scenes, 1, camera, p, 0, callback, user, c); });
+    return rtapi::guarded("rt_render", [&] { return render_tiles(scenes, 1, camera, p, 0, callback, user, Cancel{cancel}); });
 }
 
 int rt_render_ex(RtScene *s, const RtCamera *camera, const RtRenderParams *p, RtTileCallback callback, void *user,
                  RtCancelCallback cancelled, void *cancel_user) {
-    Cancel c;
-    c.fn = cancelled;
-    c.user = cancel_user;
     RtScene *scenes[1] = {s};
-    return guarded("rt_render_ex", [&] { return render_tiles(scenes, 1, camera, p, 0, callback, user, c); });
+    return rtapi::guarded("rt_render_ex",
+                          [&] { return render_tiles(scenes, 1, camera, p, 0, callback, user, Cancel{nullptr, cancelled, cancel_user}); });
 }
 
 int rt_render_multi(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *p, int strip_rows,
                     RtTileCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user) {
-    Cancel c;
-    c.fn = cancelled;
-    c.user = cancel_user;
-    return guarded("rt_render_multi", [&] { return render_tiles(scenes, n_scenes, camera, p, strip_rows, callback, user, c); });
+    const Cancel c{nullptr, cancelled, cancel_user};
+    return rtapi::guarded("rt_render_multi", [&] { return render_tiles(scenes, n_scenes, camera, p, strip_rows, callback, user, c); });
 }
 
 } // extern "C"

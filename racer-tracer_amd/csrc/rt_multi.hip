@@ -32,19 +32,14 @@ struct Share {
 
 int render_multi(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p, int strip_rows,
                  double *out) {
-    if (!scenes || n <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "no scenes");
-    for (int i = 0; i < n; ++i)
-        if (!scenes[i]) return fail(RT_ERR_INVALID_ARGUMENT, "scenes[" + std::to_string(i) + "] is NULL");
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < i; ++j)
-            if (scenes[i] == scenes[j]) return fail(RT_ERR_INVALID_ARGUMENT, "the same RtScene is listed twice (create one per share)");
-    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
-    int rc = rtapi::check_params(camera, p);
+    int rc = rtapi::check_scenes(scenes, n);
     if (rc != RT_OK) return rc;
-    if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "params->strip_* must be unset: the call assigns strips itself");
-    if (p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "the preview scale cannot be combined with strips");
-    if (strip_rows < 0) return fail(RT_ERR_INVALID_ARGUMENT, "strip_rows must not be negative");
-    if (strip_rows == 0) strip_rows = 8;
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    rc = rtapi::check_params(camera, p);
+    if (rc != RT_OK) return rc;
+    std::vector<RtRenderParams> params;
+    rc = rtapi::deal_strips(p, n, strip_rows, params);
+    if (rc != RT_OK) return rc;
 
     const size_t row_elems = (size_t)p->width * 3;
     const size_t n_elems = row_elems * (size_t)p->height;
@@ -57,22 +52,17 @@ int render_multi(RtScene *const *scenes, int n, const RtCamera *camera, const Rt
         std::vector<RtScene *> launched;
         ~Drain() {
             for (RtScene *s : launched)
-                if (hipSetDevice(s->device) == hipSuccess) (void)hipStreamSynchronize(s->stream);
+                if (hipSetDevice(s->device) == hipSuccess) (void)hipStreamSynchronize(s->buf.stream);
         }
     } drain;
     // 0. every allocation of the call before its first launch (hipMalloc waits for the device's running kernels)
     for (int i = 0; i < n; ++i) {
         Share &sh = shares[(size_t)i];
         sh.scene = scenes[i];
-        sh.params = *p;
-        if (n > 1) {
-            sh.params.strip_rows = strip_rows;
-            sh.params.strip_count = n;
-            sh.params.strip_index = i;
-        }
+        sh.params = params[(size_t)i];
         RT_HIP(hipSetDevice(sh.scene->device));
         sh.in_place = sh.scene->device == dst_device && !sh.scene->gather_staged;
-        if (!sh.in_place && sh.scene->frame.count < n_elems) RT_HIP(sh.scene->frame.alloc(n_elems));
+        if (!sh.in_place && sh.scene->buf.frame.count < n_elems) RT_HIP(sh.scene->buf.frame.alloc(n_elems));
         rc = rtapi::reserve_render_buffers(sh.scene, &sh.params, false);
         if (rc != RT_OK) return rc;
     }
@@ -83,8 +73,8 @@ int render_multi(RtScene *const *scenes, int n, const RtCamera *camera, const Rt
         RT_HIP(hipSetDevice(sh.scene->device));
         // RT_GATHER_STAGED (RtSceneOptions.gather, a test switch): the share renders into its own staging frame and is
         // copied even when it sits on the output's device, so that ONE card runs what several run
-        sh.target = sh.in_place ? out : sh.scene->frame.ptr;
-        rc = rtapi::enqueue_render(sh.scene, camera, &sh.params, sh.target, sh.scene->stream, 0, rtapi::Cancel());
+        sh.target = sh.in_place ? out : sh.scene->buf.frame.ptr;
+        rc = rtapi::enqueue_render(sh.scene, camera, &sh.params, sh.target, sh.scene->buf.stream, 0, rtapi::Cancel());
         drain.launched.push_back(sh.scene);
         if (rc != RT_OK) return rc;
     }
@@ -113,7 +103,7 @@ int render_multi(RtScene *const *scenes, int n, const RtCamera *camera, const Rt
             break;
         }
         const int src_device = sh.scene->device;
-        hipStream_t st = sh.scene->stream;
+        hipStream_t st = sh.scene->buf.stream;
         auto peer = [&](size_t off_elems, size_t bytes) {
             return bytes == 0 ? hipSuccess : hipMemcpyPeerAsync(out + off_elems, dst_device, sh.target + off_elems, src_device, bytes, st);
         };
@@ -149,7 +139,7 @@ int render_multi(RtScene *const *scenes, int n, const RtCamera *camera, const Rt
     }
     // 3. the frame is complete when every stream has drained
     for (int i = 0; i < n; ++i) {
-        if (hipSetDevice(scenes[i]->device) != hipSuccess || hipStreamSynchronize(scenes[i]->stream) != hipSuccess)
+        if (hipSetDevice(scenes[i]->device) != hipSuccess || hipStreamSynchronize(scenes[i]->buf.stream) != hipSuccess)
             if (first_error == RT_OK) first_error = fail(RT_ERR_HIP, "stream synchronisation failed on share " + std::to_string(i));
     }
     return first_error;
@@ -161,11 +151,8 @@ extern "C" {
 
 int rt_render_frame_multi_device(RtScene *const *scenes, int n_scenes, const RtCamera *camera,
                                  const RtRenderParams *params, int strip_rows, double *out_rgb_device) {
-    try {
-        return render_multi(scenes, n_scenes, camera, params, strip_rows, out_rgb_device);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_OUT_OF_MEMORY, std::string("rt_render_frame_multi_device: ") + e.what());
-    }
+    return rtapi::guarded("rt_render_frame_multi_device",
+                          [&] { return render_multi(scenes, n_scenes, camera, params, strip_rows, out_rgb_device); });
 }
 
 } // extern "C"

@@ -1,19 +1,67 @@
 // rt_scene.h — what the host-side translation units of the library share: the RtScene object
-// behind include/rt_abi.h's opaque handle, the error helpers and the one function that enqueues a
-// render (rt_api.hip).  Private to the library.
+// behind include/rt_abi.h's opaque handle, the guard and error helpers of the C entry points and the
+// one function that enqueues a render (rt_api.hip).  Private to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <exception>
+#include <new>
 #include <string>
 #include <vector>
 #include "rt_device_types.h"
 #include "rt_bvh.h"
 #include "../../include/rt_abi.h"
 
+// The trace kernels exist twice (rt_trace_common.h: ARITHMETIC): RT_ARITH_FAST, and RT_ARITH_REFERENCE behind *_exact.
+#define RT_DECLARE_LAUNCHERS(SUFFIX)                                                                                       \
+    extern "C" hipError_t rtdev_launch_trace##SUFFIX(const rtdev::TraceArgs *args, int prims_class, int textured,         \
+                                                     int specular, hipStream_t stream);                                   \
+    extern "C" hipError_t rtdev_launch_resolve##SUFFIX(const double *accum, double *out, int width, int height,           \
+                                                       int strip_rows, int strip_count, int strip_index, int samples,     \
+                                                       hipStream_t stream);                                               \
+    extern "C" int rtdev_pool_blocks_per_cu##SUFFIX(int prims_class, int textured, int specular, int bvh, size_t dyn_lds); \
+    extern "C" int rtdev_pool_static_lds##SUFFIX(int prims_class, int textured, int specular, int bvh);                 \
+    extern "C" hipError_t rtdev_launch_trace_pool##SUFFIX(const rtdev::TraceArgs *args, int prims_class, int textured,    \
+                                                          int specular, int bvh, unsigned blocks, hipStream_t stream);    \
+    extern "C" hipError_t rtdev_launch_resolve_chunks##SUFFIX(const double *partial, double *out, int width, int height,  \
+                                                              int n_chunks, int slice_rows, int strip_rows, int strip_count, \
+                                                              int strip_index, int step_x, int step_y, int cover_w,       \
+                                                              int cover_h, int out_col_step, int out_cols, int samples,   \
+                                                              hipStream_t stream);
+RT_DECLARE_LAUNCHERS()
+RT_DECLARE_LAUNCHERS(_exact)
+
 namespace rtapi {
 
-// sets the thread-local text behind rt_last_error_message and returns `code`
-int fail(int code, const std::string &msg);
+// The launchers of one arithmetic flavour (rt_api.hip: kFastLaunchers, kExactLaunchers); a scene points to its own.
+struct Launchers {
+    decltype(&rtdev_launch_trace) trace;
+    decltype(&rtdev_launch_resolve) resolve;
+    decltype(&rtdev_pool_blocks_per_cu) pool_blocks_per_cu;
+    decltype(&rtdev_pool_static_lds) pool_static_lds;
+    decltype(&rtdev_launch_trace_pool) trace_pool;
+    decltype(&rtdev_launch_resolve_chunks) resolve_chunks;
+};
+
+// set the thread-local text behind rt_last_error_message (truncated, never throws) and return `code`
+int fail(int code, const char *msg) noexcept;
+inline int fail(int code, const std::string &msg) { return fail(code, msg.c_str()); }
+// ... as "<what>: <msg>"
+int fail_in(int code, const char *what, const char *msg) noexcept;
+
+// Every exported function of the library runs its body through this: nothing unwinds into a C, Rust or ctypes caller.
+// std::bad_alloc is RT_ERR_OUT_OF_MEMORY, any other exception RT_ERR_INVALID_ARGUMENT; the message names the entry point.
+template <class F> int guarded(const char *what, F &&body) noexcept {
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        return fail_in(RT_ERR_OUT_OF_MEMORY, what, "host allocation failed");
+    } catch (const std::exception &e) {
+        return fail_in(RT_ERR_INVALID_ARGUMENT, what, e.what());
+    } catch (...) {
+        return fail_in(RT_ERR_INVALID_ARGUMENT, what, "unknown exception");
+    }
+}
 
 #define RT_HIP(call)                                                                            \
     do {                                                                                        \
@@ -58,6 +106,55 @@ struct Delivery {
     bool cancellable = false;           // the caller polls a cancel hook while this launch runs: the waves read the scene's cancel word
 };
 
+// Everything a render allocates on first use — slices, the v1 accumulator, frames, the packed RGBA, counters, the pinned
+// frame and flags, streams, events — kept per device across rt_scene_destroy / rt_scene_create (rt_api.hip:
+// render_cache_put / render_cache_take), which move the whole set.
+struct RenderBuffers {
+    DevBuf<double> partial;             // [chunks][owned rows][W][3] per-chunk sums (pooled kernel)
+    DevBuf<unsigned int> queue;         // one item counter per launch of a render call
+    DevBuf<double> accum;               // running sums, W*H*3 (v1 kernel)
+    DevBuf<double> frame;               // resolved frame for the host-output entry points
+    DevBuf<uint8_t> rgba;               // packed frame of rt_render_frame_rgba8
+    DevBuf<unsigned long long> segments; // rt_device_types.h: RT_STAT_*
+    hipStream_t stream = nullptr;       // used by the host-output entry points
+    hipEvent_t ev_begin = nullptr, ev_traced = nullptr, ev_resolved = nullptr;
+    // Delivery (rt_deliver.hip): the launch writes finished pixels straight into `host_frame` — pinned, portable host
+    // memory mapped into every device, so several scenes (devices) can fill one frame — and publishes finished regions
+    // in `host_flags`; tile_done / region_done are the device counters behind that (zero between launches).
+    double *host_frame = nullptr;
+    size_t host_frame_count = 0;
+    unsigned int *host_flags = nullptr; // [RT_MAX_REGIONS] published regions + [1] the cancel word the waves read (TraceArgs.cancel_flag)
+    DevBuf<unsigned int> tile_done, region_done;
+    uint32_t deliver_serial = 0; // the flags still hold the serials this set published: the counter moves on with the set
+    bool deliver_dirty = false;  // a delivering launch was cut short: the counters must be cleared before the next one
+    // cancel: the stream whose command processor overwrites the launches' item counters (rt_api.hip: poison_queue)
+    hipStream_t stream_ctl = nullptr;
+
+    // what rt_scene_create makes when it takes no set over: only such a set is worth caching
+    bool complete() const {
+        return stream && stream_ctl && ev_begin && ev_traced && ev_resolved && host_flags && segments.ptr;
+    }
+    void free_all(int device) {
+        (void)hipSetDevice(device);
+        partial.release();
+        queue.release();
+        accum.release();
+        frame.release();
+        rgba.release();
+        segments.release();
+        tile_done.release();
+        region_done.release();
+        if (host_frame) (void)hipHostFree(host_frame);
+        if (host_flags) (void)hipHostFree(host_flags);
+        if (ev_begin) (void)hipEventDestroy(ev_begin);
+        if (ev_traced) (void)hipEventDestroy(ev_traced);
+        if (ev_resolved) (void)hipEventDestroy(ev_resolved);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (stream_ctl) (void)hipStreamDestroy(stream_ctl);
+        *this = RenderBuffers();
+    }
+};
+
 } // namespace rtapi
 
 struct RtScene {
@@ -70,7 +167,8 @@ struct RtScene {
     int n_prims = 0, n_materials = 0, n_textures = 0, n_images = 0, n_perlins = 0;
     int perlin_identity = 1; // all permutation tables are the identity (noise.rs:121-130 never shuffles them)
     rtdev::Background bg;
-    // kernel specialisation (rt_trace_kernel.hip): 0 rects only, 1 spheres only, 2 anything
+    // kernel specialisation of both trace kernels (rt_trace_kernel.hip, rt_trace_pool_kernel.hip; rtdev::PRIMS_*):
+    // 0 rects only, 1 spheres only, 2 anything
     int prims_class = 2;
     int rect_end[3] = {0, 0, 0}; // linear loop: ends of the XY / XZ / YZ rect groups of the (grouped) device table
     int sphere_end = 0;          // ... and of the plain-sphere group behind them
@@ -103,33 +201,14 @@ struct RtScene {
     // pooled kernel (default): persistent grid = CUs x resident blocks of the variant
     bool use_v1 = false;   // RtSceneOptions.kernel == RT_KERNEL_V1: the lane-per-pixel kernel
     bool exact = false;    // RtSceneOptions.arithmetic == RT_ARITH_REFERENCE: the *_exact copy of the trace kernels
+    const rtapi::Launchers *kernels = nullptr; // ... and their launchers (rt_api.hip: scene_create)
     bool gather_staged = false; // RtSceneOptions.gather == RT_GATHER_STAGED (rt_multi.hip)
     int num_cus = 0, pool_blocks_per_cu = 1;
     int pool_blocks_per_cu_lens = 1; // ... when the camera has an aperture (its lens samples take dynamic LDS)
     int pool_static_lds = 0;         // static LDS of the variant's kernel (hipFuncGetAttributes)
     size_t pool_dyn_lds = 0, pool_dyn_lds_lens = 0; // its dynamic LDS without / with lens samples (rt_device_types.h: pool_lds_layout)
-    rtapi::DevBuf<double> partial;       // [chunks][H][W][3] per-chunk sums
-    rtapi::DevBuf<unsigned int> queue;   // one item counter per launch of a render call
-    int last_chunks = 0;
 
-    rtapi::DevBuf<double> accum;  // running sums, W*H*3 (v1 kernel)
-    rtapi::DevBuf<double> frame;  // resolved frame for the host-output entry points
-    rtapi::DevBuf<uint8_t> rgba;  // packed frame of rt_render_frame_rgba8
-    rtapi::DevBuf<unsigned long long> segments;
-    hipStream_t stream = nullptr; // used by the host-output entry points
-    hipEvent_t ev_begin = nullptr, ev_traced = nullptr, ev_resolved = nullptr;
-    // Delivery (rt_deliver.hip): the launch writes finished pixels straight into `host_frame` — pinned, portable host
-    // memory mapped into every device, so several scenes (devices) can fill one frame — and publishes finished regions
-    // in `host_flags`; tile_done / region_done are the device counters behind that (zero between launches).
-    double *host_frame = nullptr;
-    size_t host_frame_count = 0;
-    unsigned int *host_flags = nullptr; // [RT_MAX_REGIONS] published regions + [1] the cancel word the waves read (TraceArgs.cancel_flag)
-    rtapi::DevBuf<unsigned int> tile_done, region_done;
-    uint32_t deliver_serial = 0;
-    bool deliver_dirty = false; // a delivering launch was cut short: the counters must be cleared before the next one
-    // cancel: the stream whose command processor overwrites the launches' item counters (rt_api.hip: poison_queue)
-    hipStream_t stream_ctl = nullptr;
-    hipStream_t last_stream = nullptr;
+    rtapi::RenderBuffers buf;
     bool has_stats = false;
     int last_launches = 0;
 };
@@ -155,8 +234,9 @@ extern "C" int rtdev_sum_exponent(double bound, int32_t samples, int32_t *e);
 namespace rtapi {
 int check_params(const RtCamera *camera, const RtRenderParams *p);
 // Enqueue trace + resolve on `stream` (two-pass path: the resolve kernel writes out_device), or — with a Delivery —
-// ONE delivering launch that finishes its own pixels (out_device is ignored).  `cancel` is polled between the
-// sample batches of the v1 kernel only.  Returns RT_ERR_CANCEL_EVENT when cancelled (callers map that to RT_OK).
+// ONE delivering launch that finishes its own pixels (out_device is ignored).  `cancel` is polled before every launch:
+// between the sample batches of the v1 kernel, between the chunk batches of the pooled one (whose waves also read the
+// scene's cancel word while `cancel` is armed).  Returns RT_ERR_CANCEL_EVENT when cancelled (callers map that to RT_OK).
 // out_col_step / out_cols: layout the RESOLVE pass of the two-pass path writes (rt_trace_pool_kernel.hip:
 // k_resolve_chunks_f64): the plain frame, or the tile stream's column layout.
 int enqueue_render(RtScene *s, const RtCamera *camera, const RtRenderParams *p, double *out_device,
@@ -181,4 +261,9 @@ inline int owned_row_to_image_row(const RtRenderParams *p, int vr) {
 int chunk_count(int samples);
 // Rows of the owned-row grid of a render with these parameters (a multiple of strip_rows with strips).
 int owned_rows_of(const RtRenderParams *p);
+// The several-device calls (rt_deliver.hip, rt_multi.hip): a non-empty list of distinct, non-NULL scenes.
+int check_scenes(RtScene *const *scenes, int n);
+// ... and their strips: strip j of `strip_rows` rows (0: 8, written back) goes to share j % n; params[i] is share i's
+// (the caller's own with n == 1).  Refuses parameters that cannot be combined with strips dealt out by the call.
+int deal_strips(const RtRenderParams *p, int n, int &strip_rows, std::vector<RtRenderParams> &params);
 } // namespace rtapi

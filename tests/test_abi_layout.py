@@ -114,6 +114,33 @@ def test_multi_device_entry_points_validate_before_touching_a_device(rt, abi):
     never = C.cast(None, abi.RtCancelCallback)
     assert rt.lib().rt_render_multi(handles, 2, C.byref(cam), C.byref(p), 0, noop, None, never, None) == abi.RT_ERR_INVALID_ARGUMENT
     assert rt.lib().rt_render_ex(None, C.byref(cam), C.byref(p), noop, None, never, None) == abi.RT_ERR_INVALID_ARGUMENT
+    # every entry point that takes a scene or an output pointer: NULL is refused before any device is touched, and the
+    # call leaves a message of its own (each call below follows one that leaves "no scenes")
+    tm, stats, h = abi.RtToneMap(), abi.RtRenderStats(), C.c_void_p()
+    rgba = (C.c_uint8 * (16 * 16 * 4))()
+    calls = {
+        "rt_scene_create": lambda: rt.lib().rt_scene_create(None, 0, None),
+        "rt_scene_create_ex": lambda: rt.lib().rt_scene_create_ex(None, 0, None, None),
+        "rt_render_frame": lambda: rt.lib().rt_render_frame(None, C.byref(cam), C.byref(p), out),
+        "rt_render_frame_device": lambda: rt.lib().rt_render_frame_device(None, C.byref(cam), C.byref(p), None, None),
+        "rt_render": lambda: rt.lib().rt_render(None, C.byref(cam), C.byref(p), noop, None, None),
+        "rt_render_ex": lambda: rt.lib().rt_render_ex(None, C.byref(cam), C.byref(p), noop, None, never, None),
+        "rt_post_rgba8_device": lambda: rt.lib().rt_post_rgba8_device(None, C.byref(tm), None, 0, None, None, None),
+        "rt_render_frame_rgba8": lambda: rt.lib().rt_render_frame_rgba8(None, C.byref(cam), C.byref(p), C.byref(tm), rgba),
+        "rt_render_frame_multi": lambda: rt.lib().rt_render_frame_multi(handles, 2, C.byref(cam), C.byref(p), 0, None),
+        "rt_render_frame_multi_device": lambda: rt.lib().rt_render_frame_multi_device(handles, 2, C.byref(cam), C.byref(p), 0, None),
+        "rt_render_multi": lambda: rt.lib().rt_render_multi(handles, 2, C.byref(cam), C.byref(p), 0, noop, None, never, None),
+        "rt_scene_last_stats": lambda: rt.lib().rt_scene_last_stats(None, C.byref(stats)),
+    }
+    for name, call in calls.items():
+        assert rt.lib().rt_render_frame_multi(None, 0, C.byref(cam), C.byref(p), 0, out) == abi.RT_ERR_INVALID_ARGUMENT
+        assert rt.lib().rt_last_error_message() == b"no scenes"
+        assert call() == abi.RT_ERR_INVALID_ARGUMENT, name
+        assert b"NULL" in rt.lib().rt_last_error_message(), name
+    assert rt.lib().rt_scene_create(None, 0, C.byref(h)) == abi.RT_ERR_INVALID_ARGUMENT and not h.value
+    # nothing to free: both return without a device
+    rt.lib().rt_scene_destroy(None)
+    rt.lib().rt_release_cached_buffers()
 
 
 def test_scene_options_are_validated(rt, abi):
