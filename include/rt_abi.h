@@ -403,6 +403,34 @@ int rt_render(RtScene *scene, const RtCamera *camera, const RtRenderParams *para
 int rt_render_ex(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
                  RtTileCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
 
+/* One whole-frame BufferUpdate per pass (renderer/denoised.rs:210-216, renderer/image.rs:56-62):
+ * rgb = width*height*3 f64, row-major, sqrt(sum / samples_done), not tone-mapped; valid during the call only. */
+typedef void (*RtFrameCallback)(void *user, const double *rgb, int32_t samples_done, int32_t samples_total);
+
+/* The whole frame, converging: rendered in passes (renderer/denoised.rs:291-331) with one callback per pass on the
+ * calling thread, the last of them carrying the frame of rt_render_frame.
+ *  - params->samples (N) is the total.  The frame's samples are summed chunk by chunk in a chunk order that depends on N
+ *    only; a pass runs from the current chunk boundary to the first boundary at least pass_samples further on, or to N.
+ *    samples_done is always a chunk boundary; pass_samples >= N means one pass.  For N = 96 the boundaries are
+ *    0, 24, 48, 72, 84, 92, 96, so pass_samples = 1 delivers at 24, 48, 72, 84, 92, 96; pass_samples = 30 at 48, 84, 96;
+ *    pass_samples = 96 at 96.  samples_total is N in every callback.
+ *  - The last callback's frame is bit-identical to rt_render_frame's for the same inputs.  The frame after s samples
+ *    agrees with an s-spp render to the same tolerance as any two summation orders (the draws are the same).
+ *  - Fixed-point sums (RtArithmetic) use the exponent of N, so the result is exact at N; a render that rt_render_frame
+ *    refuses at N is refused here too.
+ *  - `cancelled` (may be NULL) behaves as in rt_render_ex: raised on entry, the call returns RT_ERR_CANCEL_EVENT with no
+ *    callback; raised later, the waves in flight stop at their next work item and the call returns RT_OK with no further
+ *    callback.  Frames already delivered stay delivered.
+ *  - Refused before anything is enqueued: RT_ERR_INVALID_ARGUMENT for params->strip_count > 1, params->scale > 1,
+ *    pass_samples <= 0 or a NULL callback; RT_ERR_UNSUPPORTED for a scene on the v1 kernel (RT_KERNEL_V1).
+ *  - rt_scene_last_stats afterwards describes the whole call: samples = W*H*N and segments as rt_render_frame's for the
+ *    same inputs, kernel_ms summed over the passes' launches, resolve_ms over their fold passes, kernel_launches = passes.
+ *  - The GPU works one pass ahead of the callback.  The callback must not call into the library with the same scene.
+ * A binding detects this entry point by symbol lookup (RT_ABI_VERSION is unchanged by it). */
+int rt_render_progressive(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                          int32_t pass_samples, RtFrameCallback callback, void *user,
+                          RtCancelCallback cancelled, void *cancel_user);
+
 /* What the reference does to a finished tile downstream of the renderer, on
  * the device: ScreenBuffer::update's tone map (image_buffer.rs:147-153) and
  * SavePng's packing `(c * 255.0) as u32 -> (r << 24 | g << 16 | b << 8 | 255)`

@@ -100,6 +100,18 @@ def sum_exponent(bound, samples):
     return e.value
 
 
+def progressive_passes(samples, pass_samples):
+    """rtdev_progressive_passes: the samples_done of every callback of rt_render_progressive with params.samples = samples
+    and this pass_samples, in order (chunk boundaries of the frame's chunk plan).  No device needed."""
+    out = (C.c_int32 * 64)()
+    n = C.c_int32(0)
+    check(lib().rtdev_progressive_passes(int(samples), int(pass_samples), out, len(out), C.byref(n)), "rtdev_progressive_passes")
+    if n.value > len(out):
+        out = (C.c_int32 * n.value)()
+        check(lib().rtdev_progressive_passes(int(samples), int(pass_samples), out, len(out), C.byref(n)), "rtdev_progressive_passes")
+    return list(out[:n.value])
+
+
 def device_count():
     return lib().rt_device_count()
 
@@ -208,6 +220,25 @@ class Scene:
             cancel_ptr = C.cast(cancel, C.POINTER(C.c_int)) if cancel is not None else None
             check(self._lib.rt_render(self._h, C.byref(camera), C.byref(params), cb, None, cancel_ptr), "rt_render", self._lib)
         return tiles
+
+    def render_progressive(self, camera, params, pass_samples, cancel=None, on_frame=None):
+        """rt_render_progressive -> list of (samples_done, float64 [H, W, 3] copy), one per pass, the last one equal to
+        render_frame's.  cancel: None or a callable returning True once the render should stop (as render_tiles').
+        on_frame: None or a callable(samples_done, frame) run inside each callback, with the copy that is kept."""
+        frames = []
+        h, w = params.height, params.width
+
+        def on_pass(_user, rgb, samples_done, _samples_total):
+            arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()
+            frames.append((samples_done, arr))
+            if on_frame is not None:
+                on_frame(samples_done, arr)
+
+        cb = abi.RtFrameCallback(on_pass)
+        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        check(self._lib.rt_render_progressive(self._h, C.byref(camera), C.byref(params), int(pass_samples), cb, None, hook, None),
+              "rt_render_progressive", self._lib)
+        return frames
 
     def variant(self):
         """rtdev_scene_variant: which trace kernel rt_scene_create_ex chose -> dict of abi.VARIANT_FIELDS."""

@@ -116,6 +116,9 @@ RtTileCallback = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_double), C.c_int32,
                              C.c_int32, C.c_int32)
 # int (*RtCancelCallback)(void *cancel_user): non-zero = stop (renderer.rs:25-30 do_cancel)
 RtCancelCallback = C.CFUNCTYPE(C.c_int, C.c_void_p)
+# void (*RtFrameCallback)(void *user, const double *rgb, int32_t samples_done, int32_t samples_total): one per pass of
+# rt_render_progressive
+RtFrameCallback = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_int32)
 
 # Every symbol include/rt_abi.h declares: name -> (restype, argtypes)
 PROTOTYPES = {
@@ -135,6 +138,8 @@ PROTOTYPES = {
                                RtTileCallback, C.c_void_p, RtCancelCallback, C.c_void_p]),
     "rt_render_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.c_int,
                                   RtTileCallback, C.c_void_p, RtCancelCallback, C.c_void_p]),
+    "rt_render_progressive": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.c_int32,
+                                        RtFrameCallback, C.c_void_p, RtCancelCallback, C.c_void_p]),
     "rt_post_rgba8_device": (C.c_int, [C.c_void_p, C.POINTER(RtToneMap), C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rt_render_frame_rgba8": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
@@ -158,6 +163,7 @@ DEV_PROTOTYPES = {
     "rtdev_scene_classify": (C.c_int, [C.POINTER(RtSceneDesc), C.POINTER(C.c_int32)]),
     "rtdev_scene_radiance_bound": (C.c_int, [C.POINTER(RtSceneDesc), C.POINTER(C.c_double)]),
     "rtdev_sum_exponent": (C.c_int, [C.c_double, C.c_int32, C.POINTER(C.c_int32)]),
+    "rtdev_progressive_passes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
 }
 
 

@@ -26,10 +26,12 @@ extern "C" hipError_t rtdev_launch_post_rgba8(const RtToneMap *tm, const double 
 
 namespace {
 const rtapi::Launchers kFastLaunchers = {rtdev_launch_trace,      rtdev_launch_resolve,    rtdev_pool_blocks_per_cu,
-                                         rtdev_pool_static_lds,   rtdev_launch_trace_pool, rtdev_launch_resolve_chunks};
+                                         rtdev_pool_static_lds,   rtdev_launch_trace_pool, rtdev_launch_resolve_chunks,
+                                         rtdev_launch_fold_chunks};
 const rtapi::Launchers kExactLaunchers = {rtdev_launch_trace_exact,      rtdev_launch_resolve_exact,
                                           rtdev_pool_blocks_per_cu_exact, rtdev_pool_static_lds_exact,
-                                          rtdev_launch_trace_pool_exact,  rtdev_launch_resolve_chunks_exact};
+                                          rtdev_launch_trace_pool_exact,  rtdev_launch_resolve_chunks_exact,
+                                          rtdev_launch_fold_chunks_exact};
 
 thread_local char g_last_error[1024]; // a fixed buffer: setting it cannot throw (rtapi::guarded's handlers use it)
 } // namespace
@@ -406,6 +408,7 @@ int fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtde
 } // namespace
 
 int rtapi::chunk_count(int samples) { return (int)chunk_plan(samples).size() - 1; }
+std::vector<int> rtapi::chunk_starts(int samples) { return chunk_plan(samples); }
 
 int rtapi::owned_rows_of(const RtRenderParams *p) {
     if (p->strip_count <= 1) return p->height;
@@ -545,43 +548,43 @@ int order_bvh_for_camera(RtScene *s, const RtCamera *camera, hipStream_t stream)
     return RT_OK;
 }
 
-// The pooled kernel: work items = 8x8 tiles x sample chunks, one launch per batch of chunks, then — without a Delivery —
-// the resolve pass into out_device.
-int enqueue_pool(RtScene *s, rtdev::TraceArgs &a, const RtCamera *camera, const RtRenderParams *p, double *out_device,
-                 hipStream_t stream, int batch, const Cancel &cancel, const Delivery *delivery, int out_col_step,
-                 int out_cols, int &launches) {
-    // A block must fit one CU's LDS: the primitive table of the linear loop, the textures, the Perlin gradients, the lens
-    // samples and the ray times all come on top of the kernel's static LDS (rt_device_types.h: pool_lds_layout).  A launch
-    // that does not fit is refused here, before anything is enqueued; the lens part depends on the camera.
+// The item grid and chunk table of a pooled render, after checking that a block fits one CU's LDS: the primitive table
+// of the linear loop, the textures, the Perlin gradients, the lens samples and the ray times all come on top of the
+// kernel's static LDS (rt_device_types.h: pool_lds_layout).  A launch that does not fit is refused here, before anything
+// is enqueued; the lens part depends on the camera.  max_blocks: the variant's resident blocks on the device.
+int setup_pool_grid(const RtScene *s, rtdev::TraceArgs &a, const RtRenderParams *p, std::vector<int> &starts,
+                     unsigned &max_blocks) {
     const size_t lds = (size_t)s->pool_static_lds + (a.lens_lds ? s->pool_dyn_lds_lens : s->pool_dyn_lds);
     const int blocks_per_cu = a.lens_lds ? s->pool_blocks_per_cu_lens : s->pool_blocks_per_cu;
     if (lds > rtdev::kLdsPerCu || blocks_per_cu < 1)
         return fail(RT_ERR_UNSUPPORTED, a.lens_lds ? "the trace kernel's LDS (static + tables + lens samples) exceeds a CU's 160 KiB"
                                                    : "the trace kernel's LDS (static + tables) exceeds a CU's 160 KiB");
+    max_blocks = (unsigned)(s->num_cus * blocks_per_cu);
     a.tiles_x = (a.cover_w / a.step_x + 7) / 8; // grid cells per row
     a.n_tiles = a.tiles_x * ((a.owned_rows + 7) / 8);
-    const std::vector<int> starts = chunk_plan(p->samples);
+    starts = chunk_plan(p->samples);
     const int total_chunks = (int)starts.size() - 1;
     for (int c = 0; c <= total_chunks; ++c) a.chunk_start[c] = starts[(size_t)c];
     a.chunk_samples = starts[1] - starts[0];
     a.total_chunks = total_chunks;
-    const std::vector<Launch> plan = plan_launches(starts, batch);
-    int rc = RT_OK;
-    if (delivery) { // one launch, finishing its own pixels
-        if (plan.size() != 1 || p->scale > 1) return fail(RT_ERR_UNSUPPORTED, "a delivering launch is one whole-frame launch");
-        if ((rc = setup_delivery(s, a, *delivery, total_chunks, stream)) != RT_OK) return rc;
-    }
+    return RT_OK;
+}
+
+// What precedes a pooled render's first launch, in stream order: slices and `n_launches` item counters allocated where
+// they are short, the segment and item counters cleared, the cancel word armed (`cancellable`: the waves read it with
+// every item they fetch), the tree ordered for the camera, ev_begin recorded.
+int pool_prologue(RtScene *s, rtdev::TraceArgs &a, const RtCamera *camera, const RtRenderParams *p, size_t n_launches,
+                  bool cancellable, hipStream_t stream) {
     rtapi::RenderBuffers &b = s->buf;
-    // a call whose caller polls a cancel hook: the waves read the scene's cancel word with every item they fetch
-    if (cancel.armed() || (delivery && delivery->cancellable)) {
+    if (cancellable) {
         b.host_flags[rtdev::RT_MAX_REGIONS] = 0u;
         a.cancel_flag = b.host_flags + rtdev::RT_MAX_REGIONS;
     }
     // slices hold the launch's owned rows only (the kernel compacts rows: owned_rows, tile_py0)
     a.slice_rows = a.owned_rows;
     const size_t slice_elems = (size_t)p->width * (size_t)a.slice_rows * 3;
-    if (b.partial.count < slice_elems * (size_t)total_chunks) RT_HIP(b.partial.alloc(slice_elems * (size_t)total_chunks));
-    if (b.queue.count < plan.size()) RT_HIP(b.queue.alloc(plan.size()));
+    if (b.partial.count < slice_elems * (size_t)a.total_chunks) RT_HIP(b.partial.alloc(slice_elems * (size_t)a.total_chunks));
+    if (b.queue.count < n_launches) RT_HIP(b.queue.alloc(n_launches));
     a.partial = b.partial.ptr;
     RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
 #ifdef RT_PROFILE_REGIONS
@@ -589,22 +592,52 @@ int enqueue_pool(RtScene *s, rtdev::TraceArgs &a, const RtCamera *camera, const 
     RT_HIP(hipMemsetAsync(b.segments.ptr + rtdev::RT_STAT_WALL + 2, 0xff, sizeof(unsigned long long), stream));
 #endif
     RT_HIP(hipMemsetAsync(b.queue.ptr, 0, sizeof(unsigned int) * b.queue.count, stream));
-    if ((rc = order_bvh_for_camera(s, camera, stream)) != RT_OK) return rc;
+    const int rc = order_bvh_for_camera(s, camera, stream);
+    if (rc != RT_OK) return rc;
     RT_HIP(hipEventRecord(b.ev_begin, stream));
+    return RT_OK;
+}
+
+// Launch number `index` of a render: chunks [first_chunk, first_chunk + n_chunks) of every tile.
+int launch_pool(RtScene *s, rtdev::TraceArgs &a, const std::vector<int> &starts, int first_chunk, int n_chunks, int index,
+                unsigned max_blocks, hipStream_t stream) {
+    a.sample_begin = starts[(size_t)first_chunk];
+    a.sample_end = starts[(size_t)(first_chunk + n_chunks)];
+    a.n_chunks = n_chunks;
+    a.chunk_base = first_chunk;
+    a.n_items = (uint32_t)a.n_chunks * (uint32_t)a.n_tiles;
+    if ((uint64_t)a.n_chunks * (uint64_t)a.n_tiles >= 0x40000000ull) // the item counter's top bit is the cancel poison
+        return fail(RT_ERR_UNSUPPORTED, "more than 2^30 work items in one launch");
+    a.queue = s->buf.queue.ptr + index;
+    const unsigned blocks = std::min(max_blocks, (a.n_items + 3) / 4);
+    RT_HIP(s->kernels->trace_pool(&a, s->prims_class, s->textured, s->specular, s->use_bvh, blocks, stream));
+    return RT_OK;
+}
+
+// The pooled kernel: work items = 8x8 tiles x sample chunks, one launch per batch of chunks, then — without a Delivery —
+// the resolve pass into out_device.
+int enqueue_pool(RtScene *s, rtdev::TraceArgs &a, const RtCamera *camera, const RtRenderParams *p, double *out_device,
+                 hipStream_t stream, int batch, const Cancel &cancel, const Delivery *delivery, int out_col_step,
+                 int out_cols, int &launches) {
+    std::vector<int> starts;
+    unsigned max_blocks = 0;
+    int rc = setup_pool_grid(s, a, p, starts, max_blocks);
+    if (rc != RT_OK) return rc;
+    const int total_chunks = a.total_chunks;
+    const std::vector<Launch> plan = plan_launches(starts, batch);
+    if (delivery) { // one launch, finishing its own pixels
+        if (plan.size() != 1 || p->scale > 1) return fail(RT_ERR_UNSUPPORTED, "a delivering launch is one whole-frame launch");
+        if ((rc = setup_delivery(s, a, *delivery, total_chunks, stream)) != RT_OK) return rc;
+    }
+    rtapi::RenderBuffers &b = s->buf;
+    // a call whose caller polls a cancel hook: the waves read the scene's cancel word with every item they fetch
+    if ((rc = pool_prologue(s, a, camera, p, plan.size(), cancel.armed() || (delivery && delivery->cancellable), stream)) != RT_OK)
+        return rc;
     // a slice is only written for the pixels a launch covers; unowned rows are skipped by the resolve
     int chunks_done = 0;
     for (const Launch &l : plan) {
         if (cancel.raised()) return RT_ERR_CANCEL_EVENT;
-        a.sample_begin = starts[(size_t)l.first_chunk];
-        a.sample_end = starts[(size_t)(l.first_chunk + l.n_chunks)];
-        a.n_chunks = l.n_chunks;
-        a.chunk_base = l.first_chunk;
-        a.n_items = (uint32_t)a.n_chunks * (uint32_t)a.n_tiles;
-        if ((uint64_t)a.n_chunks * (uint64_t)a.n_tiles >= 0x40000000ull) // the item counter's top bit is the cancel poison
-            return fail(RT_ERR_UNSUPPORTED, "more than 2^30 work items in one launch");
-        a.queue = b.queue.ptr + launches;
-        const unsigned blocks = std::min((unsigned)(s->num_cus * blocks_per_cu), (a.n_items + 3) / 4);
-        RT_HIP(s->kernels->trace_pool(&a, s->prims_class, s->textured, s->specular, s->use_bvh, blocks, stream));
+        if ((rc = launch_pool(s, a, starts, l.first_chunk, l.n_chunks, launches, max_blocks, stream)) != RT_OK) return rc;
         chunks_done += a.n_chunks;
         ++launches;
     }
@@ -638,9 +671,36 @@ int rtapi::enqueue_render(RtScene *s, const RtCamera *camera, const RtRenderPara
     if (rc != RT_OK) return rc;
     s->has_stats = true;
     s->last_launches = launches;
+    s->summed_times = false;
     return RT_OK;
 }
 using rtapi::enqueue_render;
+
+int rtapi::begin_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p, hipStream_t stream, int max_launches,
+                        bool cancellable, PoolPasses &pp) {
+    if (s->use_v1 || p->strip_count > 1 || p->scale > 1 || max_launches < 1)
+        return fail(RT_ERR_UNSUPPORTED, "passes are whole-frame launches of the pooled kernel");
+    RT_HIP(hipSetDevice(s->device));
+    int rc = fill_args(s, camera, p, pp.args);
+    if (rc != RT_OK) return rc;
+    if ((rc = setup_pool_grid(s, pp.args, p, pp.starts, pp.max_blocks)) != RT_OK) return rc;
+    if ((rc = pool_prologue(s, pp.args, camera, p, (size_t)max_launches, cancellable, stream)) != RT_OK) return rc;
+    pp.launches = 0;
+    pp.max_launches = max_launches;
+    s->has_stats = true;
+    s->last_launches = 0;
+    s->summed_times = false;
+    return RT_OK;
+}
+
+int rtapi::enqueue_chunks(RtScene *s, PoolPasses &pp, int c0, int c1, hipStream_t stream) {
+    if (c0 < 0 || c1 <= c0 || c1 > pp.args.total_chunks || pp.launches >= pp.max_launches)
+        return fail(RT_ERR_INVALID_ARGUMENT, "enqueue_chunks: chunk range or launch count out of range");
+    const int rc = launch_pool(s, pp.args, pp.starts, c0, c1 - c0, pp.launches, pp.max_blocks, stream);
+    if (rc != RT_OK) return rc;
+    s->last_launches = ++pp.launches;
+    return RT_OK;
+}
 
 // Block until `ev` has happened; with a cancel hook, poll it meanwhile and give up
 // (RT_ERR_CANCEL_EVENT) as soon as it is raised.
@@ -1172,8 +1232,8 @@ int last_stats(RtScene *s, RtRenderStats *out) {
 #endif
     out->samples = counters[rtdev::RT_STAT_SAMPLES]; // counted on the device where a path is handed out
     out->segments = segs;
-    out->kernel_ms = ms_trace;
-    out->resolve_ms = ms_resolve;
+    out->kernel_ms = s->summed_times ? s->summed_kernel_ms : ms_trace;
+    out->resolve_ms = s->summed_times ? s->summed_resolve_ms : ms_resolve;
     out->kernel_launches = s->last_launches;
     return RT_OK;
 }

@@ -28,7 +28,21 @@
 
 using rtapi::Cancel;
 using rtapi::Delivery;
+using rtapi::ensure_host_frame;
 using rtapi::fail;
+
+// Pinned frame + flags of the call live on shares[0]'s scene.
+int rtapi::ensure_host_frame(RtScene *s, size_t doubles) {
+    if (s->buf.host_frame_count >= doubles) return RT_OK;
+    RT_HIP(hipSetDevice(s->device));
+    if (s->buf.host_frame) (void)hipHostFree(s->buf.host_frame);
+    s->buf.host_frame = nullptr;
+    s->buf.host_frame_count = 0;
+    RT_HIP(hipHostMalloc((void **)&s->buf.host_frame, doubles * sizeof(double),
+                         hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
+    s->buf.host_frame_count = doubles;
+    return RT_OK;
+}
 
 namespace {
 
@@ -42,19 +56,6 @@ struct Share {
     int next_region = 0; // regions [0, next_region) have been seen published
     bool launched = false;
 };
-
-// Pinned frame + flags of the call live on shares[0]'s scene.
-int ensure_host_frame(RtScene *s, size_t doubles) {
-    if (s->buf.host_frame_count >= doubles) return RT_OK;
-    RT_HIP(hipSetDevice(s->device));
-    if (s->buf.host_frame) (void)hipHostFree(s->buf.host_frame);
-    s->buf.host_frame = nullptr;
-    s->buf.host_frame_count = 0;
-    RT_HIP(hipHostMalloc((void **)&s->buf.host_frame, doubles * sizeof(double),
-                         hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
-    s->buf.host_frame_count = doubles;
-    return RT_OK;
-}
 
 // Blocks until region `r` of `sh` has been published.  RT_ERR_CANCEL_EVENT when the hook is raised first.
 int wait_region(Share &sh, int r, const Cancel &cancel) {

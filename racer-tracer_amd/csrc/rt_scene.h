@@ -27,7 +27,9 @@
                                                               int n_chunks, int slice_rows, int strip_rows, int strip_count, \
                                                               int strip_index, int step_x, int step_y, int cover_w,       \
                                                               int cover_h, int out_col_step, int out_cols, int samples,   \
-                                                              hipStream_t stream);
+                                                              hipStream_t stream);                                        \
+    extern "C" hipError_t rtdev_launch_fold_chunks##SUFFIX(const double *partial, double *running, double *out, size_t n,   \
+                                                           int c0, int c1, int samples_done, hipStream_t stream);
 RT_DECLARE_LAUNCHERS()
 RT_DECLARE_LAUNCHERS(_exact)
 
@@ -41,6 +43,7 @@ struct Launchers {
     decltype(&rtdev_pool_static_lds) pool_static_lds;
     decltype(&rtdev_launch_trace_pool) trace_pool;
     decltype(&rtdev_launch_resolve_chunks) resolve_chunks;
+    decltype(&rtdev_launch_fold_chunks) fold_chunks;
 };
 
 // set the thread-local text behind rt_last_error_message (truncated, never throws) and return `code`
@@ -112,8 +115,8 @@ struct Delivery {
 struct RenderBuffers {
     DevBuf<double> partial;             // [chunks][owned rows][W][3] per-chunk sums (pooled kernel)
     DevBuf<unsigned int> queue;         // one item counter per launch of a render call
-    DevBuf<double> accum;               // running sums, W*H*3 (v1 kernel)
-    DevBuf<double> frame;               // resolved frame for the host-output entry points
+    DevBuf<double> accum;               // running sums, W*H*3 (v1 kernel; the passes of rt_render_progressive)
+    DevBuf<double> frame;               // resolved frame for the host-output entry points (two of them for rt_render_progressive)
     DevBuf<uint8_t> rgba;               // packed frame of rt_render_frame_rgba8
     DevBuf<unsigned long long> segments; // rt_device_types.h: RT_STAT_*
     hipStream_t stream = nullptr;       // used by the host-output entry points
@@ -129,6 +132,11 @@ struct RenderBuffers {
     bool deliver_dirty = false;  // a delivering launch was cut short: the counters must be cleared before the next one
     // cancel: the stream whose command processor overwrites the launches' item counters (rt_api.hip: poison_queue)
     hipStream_t stream_ctl = nullptr;
+    // rt_render_progressive (rt_progressive.hip), made on its first call: the stream that copies a pass's frame to the host
+    // and, per frame slot, the pass's trace span, the end of its fold and the end of its copy
+    hipStream_t stream_copy = nullptr;
+    hipEvent_t ev_pass_begin[2] = {nullptr, nullptr}, ev_pass_traced[2] = {nullptr, nullptr};
+    hipEvent_t ev_folded[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
 
     // what rt_scene_create makes when it takes no set over: only such a set is worth caching
     bool complete() const {
@@ -151,6 +159,10 @@ struct RenderBuffers {
         if (ev_resolved) (void)hipEventDestroy(ev_resolved);
         if (stream) (void)hipStreamDestroy(stream);
         if (stream_ctl) (void)hipStreamDestroy(stream_ctl);
+        for (hipEvent_t *evs : {ev_pass_begin, ev_pass_traced, ev_folded, ev_copied})
+            for (int k = 0; k < 2; ++k)
+                if (evs[k]) (void)hipEventDestroy(evs[k]);
+        if (stream_copy) (void)hipStreamDestroy(stream_copy);
         *this = RenderBuffers();
     }
 };
@@ -211,9 +223,14 @@ struct RtScene {
     rtapi::RenderBuffers buf;
     bool has_stats = false;
     int last_launches = 0;
+    // rt_render_progressive: the call's kernel and fold times, summed over its passes, stand in for the event spans
+    bool summed_times = false;
+    double summed_kernel_ms = 0.0, summed_resolve_ms = 0.0;
 };
 
 // Internal exports for the tests (not part of rt_abi.h; the ABI version does not cover them).
+//   rtdev_progressive_passes: the samples_done of every pass of rt_render_progressive(samples, pass_samples), in order, into
+//     out (at most n_out of them), and their number into n_passes.  No device needed.
 //   rtdev_scene_variant: what rt_scene_create_ex chose for a scene, RTDEV_VARIANT_FIELDS values in this order:
 //     kernel (0 pool, 1 v1), prims_class (rtdev::PRIMS_*), textured, specular, use_bvh, exact (RT_ARITH_REFERENCE kernels),
 //     bvh_nodes_in_lds, has_moving, perlin_in_lds, static LDS of the pool variant, its dynamic LDS without and with lens
@@ -230,6 +247,7 @@ extern "C" int rtdev_scene_variant(const RtScene *s, int32_t *out, int32_t n_out
 extern "C" int rtdev_scene_classify(const RtSceneDesc *d, int32_t out[4]);
 extern "C" int rtdev_scene_radiance_bound(const RtSceneDesc *d, double *bound);
 extern "C" int rtdev_sum_exponent(double bound, int32_t samples, int32_t *e);
+extern "C" int rtdev_progressive_passes(int32_t samples, int32_t pass_samples, int32_t *out, int32_t n_out, int32_t *n_passes);
 
 namespace rtapi {
 int check_params(const RtCamera *camera, const RtRenderParams *p);
@@ -259,6 +277,24 @@ inline int owned_row_to_image_row(const RtRenderParams *p, int vr) {
 }
 // Sample chunks a frame of `samples` samples per pixel is cut into (a function of spp only: rt_api.hip: chunk_plan).
 int chunk_count(int samples);
+// ... and their boundaries: the start sample of every chunk plus the total (chunk_count + 1 entries).
+std::vector<int> chunk_starts(int samples);
+// A whole-frame render of the pooled kernel enqueued chunk range by chunk range (rt_progressive.hip): begin_passes checks the
+// render as enqueue_render does and enqueues what precedes its first launch — counters cleared (one item counter per
+// launch, max_launches of them), the cancel word armed when `cancellable`, the tree ordered for the camera, ev_begin —
+// and enqueue_chunks launches chunks [c0, c1) of every tile into their slices.  The launches share one set of segment
+// counters, so rt_scene_last_stats counts the whole call.  Buffers must be reserved first (reserve_render_buffers).
+struct PoolPasses {
+    rtdev::TraceArgs args;
+    std::vector<int> starts; // chunk_starts(samples)
+    unsigned max_blocks = 0; // resident blocks of the variant on the device
+    int launches = 0, max_launches = 0;
+};
+int begin_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p, hipStream_t stream, int max_launches,
+                 bool cancellable, PoolPasses &pp);
+int enqueue_chunks(RtScene *s, PoolPasses &pp, int c0, int c1, hipStream_t stream);
+// The pinned host frame of the host-output entry points, at least `doubles` long (rt_deliver.hip).
+int ensure_host_frame(RtScene *s, size_t doubles);
 // Rows of the owned-row grid of a render with these parameters (a multiple of strip_rows with strips).
 int owned_rows_of(const RtRenderParams *p);
 // The several-device calls (rt_deliver.hip, rt_multi.hip): a non-empty list of distinct, non-NULL scenes.

@@ -1252,6 +1252,20 @@ __global__ __launch_bounds__(256) void k_resolve_chunks_f64(const double *__rest
     }
 }
 
+// One pass of a progressive frame (rt_progressive.hip): whole-frame slices (n = width * height * 3 elements each), the
+// slices [c0, c1) added to the running sums in index order and out = sqrt(scale * running), scale = 1 / samples so far.
+// `running` starts the frame at +0.0, so the passes together are k_resolve_chunks_f64's left fold over the same slices and
+// the last pass's frame is bit-identical to the one-shot frame.
+__global__ __launch_bounds__(256) void k_fold_chunks_f64(const double *__restrict__ partial, double *__restrict__ running,
+                                                         double *__restrict__ out, size_t n, int c0, int c1, double scale) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        double acc = running[i];
+        for (int c = c0; c < c1; ++c) acc += partial[(size_t)c * n + i];
+        running[i] = acc;
+        out[i] = sqrt(scale * acc);
+    }
+}
+
 } // namespace RT_KNS
 
 #if defined(RT_BB_COUNT) && !defined(RT_EXACT_DIV)
@@ -1353,5 +1367,15 @@ extern "C" hipError_t RT_LAUNCHER(rtdev_launch_resolve_chunks)(const double *par
     hipLaunchKernelGGL(RT_KNS::k_resolve_chunks_f64, dim3(blocks), dim3(256), 0, stream, partial, out, width, height,
                        n_chunks, slice_rows, strip_rows, strip_count, strip_index, step_x, step_y, cover_w, cover_h, out_col_step, out_cols,
                        1.0 / (double)samples);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t RT_LAUNCHER(rtdev_launch_fold_chunks)(const double *partial, double *running, double *out, size_t n, int c0,
+                                                            int c1, int samples_done, hipStream_t stream) {
+    unsigned blocks = (unsigned)((n + 255) / 256);
+    if (blocks > 4096u) blocks = 4096u;
+    if (blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(RT_KNS::k_fold_chunks_f64, dim3(blocks), dim3(256), 0, stream, partial, running, out, n, c0, c1,
+                       1.0 / (double)samples_done);
     return hipGetLastError();
 }
