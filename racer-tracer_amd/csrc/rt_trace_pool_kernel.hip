@@ -156,6 +156,16 @@ struct NoiseSlots {
 struct alignas(16) Req4 { // one 128-bit LDS access
     uint32_t x, y, z, w;
 };
+// Posts a sampler request as four 32-bit LDS stores.  One 128-bit store wants the four values in four consecutive VGPRs:
+// pixel, sample and candidate were then copied into such a quad in every iteration (v_mov_b32 around every round), and
+// the stores cost the LDS pipe, which the path loop barely uses, instead of the vector one.  (Relaxed atomic stores: plain
+// ones are merged back into the 128-bit store.)
+__device__ __forceinline__ void post_request(Req4 *slot, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
+    __hip_atomic_store(&slot->x, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->y, y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->z, z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->w, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
 // The sampler's request slots and the turbulence slots are never live at the same time (the Noise rounds of
 // an iteration end before its sampler rounds begin, and both finish with what they posted), so they share
 // their LDS: the textured variants — the BVH ones above all, whose node array already fills LDS to
@@ -231,26 +241,29 @@ __device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t p
             // so every lane takes its candidate (no copy of the result under the lanes' mask)
             const d3 p = sphere_candidate(philox4x32(pixel, sample, (seg << 8) | RT_RNG_SCATTER, base, k0, k1));
             if (round == 0 || need) result = p;
+            const bool inside = len2(p) < 1.0;
             if (need) {
-                if (len2(p) < 1.0) {
+                if (inside) {
                     need = false;
                     have = true;
                 } else {
                     base += 1u;
                 }
             }
-            pending = ballot(need);
+            pending &= ~ballot(inside); // (the comparison's own lane mask: see `pending` below)
             continue;
         }
         const int rank = lane_rank(pending);
-        if (need) req[rank] = Req4{pixel, sample, seg, base};
+        if (need) post_request(req + rank, pixel, sample, seg, base);
         const int j = lane >> lg;              // request served by this lane
         const int c = lane & ((1 << lg) - 1);  // candidate offset inside the group
         const bool serving = j < n;
         const Req4 r = req[serving ? j : 0];
         const uint32_t i = r.w + (uint32_t)c;  // candidate index = its block (rt_rng.h)
         const d3 p = sphere_candidate(philox4x32(r.x, r.y, (r.z << 8) | RT_RNG_SCATTER, i, k0, k1));
-        const uint64_t accepted = ballot(serving && len2(p) < 1.0);
+        // (ballots of the two comparisons, ANDed as scalars: a ballot of `serving && ...` is a lane mask turned into an
+        // integer and back, v_cndmask_b32 + v_cmp_ne_u32)
+        const uint64_t accepted = ballot(serving) & ballot(len2(p) < 1.0);
         // first accepted candidate of my own request, in stream order
         const int first = need ? (rank << lg) : 0;
         const uint64_t width_mask = lg == 6 ? ~0ull : ((1ull << (1 << lg)) - 1ull);
@@ -265,7 +278,9 @@ __device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t p
         } else if (need) {
             base += 1u << lg;
         }
-        pending = ballot(need);
+        // the lanes still searching: `got` implies `need`, so this is ballot(need) — from a comparison's mask rather than
+        // from the bool, whose ballot costs the two vector instructions above
+        pending &= ~ballot(got);
     }
     return have;
 }
@@ -1134,16 +1149,35 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
 
         RT_REGION(5); // sampler
         if (finish) {
-            if (is_lambert) { // lambertian.rs:27-33
+            if (!SPECULAR || is_lambert) { // lambertian.rs:27-33 (without SPECULAR every open hit is a Lambertian one)
                 const d3 dir = d + unit_fast(sph); // d holds the normal since the hit
                 // vec3.rs:127-130 near_zero keeps the normal: once in 10^23 samples, so the wave branches
-                // around the six selects it would otherwise issue every time
-                const bool near_zero = fabs(dir.x) < 1e-8 && fabs(dir.y) < 1e-8 && fabs(dir.z) < 1e-8;
-                const d3 normal = d;
-                d = dir;
-                if (ballot(near_zero) != 0) {
-                    asm volatile("; near_zero (keeps the compiler from turning the branch back into selects)");
-                    if (near_zero) d = normal;
+                // around the six selects it would otherwise issue every time.  (The ballots of the three comparisons,
+                // ANDed as scalars: no short-circuit branch, no lane mask turned into an integer and back.)
+                const uint64_t near_zero = ballot(fabs(dir.x) < 1e-8) & ballot(fabs(dir.y) < 1e-8) & ballot(fabs(dir.z) < 1e-8);
+#ifndef RT_EXACT_DIV
+                if (PRIMS == PRIMS_RECTS) {
+                    // A rect's normal is +-1 on its axis and +0 on the others (set_face_normal_axis), and a near-zero
+                    // direction means the unit sample is within 1e-8 of its opposite: rounding the negated sample to
+                    // integers gives the normal back exactly (+ 0.0 turns -0 into +0).  So d takes the new direction
+                    // in place, and the normal is not kept beside it (three v_mov_b64 per iteration at the join).
+                    d = dir;
+                    if (near_zero != 0) {
+                        asm volatile("; near_zero (keeps the compiler from turning the branch back into selects)");
+                        if ((near_zero >> lane) & 1ull) {
+                            const d3 u = unit_fast(sph);
+                            d = mk(rint(-u.x) + 0.0, rint(-u.y) + 0.0, rint(-u.z) + 0.0);
+                        }
+                    }
+                } else
+#endif
+                {
+                    const d3 normal = d;
+                    d = dir;
+                    if (near_zero != 0) {
+                        asm volatile("; near_zero (keeps the compiler from turning the branch back into selects)");
+                        if ((near_zero >> lane) & 1ull) d = normal;
+                    }
                 }
                 scattered = true;
             } else if (SPECULAR) { // metal.rs:31-42: d holds the reflected direction since the hit

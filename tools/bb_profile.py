@@ -232,7 +232,7 @@ def main():
         emit("%-8s %15.6g   %8.3f" % (u, by_unit[u], by_unit[u] / segs))
     emit()
     pmc = None
-    for rnd in ("r04", "r03"):
+    for rnd in ("r06", "r05", "r04", "r03"):  # the newest summary of the workload
         path = os.path.join(ROOT, "profiles", "%s_%s_pmc_summary.json" % (rnd, workload))
         if os.path.exists(path):
             d = json.load(open(path))
