@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the MI355X render path on BASELINE.json's workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4] [--full]
 
 A "step" is one full render of the workload frame: rt_render_frame_device on
 this rank's row strips (+ the RCCL gather of finished strips to rank 0 when
@@ -21,21 +21,32 @@ WORLD_SIZE in the environment) this process is one rank; started plainly
 (`python bench.py --gpus N`) it spawns the N ranks as child processes BEFORE
 touching the GPU, relays rank 0's JSON line and exits with their status.
 
+A plain run does only what the headline figure needs: set up, warm up, time the
+steps, dump outputs when asked, print the line.  Its `roofline` block holds the
+figures the timed steps give (kernel time, segment rate, `hbm_algorithmic`).
+Everything that takes runs of its own is behind `--full`:
+
 roofline: the trace kernel keeps ray state in registers, so HBM is not what
 bounds it; the bound is the vector ALU.  `frac` = counted f64 FLOP per second /
 the 78.6 TFLOP/s f64 vector peak, `issue_frac` = sum over instruction classes of
 count x the class's minimum issue cost / the SIMD cycles of the launch — two
-numbers that cannot exceed 1.  The counters are collected LIVE: before this
-process touches the GPU it runs rocprofv3 --pmc passes over itself (tools/pmc.py,
-one pass per counter group, about ten seconds each); `--pmc file` uses the
-committed summary under profiles/ instead (only while its source stamp matches
-the tree), `--pmc none` skips counters.  SURVEY 8(d)'s algorithmic-bytes figure
-is kept as `hbm_algorithmic`.
+numbers that cannot exceed 1.  With --full the counters are collected LIVE:
+before this process touches the GPU it runs rocprofv3 --pmc passes over itself
+(tools/pmc.py, one pass per counter group, about ten seconds each); `--pmc file`
+uses the committed summary under profiles/ instead (only while its source stamp
+matches the tree), `--pmc none` skips counters.  SURVEY 8(d)'s algorithmic-bytes
+figure is kept as `hbm_algorithmic`.
 
-Also in the line: `host_delivered` — W*H*spp over the wall time of rt_render
-with the reference's 10x10 tile grid (every tile copied out of the callback),
-and of rt_render_frame into a caller-owned host frame: what a binding of the
-reference receives, next to the device-resident `value`.
+`host_delivered` — W*H*spp over the wall time of rt_render with the reference's
+10x10 tile grid (every tile copied out of the callback), and of rt_render_frame
+into a caller-owned host frame: what a binding of the reference receives, next
+to the device-resident `value` (--full, one GPU; `--no-host-delivery` drops it).
+
+`cpu_baseline` — the CPU oracle on a bounded sample of the same frame, about
+`--cpu-seconds` long (--full, one GPU; `--no-cpu-baseline` drops it).
+
+A run with a collective (N > 1, or --force-dist) always checks the gathered
+frame against a single-rank render: that is what its frame is evidence of.
 
 `--dump-outputs DIR` writes, after the timed steps, what the last step computed
 (the resolved frame and its RGBA8 image) as DIR/<name>.npy, so that two builds
@@ -78,13 +89,18 @@ def parse():
     ap.add_argument("--workload", default="c3", choices=["c2", "c3", "c4", "c5", "random", "boxes", "emissive"])
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (debug)")
     ap.add_argument("--seed", type=int, default=0, help="override the RNG seed of the config (SURVEY 8(d): seeds 2, 3 for variance)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline's counters, the "
+                         "host-delivered rates and the CPU baseline (a plain run sets up, warms up and times the steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--pmc", default="live", choices=["live", "file", "none"],
-                    help="where the roofline's counters come from: rocprofv3 passes over this command run now (live), "
-                         "the committed profiles/ summary (file), or nowhere (none)")
+    ap.add_argument("--pmc", default=None, choices=["live", "file", "none"],
+                    help="where the roofline's counters come from: rocprofv3 passes over this command run now (live, "
+                         "the default with --full), the committed profiles/ summary (file), or nowhere (none, the "
+                         "default without --full)")
     ap.add_argument("--pmc-child", action="store_true", help="internal: one short run under rocprofv3 (tools/pmc.py)")
-    ap.add_argument("--no-host-delivery", action="store_true", help="skip the rt_render / rt_render_frame host timings")
+    ap.add_argument("--no-host-delivery", action="store_true",
+                    help="with --full: skip the rt_render / rt_render_frame host timings")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group and run the strip gather as a collective even with "
                          "ONE rank (proves librccl + an f64 device gather on a one-GPU box)")
@@ -95,8 +111,12 @@ def parse():
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.pmc_child:
-        args.steps, args.warmup, args.no_cpu_baseline, args.pmc, args.no_host_delivery = 1, 1, True, "none", True
+        args.steps, args.warmup, args.full, args.pmc = 1, 1, False, "none"
         args.dump_outputs = None
+    if args.pmc is None:
+        args.pmc = "live" if args.full else "none"
+    elif args.pmc != "none" and not args.full:
+        ap.error("--pmc %s needs --full: a plain run collects no counters" % args.pmc)
     return args
 
 
@@ -387,7 +407,7 @@ def main():
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))  # before torch / HIP are even imported
     # LIVE counters: rocprofv3 passes over this command, as children, before this process touches the GPU
-    live_summary, live_why_not = (None, "--pmc %s" % args.pmc)
+    live_summary, live_why_not = (None, "--pmc %s" % args.pmc if args.full else "counters are collected with --full")
     if args.pmc == "live":
         live_summary, live_why_not = live_pmc_summary(args)
     t_pmc = time.time() - t_start
@@ -552,7 +572,7 @@ def main():
         if dumped is not None:
             out["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
         t_host = time.time()
-        if world == 1 and dist is None and not args.no_host_delivery:
+        if args.full and world == 1 and dist is None and not args.no_host_delivery:
             out["host_delivered"] = host_delivery(rt, scene, session)
             # the reference's own boundary (10x10 tile stream into host memory) as one number next to `value`
             out["value_host_delivered"] = out["host_delivered"]["rt_render"]["value"]
@@ -560,12 +580,13 @@ def main():
                 k: round(out["host_delivered"][k]["ms"] / ms_per_step, 4) for k in ("rt_render", "rt_render_frame")}
         t_host = time.time() - t_host
         t_cpu = time.time()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(session, args.cpu_seconds)
         # where the wall time of this command went (the timed region is `steps` x `ms_per_step`; the rest is evidence)
-        out["wall_s"] = {"live_counter_passes": round(t_pmc, 1), "timed_region": round(elapsed, 2),
-                         "host_delivery_calls": round(t_host, 1), "cpu_baseline": round(time.time() - t_cpu, 1),
-                         "total": round(time.time() - t_start, 1)}
+        out["wall_s"] = {"timed_region": round(elapsed, 2), "total": round(time.time() - t_start, 1)}
+        if args.full:
+            out["wall_s"].update({"live_counter_passes": round(t_pmc, 1), "host_delivery_calls": round(t_host, 1),
+                                  "cpu_baseline": round(time.time() - t_cpu, 1)})
         if rehearsal:
             out["rehearsal"] = "N ranks on ONE GPU over gloo: functional check only"
         if args.force_dist:

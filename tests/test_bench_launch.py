@@ -26,6 +26,29 @@ def test_gpus_flag_without_launcher_spawns_ranks_not_an_error():
         assert "needs a GPU" in run.stderr or "device(s) visible" in run.stderr, run.stderr[-2000:]
 
 
+def test_plain_run_collects_nothing_beyond_the_steps_and_full_brings_it_back(monkeypatch):
+    """A plain run collects no counters (and main() takes the host-delivery and CPU-baseline timings only with --full);
+    --full collects live counters by default, as every run did before the option existed; a plain run that asks for
+    counters is refused rather than silently given none."""
+    import bench
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+        return bench.parse()
+
+    plain = parse("--gpus", "1", "--steps", "3", "--warmup", "1")
+    assert not plain.full and plain.pmc == "none" and (plain.steps, plain.warmup) == (3, 1)
+    full = parse("--full")
+    assert full.full and full.pmc == "live" and not full.no_cpu_baseline and not full.no_host_delivery
+    assert parse("--full", "--pmc", "file").pmc == "file"
+    assert parse("--pmc", "none", "--no-cpu-baseline", "--no-host-delivery").pmc == "none"
+    for pmc in ("live", "file"):
+        with pytest.raises(SystemExit):
+            parse("--pmc", pmc)
+    child = parse("--pmc-child", "--full", "--workload", "c4")   # tools/pmc.py's passes: one short plain run
+    assert not child.full and child.pmc == "none" and (child.steps, child.warmup) == (1, 1)
+
+
 @pytest.mark.gpu
 def test_bench_self_launches_two_ranks(request, gpu):
     proc = getattr(request.config, "_bench_rehearsal", None)

@@ -24,7 +24,7 @@ for w in c3 c2 c4 random boxes emissive; do
 done
 for w in c3 c2 c4 boxes emissive random; do
   extra="--no-cpu-baseline"; [ $w == c3 ] && extra=""
-  timeout -k 10 400 python3 bench.py --workload $w $extra > "$out/${round}_${w}_bench.json" 2> "$out/bench_$w.err" || { tail -5 "$out/bench_$w.err"; exit 1; }
+  timeout -k 10 400 python3 bench.py --full --workload $w $extra > "$out/${round}_${w}_bench.json" 2> "$out/bench_$w.err" || { tail -5 "$out/bench_$w.err"; exit 1; }
   python3 -c "
 import json
 d=json.load(open('$out/${round}_${w}_bench.json'))
