@@ -431,6 +431,61 @@ int rt_render_progressive(RtScene *scene, const RtCamera *camera, const RtRender
                           int32_t pass_samples, RtFrameCallback callback, void *user,
                           RtCancelCallback cancelled, void *cancel_user);
 
+/* ------------------------------------------------------------------ denoising
+ * The reference's ray_color returns the first hit's normal, position, depth and obj_id beside the colour (renderer.rs:
+ * RayImageData) and renderer/denoised.rs filters the frame pass by pass with them.  These entry points do that on the
+ * device: first-hit GUIDE buffers, then an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with object,
+ * normal and plane edge stops and an optional colour stop, in f64 throughout (DESIGN.md section 4.6 has the definition).
+ *
+ * Guides: one ray per pixel, get_ray with the lens offset at zero, u = (x + 0.5) / (W - 1), v = (y + 0.5) / (H - 1)
+ * (row 0 = top), time (time_a + time_b) / 2, no random draw; the closest hit over [0.001, inf) under the scene's own
+ * closest-hit rule.  Planes (structure of arrays, W*H pixels, row-major): normal (3 f64, after set_face_normal),
+ * position (3 f64), albedo (3 f64: the texture value clamped to [0, 1] for Lambertian and Metal, 1 for Dielectric and
+ * DiffuseLight), footprint (1 f64: t * |camera.vertical| / (H - 1), the world-space size of a pixel at the hit) and
+ * obj_id (1 int32: RtPrimitive.obj_id).  A miss has obj_id -1, normal = position = 0, albedo = 1, footprint = +inf. */
+enum RtDenoiseFlags {
+    RT_DENOISE_DEMODULATE = 1 /* filter radiance / max(albedo, 1e-3) and multiply the albedo back afterwards */
+};
+typedef struct RtDenoiseParams {
+    int32_t iterations;  /* a-trous levels, 0..10 (0: the output is an exact copy of the input) */
+    int32_t flags;       /* RtDenoiseFlags */
+    double sigma_color;  /* colour stop on sqrt(radiance); <= 0 switches it off */
+    double sigma_normal; /* normal stop; <= 0 switches it off */
+    double sigma_plane;  /* plane-distance stop in pixel footprints; <= 0 switches it off */
+    int32_t _reserved[4]; /* must be 0 */
+} RtDenoiseParams;
+typedef struct RtGuides {
+    double *normal;    /* W*H*3 */
+    double *position;  /* W*H*3 */
+    double *albedo;    /* W*H*3 */
+    double *footprint; /* W*H   */
+    int32_t *obj_id;   /* W*H   */
+} RtGuides;
+
+/* The defaults: 5 iterations, demodulation on, colour stop off, sigma_normal and sigma_plane as DESIGN.md records. */
+void rt_denoise_params_default(RtDenoiseParams *out);
+/* The guides of a whole frame (params->strip_count <= 1, params->scale <= 1) into DEVICE memory of the scene's device,
+ * enqueued on `hip_stream` (NULL = default stream) without synchronising. */
+int rt_render_guides_device(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                            const RtGuides *guides_device, void *hip_stream);
+/* Filter a gamma-encoded device frame (what rt_render_frame_device writes) with device guides of the same size into
+ * out_device (rgb_device != out_device), enqueued on `hip_stream` without synchronising.  Scratch memory is the scene's. */
+int rt_denoise_device(RtScene *scene, const RtRenderParams *params, const RtDenoiseParams *denoise,
+                      const double *rgb_device, const RtGuides *guides_device, double *out_device, void *hip_stream);
+/* Host-memory convenience, synchronous: guides, upload of rgb_host, filter, download into out_host (rgb != out). */
+int rt_denoise_frame(RtScene *scene, const RtCamera *camera, const RtRenderParams *params, const RtDenoiseParams *denoise,
+                     const double *rgb_host, double *out_host);
+/* rt_render_progressive whose every callback receives the denoised frame of its pass.  The guides are traced once before
+ * pass 0; each pass's filter runs after its fold, into a device slot of its own, so the running sums are untouched.  The
+ * last callback's frame equals rt_denoise_frame applied to rt_render_frame's frame, bit for bit.  Pass boundaries,
+ * cancel, refusals and statistics are rt_render_progressive's (resolve_ms includes the filter). */
+int rt_render_progressive_denoised(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                                   int32_t pass_samples, const RtDenoiseParams *denoise, RtFrameCallback callback,
+                                   void *user, RtCancelCallback cancelled, void *cancel_user);
+/* The four that return a code refuse, as far as they take them, NULL pointers, iterations outside 0..10, non-finite
+ * sigmas, non-zero _reserved, strips, scale > 1 and rgb == out (RT_ERR_INVALID_ARGUMENT) before they touch a device.  A binding detects them by symbol lookup (RT_ABI_VERSION is
+ * unchanged by them). */
+
 /* What the reference does to a finished tile downstream of the renderer, on
  * the device: ScreenBuffer::update's tone map (image_buffer.rs:147-153) and
  * SavePng's packing `(c * 255.0) as u32 -> (r << 24 | g << 16 | b << 8 | 255)`

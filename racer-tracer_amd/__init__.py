@@ -112,6 +112,21 @@ def progressive_passes(samples, pass_samples):
     return list(out[:n.value])
 
 
+def denoise_params(**overrides):
+    """rt_denoise_params_default, with fields overridden by keyword (iterations, flags, sigma_color, sigma_normal,
+    sigma_plane) -> abi.RtDenoiseParams.  No device needed."""
+    dp = abi.RtDenoiseParams()
+    lib().rt_denoise_params_default(C.byref(dp))
+    for k, v in overrides.items():
+        setattr(dp, k, v)
+    return dp
+
+
+def guides_struct(planes):
+    """abi.RtGuides over device tensors (a dict with normal, position, albedo, footprint, obj_id)."""
+    return abi.RtGuides(*[planes[k].data_ptr() for k in ("normal", "position", "albedo", "footprint", "obj_id")])
+
+
 def device_count():
     return lib().rt_device_count()
 
@@ -221,10 +236,12 @@ class Scene:
             check(self._lib.rt_render(self._h, C.byref(camera), C.byref(params), cb, None, cancel_ptr), "rt_render", self._lib)
         return tiles
 
-    def render_progressive(self, camera, params, pass_samples, cancel=None, on_frame=None):
+    def render_progressive(self, camera, params, pass_samples, cancel=None, on_frame=None, denoise=None):
         """rt_render_progressive -> list of (samples_done, float64 [H, W, 3] copy), one per pass, the last one equal to
         render_frame's.  cancel: None or a callable returning True once the render should stop (as render_tiles').
-        on_frame: None or a callable(samples_done, frame) run inside each callback, with the copy that is kept."""
+        on_frame: None or a callable(samples_done, frame) run inside each callback, with the copy that is kept.
+        denoise: None, True (the defaults) or an abi.RtDenoiseParams: rt_render_progressive_denoised, every frame
+        filtered, the last one equal to denoise(camera, params, render_frame(...))."""
         frames = []
         h, w = params.height, params.width
 
@@ -236,9 +253,52 @@ class Scene:
 
         cb = abi.RtFrameCallback(on_pass)
         hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
-        check(self._lib.rt_render_progressive(self._h, C.byref(camera), C.byref(params), int(pass_samples), cb, None, hook, None),
-              "rt_render_progressive", self._lib)
+        if denoise is None or denoise is False:
+            check(self._lib.rt_render_progressive(self._h, C.byref(camera), C.byref(params), int(pass_samples), cb, None, hook,
+                                                  None), "rt_render_progressive", self._lib)
+        else:
+            dp = denoise_params() if denoise is True else denoise
+            check(self._lib.rt_render_progressive_denoised(self._h, C.byref(camera), C.byref(params), int(pass_samples),
+                                                           C.byref(dp), cb, None, hook, None),
+                  "rt_render_progressive_denoised", self._lib)
         return frames
+
+    def render_guides(self, camera, params):
+        """rt_render_guides_device on device buffers of torch, copied back -> dict of numpy planes: normal, position,
+        albedo [H, W, 3] f64, footprint [H, W] f64, obj_id [H, W] int32."""
+        import torch
+        h, w = params.height, params.width
+        dev = torch.device("cuda", self.device)
+        planes = {"normal": torch.empty((h, w, 3), dtype=torch.float64, device=dev),
+                  "position": torch.empty((h, w, 3), dtype=torch.float64, device=dev),
+                  "albedo": torch.empty((h, w, 3), dtype=torch.float64, device=dev),
+                  "footprint": torch.empty((h, w), dtype=torch.float64, device=dev),
+                  "obj_id": torch.empty((h, w), dtype=torch.int32, device=dev)}
+        g = guides_struct(planes)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            check(self._lib.rt_render_guides_device(self._h, C.byref(camera), C.byref(params), C.byref(g),
+                                                    C.c_void_p(stream.cuda_stream)), "rt_render_guides_device", self._lib)
+            stream.synchronize()
+        return {k: v.cpu().numpy() for k, v in planes.items()}
+
+    def denoise_device(self, params, rgb_ptr, guides, out_ptr, dparams=None, stream=None):
+        """rt_denoise_device on device addresses (ints); guides: an abi.RtGuides of device addresses."""
+        dp = dparams if dparams is not None else denoise_params()
+        check(self._lib.rt_denoise_device(self._h, C.byref(params), C.byref(dp), C.c_void_p(rgb_ptr), C.byref(guides),
+                                          C.c_void_p(out_ptr), C.c_void_p(stream or 0)), "rt_denoise_device", self._lib)
+
+    def denoise(self, camera, params, rgb, dparams=None):
+        """rt_denoise_frame: the guides of (camera, params) and the filter over a host frame -> float64 [H, W, 3]."""
+        dp = dparams if dparams is not None else denoise_params()
+        src = np.ascontiguousarray(rgb, dtype=np.float64)
+        if src.shape != (params.height, params.width, 3):
+            raise ValueError("rgb must be float64 [H, W, 3] of the params' size")
+        out = np.zeros_like(src)
+        check(self._lib.rt_denoise_frame(self._h, C.byref(camera), C.byref(params), C.byref(dp),
+                                         src.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_double))),
+              "rt_denoise_frame", self._lib)
+        return out
 
     def variant(self):
         """rtdev_scene_variant: which trace kernel rt_scene_create_ex chose -> dict of abi.VARIANT_FIELDS."""

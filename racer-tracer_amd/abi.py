@@ -112,6 +112,19 @@ class RtSceneOptions(C.Structure):
                 ("_reserved", C.c_int32 * 4)]
 
 
+RT_DENOISE_DEMODULATE = 1
+
+
+class RtDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_int32), ("sigma_color", C.c_double), ("sigma_normal", C.c_double),
+                ("sigma_plane", C.c_double), ("_reserved", C.c_int32 * 4)]
+
+
+class RtGuides(C.Structure):
+    _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("albedo", C.c_void_p), ("footprint", C.c_void_p),
+                ("obj_id", C.c_void_p)]
+
+
 RtTileCallback = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_int32,
                              C.c_int32, C.c_int32)
 # int (*RtCancelCallback)(void *cancel_user): non-zero = stop (renderer.rs:25-30 do_cancel)
@@ -140,6 +153,16 @@ PROTOTYPES = {
                                   RtTileCallback, C.c_void_p, RtCancelCallback, C.c_void_p]),
     "rt_render_progressive": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.c_int32,
                                         RtFrameCallback, C.c_void_p, RtCancelCallback, C.c_void_p]),
+    "rt_denoise_params_default": (None, [C.POINTER(RtDenoiseParams)]),
+    "rt_render_guides_device": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.POINTER(RtGuides),
+                                          C.c_void_p]),
+    "rt_denoise_device": (C.c_int, [C.c_void_p, C.POINTER(RtRenderParams), C.POINTER(RtDenoiseParams), C.c_void_p,
+                                    C.POINTER(RtGuides), C.c_void_p, C.c_void_p]),
+    "rt_denoise_frame": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.POINTER(RtDenoiseParams),
+                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rt_render_progressive_denoised": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.c_int32,
+                                                 C.POINTER(RtDenoiseParams), RtFrameCallback, C.c_void_p, RtCancelCallback,
+                                                 C.c_void_p]),
     "rt_post_rgba8_device": (C.c_int, [C.c_void_p, C.POINTER(RtToneMap), C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rt_render_frame_rgba8": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),

@@ -407,6 +407,10 @@ int fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtde
 
 } // namespace
 
+int rtapi::fill_trace_args(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, rtdev::TraceArgs &a) {
+    return fill_args(s, camera, p, a);
+}
+
 int rtapi::chunk_count(int samples) { return (int)chunk_plan(samples).size() - 1; }
 std::vector<int> rtapi::chunk_starts(int samples) { return chunk_plan(samples); }
 
@@ -859,6 +863,7 @@ std::vector<rtdev::Prim> pack_prims(const RtSceneDesc *d) {
             q.rot_cos = 1.0;
         }
         q.material = p.material;
+        q.obj_id = p.obj_id;
         q.inv_radius = (p.kind == RT_PRIM_SPHERE || p.kind == RT_PRIM_MOVING_SPHERE) ? 1.0 / p.p[3] : 0.0;
         q.radius2 = p.p[3] * p.p[3];
         if (p.kind == RT_PRIM_MOVING_SPHERE) { // device packing: tr = pos_b - pos_a, rot_sin = time_a, rot_cos = 1/(time_b - time_a)

@@ -33,7 +33,7 @@ struct alignas(16) Prim { // 192 B
     int32_t kind;         // RtPrimitiveKind
     int32_t flags;        // RtPrimitiveFlags
     int32_t material;
-    int32_t _pad0;
+    int32_t obj_id;       // RtPrimitive.obj_id: read by the guide kernel only (rt_denoise.hip)
     double inv_radius;    // sphere: 1.0 / radius (sphere.rs:61 divides via reciprocal)
     double radius2;       // sphere: radius * radius (sphere.rs:43), formed once at upload
     double _pad1;

@@ -62,8 +62,9 @@ int reserve_passes(RtScene *s, const RtRenderParams *p, int passes, size_t n) {
     return RT_OK;
 }
 
+// dn: the filter of rt_render_progressive_denoised, or NULL
 int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams *p, int pass_samples, RtFrameCallback callback,
-                       void *user, const Cancel &cancel) {
+                       void *user, const Cancel &cancel, const RtDenoiseParams *dn = nullptr) {
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     if (!callback) return fail(RT_ERR_INVALID_ARGUMENT, "callback is NULL");
     if (pass_samples <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "pass_samples must be positive");
@@ -71,6 +72,7 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     if (rc != RT_OK) return rc;
     if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "progressive frames are whole frames: params->strip_* is not supported here");
     if (p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "progressive frames are full-resolution frames: params->scale must be 0 or 1");
+    if (dn && (rc = rtapi::check_denoise(p, dn)) != RT_OK) return rc;
     if (s->use_v1) return fail(RT_ERR_UNSUPPORTED, "rt_render_progressive needs the pooled kernel (the v1 kernel has no sample chunks)");
     if (cancel.raised()) return RT_ERR_CANCEL_EVENT; // cpu.rs:82-85, as rt_render_ex
     RT_HIP(hipSetDevice(s->device));
@@ -80,19 +82,29 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     const size_t n = (size_t)p->width * (size_t)p->height * 3; // a frame, and a slice (whole-frame slices: slice_rows = height)
     if ((rc = reserve_passes(s, p, passes, n)) != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
+    // denoised: the guides, the filter's scratch and a third device frame slot, the filter's output
+    if (dn && (rc = rtapi::reserve_denoise(s, n / 3, true)) != RT_OK) return rc;
+    if (dn && b.frame.count < 3 * n) RT_HIP(b.frame.alloc(3 * n));
+    const RtGuides guides = dn ? rtapi::scene_guides(s, n / 3) : RtGuides();
     const hipStream_t stream = b.stream, copy = b.stream_copy;
     rtapi::PoolPasses pp;
     double kernel_ms = 0.0, fold_ms = 0.0;
 
     auto enqueue_pass = [&](int k) -> int {
         const int slot = k & 1, c0 = k > 0 ? ends[(size_t)k - 1] : 0, c1 = ends[(size_t)k];
-        double *dev = b.frame.ptr + (size_t)slot * n;
+        double *dev = b.frame.ptr + (size_t)slot * n; // (then the filter's output, when denoised)
         RT_HIP(hipEventRecord(b.ev_pass_begin[slot], stream));
         const int rc2 = rtapi::enqueue_chunks(s, pp, c0, c1, stream);
         if (rc2 != RT_OK) return rc2;
         RT_HIP(hipEventRecord(b.ev_pass_traced[slot], stream));
         if (k >= 2) RT_HIP(hipStreamWaitEvent(stream, b.ev_copied[slot], 0)); // device slot k % 2 held pass k - 2's frame
         RT_HIP(s->kernels->fold_chunks(b.partial.ptr, b.accum.ptr, dev, n, c0, c1, starts[(size_t)c1], stream));
+        if (dn) { // the filter writes the third slot, which copy k - 1 must have read first
+            if (k >= 1) RT_HIP(hipStreamWaitEvent(stream, b.ev_copied[slot ^ 1], 0));
+            const int rc2 = rtapi::enqueue_denoise(s, p, dn, dev, guides, b.frame.ptr + 2 * n, stream);
+            if (rc2 != RT_OK) return rc2;
+            dev = b.frame.ptr + 2 * n;
+        }
         RT_HIP(hipEventRecord(b.ev_folded[slot], stream));
         RT_HIP(hipStreamWaitEvent(copy, b.ev_folded[slot], 0));
         RT_HIP(hipMemcpyAsync(b.host_frame + (size_t)slot * n, dev, n * sizeof(double), hipMemcpyDeviceToHost, copy));
@@ -106,6 +118,7 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
         if (rc2 != RT_OK) return rc2;
         begun = true;
         RT_HIP(hipMemsetAsync(b.accum.ptr, 0, n * sizeof(double), stream)); // the running sums start at +0.0
+        if (dn && (rc2 = rtapi::enqueue_guides(s, camera, p, guides, stream)) != RT_OK) return rc2; // once, before pass 0
         int enqueued = 0;
         for (; enqueued < passes && enqueued < 2; ++enqueued)
             if ((rc2 = enqueue_pass(enqueued)) != RT_OK) return rc2;
@@ -154,6 +167,17 @@ int rt_render_progressive(RtScene *s, const RtCamera *camera, const RtRenderPara
                           RtFrameCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user) {
     const Cancel c{nullptr, cancelled, cancel_user};
     return rtapi::guarded("rt_render_progressive", [&] { return render_progressive(s, camera, p, pass_samples, callback, user, c); });
+}
+
+int rt_render_progressive_denoised(RtScene *s, const RtCamera *camera, const RtRenderParams *p, int32_t pass_samples,
+                                   const RtDenoiseParams *denoise, RtFrameCallback callback, void *user, RtCancelCallback cancelled,
+                                   void *cancel_user) {
+    const Cancel c{nullptr, cancelled, cancel_user};
+    return rtapi::guarded("rt_render_progressive_denoised", [&]() -> int {
+        const int rc = rtapi::check_denoise(p, denoise); // (before the scene: the filter's refusals need no device)
+        if (rc != RT_OK) return rc;
+        return render_progressive(s, camera, p, pass_samples, callback, user, c, denoise);
+    });
 }
 
 int rtdev_progressive_passes(int32_t samples, int32_t pass_samples, int32_t *out, int32_t n_out, int32_t *n_passes) {

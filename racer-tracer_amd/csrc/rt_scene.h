@@ -137,6 +137,11 @@ struct RenderBuffers {
     hipStream_t stream_copy = nullptr;
     hipEvent_t ev_pass_begin[2] = {nullptr, nullptr}, ev_pass_traced[2] = {nullptr, nullptr};
     hipEvent_t ev_folded[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
+    // denoising (rt_denoise.hip), made on first use: the guides of rt_denoise_frame and rt_render_progressive_denoised —
+    // planes [normal 3 | position 3 | albedo 3 | footprint 1] x W*H doubles and obj_id x W*H — and the filter's two
+    // ping-pong buffers of W*H*3 doubles each
+    DevBuf<double> guide_planes, denoise_scratch;
+    DevBuf<int32_t> guide_ids;
 
     // what rt_scene_create makes when it takes no set over: only such a set is worth caching
     bool complete() const {
@@ -150,6 +155,9 @@ struct RenderBuffers {
         frame.release();
         rgba.release();
         segments.release();
+        guide_planes.release();
+        denoise_scratch.release();
+        guide_ids.release();
         tile_done.release();
         region_done.release();
         if (host_frame) (void)hipHostFree(host_frame);
@@ -168,6 +176,12 @@ struct RenderBuffers {
 };
 
 } // namespace rtapi
+
+// The device launchers of rt_denoise.hip (compiled once, RT_ARITH_FAST): guide rays of a whole frame, and one step of the
+// filter — demodulation (`step` < 0), a-trous iteration `step` (0-based), remodulation (`step` == iterations).
+extern "C" hipError_t rtdev_launch_guides(const rtdev::TraceArgs *args, const RtGuides *guides, hipStream_t stream);
+extern "C" hipError_t rtdev_launch_denoise_step(const RtDenoiseParams *d, int step, int width, int height, const double *in,
+                                                const RtGuides *guides, double *out, hipStream_t stream);
 
 struct RtScene {
     int device = 0;
@@ -293,6 +307,18 @@ struct PoolPasses {
 int begin_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p, hipStream_t stream, int max_launches,
                  bool cancellable, PoolPasses &pp);
 int enqueue_chunks(RtScene *s, PoolPasses &pp, int c0, int c1, hipStream_t stream);
+// Denoising (rt_denoise.hip).  check_denoise: the filter's parameters (NULL, iterations, sigmas, _reserved) and a whole
+// frame's size (strips and scale > 1 refused).  reserve_denoise: the filter's scratch and, with `own_guides`, the scene's
+// guide planes for a W*H frame, before the first launch.  scene_guides: those planes as an RtGuides.  enqueue_guides /
+// enqueue_denoise: the guide launch and the filter's launches on `stream` (arguments checked by the caller).
+int check_denoise(const RtRenderParams *p, const RtDenoiseParams *d);
+// The trace kernels' argument block of a render (rt_api.hip: fill_args), for launches of other kernels that trace rays.
+int fill_trace_args(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, rtdev::TraceArgs &a);
+int reserve_denoise(RtScene *s, size_t pixels, bool own_guides);
+RtGuides scene_guides(RtScene *s, size_t pixels);
+int enqueue_guides(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtGuides &g, hipStream_t stream);
+int enqueue_denoise(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, const double *rgb, const RtGuides &g,
+                    double *out, hipStream_t stream);
 // The pinned host frame of the host-output entry points, at least `doubles` long (rt_deliver.hip).
 int ensure_host_frame(RtScene *s, size_t doubles);
 // Rows of the owned-row grid of a render with these parameters (a multiple of strip_rows with strips).

@@ -62,6 +62,7 @@ struct Args { // config.rs:12-28
     uint64_t seed = 1;
     int device = 0;
     int devices = 1; // --devices N: render the frame on devices device .. device+N-1 (rt_render_frame_multi)
+    bool denoise = false; // --denoise: filter the assembled frame (rt_denoise_frame) before tone map and PNG
     bool help = false;
 
     static Args parse(int argc, const char *const *argv);

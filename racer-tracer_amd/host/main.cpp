@@ -4,7 +4,8 @@
 //     -s/--scene  <file.yml|sandbox|random>
 //     --image-action <png|none>
 // plus --seed, --device and --devices N (the frame is sharded over N GPUs of this
-// process the way the reference shards it over its rayon pool, cpu.rs:118-131).  The reference opens a window and renders when R
+// process the way the reference shards it over its rayon pool, cpu.rs:118-131) and --denoise (the assembled frame goes
+// through rt_denoise_frame on the first device before the tone map and the PNG).  The reference opens a window and renders when R
 // is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -22,12 +23,17 @@ struct ScreenBuffer { // image_buffer.rs:104-170: tone-map each tile, keep the f
     RthSession *session;
     int width, height;
     std::vector<double> buffer;
+    std::vector<double> raw; // --denoise: the frame before the tone map
 };
 
 void on_tile(void *user, const double *rgb, int32_t r, int32_t c, int32_t w, int32_t h) {
     ScreenBuffer *sb = static_cast<ScreenBuffer *>(user);
     std::vector<double> mapped((size_t)w * (size_t)h * 3);
     rth_tone_map(sb->session, rgb, mapped.data(), (size_t)w * (size_t)h);
+    if (!sb->raw.empty())
+        for (int row = 0; row < h; ++row)
+            memcpy(&sb->raw[((size_t)(r + row) * (size_t)sb->width + (size_t)c) * 3], &rgb[(size_t)row * (size_t)w * 3],
+                   (size_t)w * 3 * sizeof(double));
     for (int row = 0; row < h; ++row)
         memcpy(&sb->buffer[((size_t)(r + row) * (size_t)sb->width + (size_t)c) * 3], &mapped[(size_t)row * (size_t)w * 3],
                (size_t)w * 3 * sizeof(double));
@@ -44,7 +50,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -77,7 +83,8 @@ int main(int argc, char **argv) {
         }
         scenes.push_back(scene);
     }
-    ScreenBuffer sb{session, params.width, params.height, std::vector<double>((size_t)params.width * (size_t)params.height * 3, 0.0)};
+    const size_t n_rgb = (size_t)params.width * (size_t)params.height * 3;
+    ScreenBuffer sb{session, params.width, params.height, std::vector<double>(n_rgb, 0.0), std::vector<double>(args.denoise ? n_rgb : 0, 0.0)};
     fprintf(stderr, "Rendering image...\n"); // interactive.rs:229
     auto t0 = std::chrono::steady_clock::now();
     // the reference's tile stream (cpu.rs:64-70): every finished tile goes through ScreenBuffer::update's tone map;
@@ -86,6 +93,13 @@ int main(int argc, char **argv) {
         rc = rt_render(scenes[0], rth_session_camera(session), &params, on_tile, &sb, nullptr);
     } else {
         rc = rt_render_multi(scenes.data(), (int)scenes.size(), rth_session_camera(session), &params, 0, on_tile, &sb, nullptr, nullptr);
+    }
+    if (rc == RT_OK && args.denoise) { // the whole frame, filtered, then tone-mapped like the tiles were
+        RtDenoiseParams dp;
+        rt_denoise_params_default(&dp);
+        std::vector<double> filtered(n_rgb);
+        rc = rt_denoise_frame(scenes[0], rth_session_camera(session), &params, &dp, sb.raw.data(), filtered.data());
+        if (rc == RT_OK) rth_tone_map(session, filtered.data(), sb.buffer.data(), n_rgb / 3);
     }
     double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rc != RT_OK) {

@@ -1,0 +1,222 @@
+"""The denoiser on the device (csrc/rt_denoise.hip): guide buffers against the CPU oracle, the filter
+against its numpy model (tests/denoise_model.py), the object edge stop, the picture quality it buys, the progressive form
+and the CLI's --denoise."""
+import ctypes as C
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import denoise_model as M
+import scenes_py as S
+import variant_scenes as V
+
+pytestmark = pytest.mark.gpu
+abi = S.abi
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def moving_scene():
+    """Moving spheres over a ground sphere: the guides' time (the middle of the shutter) decides where they are hit."""
+    textures = [abi.solid((0.5, 0.5, 0.5)), abi.solid((0.9, 0.2, 0.1)), abi.solid((0.1, 0.3, 0.9))]
+    materials = [abi.material(S.L, 0), abi.material(S.L, 1), abi.material(S.M, 2, fuzz=0.2)]
+    prims = [abi.sphere((0.0, -1000.0, 0.0), 1000.0, 0, 1),
+             abi.moving_sphere((-1.0, 0.5, 0.0), (-1.0, 1.0, 0.0), 0.5, 1, 2),
+             abi.moving_sphere((1.0, 0.5, 0.0), (1.6, 0.5, 0.0), 0.5, 2, 3)]
+    cam = dict(look_from=(0.0, 2.0, 6.0), look_at=(0.0, 0.5, 0.0), vfov=40.0, aperture=0.0, focus_distance=6.0)
+    return abi.SceneBundle(prims, materials, textures, abi.sky()), cam
+
+
+GUIDE_SCENES = {
+    "three_balls": lambda: S.three_balls()[:2],
+    "cornell_box_boxes": lambda: S.cornell_box_boxes()[:2],
+    "bvh_in_lds": lambda: V.build((V.ANY, 1, 1, 1)),
+    "bvh_global": lambda: V.large_bvh_scene(),
+    "moving": moving_scene,
+}
+
+
+@pytest.mark.parametrize("name", list(GUIDE_SCENES))
+def test_guides_match_the_oracle(rt, orc, gpu, name):
+    bundle, cam = GUIDE_SCENES[name]()
+    w, h = 200, 150
+    camera = S.camera_for(cam, w, h)
+    scene = rt.Scene(bundle, closest_hit=abi.RT_HIT_BVH if name.startswith("bvh") else abi.RT_HIT_AUTO)
+    try:
+        if name.startswith("bvh"):
+            assert scene.variant()["use_bvh"] == 1
+            assert scene.variant()["bvh_nodes_in_lds"] == (1 if name == "bvh_in_lds" else 0)
+        got = scene.render_guides(camera, abi.render_params(w, h, 1))
+    finally:
+        scene.close()
+    want = M.oracle_guides(orc, bundle, camera, w, h)
+    same = got["obj_id"] == want["obj_id"]
+    assert same.mean() >= 0.9999, "obj_id differs on %d pixels" % (~same).sum()
+    assert (want["obj_id"] >= 0).any()
+    for plane in ("normal", "position", "albedo"):
+        assert np.max(np.abs(got[plane][same] - want[plane][same])) < 1e-9, plane
+    hit = same & (want["obj_id"] >= 0)
+    assert np.max(np.abs(got["footprint"][hit] - want["footprint"][hit])) < 1e-9
+    miss = same & (want["obj_id"] < 0)
+    assert np.all(np.isinf(got["footprint"][miss])) and np.all(got["albedo"][miss] == 1.0)
+    assert np.all(got["normal"][miss] == 0.0) and np.all(got["position"][miss] == 0.0)
+
+
+def _device_denoise(rt, scene, params, rgb, guides_np, dp):
+    import torch
+    dev = torch.device("cuda", scene.device)
+    planes = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in guides_np.items()}
+    src = torch.from_numpy(np.ascontiguousarray(rgb)).to(dev)
+    out = torch.full_like(src, float("nan"))
+    g = rt.guides_struct(planes)
+    torch.cuda.synchronize(dev)
+    scene.denoise_device(params, src.data_ptr(), g, out.data_ptr(), dp)
+    torch.cuda.synchronize(dev)
+    return out.cpu().numpy()
+
+
+FILTER_CASES = [(k, flags, sc) for k in (0, 1, 5) for flags in (0, abi.RT_DENOISE_DEMODULATE) for sc in (0.0, 0.5)]
+
+
+@pytest.mark.parametrize("scene_name", ["cornell_box_boxes", "three_balls"])
+def test_the_filter_matches_the_model(rt, gpu, scene_name):
+    bundle, cam = GUIDE_SCENES[scene_name]()
+    w, h = 96, 80
+    camera, params = S.camera_for(cam, w, h), abi.render_params(w, h, 16)
+    scene = rt.Scene(bundle)
+    try:
+        rgb = scene.render_frame(camera, params)
+        guides = scene.render_guides(camera, params)
+        for k, flags, sc in FILTER_CASES:
+            dp = rt.denoise_params(iterations=k, flags=flags, sigma_color=sc)
+            got = _device_denoise(rt, scene, params, rgb, guides, dp)
+            want = M.denoise(rgb, guides, **M.params_kwargs(dp))
+            if k == 0:
+                assert np.array_equal(got, rgb)
+            assert np.max(np.abs(got - want)) < 1e-10, (k, flags, sc)
+            # the host-memory form is the same filter on the same guides
+            assert np.array_equal(scene.denoise(camera, params, rgb, dp), got), (k, flags, sc)
+    finally:
+        scene.close()
+
+
+def test_edge_stop_keeps_each_ball_within_its_own_range(rt, gpu):
+    bundle, cam, _ = S.two_balls()
+    w, h = 160, 120
+    camera, params = S.camera_for(cam, w, h), abi.render_params(w, h, 16)
+    scene = rt.Scene(bundle)
+    try:
+        rgb = scene.render_frame(camera, params)
+        guides = scene.render_guides(camera, params)
+        out = scene.denoise(camera, params, rgb)
+    finally:
+        scene.close()
+    alb = np.maximum(guides["albedo"], 1e-3)
+    I, J = rgb * rgb / alb, out * out / alb
+    for oid in (1, 2):
+        m = guides["obj_id"] == oid
+        assert m.sum() > 100
+        lo, hi = I[m].min(axis=0), I[m].max(axis=0)
+        assert np.all(J[m] >= lo * (1 - 1e-9) - 1e-12) and np.all(J[m] <= hi * (1 + 1e-9) + 1e-12), oid
+
+
+def test_denoising_halves_the_error_of_a_16_spp_cornell_box_boxes(rt, gpu):
+    bundle, cam, _ = S.cornell_box_boxes()
+    w = h = 256
+    camera = S.camera_for(cam, w, h)
+    scene = rt.Scene(bundle)
+    try:
+        ref = scene.render_frame(camera, abi.render_params(w, h, 4096, seed=7))
+        params = abi.render_params(w, h, 16, seed=1)
+        noisy = scene.render_frame(camera, params)
+        den = scene.denoise(camera, params, noisy)
+    finally:
+        scene.close()
+    raw, filtered = M.gamma_rmse(noisy, ref), M.gamma_rmse(den, ref)
+    assert filtered <= 0.5 * raw, (raw, filtered)
+
+
+# ---- progressive ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("form", list(V.SPECS), ids=lambda f: "%s%s%s%s" % ("RSA"[f[0]], "t" if f[1] else "", "s" if f[2] else "",
+                                                                              "-bvh" if f[3] else ""))
+def test_progressive_denoised_ends_on_the_denoised_one_shot_frame(rt, gpu, form):
+    bundle, cam = V.build(form)
+    closest_hit = abi.RT_HIT_BVH if form[3] else abi.RT_HIT_LINEAR
+    camera, params = S.camera_for(cam, V.W, V.H), abi.render_params(V.W, V.H, 96, max_depth=V.DEPTH)
+    scene = rt.Scene(bundle, closest_hit=closest_hit)
+    try:
+        want = scene.denoise(camera, params, scene.render_frame(camera, params))
+        for pass_samples in (1, 30):
+            frames = scene.render_progressive(camera, params, pass_samples, denoise=True)
+            assert [d for d, _ in frames] == rt.progressive_passes(params.samples, pass_samples)
+            assert np.array_equal(frames[-1][1], want), pass_samples
+        # every frame is the denoised running frame: the first one against the plain pass's frame
+        plain = scene.render_progressive(camera, params, 30)
+        assert np.array_equal(frames[0][1], scene.denoise(camera, params, plain[0][1]))
+    finally:
+        scene.close()
+
+
+def test_progressive_denoised_cancel_and_refusals(rt, gpu):
+    bundle, cam, _ = S.cornell_box()
+    w, h = 160, 90
+    camera, params = S.camera_for(cam, w, h), abi.render_params(w, h, 2048)
+    small = abi.render_params(w, h, 96)
+    scene = rt.Scene(bundle)
+    try:
+        want = scene.denoise(camera, small, scene.render_frame(camera, small))
+        calls = []
+        with pytest.raises(rt.RtError) as err:
+            scene.render_progressive(camera, small, 1, cancel=lambda: True, on_frame=lambda *a: calls.append(a), denoise=True)
+        assert err.value.code == abi.RT_ERR_CANCEL_EVENT and calls == []
+        raised = []
+        frames = scene.render_progressive(camera, params, 64, cancel=lambda: bool(raised),
+                                          on_frame=lambda done, _: raised.append(done), denoise=True)
+        first = rt.progressive_passes(2048, 64)[0]
+        assert [d for d, _ in frames] == [first] and raised == [first]
+        for p, code in ((abi.render_params(w, h, 96, strip_rows=8, strip_count=2, strip_index=0), abi.RT_ERR_INVALID_ARGUMENT),
+                        (abi.render_params(w, h, 96, scale=2), abi.RT_ERR_INVALID_ARGUMENT)):
+            with pytest.raises(rt.RtError) as err:
+                scene.render_progressive(camera, p, 1, denoise=True)
+            assert err.value.code == code
+        with pytest.raises(rt.RtError) as err:
+            scene.render_progressive(camera, small, 0, denoise=True)
+        assert err.value.code == abi.RT_ERR_INVALID_ARGUMENT
+        with pytest.raises(rt.RtError) as err:
+            scene.render_progressive(camera, small, 1, denoise=rt.denoise_params(iterations=11))
+        assert err.value.code == abi.RT_ERR_INVALID_ARGUMENT
+        # nothing stale after all that
+        assert np.array_equal(scene.render_progressive(camera, small, 30, denoise=True)[-1][1], want)
+    finally:
+        scene.close()
+    v1 = rt.Scene(bundle, kernel=abi.RT_KERNEL_V1)
+    try:
+        with pytest.raises(rt.RtError) as err:
+            v1.render_progressive(camera, small, 1, denoise=True)
+        assert err.value.code == abi.RT_ERR_UNSUPPORTED
+    finally:
+        v1.close()
+
+
+# ---- CLI --------------------------------------------------------------------------------------------------------------
+
+def test_cli_denoise_writes_a_different_png(gpu):
+    exe = os.path.join(ROOT, "racer-tracer_amd", "bin", "racer-tracer-amd")
+    base = [exe, "-c", os.path.join(ROOT, "scenes", "config_c1.yml"), "-s", os.path.join(ROOT, "scenes", "three_balls.yml"),
+            "--image-action", "png", "--seed", "1"]
+    pngs = []
+    for extra in ([], ["--denoise"]):
+        out = tempfile.mkdtemp(prefix="rt_cli_denoise_")
+        r = subprocess.run(base + extra, capture_output=True, text=True, cwd=out, timeout=600)
+        assert r.returncode == 0, r.stderr
+        m = re.search(r"Saved image to: (.+)", r.stderr)
+        assert m, r.stderr
+        path = m.group(1).strip()
+        if not os.path.isabs(path):
+            path = os.path.join(out, path)
+        pngs.append(open(path, "rb").read())
+    assert pngs[0] != pngs[1]
