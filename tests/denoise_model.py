@@ -2,7 +2,8 @@
 
 guides: dict of numpy planes as Scene.render_guides returns them — normal, position, albedo [H, W, 3] f64, footprint [H, W]
 f64, obj_id [H, W] int32.  The arithmetic follows the kernel's order (taps dy, then dx; weights h(dx) h(dy) w_n w_x w_c), so
-the two agree to rounding.  oracle_guides() forms the same planes with the CPU oracle.
+the two agree to rounding.  oracle_guides() forms the same planes with the CPU oracle.  The model itself is held to
+tests/denoise_reference.py, a 40-digit restatement of DESIGN.md 4.6 that shares nothing with it.
 """
 import ctypes as C
 import math
@@ -110,6 +111,69 @@ def oracle_guides(orc, bundle, cam, width, height):
     finally:
         lib.orc_scene_free(scene)
     return g
+
+
+def synthetic_guides(h=24, w=32, seed=3):
+    """Caller-made guide planes [h, w] that reach the filter's corners, and the generator that made them.
+
+    Two objects split by a diagonal with noisy normals and positions on two planes; a miss band on the left (w >= 10)
+    and misses on a lattice inside the frame; single-pixel islands (id 7) on another lattice, none 4-adjacent to another;
+    a footprint that jumps by up to 20x from one pixel to the next; albedo channels at 0 and in (0, 1e-3), below the
+    demodulation clamp.  Misses carry the values rt_abi.h gives them: id -1, normal and position 0, albedo 1,
+    footprint inf."""
+    rng = np.random.default_rng(seed)
+    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    ids = np.where(xs + ys < (h + w) // 2, 1, 2).astype(np.int32)
+    ids[(ys % 4 == 1) & (xs % 5 == 1)] = 7
+    ids[:, :w // 10] = -1
+    ids[(ys % 3 == 0) & (xs % 4 == 1)] = -1
+    n = np.zeros((h, w, 3))
+    n[..., 2] = 1.0
+    n[ids == 2] = (0.0, 0.6, 0.8)
+    n[ids == 7] = (0.6, 0.0, 0.8)
+    n = n + rng.normal(0.0, 0.05, n.shape)
+    x = np.stack([xs * 0.1, ys * 0.1, rng.normal(0.0, 0.01, (h, w))], axis=-1)
+    x[ids == 2, 2] += 0.2 * ys[ids == 2]
+    albedo = rng.uniform(0.05, 1.0, (h, w, 3))
+    pick = rng.random((h, w, 3))
+    albedo[pick < 0.06] = 0.0
+    low = (pick >= 0.06) & (pick < 0.12)
+    albedo[low] = rng.uniform(1e-6, 9e-4, low.sum())
+    g = {"normal": n, "position": x, "albedo": albedo, "footprint": 0.05 * np.exp(rng.uniform(-1.5, 1.5, (h, w))),
+         "obj_id": ids}
+    miss = ids < 0
+    g["normal"][miss] = 0.0
+    g["position"][miss] = 0.0
+    g["albedo"][miss] = 1.0
+    g["footprint"][miss] = np.inf
+    return g, rng
+
+
+def synthetic_frame(g, rng):
+    """A gamma-encoded frame for synthetic_guides: g in [0.2, 1.5) with about 8 % of the pixels scaled by 10..630 (up to
+    g ~ 1e3), about 5 % black and about 5 % of the channels 0."""
+    h, w = g["obj_id"].shape
+    rgb = rng.uniform(0.2, 1.5, (h, w, 3))
+    pick = rng.random((h, w))
+    rgb[pick < 0.08] *= 10.0 ** rng.uniform(1.0, 2.8, ((pick < 0.08).sum(), 1))
+    rgb[(pick >= 0.08) & (pick < 0.13)] = 0.0
+    rgb[rng.random((h, w, 3)) < 0.05] = 0.0
+    return rgb
+
+
+# Where a true output's square (the linear radiance) lies below the f64 normal range (|g| < 2^-511), no f64 pipeline can
+# produce it: an edge stop of exp(-x), x > 745, underflows to 0.  A high-precision reference still carries e^-800 of a
+# neighbour into a black pixel, so there, and only there, any value below the bound is accepted.
+TINY = 2.0 ** -511
+
+
+def mismatch(got, want, rel):
+    """Number of channels where |got - want| > rel |want| (zeros exact, values below TINY aside)."""
+    got, want = np.asarray(got), np.asarray(want)
+    with np.errstate(invalid="ignore"):
+        ok = np.abs(got - want) <= rel * np.abs(want)
+    ok |= (np.abs(want) < TINY) & (np.abs(got) < TINY)
+    return int((~ok).sum())
 
 
 def gamma_rmse(a, b):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import denoise_model as M
+import denoise_reference as R
 import scenes_py as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,45 +22,26 @@ ENTRY_POINTS = ("rt_denoise_params_default", "rt_render_guides_device", "rt_deno
 
 # ---- the model on synthetic input -----------------------------------------------------------------------------------
 
-def synthetic_guides(h=24, w=32, seed=3):
-    """Two objects split by a diagonal, a miss band on the left, noisy normals and positions on planes."""
-    rng = np.random.default_rng(seed)
-    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    ids = np.where(xs + ys < (h + w) // 2, 1, 2).astype(np.int32)
-    ids[:, :3] = -1
-    n = np.zeros((h, w, 3))
-    n[..., 2] = 1.0
-    n[ids == 2] = (0.0, 0.6, 0.8)
-    n = n + rng.normal(0.0, 0.05, n.shape)
-    x = np.stack([xs * 0.1, ys * 0.1, rng.normal(0.0, 0.01, (h, w))], axis=-1)
-    g = {"normal": n, "position": x, "albedo": rng.uniform(0.05, 1.0, (h, w, 3)), "footprint": np.full((h, w), 0.1),
-         "obj_id": ids}
-    miss = ids < 0
-    g["normal"][miss] = 0.0
-    g["position"][miss] = 0.0
-    g["albedo"][miss] = 1.0
-    g["footprint"][miss] = np.inf
-    return g, rng
-
-
 SETTINGS = [dict(), dict(flags=0), dict(sigma_color=0.5), dict(sigma_normal=0.0, sigma_plane=0.0),
             dict(iterations=1), dict(iterations=10, sigma_color=2.0)]
 
 
 @pytest.mark.parametrize("kw", SETTINGS, ids=lambda kw: ",".join("%s=%s" % i for i in kw.items()) or "defaults")
 def test_a_constant_radiance_stays_constant(kw):
-    g, _ = synthetic_guides()
+    g, _ = M.synthetic_guides()
     flags = kw.get("flags", M.DEMODULATE)
     L = np.full(g["albedo"].shape, 0.3)
-    if flags & M.DEMODULATE:   # constant demodulated radiance: the frame carries the albedo
-        L = L * g["albedo"]
+    want = np.sqrt(L)
+    if flags & M.DEMODULATE:   # constant demodulated radiance: the frame carries the (clamped) albedo, the output the albedo
+        L = L * np.maximum(g["albedo"], 1e-3)
+        want = np.sqrt(0.3 * g["albedo"])
     rgb = np.sqrt(L)
     out = M.denoise(rgb, g, **kw)
-    assert np.max(np.abs(out - rgb)) < 1e-12
+    assert np.max(np.abs(out - want)) < 1e-12
 
 
 def test_zero_iterations_is_an_exact_copy():
-    g, rng = synthetic_guides()
+    g, rng = M.synthetic_guides()
     rgb = rng.uniform(0.0, 2.0, g["albedo"].shape)
     for flags in (0, M.DEMODULATE):
         out = M.denoise(rgb, g, iterations=0, flags=flags, sigma_color=1.0)
@@ -68,7 +50,7 @@ def test_zero_iterations_is_an_exact_copy():
 
 @pytest.mark.parametrize("kw", SETTINGS[:4], ids=["defaults", "no-demod", "colour", "no-stops"])
 def test_every_output_is_a_convex_combination_of_its_objects_inputs(kw):
-    g, rng = synthetic_guides()
+    g, rng = M.synthetic_guides()
     rgb = rng.uniform(0.0, 2.0, g["albedo"].shape)
     I = rgb * rgb
     if kw.get("flags", M.DEMODULATE) & M.DEMODULATE:
@@ -81,17 +63,18 @@ def test_every_output_is_a_convex_combination_of_its_objects_inputs(kw):
         lo, hi = I[m].min(axis=0), I[m].max(axis=0)
         assert np.all(out_I[m] >= lo - 1e-12) and np.all(out_I[m] <= hi + 1e-12)
     # ... and after five levels too, per object, in demodulated space
+    # (out^2 = I_5 albedo: the bounds are carried to the output, where an albedo below the clamp or 0 leaves I_5 unreadable)
     out = M.denoise(rgb, g, **dict(kw, iterations=5))
     L = out * out
-    J = L / np.maximum(g["albedo"], 1e-3) if flags & M.DEMODULATE else L
+    a = g["albedo"] if flags & M.DEMODULATE else np.ones_like(L)
     for oid in (1, 2):
         m = g["obj_id"] == oid
-        assert np.all(J[m] >= I[m].min(axis=0) * (1 - 1e-12) - 1e-12)
-        assert np.all(J[m] <= I[m].max(axis=0) * (1 + 1e-12) + 1e-12)
+        assert np.all(L[m] >= I[m].min(axis=0) * a[m] * (1 - 1e-12) - 1e-12)
+        assert np.all(L[m] <= I[m].max(axis=0) * a[m] * (1 + 1e-12) + 1e-12)
 
 
 def test_an_object_takes_nothing_from_its_neighbours():
-    g, rng = synthetic_guides()
+    g, rng = M.synthetic_guides()
     rgb = rng.uniform(0.0, 1.0, g["albedo"].shape)
     other = rgb.copy()
     other[g["obj_id"] == 2] *= 5.0    # change object 2 only
@@ -100,13 +83,90 @@ def test_an_object_takes_nothing_from_its_neighbours():
 
 
 def test_misses_pass_through():
-    g, rng = synthetic_guides()
+    g, rng = M.synthetic_guides()
     rgb = rng.uniform(0.0, 3.0, g["albedo"].shape)
     for kw in SETTINGS:
         out = M.denoise(rgb, g, **kw)
         miss = g["obj_id"] < 0
         # (albedo 1 on a miss; sqrt(g * g) == g for every non-negative double that neither underflows nor overflows)
         assert np.array_equal(out[miss], rgb[miss])
+
+
+# ---- the model against the independent reference (tests/denoise_reference.py) ---------------------------------------
+
+REF_SHAPES = [(2, 2), (9, 2), (13, 9), (17, 11)]     # (width, height): odd, and wider than tall and taller than wide
+# a pairwise list: iterations 0, 1, 2, 5 and 10; each stop on and off; demodulation on and off
+REF_SETTINGS = [dict(iterations=0, sigma_color=1.0),
+                dict(iterations=1),
+                dict(iterations=1, flags=0, sigma_normal=0.0, sigma_color=4.0),
+                dict(iterations=2, sigma_plane=0.0, sigma_color=4.0),
+                dict(iterations=2, flags=0, sigma_normal=0.0, sigma_plane=0.0),
+                dict(iterations=5, sigma_color=1.0),
+                dict(iterations=5, flags=0, sigma_plane=0.0),
+                dict(iterations=10, sigma_color=40.0),
+                dict(iterations=10, flags=0, sigma_normal=0.0, sigma_color=0.5)]
+REL = 1e-12
+
+
+def reference_mismatch(got, ref):
+    return M.mismatch(got, ref, REL)
+
+
+def _shape_id(s):
+    return "%dx%d" % s
+
+
+def _setting_id(kw):
+    return ",".join("%s=%s" % i for i in kw.items())
+
+
+@pytest.mark.parametrize("shape", REF_SHAPES, ids=_shape_id)
+@pytest.mark.parametrize("kw", REF_SETTINGS, ids=_setting_id)
+def test_the_model_matches_the_independent_reference(shape, kw):
+    w, h = shape
+    g, rng = M.synthetic_guides(h, w, seed=100 * w + h)
+    rgb = M.synthetic_frame(g, rng)
+    ref = np.asarray(R.denoise(rgb, g, **kw))
+    assert ref.shape == rgb.shape and np.all(np.isfinite(ref))
+    got = M.denoise(rgb, g, **kw)
+    assert reference_mismatch(got, ref) == 0, np.max(np.abs(got - ref) / np.maximum(np.abs(ref), 1e-300))
+    if kw["iterations"] == 0:
+        assert np.array_equal(ref, rgb)
+
+
+def test_the_synthetic_guides_reach_the_corners():
+    g, rng = M.synthetic_guides(11, 17, seed=1711)
+    rgb = M.synthetic_frame(g, rng)
+    ids, alb, hit = g["obj_id"], g["albedo"], g["obj_id"] >= 0
+    assert (alb[hit] == 0.0).any() and ((alb[hit] > 0.0) & (alb[hit] < 1e-3)).any()
+    assert (rgb[hit] == 0.0).all(axis=-1).any() and rgb.max() > 300.0
+    inner = ids[1:-1, 1:-1]
+    assert (inner < 0).any(), "no miss inside the frame"
+    island = (inner != ids[:-2, 1:-1]) & (inner != ids[2:, 1:-1]) & (inner != ids[1:-1, :-2]) & (inner != ids[1:-1, 2:])
+    assert (island & (inner >= 0)).any(), "no single-pixel object"
+    fp = g["footprint"]
+    both = hit[:, 1:] & hit[:, :-1]
+    assert np.max(np.maximum(fp[:, 1:], fp[:, :-1])[both] / np.minimum(fp[:, 1:], fp[:, :-1])[both]) > 5.0
+
+
+@pytest.mark.parametrize("kw", [dict(iterations=1), dict(iterations=2), dict(iterations=3, sigma_color=40.0)],
+                         ids=_setting_id)
+def test_the_reference_tells_the_plane_stops_footprint_apart(kw):
+    """Dividing the plane distance by the neighbour's footprint instead of the centre's is caught."""
+    g, rng = M.synthetic_guides(11, 17, seed=1711)
+    rgb = M.synthetic_frame(g, rng)
+    ref = np.asarray(R.denoise(rgb, g, **kw))
+    assert reference_mismatch(np.asarray(R.denoise(rgb, g, footprint_of="q", **kw)), ref) > 50
+
+
+@pytest.mark.parametrize("kw", [dict(iterations=2, sigma_color=40.0), dict(iterations=3, sigma_color=4.0)],
+                         ids=_setting_id)
+def test_the_reference_tells_the_colour_stop_schedule_apart(kw):
+    """A colour stop of sigma_c at every level instead of sigma_c 2^-i is caught."""
+    g, rng = M.synthetic_guides(11, 17, seed=1711)
+    rgb = M.synthetic_frame(g, rng)
+    ref = np.asarray(R.denoise(rgb, g, **kw))
+    assert reference_mismatch(np.asarray(R.denoise(rgb, g, color_halves=False, **kw)), ref) > 50
 
 
 # ---- the model on oracle renders ------------------------------------------------------------------------------------

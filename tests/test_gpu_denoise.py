@@ -204,11 +204,13 @@ def test_progressive_denoised_cancel_and_refusals(rt, gpu):
 
 # ---- CLI --------------------------------------------------------------------------------------------------------------
 
-def test_cli_denoise_writes_a_different_png(gpu):
+def test_cli_denoise_writes_a_different_png(rt, host, gpu):
+    """--denoise changes the PNG, which holds pack_rgba8(tone_map(denoise(render_frame))) of the same config, scene and
+    seed and is named after the SHA-256 of those bytes."""
     exe = os.path.join(ROOT, "racer-tracer_amd", "bin", "racer-tracer-amd")
-    base = [exe, "-c", os.path.join(ROOT, "scenes", "config_c1.yml"), "-s", os.path.join(ROOT, "scenes", "three_balls.yml"),
-            "--image-action", "png", "--seed", "1"]
-    pngs = []
+    config, scene_yml = os.path.join(ROOT, "scenes", "config_c1.yml"), os.path.join(ROOT, "scenes", "three_balls.yml")
+    base = [exe, "-c", config, "-s", scene_yml, "--image-action", "png", "--seed", "1"]
+    pngs, paths = [], []
     for extra in ([], ["--denoise"]):
         out = tempfile.mkdtemp(prefix="rt_cli_denoise_")
         r = subprocess.run(base + extra, capture_output=True, text=True, cwd=out, timeout=600)
@@ -219,4 +221,15 @@ def test_cli_denoise_writes_a_different_png(gpu):
         if not os.path.isabs(path):
             path = os.path.join(out, path)
         pngs.append(open(path, "rb").read())
+        paths.append(path)
     assert pngs[0] != pngs[1]
+    session = host.Session(config, scene=scene_yml, image_action="png", seed=1)
+    scene = rt.Scene(session)
+    try:
+        p, cam = session.params, session.camera
+        want = host.pack_rgba8(session.tone_map(scene.denoise(cam, p, scene.render_frame(cam, p))))
+    finally:
+        scene.close()
+        session.close()
+    assert np.array_equal(host.decode_image(paths[1]), want)
+    assert os.path.basename(paths[1]) == host.sha256_hex(want.tobytes()) + ".png"
