@@ -486,6 +486,50 @@ int rt_render_progressive_denoised(RtScene *scene, const RtCamera *camera, const
  * sigmas, non-zero _reserved, strips, scale > 1 and rgb == out (RT_ERR_INVALID_ARGUMENT) before they touch a device.  A binding detects them by symbol lookup (RT_ABI_VERSION is
  * unchanged by them). */
 
+/* ---------------------------------------------------------------- adaptive sampling
+ * rt_render_progressive's passes, with the 8x8 tiles that have converged left out of the passes after it (DESIGN.md
+ * section 4.7).
+ *  - Passes and decisions.  The passes are rt_render_progressive's for (N = params->samples, pass_samples).  After each
+ *    pass every tile still running is evaluated; let s be its samples done and k its chunks done.  It is eligible when
+ *    k >= 4 and s >= min_samples, and it stops when it is eligible and its error is <= threshold.  A stopped tile traces
+ *    nothing further.  The call ends after the last pass, or as soon as no tile is running.
+ *  - Error of a tile.  Per pixel and channel, from the tile's chunk sums S_j over n_j samples (j = 1..k, s = sum n_j):
+ *    m = S / s with S = sum S_j; V = max(0, sum S_j^2 / n_j - S m) / (k - 1) (batch means); sigma = sqrt(V / s);
+ *    e = sigma / (sqrt(m + sigma) + sqrt(m)) — which is sqrt(m + sigma) - sqrt(m), how far one standard error moves the
+ *    gamma-encoded value — and e = 0 where sigma = 0 (a black or constant pixel; no floor constant).  The tile's error is
+ *    the largest e over its pixels inside the image and their three channels.  out_tile_error holds each tile's error at
+ *    its last pass, or -1 if that pass ended with fewer than 2 chunks.
+ *  - Frame.  Every pixel equals, bit for bit, rt_render_progressive's frame after out_samples[p] samples (same scene,
+ *    camera, params and pass_samples).  out_samples is constant over each 8x8 tile and always a pass boundary.  With
+ *    threshold <= 0 the frame is rt_render_frame's, bit for bit, and every count is N.
+ *  - Callback (may be NULL).  One after every pass that traced a tile: running tiles at the pass boundary, stopped tiles
+ *    frozen at their own; samples_done is the pass boundary, samples_total N.  The last callback's frame equals out_rgb.
+ *    The GPU runs the next pass during the callback, which must not call into the library with the same scene.
+ *  - Cancel behaves as in rt_render_progressive: raised on entry, RT_ERR_CANCEL_EVENT with no callback; raised later,
+ *    RT_OK with nothing further delivered, and out_* hold the state of the last callback (untouched when none came).
+ *  - Refused with RT_ERR_INVALID_ARGUMENT before the scene is looked at: NULL adaptive or out_rgb, a non-finite threshold,
+ *    pass_samples <= 0, min_samples < 0, a non-zero _reserved, params->strip_count > 1 or params->scale > 1.  A scene on
+ *    the v1 kernel gets RT_ERR_UNSUPPORTED, and what rt_render_frame refuses at N is refused here too (the fixed-point
+ *    sums take N's exponent, as in rt_render_progressive).
+ *  - rt_scene_last_stats afterwards: samples is the device's own count (= the sum of out_samples), segments the device's
+ *    count, kernel_ms and resolve_ms summed over the passes, kernel_launches = the passes run.
+ * A binding detects these entry points by symbol lookup (RT_ABI_VERSION is unchanged by them). */
+typedef struct RtAdaptiveParams {
+    double threshold;     /* a tile stops once its error is <= threshold; <= 0: no tile ever stops */
+    int32_t pass_samples; /* decisions at the ends of rt_render_progressive's passes for this value (> 0) */
+    int32_t min_samples;  /* no tile stops before this many samples (>= 0) */
+    int32_t _reserved[4]; /* must be 0 */
+} RtAdaptiveParams;
+
+/* The defaults: threshold 0.01, pass_samples 64, min_samples 0.  A NULL is ignored. */
+void rt_adaptive_params_default(RtAdaptiveParams *out);
+int rt_render_adaptive(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                       const RtAdaptiveParams *adaptive,
+                       double *out_rgb,        /* HOST, W*H*3 f64, required */
+                       int32_t *out_samples,   /* HOST, W*H: the samples each pixel received; may be NULL */
+                       double *out_tile_error, /* HOST, ceil(W/8)*ceil(H/8), row-major tiles; may be NULL */
+                       RtFrameCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
+
 /* What the reference does to a finished tile downstream of the renderer, on
  * the device: ScreenBuffer::update's tone map (image_buffer.rs:147-153) and
  * SavePng's packing `(c * 255.0) as u32 -> (r << 24 | g << 16 | b << 8 | 255)`

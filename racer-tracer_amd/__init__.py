@@ -122,6 +122,16 @@ def denoise_params(**overrides):
     return dp
 
 
+def adaptive_params(**overrides):
+    """rt_adaptive_params_default, with fields overridden by keyword (threshold, pass_samples, min_samples)
+    -> abi.RtAdaptiveParams.  No device needed."""
+    ap = abi.RtAdaptiveParams()
+    lib().rt_adaptive_params_default(C.byref(ap))
+    for k, v in overrides.items():
+        setattr(ap, k, v)
+    return ap
+
+
 def guides_struct(planes):
     """abi.RtGuides over device tensors (a dict with normal, position, albedo, footprint, obj_id)."""
     return abi.RtGuides(*[planes[k].data_ptr() for k in ("normal", "position", "albedo", "footprint", "obj_id")])
@@ -262,6 +272,35 @@ class Scene:
                                                            C.byref(dp), cb, None, hook, None),
                   "rt_render_progressive_denoised", self._lib)
         return frames
+
+    def render_adaptive(self, camera, params, threshold=None, pass_samples=None, min_samples=None, cancel=None,
+                        on_frame=None):
+        """rt_render_adaptive -> (frame float64 [H, W, 3], samples int32 [H, W], tile_error float64 [ceil(H/8), ceil(W/8)],
+        frames), frames being the list of (samples_done, float64 [H, W, 3] copy) of the callbacks.  threshold, pass_samples,
+        min_samples: None keeps rt_adaptive_params_default's value.  cancel and on_frame as render_progressive's."""
+        overrides = {k: v for k, v in (("threshold", threshold), ("pass_samples", pass_samples),
+                                       ("min_samples", min_samples)) if v is not None}
+        ap = adaptive_params(**overrides)
+        h, w = params.height, params.width
+        frame = np.zeros((h, w, 3), dtype=np.float64)
+        samples = np.zeros((h, w), dtype=np.int32)
+        tile_error = np.zeros(((h + 7) // 8, (w + 7) // 8), dtype=np.float64)
+        frames = []
+
+        def on_pass(_user, rgb, samples_done, _samples_total):
+            arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()
+            frames.append((samples_done, arr))
+            if on_frame is not None:
+                on_frame(samples_done, arr)
+
+        cb = abi.RtFrameCallback(on_pass)
+        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        check(self._lib.rt_render_adaptive(self._h, C.byref(camera), C.byref(params), C.byref(ap),
+                                           frame.ctypes.data_as(C.POINTER(C.c_double)),
+                                           samples.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           tile_error.ctypes.data_as(C.POINTER(C.c_double)), cb, None, hook, None),
+              "rt_render_adaptive", self._lib)
+        return frame, samples, tile_error, frames
 
     def render_guides(self, camera, params):
         """rt_render_guides_device on device buffers of torch, copied back -> dict of numpy planes: normal, position,

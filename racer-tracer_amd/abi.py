@@ -120,6 +120,11 @@ class RtDenoiseParams(C.Structure):
                 ("sigma_plane", C.c_double), ("_reserved", C.c_int32 * 4)]
 
 
+class RtAdaptiveParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("pass_samples", C.c_int32), ("min_samples", C.c_int32),
+                ("_reserved", C.c_int32 * 4)]
+
+
 class RtGuides(C.Structure):
     _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("albedo", C.c_void_p), ("footprint", C.c_void_p),
                 ("obj_id", C.c_void_p)]
@@ -163,6 +168,10 @@ PROTOTYPES = {
     "rt_render_progressive_denoised": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.c_int32,
                                                  C.POINTER(RtDenoiseParams), RtFrameCallback, C.c_void_p, RtCancelCallback,
                                                  C.c_void_p]),
+    "rt_adaptive_params_default": (None, [C.POINTER(RtAdaptiveParams)]),
+    "rt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.POINTER(RtAdaptiveParams),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), RtFrameCallback,
+                                     C.c_void_p, RtCancelCallback, C.c_void_p]),
     "rt_post_rgba8_device": (C.c_int, [C.c_void_p, C.POINTER(RtToneMap), C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rt_render_frame_rgba8": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),

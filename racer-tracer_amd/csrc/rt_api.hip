@@ -27,11 +27,11 @@ extern "C" hipError_t rtdev_launch_post_rgba8(const RtToneMap *tm, const double 
 namespace {
 const rtapi::Launchers kFastLaunchers = {rtdev_launch_trace,      rtdev_launch_resolve,    rtdev_pool_blocks_per_cu,
                                          rtdev_pool_static_lds,   rtdev_launch_trace_pool, rtdev_launch_resolve_chunks,
-                                         rtdev_launch_fold_chunks};
+                                         rtdev_launch_fold_chunks, rtdev_launch_fold_adaptive};
 const rtapi::Launchers kExactLaunchers = {rtdev_launch_trace_exact,      rtdev_launch_resolve_exact,
                                           rtdev_pool_blocks_per_cu_exact, rtdev_pool_static_lds_exact,
                                           rtdev_launch_trace_pool_exact,  rtdev_launch_resolve_chunks_exact,
-                                          rtdev_launch_fold_chunks_exact};
+                                          rtdev_launch_fold_chunks_exact, rtdev_launch_fold_adaptive_exact};
 
 thread_local char g_last_error[1024]; // a fixed buffer: setting it cannot throw (rtapi::guarded's handlers use it)
 } // namespace
@@ -602,15 +602,21 @@ int pool_prologue(RtScene *s, rtdev::TraceArgs &a, const RtCamera *camera, const
     return RT_OK;
 }
 
-// Launch number `index` of a render: chunks [first_chunk, first_chunk + n_chunks) of every tile.
+// Launch number `index` of a render: chunks [first_chunk, first_chunk + n_chunks) of every tile, or of the n_list tiles of
+// `tile_list` (device memory; one-region launches only).
 int launch_pool(RtScene *s, rtdev::TraceArgs &a, const std::vector<int> &starts, int first_chunk, int n_chunks, int index,
-                unsigned max_blocks, hipStream_t stream) {
+                unsigned max_blocks, hipStream_t stream, const uint32_t *tile_list = nullptr, uint32_t n_list = 0) {
+    if (tile_list && (a.n_regions > 1 || n_list > (uint32_t)a.n_tiles))
+        return fail(RT_ERR_INVALID_ARGUMENT, "a tile list is for one-region launches, at most one entry per tile");
     a.sample_begin = starts[(size_t)first_chunk];
     a.sample_end = starts[(size_t)(first_chunk + n_chunks)];
     a.n_chunks = n_chunks;
     a.chunk_base = first_chunk;
-    a.n_items = (uint32_t)a.n_chunks * (uint32_t)a.n_tiles;
-    if ((uint64_t)a.n_chunks * (uint64_t)a.n_tiles >= 0x40000000ull) // the item counter's top bit is the cancel poison
+    a.tile_list = tile_list;
+    a.n_list = tile_list ? n_list : 0u;
+    const uint32_t tiles = tile_list ? n_list : (uint32_t)a.n_tiles;
+    a.n_items = (uint32_t)a.n_chunks * tiles;
+    if ((uint64_t)a.n_chunks * (uint64_t)tiles >= 0x40000000ull) // the item counter's top bit is the cancel poison
         return fail(RT_ERR_UNSUPPORTED, "more than 2^30 work items in one launch");
     a.queue = s->buf.queue.ptr + index;
     const unsigned blocks = std::min(max_blocks, (a.n_items + 3) / 4);
@@ -697,10 +703,11 @@ int rtapi::begin_passes(RtScene *s, const RtCamera *camera, const RtRenderParams
     return RT_OK;
 }
 
-int rtapi::enqueue_chunks(RtScene *s, PoolPasses &pp, int c0, int c1, hipStream_t stream) {
+int rtapi::enqueue_chunks(RtScene *s, PoolPasses &pp, int c0, int c1, hipStream_t stream, const uint32_t *tile_list,
+                          uint32_t n_list) {
     if (c0 < 0 || c1 <= c0 || c1 > pp.args.total_chunks || pp.launches >= pp.max_launches)
         return fail(RT_ERR_INVALID_ARGUMENT, "enqueue_chunks: chunk range or launch count out of range");
-    const int rc = launch_pool(s, pp.args, pp.starts, c0, c1 - c0, pp.launches, pp.max_blocks, stream);
+    const int rc = launch_pool(s, pp.args, pp.starts, c0, c1 - c0, pp.launches, pp.max_blocks, stream, tile_list, n_list);
     if (rc != RT_OK) return rc;
     s->last_launches = ++pp.launches;
     return RT_OK;

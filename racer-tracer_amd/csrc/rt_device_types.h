@@ -246,8 +246,37 @@ struct TraceArgs {
     // The other variants, and every RT_ARITH_REFERENCE kernel, add doubles in the order the samples finish, one item at a time.
     double sum_scale, sum_unscale;
     int32_t time_lds;  // the scene has a MovingSphere: the ray times of the batches sit behind the lens samples in dynamic LDS
-    int32_t _pad_sum;
+    uint32_t n_list;   // entries of tile_list (below)
     int32_t dbg[4];        // developer knobs (env RT_DBG0..3), 0 in production
+    // TILE LIST (rt_render_adaptive, one-region launches only): NULL — every launch but the adaptive passes — or the
+    // n_list tiles (indices into the tiles_x-wide grid) this launch traces, in any order: item = chunk * n_list + slot,
+    // tile = tile_list[slot].  (Last in the block, so that no other field moves.)
+    const uint32_t *tile_list;
+};
+
+// One pass of rt_render_adaptive's fold (rt_trace_pool_kernel.hip: k_fold_adaptive_f64), one wave per 8x8 tile of the whole
+// frame.  Whole-frame slices, as rt_render_progressive's.  A running tile (tile_stop 0) folds the slices [c0, c1) into
+// `running` and their squares over their sample counts into `squares`, writes its pixels, its error and either stops or
+// appends itself to next_list; a stopped tile rewrites its pixels from its own scale and carries its error over.
+struct AdaptiveFold {
+    const double *partial;   // [chunk][H][W][3]
+    double *running;         // S: the running sums (W*H*3)
+    double *squares;         // Q: sum over the chunks done of S_j^2 / n_j (W*H*3)
+    double *out;             // the pass's frame slot: sqrt(scale * S)
+    int32_t *tile_stop;      // per tile: 0 while it runs, else the samples it stopped at
+    double *tile_scale;      // per tile: the scale of the pass that stopped it (1 / those samples)
+    const double *err_prev;  // per tile: error after the previous pass
+    double *err;             // ... after this one (-1: fewer than 2 chunks)
+    uint32_t *next_list;     // the tiles that run on, in any order ...
+    uint32_t *next_count;    // ... and their number (zero before the pass)
+    int32_t width, height, tiles_x, n_tiles;
+    int32_t c0, c1;          // chunks of this pass; c1 = the chunks done
+    int32_t samples_done;    // chunk_start[c1]
+    int32_t eligible;        // a tile may stop here: c1 >= 4, samples_done >= min_samples and threshold > 0
+    double scale;            // 1.0 / samples_done, as the host computes it for rt_render_progressive's fold
+    double inv_batches;      // 1.0 / (c1 - 1), 0 when c1 < 2
+    double threshold;
+    double inv_chunk[RT_MAX_CHUNKS]; // 1.0 / the samples of each chunk
 };
 
 // The dynamic LDS of a pooled trace-kernel block, in the order k_trace_pool_f64 lays it out (rt_trace_pool_kernel.hip):

@@ -1,5 +1,5 @@
-// rt_progressive.hip — rt_render_progressive: the whole frame handed to the caller once per pass while it converges, the
-// last pass's frame being rt_render_frame's.
+// rt_progressive.hip — rt_render_progressive and rt_render_adaptive: the whole frame handed to the caller once per pass
+// while it converges, the last pass's frame being rt_render_frame's.
 //
 // The reference's author wanted this shape: renderer/denoised.rs:291-331 renders the frame in passes and writes a
 // whole-frame BufferUpdate after each (:210-216).  Here a pass is a run of whole chunks of the frame's chunk plan (rt_api.hip:
@@ -16,8 +16,14 @@
 // every k it waits for copy k (polling the cancel hook), runs callback k on the pinned slot and only then enqueues pass
 // k + 2 — whose fold waits for copy k (same device slot) and whose copy overwrites the pinned slot callback k has read.
 //
+// rt_render_adaptive runs the same passes through the same loop: pass k traces the tiles that
+// fold k - 1 left running (TraceArgs.tile_list), k_fold_adaptive_f64 folds, measures every running tile's error and
+// stops it or lists it for pass k + 1, and the count of running tiles travels to the host ahead of the frame.
+//
 // Host code only.
 #include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 #include "rt_scene.h"
@@ -41,32 +47,68 @@ std::vector<int> pass_ends(const std::vector<int> &starts, int pass_samples) {
     return ends;
 }
 
+// rt_render_adaptive's side of a call (rt_render_progressive and its denoised form have none): its parameters, checked,
+// and the caller's outputs.
+struct Adaptive {
+    const RtAdaptiveParams *params;
+    double *out_rgb;
+    int32_t *out_samples;
+    double *out_tile_error;
+};
+
+// What rt_render_adaptive refuses before it looks at the scene.
+int check_adaptive(const RtRenderParams *p, const RtAdaptiveParams *a, const double *out_rgb) {
+    if (!a) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive is NULL");
+    if (!out_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgb is NULL");
+    if (!std::isfinite(a->threshold)) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive->threshold must be finite");
+    if (a->pass_samples <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive->pass_samples must be positive");
+    if (a->min_samples < 0) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive->min_samples must not be negative");
+    for (int k = 0; k < 4; ++k)
+        if (a->_reserved[k] != 0) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive->_reserved must be 0");
+    if (p && p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive frames are whole frames: params->strip_* is not supported here");
+    if (p && p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive frames are full-resolution frames: params->scale must be 0 or 1");
+    return RT_OK;
+}
+
 // Everything the call needs, allocated before its first launch (a hipMalloc between passes would wait for the running
-// kernels): slices, one item counter per pass, the running sums, two device and two pinned frame slots, the copy stream and
-// the events of the two slots.
-int reserve_passes(RtScene *s, const RtRenderParams *p, int passes, size_t n) {
+// kernels): slices, one item counter per pass, the running sums, `slots` device and pinned frame slots, the copy stream and
+// the events of the slots; adaptive (n_tiles > 0): the sums of squares and the per-tile state, lists and counts.
+int reserve_passes(RtScene *s, const RtRenderParams *p, int passes, size_t n, int slots, size_t n_tiles) {
     int rc = rtapi::reserve_render_buffers(s, p, false);
     if (rc != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     if (b.queue.count < (size_t)passes) RT_HIP(b.queue.alloc((size_t)passes));
     if (b.accum.count < n) RT_HIP(b.accum.alloc(n));
-    if (b.frame.count < 2 * n) RT_HIP(b.frame.alloc(2 * n));
-    if ((rc = rtapi::ensure_host_frame(s, 2 * n)) != RT_OK) return rc;
+    if (b.frame.count < (size_t)slots * n) RT_HIP(b.frame.alloc((size_t)slots * n));
+    if ((rc = rtapi::ensure_host_frame(s, (size_t)slots * n)) != RT_OK) return rc;
     if (!b.stream_copy) RT_HIP(hipStreamCreateWithFlags(&b.stream_copy, hipStreamNonBlocking));
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < slots; ++k) {
         if (!b.ev_pass_begin[k]) RT_HIP(hipEventCreate(&b.ev_pass_begin[k]));
         if (!b.ev_pass_traced[k]) RT_HIP(hipEventCreate(&b.ev_pass_traced[k]));
         if (!b.ev_folded[k]) RT_HIP(hipEventCreate(&b.ev_folded[k]));
         if (!b.ev_copied[k]) RT_HIP(hipEventCreateWithFlags(&b.ev_copied[k], hipEventDisableTiming));
+        if (n_tiles && !b.ev_counted[k]) RT_HIP(hipEventCreateWithFlags(&b.ev_counted[k], hipEventDisableTiming));
+    }
+    if (n_tiles) {
+        if (b.squares.count < n) RT_HIP(b.squares.alloc(n));
+        if (b.tile_stop.count < n_tiles) RT_HIP(b.tile_stop.alloc(n_tiles));
+        if (b.tile_scale.count < n_tiles) RT_HIP(b.tile_scale.alloc(n_tiles));
+        if (b.tile_err.count < 3 * n_tiles) RT_HIP(b.tile_err.alloc(3 * n_tiles));
+        if (b.tile_lists.count < 2 * n_tiles) RT_HIP(b.tile_lists.alloc(2 * n_tiles));
+        if (b.tile_counts.count < (size_t)passes) RT_HIP(b.tile_counts.alloc((size_t)passes));
+        if (!b.host_counts) RT_HIP(hipHostMalloc((void **)&b.host_counts, sizeof(uint32_t) * rtdev::RT_MAX_CHUNKS, hipHostMallocDefault));
     }
     return RT_OK;
 }
 
-// dn: the filter of rt_render_progressive_denoised, or NULL
+// dn: the filter of rt_render_progressive_denoised, or NULL.  ad: rt_render_adaptive's outputs and parameters, or NULL.
+// The adaptive form keeps three frame slots and enqueues pass k + 1 as soon as pass k's running-tile count has arrived —
+// before callback k, and only if a tile still runs — so that a cancel seen while pass k + 1 waits still finds the slots
+// of pass k whole (pass k + 2 may be enqueued by then).
 int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams *p, int pass_samples, RtFrameCallback callback,
-                       void *user, const Cancel &cancel, const RtDenoiseParams *dn = nullptr) {
+                       void *user, const Cancel &cancel, const RtDenoiseParams *dn = nullptr, const Adaptive *ad = nullptr) {
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    if (!callback) return fail(RT_ERR_INVALID_ARGUMENT, "callback is NULL");
+    if (!callback && !ad) return fail(RT_ERR_INVALID_ARGUMENT, "callback is NULL");
     if (pass_samples <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "pass_samples must be positive");
     int rc = rtapi::check_params(camera, p);
     if (rc != RT_OK) return rc;
@@ -80,7 +122,10 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     const std::vector<int> ends = pass_ends(starts, pass_samples);
     const int passes = (int)ends.size();
     const size_t n = (size_t)p->width * (size_t)p->height * 3; // a frame, and a slice (whole-frame slices: slice_rows = height)
-    if ((rc = reserve_passes(s, p, passes, n)) != RT_OK) return rc;
+    const int slots = ad ? 3 : 2;
+    const int tiles_x = (p->width + 7) / 8;
+    const size_t n_tiles = ad ? (size_t)tiles_x * (size_t)((p->height + 7) / 8) : 0;
+    if ((rc = reserve_passes(s, p, passes, n, slots, n_tiles)) != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     // denoised: the guides, the filter's scratch and a third device frame slot, the filter's output
     if (dn && (rc = rtapi::reserve_denoise(s, n / 3, true)) != RT_OK) return rc;
@@ -89,16 +134,49 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     const hipStream_t stream = b.stream, copy = b.stream_copy;
     rtapi::PoolPasses pp;
     double kernel_ms = 0.0, fold_ms = 0.0;
+    uint32_t running = (uint32_t)n_tiles; // adaptive: the tiles the next pass traces
+    int delivered = -1;                    // the last pass whose callback has run
 
     auto enqueue_pass = [&](int k) -> int {
-        const int slot = k & 1, c0 = k > 0 ? ends[(size_t)k - 1] : 0, c1 = ends[(size_t)k];
+        const int slot = k % slots, c0 = k > 0 ? ends[(size_t)k - 1] : 0, c1 = ends[(size_t)k];
         double *dev = b.frame.ptr + (size_t)slot * n; // (then the filter's output, when denoised)
         RT_HIP(hipEventRecord(b.ev_pass_begin[slot], stream));
-        const int rc2 = rtapi::enqueue_chunks(s, pp, c0, c1, stream);
+        // adaptive: pass 0 traces every tile, pass k the list fold k - 1 wrote
+        const uint32_t *list = ad && k > 0 ? b.tile_lists.ptr + (size_t)(k & 1) * n_tiles : nullptr;
+        const int rc2 = rtapi::enqueue_chunks(s, pp, c0, c1, stream, list, running);
         if (rc2 != RT_OK) return rc2;
         RT_HIP(hipEventRecord(b.ev_pass_traced[slot], stream));
-        if (k >= 2) RT_HIP(hipStreamWaitEvent(stream, b.ev_copied[slot], 0)); // device slot k % 2 held pass k - 2's frame
-        RT_HIP(s->kernels->fold_chunks(b.partial.ptr, b.accum.ptr, dev, n, c0, c1, starts[(size_t)c1], stream));
+        if (k >= slots) RT_HIP(hipStreamWaitEvent(stream, b.ev_copied[slot], 0)); // device slot k % slots held pass k - slots's frame
+        if (ad) {
+            rtdev::AdaptiveFold f;
+            memset(&f, 0, sizeof f);
+            f.partial = b.partial.ptr;
+            f.running = b.accum.ptr;
+            f.squares = b.squares.ptr;
+            f.out = dev;
+            f.tile_stop = b.tile_stop.ptr;
+            f.tile_scale = b.tile_scale.ptr;
+            f.err_prev = b.tile_err.ptr + (size_t)((k + slots - 1) % slots) * n_tiles;
+            f.err = b.tile_err.ptr + (size_t)slot * n_tiles;
+            f.next_list = b.tile_lists.ptr + (size_t)((k + 1) & 1) * n_tiles;
+            f.next_count = b.tile_counts.ptr + k;
+            f.width = p->width;
+            f.height = p->height;
+            f.tiles_x = tiles_x;
+            f.n_tiles = (int32_t)n_tiles;
+            f.c0 = c0;
+            f.c1 = c1;
+            f.samples_done = starts[(size_t)c1];
+            const RtAdaptiveParams &a = *ad->params;
+            f.eligible = c1 >= 4 && f.samples_done >= a.min_samples && a.threshold > 0.0;
+            f.scale = 1.0 / (double)f.samples_done; // what rtdev_launch_fold_chunks passes
+            f.inv_batches = c1 >= 2 ? 1.0 / (double)(c1 - 1) : 0.0;
+            f.threshold = a.threshold;
+            for (size_t c = 0; c + 1 < starts.size(); ++c) f.inv_chunk[c] = 1.0 / (double)(starts[c + 1] - starts[c]);
+            RT_HIP(s->kernels->fold_adaptive(&f, stream));
+        } else {
+            RT_HIP(s->kernels->fold_chunks(b.partial.ptr, b.accum.ptr, dev, n, c0, c1, starts[(size_t)c1], stream));
+        }
         if (dn) { // the filter writes the third slot, which copy k - 1 must have read first
             if (k >= 1) RT_HIP(hipStreamWaitEvent(stream, b.ev_copied[slot ^ 1], 0));
             const int rc2 = rtapi::enqueue_denoise(s, p, dn, dev, guides, b.frame.ptr + 2 * n, stream);
@@ -107,6 +185,10 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
         }
         RT_HIP(hipEventRecord(b.ev_folded[slot], stream));
         RT_HIP(hipStreamWaitEvent(copy, b.ev_folded[slot], 0));
+        if (ad) { // the count first: the calling thread enqueues the next pass on it, not on the frame
+            RT_HIP(hipMemcpyAsync(b.host_counts + k, b.tile_counts.ptr + k, sizeof(uint32_t), hipMemcpyDeviceToHost, copy));
+            RT_HIP(hipEventRecord(b.ev_counted[slot], copy));
+        }
         RT_HIP(hipMemcpyAsync(b.host_frame + (size_t)slot * n, dev, n * sizeof(double), hipMemcpyDeviceToHost, copy));
         RT_HIP(hipEventRecord(b.ev_copied[slot], copy));
         return RT_OK;
@@ -117,13 +199,27 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
         int rc2 = rtapi::begin_passes(s, camera, p, stream, passes, cancel.armed(), pp);
         if (rc2 != RT_OK) return rc2;
         begun = true;
+        if (ad && pp.args.n_tiles != (int)n_tiles) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive: tile grid mismatch");
         RT_HIP(hipMemsetAsync(b.accum.ptr, 0, n * sizeof(double), stream)); // the running sums start at +0.0
+        if (ad) { // ... and so do the squares; every tile runs, no tile has been counted
+            RT_HIP(hipMemsetAsync(b.squares.ptr, 0, n * sizeof(double), stream));
+            RT_HIP(hipMemsetAsync(b.tile_stop.ptr, 0, n_tiles * sizeof(int32_t), stream));
+            RT_HIP(hipMemsetAsync(b.tile_counts.ptr, 0, (size_t)passes * sizeof(uint32_t), stream));
+        }
         if (dn && (rc2 = rtapi::enqueue_guides(s, camera, p, guides, stream)) != RT_OK) return rc2; // once, before pass 0
         int enqueued = 0;
-        for (; enqueued < passes && enqueued < 2; ++enqueued)
+        for (; enqueued < passes && enqueued < (ad ? 1 : 2); ++enqueued)
             if ((rc2 = enqueue_pass(enqueued)) != RT_OK) return rc2;
         for (int k = 0; k < passes; ++k) {
-            const int slot = k & 1;
+            const int slot = k % slots;
+            if (ad) { // pass k + 1 goes out as soon as it is known to trace something
+                if ((rc2 = rtapi::wait_event(b.ev_counted[slot], cancel)) != RT_OK) return rc2;
+                running = b.host_counts[k];
+                if (running > 0 && enqueued < passes) {
+                    if (cancel.raised()) return RT_ERR_CANCEL_EVENT;
+                    if ((rc2 = enqueue_pass(enqueued++)) != RT_OK) return rc2;
+                }
+            }
             if ((rc2 = rtapi::wait_event(b.ev_copied[slot], cancel)) != RT_OK) return rc2;
             RT_HIP(hipEventSynchronize(b.ev_folded[slot])); // (done: the copy waited for it)
             float ms = 0.f;
@@ -132,8 +228,11 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
             RT_HIP(hipEventElapsedTime(&ms, b.ev_pass_traced[slot], b.ev_folded[slot]));
             fold_ms += ms;
             if (cancel.raised()) return RT_ERR_CANCEL_EVENT;
-            callback(user, b.host_frame + (size_t)slot * n, starts[(size_t)ends[(size_t)k]], p->samples);
-            if (enqueued < passes) {
+            if (callback) callback(user, b.host_frame + (size_t)slot * n, starts[(size_t)ends[(size_t)k]], p->samples);
+            delivered = k;
+            if (ad) {
+                if (running == 0) break; // every tile has stopped
+            } else if (enqueued < passes) {
                 if (cancel.raised()) return RT_ERR_CANCEL_EVENT; // enqueue nothing more
                 if ((rc2 = enqueue_pass(enqueued++)) != RT_OK) return rc2;
             }
@@ -156,7 +255,23 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     if (rc == RT_OK && (e1 != hipSuccess || e2 != hipSuccess))
         return fail(RT_ERR_HIP, std::string("rt_render_progressive: stream synchronisation failed: ") +
                                     hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-    return rc;
+    if (rc != RT_OK || !ad || delivered < 0) return rc;
+    // adaptive: the outputs are the state of the last callback.  Its frame and tile errors are in slot `delivered` % 3,
+    // which no later pass has written (at most two passes run beyond it); a tile stopped after it ran on to its boundary.
+    const int slot = delivered % slots, done = starts[(size_t)ends[(size_t)delivered]];
+    memcpy(ad->out_rgb, b.host_frame + (size_t)slot * n, n * sizeof(double));
+    if (ad->out_tile_error)
+        RT_HIP(hipMemcpy(ad->out_tile_error, b.tile_err.ptr + (size_t)slot * n_tiles, n_tiles * sizeof(double), hipMemcpyDeviceToHost));
+    if (ad->out_samples) {
+        std::vector<int32_t> stop(n_tiles);
+        RT_HIP(hipMemcpy(stop.data(), b.tile_stop.ptr, n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int y = 0; y < p->height; ++y)
+            for (int x = 0; x < p->width; ++x) {
+                const int32_t t = stop[(size_t)(y / 8) * (size_t)tiles_x + (size_t)(x / 8)];
+                ad->out_samples[(size_t)y * (size_t)p->width + (size_t)x] = t != 0 && t <= done ? t : done;
+            }
+    }
+    return RT_OK;
 }
 
 } // namespace
@@ -177,6 +292,26 @@ int rt_render_progressive_denoised(RtScene *s, const RtCamera *camera, const RtR
         const int rc = rtapi::check_denoise(p, denoise); // (before the scene: the filter's refusals need no device)
         if (rc != RT_OK) return rc;
         return render_progressive(s, camera, p, pass_samples, callback, user, c, denoise);
+    });
+}
+
+void rt_adaptive_params_default(RtAdaptiveParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof *out);
+    out->threshold = 0.01;
+    out->pass_samples = 64;
+    out->min_samples = 0;
+}
+
+int rt_render_adaptive(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtAdaptiveParams *adaptive,
+                       double *out_rgb, int32_t *out_samples, double *out_tile_error, RtFrameCallback callback, void *user,
+                       RtCancelCallback cancelled, void *cancel_user) {
+    const Cancel c{nullptr, cancelled, cancel_user};
+    return rtapi::guarded("rt_render_adaptive", [&]() -> int {
+        const int rc = check_adaptive(p, adaptive, out_rgb); // (before the scene: these refusals need no device)
+        if (rc != RT_OK) return rc;
+        const Adaptive ad{adaptive, out_rgb, out_samples, out_tile_error};
+        return render_progressive(s, camera, p, adaptive->pass_samples, callback, user, c, nullptr, &ad);
     });
 }
 

@@ -29,7 +29,8 @@
                                                               int cover_h, int out_col_step, int out_cols, int samples,   \
                                                               hipStream_t stream);                                        \
     extern "C" hipError_t rtdev_launch_fold_chunks##SUFFIX(const double *partial, double *running, double *out, size_t n,   \
-                                                           int c0, int c1, int samples_done, hipStream_t stream);
+                                                           int c0, int c1, int samples_done, hipStream_t stream);    \
+    extern "C" hipError_t rtdev_launch_fold_adaptive##SUFFIX(const rtdev::AdaptiveFold *f, hipStream_t stream);
 RT_DECLARE_LAUNCHERS()
 RT_DECLARE_LAUNCHERS(_exact)
 
@@ -44,6 +45,7 @@ struct Launchers {
     decltype(&rtdev_launch_trace_pool) trace_pool;
     decltype(&rtdev_launch_resolve_chunks) resolve_chunks;
     decltype(&rtdev_launch_fold_chunks) fold_chunks;
+    decltype(&rtdev_launch_fold_adaptive) fold_adaptive;
 };
 
 // set the thread-local text behind rt_last_error_message (truncated, never throws) and return `code`
@@ -117,6 +119,12 @@ struct RenderBuffers {
     DevBuf<unsigned int> queue;         // one item counter per launch of a render call
     DevBuf<double> accum;               // running sums, W*H*3 (v1 kernel; the passes of rt_render_progressive)
     DevBuf<double> frame;               // resolved frame for the host-output entry points (two of them for rt_render_progressive)
+    // rt_render_adaptive (rt_progressive.hip), on first use: the running sums of squares (W*H*3), per tile its stop, its
+    // scale and its error in three pass slots, two tile lists and one running-tile count per pass (+ their pinned copies)
+    DevBuf<double> squares, tile_scale, tile_err;
+    DevBuf<int32_t> tile_stop;
+    DevBuf<uint32_t> tile_lists, tile_counts;
+    uint32_t *host_counts = nullptr;    // [RT_MAX_CHUNKS] pinned
     DevBuf<uint8_t> rgba;               // packed frame of rt_render_frame_rgba8
     DevBuf<unsigned long long> segments; // rt_device_types.h: RT_STAT_*
     hipStream_t stream = nullptr;       // used by the host-output entry points
@@ -133,10 +141,11 @@ struct RenderBuffers {
     // cancel: the stream whose command processor overwrites the launches' item counters (rt_api.hip: poison_queue)
     hipStream_t stream_ctl = nullptr;
     // rt_render_progressive (rt_progressive.hip), made on its first call: the stream that copies a pass's frame to the host
-    // and, per frame slot, the pass's trace span, the end of its fold and the end of its copy
+    // and, per frame slot (two; three for rt_render_adaptive), the pass's trace span, the end of its fold, the end of the
+    // copy of its running-tile count (adaptive) and the end of its frame's copy
     hipStream_t stream_copy = nullptr;
-    hipEvent_t ev_pass_begin[2] = {nullptr, nullptr}, ev_pass_traced[2] = {nullptr, nullptr};
-    hipEvent_t ev_folded[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
+    hipEvent_t ev_pass_begin[3] = {}, ev_pass_traced[3] = {};
+    hipEvent_t ev_folded[3] = {}, ev_counted[3] = {}, ev_copied[3] = {};
     // denoising (rt_denoise.hip), made on first use: the guides of rt_denoise_frame and rt_render_progressive_denoised —
     // planes [normal 3 | position 3 | albedo 3 | footprint 1] x W*H doubles and obj_id x W*H — and the filter's two
     // ping-pong buffers of W*H*3 doubles each
@@ -153,6 +162,13 @@ struct RenderBuffers {
         queue.release();
         accum.release();
         frame.release();
+        squares.release();
+        tile_scale.release();
+        tile_err.release();
+        tile_stop.release();
+        tile_lists.release();
+        tile_counts.release();
+        if (host_counts) (void)hipHostFree(host_counts);
         rgba.release();
         segments.release();
         guide_planes.release();
@@ -167,8 +183,8 @@ struct RenderBuffers {
         if (ev_resolved) (void)hipEventDestroy(ev_resolved);
         if (stream) (void)hipStreamDestroy(stream);
         if (stream_ctl) (void)hipStreamDestroy(stream_ctl);
-        for (hipEvent_t *evs : {ev_pass_begin, ev_pass_traced, ev_folded, ev_copied})
-            for (int k = 0; k < 2; ++k)
+        for (hipEvent_t *evs : {ev_pass_begin, ev_pass_traced, ev_folded, ev_counted, ev_copied})
+            for (int k = 0; k < 3; ++k)
                 if (evs[k]) (void)hipEventDestroy(evs[k]);
         if (stream_copy) (void)hipStreamDestroy(stream_copy);
         *this = RenderBuffers();
@@ -306,7 +322,9 @@ struct PoolPasses {
 };
 int begin_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p, hipStream_t stream, int max_launches,
                  bool cancellable, PoolPasses &pp);
-int enqueue_chunks(RtScene *s, PoolPasses &pp, int c0, int c1, hipStream_t stream);
+// tile_list: NULL (every tile) or n_list tiles of the grid in device memory (TraceArgs.tile_list).
+int enqueue_chunks(RtScene *s, PoolPasses &pp, int c0, int c1, hipStream_t stream, const uint32_t *tile_list = nullptr,
+                   uint32_t n_list = 0);
 // Denoising (rt_denoise.hip).  check_denoise: the filter's parameters (NULL, iterations, sigmas, _reserved) and a whole
 // frame's size (strips and scale > 1 refused).  reserve_denoise: the filter's scratch and, with `own_guides`, the scene's
 // guide planes for a W*H frame, before the first launch.  scene_guides: those planes as an RtGuides.  enqueue_guides /

@@ -648,8 +648,12 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             reg_ty0 = K->regions[region].ty0;
             reg_tiles = (uint32_t)reg_ntx * (uint32_t)K->regions[region].nty;
         }
+        // the adaptive passes (one region): the launch's tiles are a list, one wave-uniform load per item
+        const uint32_t *tile_list = kernargs_here()->tile_list;
+        if (tile_list != nullptr) reg_tiles = kernargs_here()->n_list;
         const uint32_t chunk = local / reg_tiles;
-        const uint32_t tile = local - chunk * reg_tiles;
+        uint32_t tile = local - chunk * reg_tiles;
+        if (tile_list != nullptr) tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile_list[tile]);
         const int ty = reg_ty0 + (int)(tile / (uint32_t)reg_ntx);
         const int tx = reg_tx0 + (int)(tile % (uint32_t)reg_ntx);
         const int cur = (int)(state >> 6) & 1;
@@ -1300,6 +1304,94 @@ __global__ __launch_bounds__(256) void k_fold_chunks_f64(const double *__restric
     }
 }
 
+// One pass of rt_render_adaptive (rt_progressive.hip; rtdev::AdaptiveFold): one wave per 8x8 tile, one lane per pixel,
+// 16 tiles to a block.
+// A running tile folds exactly as k_fold_chunks_f64 does — same left fold from +0.0, same sqrt(scale * acc) — so its
+// pixels are the progressive frame's bits.  Its error (include/rt_abi.h) is the largest over its pixels and channels of
+// e = sigma / (sqrt(m + sigma) + sqrt(m)) with m = S / s, V = max(0, Q - S m) / (k - 1) over the k chunks as batch means,
+// sigma = sqrt(V / s); e = 0 where sigma = 0, so a black pixel needs no floor.  A stopped tile rewrites its pixels from
+// its own scale: the same bits as at its stop, so every frame slot is whole without a copy between them.
+__global__ __launch_bounds__(1024) void k_fold_adaptive_f64(const AdaptiveFold F) {
+    // the tiles that run on are appended to the next list with ONE atomic per block of 16 tiles: one per tile, all on the
+    // same counter, serialised at L2 and cost 0.38 ms a pass on a 1080p frame
+    __shared__ uint32_t keep_of[16];
+    __shared__ uint32_t list_base;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = (int)blockIdx.x * 16 + wave; // wave-uniform
+    uint32_t keep = 0; // (lane 0) this wave's tile runs on
+    if (t < F.n_tiles) {
+        const int tx = t % F.tiles_x, ty = t / F.tiles_x;
+        const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
+        const bool valid = px < F.width && py < F.height;
+        const size_t n = (size_t)F.width * (size_t)F.height * 3;
+        const size_t i = valid ? ((size_t)py * (size_t)F.width + (size_t)px) * 3 : 0;
+        double acc[3] = {0.0, 0.0, 0.0}, q[3] = {0.0, 0.0, 0.0};
+        if (valid)
+            for (int ch = 0; ch < 3; ++ch) acc[ch] = F.running[i + ch];
+        const int stop = __builtin_amdgcn_readfirstlane(F.tile_stop[t]);
+        if (stop != 0) {
+            const double scale = F.tile_scale[t];
+            if (valid)
+                for (int ch = 0; ch < 3; ++ch) F.out[i + ch] = sqrt(scale * acc[ch]);
+            if (lane == 0) F.err[t] = F.err_prev[t];
+        } else {
+            double e_max = 0.0;
+            if (valid) {
+                for (int ch = 0; ch < 3; ++ch) q[ch] = F.squares[i + ch];
+                for (int c = F.c0; c < F.c1; ++c) {
+                    const double *src = F.partial + (size_t)c * n + i;
+                    const double v0 = src[0], v1 = src[1], v2 = src[2], inv = F.inv_chunk[c];
+                    acc[0] += v0;
+                    acc[1] += v1;
+                    acc[2] += v2;
+                    q[0] += v0 * v0 * inv;
+                    q[1] += v1 * v1 * inv;
+                    q[2] += v2 * v2 * inv;
+                }
+                for (int ch = 0; ch < 3; ++ch) {
+                    F.running[i + ch] = acc[ch];
+                    F.squares[i + ch] = q[ch];
+                    F.out[i + ch] = sqrt(F.scale * acc[ch]);
+                    if (F.c1 >= 2) { // (the error is compared to a threshold, not bit for bit: reciprocals from the host)
+                        const double m = acc[ch] * F.scale;
+                        const double var = fmax(0.0, q[ch] - acc[ch] * m) * F.inv_batches;
+                        const double sigma = sqrt(var * F.scale);
+                        const double e = sigma > 0.0 ? sigma / (sqrt(m + sigma) + sqrt(m)) : 0.0;
+                        e_max = e > e_max ? e : e_max;
+                    }
+                }
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                const double o = __shfl_xor(e_max, off, 64);
+                e_max = o > e_max ? o : e_max;
+            }
+            if (lane == 0) {
+                const double err = F.c1 >= 2 ? e_max : -1.0;
+                F.err[t] = err;
+                if (F.eligible && err <= F.threshold) {
+                    F.tile_stop[t] = F.samples_done;
+                    F.tile_scale[t] = F.scale;
+                } else {
+                    keep = 1u;
+                }
+            }
+        }
+    }
+    if (lane == 0) keep_of[wave] = keep;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t total = 0;
+        for (int w = 0; w < 16; ++w) total += keep_of[w];
+        list_base = total ? atomicAdd(F.next_count, total) : 0u;
+    }
+    __syncthreads();
+    if (lane == 0 && keep) {
+        uint32_t at = list_base;
+        for (int w = 0; w < wave; ++w) at += keep_of[w];
+        F.next_list[at] = (uint32_t)t;
+    }
+}
+
 } // namespace RT_KNS
 
 #if defined(RT_BB_COUNT) && !defined(RT_EXACT_DIV)
@@ -1411,5 +1503,11 @@ extern "C" hipError_t RT_LAUNCHER(rtdev_launch_fold_chunks)(const double *partia
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(RT_KNS::k_fold_chunks_f64, dim3(blocks), dim3(256), 0, stream, partial, running, out, n, c0, c1,
                        1.0 / (double)samples_done);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t RT_LAUNCHER(rtdev_launch_fold_adaptive)(const rtdev::AdaptiveFold *f, hipStream_t stream) {
+    if (f->n_tiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(RT_KNS::k_fold_adaptive_f64, dim3((unsigned)(f->n_tiles + 15) / 16), dim3(1024), 0, stream, *f);
     return hipGetLastError();
 }

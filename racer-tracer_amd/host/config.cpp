@@ -1,6 +1,7 @@
 // config.cpp — see config.h.
 #include "config.h"
 #include <array>
+#include <cmath>
 #include <cerrno>
 #include <cstdlib>
 #include <cstring>
@@ -203,9 +204,19 @@ Args Args::parse(int argc, const char *const *argv) {
         else if (s == "--device") a.device = std::atoi(val().c_str());
         else if (s == "--devices") a.devices = std::atoi(val().c_str());
         else if (s == "--denoise" && !has_inline) a.denoise = true;
+        else if (s == "--adaptive") {
+            const std::string v = val();
+            char *end = nullptr;
+            const double t = std::strtod(v.c_str(), &end);
+            if (v.empty() || end == nullptr || *end != '\0' || !std::isfinite(t) || !(t > 0.0))
+                throw TracerError::ArgumentParsingError("--adaptive needs a positive threshold, not '" + v + "'");
+            a.adaptive = t;
+        }
         else if (s == "-h" || s == "--help") a.help = true;
         else throw TracerError::ArgumentParsingError("unknown argument " + s);
     }
+    if (a.adaptive > 0.0 && a.devices > 1)
+        throw TracerError::ArgumentParsingError("--adaptive renders on one device: it does not combine with --devices > 1");
     return a;
 }
 

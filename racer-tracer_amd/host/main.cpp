@@ -5,8 +5,9 @@
 //     --image-action <png|none>
 // plus --seed, --device and --devices N (the frame is sharded over N GPUs of this
 // process the way the reference shards it over its rayon pool, cpu.rs:118-131) and --denoise (the assembled frame goes
-// through rt_denoise_frame on the first device before the tone map and the PNG).  The reference opens a window and renders when R
-// is released (scene_controller/interactive.rs:83-86); this renders the final
+// through rt_denoise_frame on the first device before the tone map and the PNG) and --adaptive T (one device renders the
+// frame through rt_render_adaptive, a tile stopping once its error is at most T; --denoise filters that frame).
+// The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
 #include <cstdio>
@@ -23,7 +24,7 @@ struct ScreenBuffer { // image_buffer.rs:104-170: tone-map each tile, keep the f
     RthSession *session;
     int width, height;
     std::vector<double> buffer;
-    std::vector<double> raw; // --denoise: the frame before the tone map
+    std::vector<double> raw; // --denoise, --adaptive: the frame before the tone map
 };
 
 void on_tile(void *user, const double *rgb, int32_t r, int32_t c, int32_t w, int32_t h) {
@@ -50,7 +51,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -84,12 +85,24 @@ int main(int argc, char **argv) {
         scenes.push_back(scene);
     }
     const size_t n_rgb = (size_t)params.width * (size_t)params.height * 3;
-    ScreenBuffer sb{session, params.width, params.height, std::vector<double>(n_rgb, 0.0), std::vector<double>(args.denoise ? n_rgb : 0, 0.0)};
+    ScreenBuffer sb{session, params.width, params.height, std::vector<double>(n_rgb, 0.0), std::vector<double>(args.denoise || args.adaptive > 0.0 ? n_rgb : 0, 0.0)};
     fprintf(stderr, "Rendering image...\n"); // interactive.rs:229
     auto t0 = std::chrono::steady_clock::now();
-    // the reference's tile stream (cpu.rs:64-70): every finished tile goes through ScreenBuffer::update's tone map;
-    // with several devices a tile column arrives once every device has finished its strips of it
-    if (scenes.size() == 1) {
+    double traced = 1.0; // --adaptive: the fraction of the frame's samples traced
+    if (args.adaptive > 0.0) { // the whole frame at once; tone-mapped below (after the filter, with --denoise)
+        RtAdaptiveParams ap;
+        rt_adaptive_params_default(&ap);
+        ap.threshold = args.adaptive;
+        std::vector<int32_t> counts(n_rgb / 3);
+        rc = rt_render_adaptive(scenes[0], rth_session_camera(session), &params, &ap, sb.raw.data(), counts.data(), nullptr, nullptr,
+                                nullptr, nullptr, nullptr);
+        double sum = 0.0;
+        for (int32_t c : counts) sum += (double)c;
+        traced = sum / ((double)counts.size() * (double)params.samples);
+        if (rc == RT_OK && !args.denoise) rth_tone_map(session, sb.raw.data(), sb.buffer.data(), n_rgb / 3);
+    } else if (scenes.size() == 1) {
+        // the reference's tile stream (cpu.rs:64-70): every finished tile goes through ScreenBuffer::update's tone map;
+        // with several devices a tile column arrives once every device has finished its strips of it
         rc = rt_render(scenes[0], rth_session_camera(session), &params, on_tile, &sb, nullptr);
     } else {
         rc = rt_render_multi(scenes.data(), (int)scenes.size(), rth_session_camera(session), &params, 0, on_tile, &sb, nullptr, nullptr);
@@ -113,6 +126,9 @@ int main(int argc, char **argv) {
             st.segments += one.segments;
             st.kernel_ms = one.kernel_ms > st.kernel_ms ? one.kernel_ms : st.kernel_ms;
         }
+        if (args.adaptive > 0.0)
+            fprintf(stderr, "Adaptive sampling (threshold %g) traced %.1f %% of the %d samples per pixel.\n", args.adaptive,
+                    100.0 * traced, params.samples);
         fprintf(stderr, "It took %.3f seconds to render the image. (%.1f Msamples/s, %.2f segments/sample, kernel %.1f ms)\n",
                 secs, (double)st.samples / secs / 1e6, st.samples ? (double)st.segments / (double)st.samples : 0.0, st.kernel_ms);
         if (rth_session_image_action(session) == RTH_IMAGE_ACTION_SAVE_PNG) { // main.rs:153-156
