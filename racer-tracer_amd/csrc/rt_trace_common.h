@@ -171,10 +171,11 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
     return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 }
 
-__device__ __forceinline__ u4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                            uint32_t k0, uint32_t k1) {
+// Philox rounds FIRST .. RT_PHILOX_ROUNDS - 1 on the counter words, k0 / k1 being round FIRST's keys
+template <int FIRST>
+__device__ __forceinline__ u4 philox_rounds(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
-    for (int r = 0; r < RT_PHILOX_ROUNDS; ++r) {
+    for (int r = FIRST; r < RT_PHILOX_ROUNDS; ++r) {
         uint64_t p0 = (uint64_t)RT_PHILOX_M0 * c0;
         uint64_t p1 = (uint64_t)RT_PHILOX_M1 * c2;
         uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
@@ -187,6 +188,46 @@ __device__ __forceinline__ u4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, 
         k1 += RT_PHILOX_W1;
     }
     return u4{c0, c1, c2, c3};
+}
+
+__device__ __forceinline__ u4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                            uint32_t k0, uint32_t k1) {
+    return philox_rounds<0>(c0, c1, c2, c3, k0, k1);
+}
+
+// The part of a scatter draw's Philox that does not depend on its block.  The block (counter word 3) enters philox4x32
+// only through an XOR into word 2 in round 1, so both multiplies of round 1, the M0 multiply of round 2 and the M1
+// multiply of round 3 are the same for every candidate of one (pixel, sample, segment): 4 of the 14 multiplies.  What
+// they leave is five words, the round keys folded in (rounds counted from 1):
+//   b: round 1's new word 2 without the block, which is XORed into it
+//   y: the rest of round 2's new word 0 (beside the high word of M1 * (b ^ block))
+//   x, z: the rest of round 3's new words 0 and 2 (beside the low word of that product and the high word of M0 * word 0)
+//   w: round 3's new word 1
+struct ScatterPrefix {
+    uint32_t b, y, x, w, z;
+};
+static_assert(RT_PHILOX_ROUNDS >= 3, "the scatter prefix spans three rounds");
+
+__device__ __forceinline__ ScatterPrefix scatter_prefix(uint32_t pixel, uint32_t sample, uint32_t seg, uint32_t k0,
+                                                        uint32_t k1) {
+    const uint64_t p0 = (uint64_t)RT_PHILOX_M0 * pixel; // round 1
+    const uint64_t p1 = (uint64_t)RT_PHILOX_M1 * ((seg << 8) | RT_RNG_SCATTER);
+    const uint32_t a = xor3((uint32_t)(p1 >> 32), sample, k0);
+    const uint64_t q0 = (uint64_t)RT_PHILOX_M0 * a; // round 2: its word 2 is the block's XOR away, its M0 multiply is not
+    const uint32_t c2 = xor3((uint32_t)(q0 >> 32), (uint32_t)p0, k1 + RT_PHILOX_W1);
+    const uint64_t r1 = (uint64_t)RT_PHILOX_M1 * c2; // round 3's M1 multiply
+    return ScatterPrefix{(uint32_t)(p0 >> 32) ^ k1, (uint32_t)p1 ^ (k0 + RT_PHILOX_W0),
+                         (uint32_t)(r1 >> 32) ^ (k0 + 2u * RT_PHILOX_W0), (uint32_t)r1,
+                         (uint32_t)q0 ^ (k1 + 2u * RT_PHILOX_W1)};
+}
+
+// philox4x32(pixel, sample, (seg << 8) | RT_RNG_SCATTER, block, k0, k1), bit for bit, from scatter_prefix(pixel, sample,
+// seg, k0, k1): two multiplies for rounds 2 and 3, then rounds 4 .. RT_PHILOX_ROUNDS as in philox4x32
+__device__ __forceinline__ u4 philox_from_prefix(const ScatterPrefix &P, uint32_t block, uint32_t k0, uint32_t k1) {
+    const uint64_t s = (uint64_t)RT_PHILOX_M1 * (P.b ^ block);    // round 2's M1 multiply
+    const uint64_t t = (uint64_t)RT_PHILOX_M0 * ((uint32_t)(s >> 32) ^ P.y); // round 3's M0 multiply
+    return philox_rounds<3>(P.x ^ (uint32_t)s, P.w, (uint32_t)(t >> 32) ^ P.z, (uint32_t)t, k0 + 3u * RT_PHILOX_W0,
+                            k1 + 3u * RT_PHILOX_W1);
 }
 
 // (((u64)hi << 32 | lo) >> 11) * 2^-53, exactly (two exact conversions, exact sum)

@@ -152,19 +152,53 @@ struct NoiseSlots {
     int perlin[8];     // ... and gradient table
     double term[8][8]; // 0.5^o * noise(2^o * p) of the round's octaves, summed in order by the requester
 };
-// A request of the cooperative samplers: {pixel, sample, segment, next candidate}
+// A request of the lens-disk sampler: {pixel, sample, 0, next candidate}
 struct alignas(16) Req4 { // one 128-bit LDS access
     uint32_t x, y, z, w;
 };
-// Posts a sampler request as four 32-bit LDS stores.  One 128-bit store wants the four values in four consecutive VGPRs:
-// pixel, sample and candidate were then copied into such a quad in every iteration (v_mov_b32 around every round), and
-// the stores cost the LDS pipe, which the path loop barely uses, instead of the vector one.  (Relaxed atomic stores: plain
-// ones are merged back into the 128-bit store.)
-__device__ __forceinline__ void post_request(Req4 *slot, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
-    __hip_atomic_store(&slot->x, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    __hip_atomic_store(&slot->y, y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    __hip_atomic_store(&slot->z, z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    __hip_atomic_store(&slot->w, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+// A request of the sphere sampler: the scatter prefix of (pixel, sample, segment) and the next candidate.  After the
+// round's ballot the same 24 bytes carry the answer back: the first accepted candidate of the group that served the slot
+// writes its three coordinates over the request, and the requester reads them from there.
+struct alignas(8) SphereSlot {
+    uint32_t b, y, x, w, z, base;
+};
+static_assert(sizeof(SphereSlot) == 3 * sizeof(double), "a slot holds the request or the sample");
+// Posts a sphere sampler request as six 32-bit LDS stores.  Wider stores want the values in consecutive VGPRs: pixel,
+// sample and candidate were then copied into such a quad in every iteration (v_mov_b32 around every round), and the
+// stores cost the LDS pipe, which the path loop barely uses, instead of the vector one.  (Relaxed atomic stores: plain
+// ones are merged back into wider stores.)
+__device__ __forceinline__ void post_request(SphereSlot *slot, const ScatterPrefix &P, uint32_t base) {
+    __hip_atomic_store(&slot->b, P.b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->y, P.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->x, P.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->w, P.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->z, P.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->base, base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+// v = p in the lanes of `mask`, in v's own registers.  Written in C++, a masked write of the sphere sampler's `result` is a
+// branch around it, and the compiler copied `result` on both sides of the branch and back at the join; this does the
+// masking itself, so to the compiler it is an unconditional update of `v` in place.
+__device__ __forceinline__ void move_masked(const d3 &p, uint64_t mask, d3 &v) {
+    uint64_t saved;
+    asm volatile("s_and_saveexec_b64 %[saved], %[mask]\n\t"
+                 "v_mov_b64 %[x], %[px]\n\t"
+                 "v_mov_b64 %[y], %[py]\n\t"
+                 "v_mov_b64 %[z], %[pz]\n\t"
+                 "s_mov_b64 exec, %[saved]"
+                 : [x] "+v"(v.x), [y] "+v"(v.y), [z] "+v"(v.z), [saved] "=&s"(saved)
+                 : [mask] "s"(mask), [px] "v"(p.x), [py] "v"(p.y), [pz] "v"(p.z)
+                 : "scc");
+}
+// The lowest set bit of every group of 2^lg bits of x (1 <= lg <= 6), in the scalar unit: x & -x within each group, the
+// negation done per group as (~x without the groups' top bits) + 1 in every group, whose carry stops at the group's top
+// bit, XOR the top bits of ~x
+__device__ __forceinline__ uint64_t lowest_in_groups(uint64_t x, int lg) {
+    const int q = 1 << lg;
+    uint64_t low = 1; // bit 0 of every group, doubled out (a shift by 64 or more is one by 0, which adds nothing)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) low |= low << ((q << k) & 63);
+    const uint64_t top = low << (q - 1);
+    return x & (((~x & ~top) + low) ^ (~x & top));
 }
 // The sampler's request slots and the turbulence slots are never live at the same time (the Noise rounds of
 // an iteration end before its sampler rounds begin, and both finish with what they posted), so they share
@@ -174,10 +208,12 @@ __device__ __forceinline__ void post_request(Req4 *slot, uint32_t x, uint32_t y,
 // slots are all they use; variants without textures have no Noise lookups to make room for.)
 template <bool TEXTURED> union SamplerScratch {
     Req4 req[32];
+    SphereSlot sphere[32];
     NoiseSlots noise;
 };
 template <> union SamplerScratch<false> {
     Req4 req[32];
+    SphereSlot sphere[32];
 };
 
 // What the END of an item needs of it (finish_item), parked while the item's last paths are in flight and the wave already
@@ -220,13 +256,18 @@ template <bool TEXTURED, int NBUF, bool OVERLAP> struct WaveLds {
 // at the same stream position in the next call.
 // The round count is a template constant: two rounds (the plain variants) are unrolled into straight-line code.  The
 // first round writes `result` in EVERY lane (no lane holds a sample yet), so only the later rounds write it under the
-// mask of the lanes still searching — a masked write is a copy of the old value at the join (C3 -0.8 %).
+// mask of the lanes still searching — a masked write is a copy of the old value at the join (C3 -0.8 %); both kinds of
+// round end in ONE such write (move_masked), after their branches have joined.
+// Every candidate is drawn from the scatter prefix of its request (philox_from_prefix): each lane forms its own once per
+// call, and a grouped round posts it, so a candidate costs 10 multiplies instead of 14.  A grouped round's answer comes
+// back through the request's slot, not through lane shuffles.
 template <int MAX_ROUNDS>
 __device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t pixel, uint32_t sample, uint32_t seg,
                                                            uint32_t &base, uint32_t k0, uint32_t k1, int lane,
-                                                           Req4 *req, d3 &result) {
+                                                           SphereSlot *slot, d3 &result) {
     bool have = false;
     uint64_t pending = ballot(need);
+    const ScatterPrefix own = scatter_prefix(pixel, sample, seg, k0, k1);
     for (int round = 0; round < MAX_ROUNDS && pending != 0; ++round) {
         const int n = __popcll(pending);
         // a round costs the whole wave ~70 instructions; past the first it only runs while enough requests are
@@ -235,12 +276,15 @@ __device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t p
         if (round > 0 && n < 8) break;
         // group size q = 2^lg, the largest power of two with n * q <= 64
         const int lg = n > 32 ? 0 : (n > 16 ? 1 : (n > 8 ? 2 : (n > 4 ? 3 : (n > 2 ? 4 : (n > 1 ? 5 : 6)))));
-        if (lg == 0) { // more than 32 requests: one candidate each, so every lane tests its OWN (no LDS, no shuffle)
-            // `result` only means something to a lane that returns true: a lane that still needs a sample may take every
-            // candidate it looks at, rejected ones included, without a select; in the first round no lane has one yet,
-            // so every lane takes its candidate (no copy of the result under the lanes' mask)
-            const d3 p = sphere_candidate(philox4x32(pixel, sample, (seg << 8) | RT_RNG_SCATTER, base, k0, k1));
-            if (round == 0 || need) result = p;
+        // what `result` takes: in every lane in the first round, in the lanes of `take` in the later ones.  `result` only
+        // means something to a lane that returns true, so a lane that still needs a sample may take whatever its round
+        // left it, a rejected candidate included.
+        d3 cand;
+        uint64_t take;
+        if (lg == 0) { // more than 32 requests: one candidate each, so every lane tests its OWN (no LDS)
+            const d3 p = sphere_candidate(philox_from_prefix(own, base, k0, k1));
+            cand = p;
+            take = pending; // ballot(need)
             const bool inside = len2(p) < 1.0;
             if (need) {
                 if (inside) {
@@ -251,36 +295,51 @@ __device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t p
                 }
             }
             pending &= ~ballot(inside); // (the comparison's own lane mask: see `pending` below)
-            continue;
+        } else {
+            const int rank = lane_rank(pending);
+            if (need) post_request(slot + rank, own, base);
+            const int j = lane >> lg;              // request served by this lane
+            const int c = lane & ((1 << lg) - 1);  // candidate offset inside the group
+            const bool serving = j < n;
+            SphereSlot *const served = slot + (serving ? j : 0);
+            const ScatterPrefix r = {served->b, served->y, served->x, served->w, served->z};
+            const uint32_t i = served->base + (uint32_t)c; // candidate index = its block (rt_rng.h)
+            const d3 p = sphere_candidate(philox_from_prefix(r, i, k0, k1));
+            // (ballots of the two comparisons, ANDed as scalars: a ballot of `serving && ...` is a lane mask turned into an
+            // integer and back, v_cndmask_b32 + v_cmp_ne_u32)
+            const uint64_t accepted = ballot(serving) & ballot(len2(p) < 1.0);
+            // The first accepted candidate of every group, in stream order, answers its request in the slot it was read
+            // from (after that read: one wave's LDS accesses complete in order, and the empty asm keeps the compiler from
+            // moving the double stores above the word loads).
+            asm volatile("" ::: "memory");
+            if (__builtin_amdgcn_inverse_ballot_w64(lowest_in_groups(accepted, lg))) {
+                double *const answer = reinterpret_cast<double *>(served);
+                answer[0] = p.x;
+                answer[1] = p.y;
+                answer[2] = p.z;
+            }
+            asm volatile("" ::: "memory"); // (and the answers' loads below them)
+            // did my own request get one?  (a ballot of the comparison, ANDed with `pending` = ballot(need) as scalars)
+            const int first = need ? (rank << lg) : 0;
+            const uint64_t width_mask = lg == 6 ? ~0ull : ((1ull << (1 << lg)) - 1ull);
+            const uint64_t got = pending & ballot(((accepted >> first) & width_mask) != 0);
+            // every lane reads a slot: what it finds means nothing to a lane that got none
+            const double *const answer = reinterpret_cast<const double *>(slot + (need ? rank : 0));
+            cand = mk(answer[0], answer[1], answer[2]);
+            take = got;
+            if (__builtin_amdgcn_inverse_ballot_w64(got)) {
+                need = false;
+                have = true;
+            } else if (need) {
+                base += 1u << lg;
+            }
+            pending &= ~got; // the lanes still searching
         }
-        const int rank = lane_rank(pending);
-        if (need) post_request(req + rank, pixel, sample, seg, base);
-        const int j = lane >> lg;              // request served by this lane
-        const int c = lane & ((1 << lg) - 1);  // candidate offset inside the group
-        const bool serving = j < n;
-        const Req4 r = req[serving ? j : 0];
-        const uint32_t i = r.w + (uint32_t)c;  // candidate index = its block (rt_rng.h)
-        const d3 p = sphere_candidate(philox4x32(r.x, r.y, (r.z << 8) | RT_RNG_SCATTER, i, k0, k1));
-        // (ballots of the two comparisons, ANDed as scalars: a ballot of `serving && ...` is a lane mask turned into an
-        // integer and back, v_cndmask_b32 + v_cmp_ne_u32)
-        const uint64_t accepted = ballot(serving) & ballot(len2(p) < 1.0);
-        // first accepted candidate of my own request, in stream order
-        const int first = need ? (rank << lg) : 0;
-        const uint64_t width_mask = lg == 6 ? ~0ull : ((1ull << (1 << lg)) - 1ull);
-        const uint64_t mine = need ? ((accepted >> first) & width_mask) : 0ull;
-        const bool got = mine != 0;
-        const int src = got ? first + __ffsll((unsigned long long)mine) - 1 : lane;
-        const double rx = shfl_d(p.x, src), ry = shfl_d(p.y, src), rz = shfl_d(p.z, src);
-        if (round == 0 || need) result = mk(rx, ry, rz); // (its own candidate's coordinates when it got none: see above)
-        if (got) {
-            need = false;
-            have = true;
-        } else if (need) {
-            base += 1u << lg;
+        if (round == 0) {
+            result = cand;
+        } else {
+            move_masked(cand, take, result);
         }
-        // the lanes still searching: `got` implies `need`, so this is ballot(need) — from a comparison's mask rather than
-        // from the bool, whose ballot costs the two vector instructions above
-        pending &= ~ballot(got);
     }
     return have;
 }
@@ -1146,7 +1205,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         RT_REGION(10); // Noise rounds
         d3 sph = mk(0.0, 0.0, 0.0); // (left uninitialised, three moves fewer per iteration cost the plain variants 16 bytes of scratch)
         if (coop_random_in_unit_sphere<(TEXTURED || SPECULAR) ? 4 : 2>(waiting, rng.pixel, rng.sample, seg, cand_base, A.seed_lo,
-                                                                       A.seed_hi, lane, L.scratch.req, sph)) {
+                                                                       A.seed_hi, lane, L.scratch.sphere, sph)) {
             waiting = false;
             finish = true;
         }
