@@ -530,6 +530,43 @@ int rt_render_adaptive(RtScene *scene, const RtCamera *camera, const RtRenderPar
                        double *out_tile_error, /* HOST, ceil(W/8)*ceil(H/8), row-major tiles; may be NULL */
                        RtFrameCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
 
+/* ---------------------------------------------------------------- next-event estimation
+ * A second estimator for whole frames: the plain path of rt_render_frame with one light sample
+ * at every Lambertian vertex whose bounce ray is traced (segment + 1 < max_depth), both terms weighted by multiple
+ * importance sampling.  Its mean is the plain frame's mean: every draw of the plain estimator keeps its address
+ * (rt_rng.h), so a sample's bounce path is the path rt_render_frame traces; the light sample draws from RT_RNG_LIGHT.
+ *  - Lights are listed at rt_scene_create, in table order, at most 64: an unwrapped Sphere of positive radius or an
+ *    unwrapped XY / XZ / YZ rect of non-zero area whose material is DiffuseLight.  Every other emitter is found by bounce
+ *    rays only, with weight 1.  Any subset of the emitters gives an unbiased frame, so max_lights caps the list and 0
+ *    lists none: the plain estimator.
+ *  - Sums are per pixel in f64, in sample order: the frame does not depend on tiles, scheduling or a radiance bound.
+ *    The output is sqrt(sum / samples), not tone-mapped, as rt_render_frame's.
+ *  - Refused with RT_ERR_INVALID_ARGUMENT before a device is touched: NULL pointers, an unknown heuristic, max_lights
+ *    outside 0..64, a non-zero _reserved, params->strip_count > 1 and params->scale > 1.
+ *  - rt_scene_last_stats afterwards: samples, path segments (shadow rays are not counted) and kernel_ms of the call.
+ * A binding detects these entry points by symbol lookup (RT_ABI_VERSION is unchanged by them). */
+enum RtMisHeuristic {
+    RT_MIS_POWER = 0,  /* w = p^2 / (p^2 + q^2) */
+    RT_MIS_BALANCE = 1 /* w = p / (p + q)       */
+};
+typedef struct RtLightSamplingParams {
+    int32_t heuristic;    /* RtMisHeuristic */
+    int32_t max_lights;   /* 0..64; 0 = no light listed: the plain estimator's frame */
+    int32_t _reserved[6]; /* must be 0 */
+} RtLightSamplingParams;
+/* The defaults: RT_MIS_POWER, 64 lights.  A NULL is ignored. */
+void rt_light_sampling_params_default(RtLightSamplingParams *out);
+/* The scene's listed lights as indices into RtSceneDesc.primitives, in table order, before any max_lights cap: the first
+ * min(capacity, count) into out_prims (may be NULL when capacity is 0), their number into *out_count. */
+int rt_scene_lights(RtScene *scene, int32_t *out_prims, int32_t capacity, int32_t *out_count);
+/* out_rgb: HOST memory, width*height*3 f64.  Synchronous. */
+int rt_render_frame_nee(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                        const RtLightSamplingParams *light_sampling, double *out_rgb);
+/* rgb_device: DEVICE memory of the scene's device, enqueued on `hip_stream` (NULL = default stream) without
+ * synchronising, e.g. ahead of rt_denoise_device. */
+int rt_render_frame_nee_device(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                               const RtLightSamplingParams *light_sampling, double *rgb_device, void *hip_stream);
+
 /* What the reference does to a finished tile downstream of the renderer, on
  * the device: ScreenBuffer::update's tone map (image_buffer.rs:147-153) and
  * SavePng's packing `(c * 255.0) as u32 -> (r << 24 | g << 16 | b << 8 | 255)`

@@ -66,6 +66,9 @@
 #define RT_RNG_SCENE 7      /* host: the procedural `random` scene (scene/random.rs:39-70):   */
                             /* pixel = n for the loader's n-th random_double(), sample =      */
                             /* RT_RNG_SAMPLE_TABLE, segment 0, block 0: d0                     */
+#define RT_RNG_LIGHT 8      /* rt_render_frame_nee: the light sample of the Lambertian vertex   */
+                            /* of segment `seg`.  block 0: three 42-bit draws */
+                            /* packed as RT_RNG_SCATTER's; e0 picks the light, e1, e2 its point */
 
 /* Philox4x32 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3",
  * SC'11) with SEVEN rounds: the paper's Crush-resistant member of the family (Philox4x32-7

@@ -132,6 +132,16 @@ def adaptive_params(**overrides):
     return ap
 
 
+def light_sampling_params(**overrides):
+    """rt_light_sampling_params_default, with fields overridden by keyword (heuristic, max_lights)
+    -> abi.RtLightSamplingParams.  No device needed."""
+    ls = abi.RtLightSamplingParams()
+    lib().rt_light_sampling_params_default(C.byref(ls))
+    for k, v in overrides.items():
+        setattr(ls, k, v)
+    return ls
+
+
 def guides_struct(planes):
     """abi.RtGuides over device tensors (a dict with normal, position, albedo, footprint, obj_id)."""
     return abi.RtGuides(*[planes[k].data_ptr() for k in ("normal", "position", "albedo", "footprint", "obj_id")])
@@ -212,6 +222,28 @@ class Scene:
         check(self._lib.rt_render_frame(self._h, C.byref(camera), C.byref(params),
                                     out.ctypes.data_as(C.POINTER(C.c_double))), "rt_render_frame", self._lib)
         return out
+
+    def render_frame_nee(self, camera, params, heuristic=None, max_lights=None):
+        """rt_render_frame_nee -> float64 [H, W, 3], gamma-encoded, not tone-mapped.  heuristic (abi.RT_MIS_*) and
+        max_lights: None keeps rt_light_sampling_params_default's value."""
+        ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
+        out = np.zeros((params.height, params.width, 3), dtype=np.float64)
+        check(self._lib.rt_render_frame_nee(self._h, C.byref(camera), C.byref(params), C.byref(ls),
+                                            out.ctypes.data_as(C.POINTER(C.c_double))), "rt_render_frame_nee", self._lib)
+        return out
+
+    def render_frame_nee_device(self, camera, params, out_ptr, stream=None, heuristic=None, max_lights=None):
+        """rt_render_frame_nee_device: out_ptr = device address (int), stream = hipStream_t (int)."""
+        ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
+        check(self._lib.rt_render_frame_nee_device(self._h, C.byref(camera), C.byref(params), C.byref(ls), C.c_void_p(out_ptr),
+                                                   C.c_void_p(stream or 0)), "rt_render_frame_nee_device", self._lib)
+
+    def lights(self):
+        """rt_scene_lights -> the listed lights (indices into the description's primitives, table order, uncapped)."""
+        n = C.c_int32(0)
+        out = (C.c_int32 * 64)()
+        check(self._lib.rt_scene_lights(self._h, out, len(out), C.byref(n)), "rt_scene_lights", self._lib)
+        return list(out[:n.value])
 
     def render_frame_device(self, camera, params, out_ptr, stream=None):
         """rt_render_frame_device: out_ptr = device address (int), stream = hipStream_t (int)."""

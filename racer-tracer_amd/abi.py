@@ -125,6 +125,13 @@ class RtAdaptiveParams(C.Structure):
                 ("_reserved", C.c_int32 * 4)]
 
 
+RT_MIS_POWER, RT_MIS_BALANCE = 0, 1
+
+
+class RtLightSamplingParams(C.Structure):
+    _fields_ = [("heuristic", C.c_int32), ("max_lights", C.c_int32), ("_reserved", C.c_int32 * 6)]
+
+
 class RtGuides(C.Structure):
     _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("albedo", C.c_void_p), ("footprint", C.c_void_p),
                 ("obj_id", C.c_void_p)]
@@ -172,6 +179,12 @@ PROTOTYPES = {
     "rt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.POINTER(RtAdaptiveParams),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), RtFrameCallback,
                                      C.c_void_p, RtCancelCallback, C.c_void_p]),
+    "rt_light_sampling_params_default": (None, [C.POINTER(RtLightSamplingParams)]),
+    "rt_scene_lights": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
+    "rt_render_frame_nee": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
+                                      C.POINTER(RtLightSamplingParams), C.POINTER(C.c_double)]),
+    "rt_render_frame_nee_device": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
+                                             C.POINTER(RtLightSamplingParams), C.c_void_p, C.c_void_p]),
     "rt_post_rgba8_device": (C.c_int, [C.c_void_p, C.POINTER(RtToneMap), C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rt_render_frame_rgba8": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),

@@ -935,8 +935,10 @@ std::vector<rtdev::Perlin> pack_perlins(const RtSceneDesc *d, int &identity) {
 }
 
 // Linear loop: group the table (rt_device_types.h: rect_end, sphere_end, box_end); the order inside a group is kept.
-void group_linear_table(RtScene *s, std::vector<rtdev::Prim> &prims) {
+// `order` (the description index of each record) is permuted alongside.
+void group_linear_table(RtScene *s, std::vector<rtdev::Prim> &prims, std::vector<int32_t> &order) {
     std::vector<rtdev::Prim> sorted;
+    std::vector<int32_t> sorted_order;
     sorted.reserve(prims.size());
     auto group_of = [](const rtdev::Prim &q) {
         if (q.flags == 0 && q.kind == RT_PRIM_XY_RECT) return 0;
@@ -947,13 +949,17 @@ void group_linear_table(RtScene *s, std::vector<rtdev::Prim> &prims) {
         return 5;
     };
     for (int g = 0; g < 6; ++g) {
-        for (const rtdev::Prim &q : prims)
-            if (group_of(q) == g) sorted.push_back(q);
+        for (size_t j = 0; j < prims.size(); ++j)
+            if (group_of(prims[j]) == g) {
+                sorted.push_back(prims[j]);
+                sorted_order.push_back(order[j]);
+            }
         if (g < 3) s->rect_end[g] = (int)sorted.size();
         if (g == 3) s->sphere_end = (int)sorted.size();
         if (g == 4) s->box_end = (int)sorted.size();
     }
     prims.swap(sorted);
+    order.swap(sorted_order);
 }
 
 constexpr size_t kBvhLdsBytes = 32 * 1024; // a node array up to this size is staged in dynamic LDS
@@ -1135,13 +1141,18 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
     // RT_ARITH_REFERENCE copies (f64 sums, one item per wave at a time, the reference's own divisions: ~25 % slower).
     if (s->radiance_bound == 0.0 && !s->use_v1 && (s->use_bvh || s->prims_class == 2)) s->exact = true;
     s->kernels = s->exact ? &kExactLaunchers : &kFastLaunchers;
+    std::vector<int32_t> order((size_t)d->n_primitives); // description index of each device record
+    for (size_t j = 0; j < order.size(); ++j) order[j] = (int32_t)j;
     if (s->use_bvh) {
-        if ((rc = upload_bvh(s, choose_bvh(d, s), prims)) != RT_OK) return rc;
+        const rtdev::BvhBuild bvh = choose_bvh(d, s);
+        if ((rc = upload_bvh(s, bvh, prims)) != RT_OK) return rc;
+        order.assign(bvh.prim_index.begin(), bvh.prim_index.end());
     } else { // the linear-loop variants keep the whole primitive table in LDS
         if ((size_t)d->n_primitives * sizeof(rtdev::Prim) > 120 * 1024)
             return fail(RT_ERR_UNSUPPORTED, "RT_HIT_LINEAR: the primitive table does not fit in LDS");
-        group_linear_table(s, prims);
+        group_linear_table(s, prims, order);
     }
+    if ((rc = rtapi::build_light_list(s, d, order)) != RT_OK) return rc;
     if ((rc = upload(s->prims, prims)) != RT_OK) return rc;
     if ((rc = upload(s->textures, textures)) != RT_OK) return rc;
     if ((rc = upload(s->images, images)) != RT_OK) return rc;
@@ -1315,6 +1326,8 @@ void rt_scene_destroy(RtScene *s) {
     s->bvh_nodes_ordered.release();
     s->bvh_prim_index.release();
     s->leaf_geo.release();
+    s->nee_slot.release();
+    s->nee_prim.release();
     // what a render allocates — slices, frames, pinned memory, counters, streams, events — outlives the scene: the
     // reference rebuilds its scene on every object event (main.rs:174-189), and the next rt_scene_create on this
     // device takes these over instead of paying hipMalloc / hipHostMalloc again (render_cache_put); should the cache

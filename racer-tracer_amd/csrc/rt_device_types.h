@@ -254,6 +254,15 @@ struct TraceArgs {
     const uint32_t *tile_list;
 };
 
+// The light list of an rt_render_frame_nee launch (rt_nee.hip, rt_nee_kernel.hip: k_nee_f64): slot[i] = the list index of
+// device primitive i, or -1; prim[k] = the device primitive of light k.  Light k is sampled when k < n_lights.
+struct NeeArgs {
+    const int32_t *slot;
+    const int32_t *prim;
+    int32_t n_lights;
+    int32_t heuristic; // RtMisHeuristic: 0 power (beta = 2), 1 balance (beta = 1)
+};
+
 // One pass of rt_render_adaptive's fold (rt_trace_pool_kernel.hip: k_fold_adaptive_f64), one wave per 8x8 tile of the whole
 // frame.  Whole-frame slices, as rt_render_progressive's.  A running tile (tile_stop 0) folds the slices [c0, c1) into
 // `running` and their squares over their sample counts into `squares`, writes its pixels, its error and either stops or

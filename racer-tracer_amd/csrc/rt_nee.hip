@@ -1,0 +1,151 @@
+// rt_nee.hip — next-event estimation: the scene's light list and the entry points rt_render_frame_nee,
+// rt_render_frame_nee_device, rt_scene_lights and rt_light_sampling_params_default (include/rt_abi.h).  The kernel is
+// rt_nee_kernel.hip's k_nee_f64, compiled in both arithmetic flavours; a scene uses its own (RtScene.exact).
+#include "rt_scene.h"
+
+#include <algorithm>
+#include <cstring>
+
+using rtapi::fail;
+
+namespace {
+
+constexpr int kMaxLights = 64;
+
+// Listed: an unwrapped Sphere of positive radius or an unwrapped rect of non-zero area, made of DiffuseLight
+bool listed(const RtSceneDesc *d, const RtPrimitive &p) {
+    if (p.flags != 0 || p.material < 0 || p.material >= d->n_materials) return false;
+    if (d->materials[p.material].kind != RT_MAT_DIFFUSE_LIGHT) return false;
+    if (p.kind == RT_PRIM_SPHERE) return p.p[3] > 0.0;
+    if (p.kind == RT_PRIM_XY_RECT || p.kind == RT_PRIM_XZ_RECT || p.kind == RT_PRIM_YZ_RECT)
+        return (p.p[1] - p.p[0]) * (p.p[3] - p.p[2]) != 0.0;
+    return false;
+}
+
+// Everything that is refused before a device is touched; the scene last, so that each refusal names its own cause
+int check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls) {
+    if (!camera || !p || !ls) return fail(RT_ERR_INVALID_ARGUMENT, "camera/params/light_sampling is NULL");
+    if (ls->heuristic != RT_MIS_POWER && ls->heuristic != RT_MIS_BALANCE)
+        return fail(RT_ERR_INVALID_ARGUMENT, "light_sampling->heuristic is not an RtMisHeuristic");
+    if (ls->max_lights < 0 || ls->max_lights > kMaxLights)
+        return fail(RT_ERR_INVALID_ARGUMENT, "light_sampling->max_lights must be in 0..64");
+    for (int32_t r : ls->_reserved)
+        if (r != 0) return fail(RT_ERR_INVALID_ARGUMENT, "light_sampling->_reserved must be 0");
+    if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_frame_nee renders whole frames: params->strip_* is not supported");
+    if (p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_frame_nee renders full-resolution frames: params->scale must be 0 or 1");
+    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    return rtapi::check_params(camera, p);
+}
+
+// One launch of k_nee_f64 over the whole frame into the scene's accumulator, then the resolve pass into out_device
+int enqueue_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, double *out_device,
+                hipStream_t stream) {
+    RT_HIP(hipSetDevice(s->device));
+    rtdev::TraceArgs a;
+    // the render's own argument block (tables, tree, camera, grid); its fixed-point sums are the pooled kernel's, and this
+    // kernel sums in f64, so they are sized for one sample (which no bound refuses) and not read
+    RtRenderParams one = *p;
+    one.samples = 1;
+    int rc = rtapi::fill_trace_args(s, camera, &one, a);
+    if (rc != RT_OK) return rc;
+    a.samples = p->samples;
+    a.sample_begin = 0;
+    a.sample_end = p->samples;
+    if (!s->use_bvh) a.n_bvh_nodes = 0;
+    rtapi::RenderBuffers &b = s->buf;
+    const size_t n = (size_t)p->width * (size_t)p->height * 3;
+    if (b.accum.count < n) RT_HIP(b.accum.alloc(n));
+    a.accum = b.accum.ptr;
+    rtdev::NeeArgs nee;
+    nee.slot = s->nee_slot.ptr;
+    nee.prim = s->nee_prim.ptr;
+    nee.n_lights = std::min(ls->max_lights, (int32_t)s->lights.size());
+    nee.heuristic = ls->heuristic;
+    RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
+    RT_HIP(hipEventRecord(b.ev_begin, stream));
+    RT_HIP((s->exact ? rtdev_launch_nee_exact : rtdev_launch_nee)(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh,
+                                                                  stream));
+    RT_HIP(hipEventRecord(b.ev_traced, stream));
+    RT_HIP(s->kernels->resolve(b.accum.ptr, out_device, p->width, p->height, p->height, 1, 0, p->samples, stream));
+    RT_HIP(hipEventRecord(b.ev_resolved, stream));
+    s->has_stats = true;
+    s->last_launches = 1;
+    s->summed_times = false;
+    return RT_OK;
+}
+
+int render_frame_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, double *out) {
+    int rc = check_nee(s, camera, p, ls);
+    if (rc != RT_OK) return rc;
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgb is NULL");
+    RT_HIP(hipSetDevice(s->device));
+    rtapi::RenderBuffers &b = s->buf;
+    const size_t n = (size_t)p->width * (size_t)p->height * 3;
+    if (b.frame.count < n) RT_HIP(b.frame.alloc(n));
+    if ((rc = enqueue_nee(s, camera, p, ls, b.frame.ptr, b.stream)) != RT_OK) return rc;
+    RT_HIP(hipStreamSynchronize(b.stream));
+    RT_HIP(hipMemcpy(out, b.frame.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int render_frame_nee_device(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                            double *out, void *stream) {
+    int rc = check_nee(s, camera, p, ls);
+    if (rc != RT_OK) return rc;
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device is NULL");
+    return enqueue_nee(s, camera, p, ls, out, (hipStream_t)stream);
+}
+
+int scene_lights(const RtScene *s, int32_t *out, int32_t capacity, int32_t *count) {
+    if (!s || !count) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out_count is NULL");
+    if (capacity < 0 || (capacity > 0 && !out)) return fail(RT_ERR_INVALID_ARGUMENT, "out_prims is NULL or capacity is negative");
+    *count = (int32_t)s->lights.size();
+    for (int32_t k = 0; k < capacity && k < *count; ++k) out[k] = s->lights[(size_t)k];
+    return RT_OK;
+}
+
+} // namespace
+
+int rtapi::build_light_list(RtScene *s, const RtSceneDesc *d, const std::vector<int32_t> &order) {
+    s->lights.clear();
+    for (int32_t i = 0; i < d->n_primitives && (int)s->lights.size() < kMaxLights; ++i)
+        if (listed(d, d->primitives[i])) s->lights.push_back(i);
+    std::vector<int32_t> device_of(order.size(), -1);
+    for (size_t j = 0; j < order.size(); ++j) device_of[(size_t)order[j]] = (int32_t)j;
+    std::vector<int32_t> slot(order.size(), -1), prim(s->lights.size());
+    for (size_t k = 0; k < s->lights.size(); ++k) {
+        prim[k] = device_of[(size_t)s->lights[k]];
+        slot[(size_t)prim[k]] = (int32_t)k;
+    }
+    RT_HIP(s->nee_slot.alloc(slot.size()));
+    if (!slot.empty()) RT_HIP(hipMemcpy(s->nee_slot.ptr, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    RT_HIP(s->nee_prim.alloc(prim.size()));
+    if (!prim.empty()) RT_HIP(hipMemcpy(s->nee_prim.ptr, prim.data(), prim.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+extern "C" {
+
+void rt_light_sampling_params_default(RtLightSamplingParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof *out);
+    out->heuristic = RT_MIS_POWER;
+    out->max_lights = kMaxLights;
+}
+
+int rt_scene_lights(RtScene *s, int32_t *out_prims, int32_t capacity, int32_t *out_count) {
+    return rtapi::guarded("rt_scene_lights", [&] { return scene_lights(s, out_prims, capacity, out_count); });
+}
+
+int rt_render_frame_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                        double *out_rgb) {
+    return rtapi::guarded("rt_render_frame_nee", [&] { return render_frame_nee(s, camera, p, ls, out_rgb); });
+}
+
+int rt_render_frame_nee_device(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                               double *rgb_device, void *hip_stream) {
+    return rtapi::guarded("rt_render_frame_nee_device",
+                          [&] { return render_frame_nee_device(s, camera, p, ls, rgb_device, hip_stream); });
+}
+
+} // extern "C"

@@ -199,6 +199,12 @@ extern "C" hipError_t rtdev_launch_guides(const rtdev::TraceArgs *args, const Rt
 extern "C" hipError_t rtdev_launch_denoise_step(const RtDenoiseParams *d, int step, int width, int height, const double *in,
                                                 const RtGuides *guides, double *out, hipStream_t stream);
 
+// The launchers of rt_nee_kernel.hip (both arithmetic flavours): the whole frame's NEE samples into args->accum.
+extern "C" hipError_t rtdev_launch_nee(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class, int textured,
+                                       int specular, int bvh, hipStream_t stream);
+extern "C" hipError_t rtdev_launch_nee_exact(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class,
+                                             int textured, int specular, int bvh, hipStream_t stream);
+
 struct RtScene {
     int device = 0;
     rtapi::DevBuf<rtdev::Prim> prims;
@@ -249,6 +255,11 @@ struct RtScene {
     int pool_blocks_per_cu_lens = 1; // ... when the camera has an aperture (its lens samples take dynamic LDS)
     int pool_static_lds = 0;         // static LDS of the variant's kernel (hipFuncGetAttributes)
     size_t pool_dyn_lds = 0, pool_dyn_lds_lens = 0; // its dynamic LDS without / with lens samples (rt_device_types.h: pool_lds_layout)
+
+    // next-event estimation (rt_nee.hip): the listed lights as description indices, in table order (at most 64), and on
+    // the device rtdev::NeeArgs' slot per device primitive and device primitive per light
+    std::vector<int32_t> lights;
+    rtapi::DevBuf<int32_t> nee_slot, nee_prim;
 
     rtapi::RenderBuffers buf;
     bool has_stats = false;
@@ -337,6 +348,9 @@ RtGuides scene_guides(RtScene *s, size_t pixels);
 int enqueue_guides(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtGuides &g, hipStream_t stream);
 int enqueue_denoise(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, const double *rgb, const RtGuides &g,
                     double *out, hipStream_t stream);
+// The scene's light list (rt_nee.hip), made by rt_scene_create once the device table's order is final: order[j] is the
+// description index of device primitive j.
+int build_light_list(RtScene *s, const RtSceneDesc *d, const std::vector<int32_t> &order);
 // The pinned host frame of the host-output entry points, at least `doubles` long (rt_deliver.hip).
 int ensure_host_frame(RtScene *s, size_t doubles);
 // Rows of the owned-row grid of a render with these parameters (a multiple of strip_rows with strips).

@@ -204,6 +204,7 @@ Args Args::parse(int argc, const char *const *argv) {
         else if (s == "--device") a.device = std::atoi(val().c_str());
         else if (s == "--devices") a.devices = std::atoi(val().c_str());
         else if (s == "--denoise" && !has_inline) a.denoise = true;
+        else if (s == "--nee" && !has_inline) a.nee = true;
         else if (s == "--adaptive") {
             const std::string v = val();
             char *end = nullptr;
@@ -217,6 +218,10 @@ Args Args::parse(int argc, const char *const *argv) {
     }
     if (a.adaptive > 0.0 && a.devices > 1)
         throw TracerError::ArgumentParsingError("--adaptive renders on one device: it does not combine with --devices > 1");
+    if (a.nee && a.adaptive > 0.0)
+        throw TracerError::ArgumentParsingError("--nee and --adaptive are two estimators: pick one");
+    if (a.nee && a.devices > 1)
+        throw TracerError::ArgumentParsingError("--nee renders on one device: it does not combine with --devices > 1");
     return a;
 }
 

@@ -6,7 +6,8 @@
 // plus --seed, --device and --devices N (the frame is sharded over N GPUs of this
 // process the way the reference shards it over its rayon pool, cpu.rs:118-131) and --denoise (the assembled frame goes
 // through rt_denoise_frame on the first device before the tone map and the PNG) and --adaptive T (one device renders the
-// frame through rt_render_adaptive, a tile stopping once its error is at most T; --denoise filters that frame).
+// frame through rt_render_adaptive, a tile stopping once its error is at most T; --denoise filters that frame) and --nee (one
+// device renders the frame through rt_render_frame_nee, next-event estimation; --denoise filters that frame).
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -51,7 +52,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -85,7 +86,7 @@ int main(int argc, char **argv) {
         scenes.push_back(scene);
     }
     const size_t n_rgb = (size_t)params.width * (size_t)params.height * 3;
-    ScreenBuffer sb{session, params.width, params.height, std::vector<double>(n_rgb, 0.0), std::vector<double>(args.denoise || args.adaptive > 0.0 ? n_rgb : 0, 0.0)};
+    ScreenBuffer sb{session, params.width, params.height, std::vector<double>(n_rgb, 0.0), std::vector<double>(args.denoise || args.adaptive > 0.0 || args.nee ? n_rgb : 0, 0.0)};
     fprintf(stderr, "Rendering image...\n"); // interactive.rs:229
     auto t0 = std::chrono::steady_clock::now();
     double traced = 1.0; // --adaptive: the fraction of the frame's samples traced
@@ -99,6 +100,11 @@ int main(int argc, char **argv) {
         double sum = 0.0;
         for (int32_t c : counts) sum += (double)c;
         traced = sum / ((double)counts.size() * (double)params.samples);
+        if (rc == RT_OK && !args.denoise) rth_tone_map(session, sb.raw.data(), sb.buffer.data(), n_rgb / 3);
+    } else if (args.nee) { // the whole frame at once; tone-mapped below (after the filter, with --denoise)
+        RtLightSamplingParams ls;
+        rt_light_sampling_params_default(&ls);
+        rc = rt_render_frame_nee(scenes[0], rth_session_camera(session), &params, &ls, sb.raw.data());
         if (rc == RT_OK && !args.denoise) rth_tone_map(session, sb.raw.data(), sb.buffer.data(), n_rgb / 3);
     } else if (scenes.size() == 1) {
         // the reference's tile stream (cpu.rs:64-70): every finished tile goes through ScreenBuffer::update's tone map;

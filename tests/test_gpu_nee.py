@@ -1,0 +1,196 @@
+"""rt_render_frame_nee on the MI355X: equal to tests/nee_model.py, the plain frame wherever nothing is listed, unbiased
+where the model cannot go, less noisy than the plain estimator on cornell_box, deterministic, and the same through every
+entry point and the CLI."""
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import nee_model as NM
+import scenes_py as S
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _params(abi, w, h, spp, depth=10, seed=1):
+    p = abi.render_params(w, h, spp, max_depth=depth)
+    p.seed = seed
+    return p
+
+
+def _parity(got, want):
+    """The parity tolerance of tests/test_gpu_parity.py: max < 1e-3, fewer than 0.2 % of the pixels beyond 1e-9."""
+    d = np.abs(got - want).max(axis=2)
+    assert float(d.max()) < 1e-3, float(d.max())
+    assert float(np.mean(d > 1e-9)) < 0.002, float(np.mean(d > 1e-9))
+
+
+def _scene(name, abi):
+    if name == "mixed":
+        return NM.mixed_scene(abi)
+    bundle, cam, _ = getattr(S, name)()
+    return bundle, cam
+
+
+@pytest.mark.parametrize("name", ["cornell_box", "mixed"])
+def test_equal_to_the_model(rt, orc, abi, gpu, name):
+    bundle, cam = _scene(name, abi)
+    c = S.camera_for(cam, 16, 16)
+    scene = rt.Scene(bundle)
+    model = NM.Model(orc, bundle.desc)
+    try:
+        for depth, heuristic in ((1, NM.POWER), (3, NM.POWER), (3, NM.BALANCE), (10, NM.POWER), (10, NM.BALANCE)):
+            p = _params(abi, 16, 16, 8, depth, seed=7)
+            got = scene.render_frame_nee(c, p, heuristic=heuristic)
+            segments = scene.last_stats().segments
+            want, want_segments = model.render(c, p, heuristic=heuristic)
+            _parity(got, want)
+            # the same paths: the plain estimator's segment count (shadow rays are not counted)
+            _, plain_segments = orc.render(bundle.desc, c, p)
+            assert want_segments == plain_segments
+            assert abs(int(segments) - plain_segments) <= 4, (depth, segments, plain_segments)
+    finally:
+        scene.close()
+
+
+def _wrapped_light_cornell(abi):
+    bundle, cam, _ = S.cornell_box()
+    prims = list(bundle.primitives)[:6]
+    prims[5].flags = abi.RT_PRIM_HAS_TRANSLATE  # a zero Translate: the same light, unlisted
+    prims[5].translate = abi.D3(0.0, 0.0, 0.0)
+    return abi.SceneBundle(prims, list(bundle.materials)[:4], list(bundle.textures)[:4], bundle.desc.background), cam
+
+
+@pytest.mark.parametrize("case", ["max_lights_0", "three_balls", "wrapped_light"])
+def test_plain_when_nothing_is_listed(rt, orc, abi, gpu, case):
+    if case == "wrapped_light":
+        bundle, cam = _wrapped_light_cornell(abi)
+    else:
+        bundle, cam = _scene("three_balls" if case == "three_balls" else "cornell_box", abi)
+    c = S.camera_for(cam, 32, 32)
+    p = _params(abi, 32, 32, 16, 10, seed=3)
+    scene = rt.Scene(bundle)
+    try:
+        if case != "max_lights_0":
+            assert scene.lights() == []
+        got = scene.render_frame_nee(c, p, max_lights=0 if case == "max_lights_0" else None)
+    finally:
+        scene.close()
+    want, _ = orc.render(bundle.desc, c, p)
+    _parity(got, want)
+
+
+@pytest.mark.parametrize("case", ["cornell_box_boxes", "emissive", "mixed_bvh"])
+def test_unbiased_where_the_model_cannot_go(rt, abi, host, gpu, case):
+    """Boxes and wrappers, Perlin and the lens, a BVH: NEE's linear-radiance block means against the plain frame's, with
+    standard errors from 8 independent seeds each."""
+    session = None
+    w, h = 32, 32
+    if case == "emissive":  # the scene's own camera, at 32x32 (the aspect changes; the estimators see the same rays)
+        session = host.Session(os.path.join(ROOT, "scenes", "config_c3.yml"), scene=os.path.join(ROOT, "scenes", "emissive.yml"))
+        desc, c = session, session.camera
+    else:
+        desc, cam = _scene("cornell_box_boxes" if case == "cornell_box_boxes" else "mixed", abi)
+        c = S.camera_for(cam, w, h)
+    scene = rt.Scene(desc, closest_hit=abi.RT_HIT_BVH if case == "mixed_bvh" else abi.RT_HIT_AUTO)
+    try:
+        if case == "mixed_bvh":
+            assert scene.variant()["use_bvh"] == 1
+        nee, plain = [], []
+        for k in range(8):
+            nee.append(scene.render_frame_nee(c, _params(abi, w, h, 512, 10, seed=100 + k)))
+            plain.append(scene.render_frame(c, _params(abi, w, h, 2048, 10, seed=900 + k)))
+    finally:
+        scene.close()
+        if session is not None:
+            session.close()
+    z = NM.block_z(nee, plain, block=8)
+    assert np.all(np.abs(z) <= 5.0), np.abs(z).max()
+    assert float(np.mean(z * z)) <= 2.0, float(np.mean(z * z))
+
+
+def test_less_noise_on_cornell_box(rt, abi, gpu):
+    bundle, cam, _ = S.cornell_box()
+    c = S.camera_for(cam, 128, 128)
+    scene = rt.Scene(bundle)
+    try:
+        ref = scene.render_frame(c, _params(abi, 128, 128, 16384, 10, seed=77))
+        plain = scene.render_frame(c, _params(abi, 128, 128, 64, 10, seed=5))
+        nee = scene.render_frame_nee(c, _params(abi, 128, 128, 64, 10, seed=5))
+    finally:
+        scene.close()
+    rmse = lambda f: float(np.sqrt(np.mean((f - ref) ** 2)))  # noqa: E731
+    ratio = rmse(nee) / rmse(plain)
+    print("cornell_box 128x128x64: gamma RMSE plain %.5f, NEE %.5f, ratio %.3f" % (rmse(plain), rmse(nee), ratio))
+    assert ratio <= 0.6, ratio
+
+
+def test_deterministic_and_independent_of_tiles_and_arithmetic(rt, abi, gpu):
+    bundle, cam = NM.mixed_scene(abi)
+    c = S.camera_for(cam, 40, 24)
+    p = _params(abi, 40, 24, 32, 10, seed=9)
+    scene = rt.Scene(bundle)
+    exact = rt.Scene(bundle, arithmetic=abi.RT_ARITH_REFERENCE)
+    try:
+        a = scene.render_frame_nee(c, p)
+        assert np.array_equal(a, scene.render_frame_nee(c, p))
+        p2 = _params(abi, 40, 24, 32, 10, seed=9)
+        p2.tiles_w, p2.tiles_h = 3, 7
+        assert np.array_equal(a, scene.render_frame_nee(c, p2))
+        assert exact.variant()["exact"] == 1
+        _parity(exact.render_frame_nee(c, p), a)
+    finally:
+        scene.close()
+        exact.close()
+
+
+def test_light_list_and_device_entry_point(rt, abi, gpu):
+    import torch
+    bundle, cam = NM.mixed_scene(abi)
+    for hit in (abi.RT_HIT_LINEAR, abi.RT_HIT_BVH):
+        scene = rt.Scene(bundle, closest_hit=hit)
+        try:
+            assert scene.lights() == NM.light_list(bundle.desc) == [2, 3, 8]
+            c = S.camera_for(cam, 24, 16)
+            p = _params(abi, 24, 16, 8, 6, seed=4)
+            host_frame = scene.render_frame_nee(c, p, max_lights=2)
+            dev = torch.device("cuda", 0)
+            out = torch.zeros((16, 24, 3), dtype=torch.float64, device=dev)
+            stream = torch.cuda.Stream(dev)
+            with torch.cuda.stream(stream):
+                scene.render_frame_nee_device(c, p, out.data_ptr(), stream=stream.cuda_stream, max_lights=2)
+            stream.synchronize()
+            assert np.array_equal(out.cpu().numpy(), host_frame)
+            st = scene.last_stats()
+            assert st.samples == 24 * 16 * 8 and st.kernel_ms > 0
+        finally:
+            scene.close()
+
+
+def test_cli_nee_writes_the_nee_frame(rt, host, gpu):
+    exe = os.path.join(ROOT, "racer-tracer_amd", "bin", "racer-tracer-amd")
+    config, scene_yml = os.path.join(ROOT, "scenes", "config_c1.yml"), os.path.join(ROOT, "scenes", "cornell_box.yml")
+    out = tempfile.mkdtemp(prefix="rt_cli_nee_")
+    r = subprocess.run([exe, "-c", config, "-s", scene_yml, "--image-action", "png", "--seed", "1", "--nee"],
+                       capture_output=True, text=True, cwd=out, timeout=600)
+    assert r.returncode == 0, r.stderr
+    m = re.search(r"Saved image to: (.+)", r.stderr)
+    assert m, r.stderr
+    path = m.group(1).strip()
+    path = path if os.path.isabs(path) else os.path.join(out, path)
+    session = host.Session(config, scene=scene_yml, image_action="png", seed=1)
+    scene = rt.Scene(session)
+    try:
+        p, cam = session.params, session.camera
+        want = host.pack_rgba8(session.tone_map(scene.render_frame_nee(cam, p)))
+    finally:
+        scene.close()
+        session.close()
+    assert np.array_equal(host.decode_image(path), want)
+    for bad in (["--nee", "--adaptive", "0.01"], ["--nee", "--devices", "2"]):
+        r = subprocess.run([exe, "-c", config, "-s", scene_yml] + bad, capture_output=True, text=True, cwd=out, timeout=60)
+        assert r.returncode != 0 and "--nee" in r.stderr
