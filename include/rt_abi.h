@@ -567,6 +567,48 @@ int rt_render_frame_nee(RtScene *scene, const RtCamera *camera, const RtRenderPa
 int rt_render_frame_nee_device(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
                                const RtLightSamplingParams *light_sampling, double *rgb_device, void *hip_stream);
 
+/* ---------------------------------------------------------------- next-event estimation in passes
+ * rt_render_progressive and rt_render_adaptive with the next-event estimator: whole frames while
+ * they converge, a cancel hook and the adaptive stop rule for rt_render_frame_nee's frames.
+ *  - Passes.  The pass boundaries are exactly rt_render_progressive's for (N = params->samples, pass_samples): the chunk
+ *    plan of N, a pass running to the first chunk boundary at least pass_samples further on.
+ *  - Frames.  The NEE kernel sums each pixel in f64 in sample order and every draw is addressed by (pixel, sample, ...), so
+ *    nothing a sample contributes depends on N, and the passes carry each pixel's running sum from one launch to the next.
+ *    Therefore the frame a callback receives with samples_done = s is bit-identical to rt_render_frame_nee with
+ *    params->samples = s and everything else equal — for EVERY pass, not only the last (rt_render_progressive promises
+ *    that for its last frame only).
+ *  - Adaptive.  Tiles, eligibility (k >= 4 chunks, s >= min_samples), the error formula, out_samples, out_tile_error (-1
+ *    with fewer than 2 chunks), the callback, the early end when no tile runs and the statistics are rt_render_adaptive's,
+ *    with S_j the NEE chunk sums of the tile's pixels (S_j is formed as the difference of the pixel's running sum at the
+ *    chunk's two boundaries).  Every pixel of out_rgb and of every callback frame equals, bit for bit, rt_render_frame_nee
+ *    at samples = out_samples[p] (in a callback: min(out_samples[p], samples_done)).  With threshold <= 0 the frame is
+ *    rt_render_frame_nee's at N and every count is N.
+ *  - Cancel as in rt_render_progressive / rt_render_adaptive: raised on entry, RT_ERR_CANCEL_EVENT and no callback; raised
+ *    later, RT_OK, nothing further delivered, and out_* hold the state of the last callback (untouched when none came).
+ *    The waves read the cancel word when they start and at every chunk boundary inside a pass.  A render on the same scene
+ *    afterwards sees nothing stale.
+ *  - Refused with RT_ERR_INVALID_ARGUMENT before a device is touched: everything rt_render_frame_nee refuses (NULL
+ *    pointers, an unknown heuristic, max_lights outside 0..64, a non-zero _reserved, params->strip_count > 1,
+ *    params->scale > 1); pass_samples <= 0 and a NULL callback for the progressive form; everything rt_render_adaptive
+ *    refuses about `adaptive` and out_rgb for the adaptive form.  The NEE kernel is a kernel of its own, so a scene created
+ *    with RT_KERNEL_V1 is NOT refused (unlike rt_render_progressive and rt_render_adaptive).
+ *  - No radiance bound and no fixed-point sums, as rt_render_frame_nee: a scene that rt_render_frame refuses at N for its
+ *    exponent renders here.
+ *  - max_lights = 0, or a scene without a listed light: the plain estimator in passes.
+ *  - rt_scene_last_stats afterwards: samples is the device's own count (W*H*N progressive, the sum of out_samples adaptive),
+ *    segments counts path segments only (shadow rays are not counted; progressive: exactly rt_render_frame_nee's count at
+ *    N), kernel_ms and resolve_ms are summed over the passes, kernel_launches = the passes run.
+ * A binding detects these entry points by symbol lookup (RT_ABI_VERSION is unchanged by them). */
+int rt_render_progressive_nee(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                              const RtLightSamplingParams *light_sampling, int32_t pass_samples,
+                              RtFrameCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
+int rt_render_adaptive_nee(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                           const RtLightSamplingParams *light_sampling, const RtAdaptiveParams *adaptive,
+                           double *out_rgb,        /* HOST, W*H*3 f64, required */
+                           int32_t *out_samples,   /* HOST, W*H: the samples each pixel received; may be NULL */
+                           double *out_tile_error, /* HOST, ceil(W/8)*ceil(H/8), row-major tiles; may be NULL */
+                           RtFrameCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
+
 /* What the reference does to a finished tile downstream of the renderer, on
  * the device: ScreenBuffer::update's tone map (image_buffer.rs:147-153) and
  * SavePng's packing `(c * 255.0) as u32 -> (r << 24 | g << 16 | b << 8 | 255)`

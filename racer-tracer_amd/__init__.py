@@ -334,6 +334,55 @@ class Scene:
               "rt_render_adaptive", self._lib)
         return frame, samples, tile_error, frames
 
+    def render_progressive_nee(self, camera, params, pass_samples, heuristic=None, max_lights=None, cancel=None, on_frame=None):
+        """rt_render_progressive_nee -> list of (samples_done, float64 [H, W, 3] copy), one per pass, EACH equal to
+        render_frame_nee's frame at samples = samples_done.  heuristic and max_lights as render_frame_nee's; cancel and
+        on_frame as render_progressive's."""
+        ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
+        frames = []
+        h, w = params.height, params.width
+
+        def on_pass(_user, rgb, samples_done, _samples_total):
+            arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()
+            frames.append((samples_done, arr))
+            if on_frame is not None:
+                on_frame(samples_done, arr)
+
+        cb = abi.RtFrameCallback(on_pass)
+        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        check(self._lib.rt_render_progressive_nee(self._h, C.byref(camera), C.byref(params), C.byref(ls), int(pass_samples), cb,
+                                                  None, hook, None), "rt_render_progressive_nee", self._lib)
+        return frames
+
+    def render_adaptive_nee(self, camera, params, threshold=None, pass_samples=None, min_samples=None, heuristic=None,
+                            max_lights=None, cancel=None, on_frame=None):
+        """rt_render_adaptive_nee -> (frame, samples, tile_error, frames) as render_adaptive's, every pixel being
+        render_frame_nee's at its own sample count.  heuristic and max_lights as render_frame_nee's."""
+        ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
+        overrides = {k: v for k, v in (("threshold", threshold), ("pass_samples", pass_samples),
+                                       ("min_samples", min_samples)) if v is not None}
+        ap = adaptive_params(**overrides)
+        h, w = params.height, params.width
+        frame = np.zeros((h, w, 3), dtype=np.float64)
+        samples = np.zeros((h, w), dtype=np.int32)
+        tile_error = np.zeros(((h + 7) // 8, (w + 7) // 8), dtype=np.float64)
+        frames = []
+
+        def on_pass(_user, rgb, samples_done, _samples_total):
+            arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()
+            frames.append((samples_done, arr))
+            if on_frame is not None:
+                on_frame(samples_done, arr)
+
+        cb = abi.RtFrameCallback(on_pass)
+        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        check(self._lib.rt_render_adaptive_nee(self._h, C.byref(camera), C.byref(params), C.byref(ls), C.byref(ap),
+                                               frame.ctypes.data_as(C.POINTER(C.c_double)),
+                                               samples.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               tile_error.ctypes.data_as(C.POINTER(C.c_double)), cb, None, hook, None),
+              "rt_render_adaptive_nee", self._lib)
+        return frame, samples, tile_error, frames
+
     def render_guides(self, camera, params):
         """rt_render_guides_device on device buffers of torch, copied back -> dict of numpy planes: normal, position,
         albedo [H, W, 3] f64, footprint [H, W] f64, obj_id [H, W] int32."""

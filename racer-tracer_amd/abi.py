@@ -185,6 +185,13 @@ PROTOTYPES = {
                                       C.POINTER(RtLightSamplingParams), C.POINTER(C.c_double)]),
     "rt_render_frame_nee_device": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
                                              C.POINTER(RtLightSamplingParams), C.c_void_p, C.c_void_p]),
+    "rt_render_progressive_nee": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
+                                            C.POINTER(RtLightSamplingParams), C.c_int32, RtFrameCallback, C.c_void_p,
+                                            RtCancelCallback, C.c_void_p]),
+    "rt_render_adaptive_nee": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
+                                         C.POINTER(RtLightSamplingParams), C.POINTER(RtAdaptiveParams), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_double), RtFrameCallback, C.c_void_p,
+                                         RtCancelCallback, C.c_void_p]),
     "rt_post_rgba8_device": (C.c_int, [C.c_void_p, C.POINTER(RtToneMap), C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rt_render_frame_rgba8": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),

@@ -254,13 +254,36 @@ struct TraceArgs {
     const uint32_t *tile_list;
 };
 
-// The light list of an rt_render_frame_nee launch (rt_nee.hip, rt_nee_kernel.hip: k_nee_f64): slot[i] = the list index of
+// The light list of an NEE launch (rt_nee.hip; rt_nee_kernel.hip: k_nee_f64, rt_nee_pass_kernel.hip: k_nee_pass_f64): slot[i] = the list index of
 // device primitive i, or -1; prim[k] = the device primitive of light k.  Light k is sampled when k < n_lights.
 struct NeeArgs {
     const int32_t *slot;
     const int32_t *prim;
     int32_t n_lights;
     int32_t heuristic; // RtMisHeuristic: 0 power (beta = 2), 1 balance (beta = 1)
+};
+
+// The decision step behind a pass (rt_nee_pass_kernel.hip: k_nee_decide_f64), one wave per 8x8 tile of the whole frame:
+// AdaptiveFold's second half.  A running tile (tile_stop 0) writes its pixels and its error and either stops or appends
+// itself to next_list; a stopped tile rewrites its pixels from its own scale and carries its error over.
+struct NeeDecide {
+    const double *running;   // S: the running sums (W*H*3)
+    const double *squares;   // Q: per pixel and channel the sum over the chunks done of S_j^2 / n_j (W*H*3)
+    double *out;             // the pass's frame slot: sqrt(scale * S)
+    int32_t *tile_stop;      // per tile: 0 while it runs, else the samples it stopped at
+    double *tile_scale;      // per tile: the scale of the pass that stopped it (1 / those samples)
+    const double *err_prev;  // per tile: error after the previous pass
+    double *err;             // ... after this one (-1: fewer than 2 chunks)
+    uint32_t *next_list;     // the tiles that run on, in any order (NULL: no list is kept) ...
+    uint32_t *next_count;    // ... and their number (zero before the pass)
+    int32_t width, height, tiles_x, n_tiles;
+    int32_t chunks_done;     // chunks of the frame behind this pass
+    int32_t samples_done;    // chunk_start[chunks_done]
+    int32_t eligible;        // a tile may stop here: chunks_done >= 4, samples_done >= min_samples and threshold > 0
+    int32_t _pad;
+    double scale;            // 1.0 / samples_done, as the host computes it for the resolve of rt_render_frame_nee
+    double inv_batches;      // 1.0 / (chunks_done - 1), 0 when chunks_done < 2
+    double threshold;
 };
 
 // One pass of rt_render_adaptive's fold (rt_trace_pool_kernel.hip: k_fold_adaptive_f64), one wave per 8x8 tile of the whole

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 using rtapi::fail;
 
@@ -22,8 +23,11 @@ bool listed(const RtSceneDesc *d, const RtPrimitive &p) {
     return false;
 }
 
+} // namespace
+
 // Everything that is refused before a device is touched; the scene last, so that each refusal names its own cause
-int check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls) {
+int rtapi::check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                     const char *what) {
     if (!camera || !p || !ls) return fail(RT_ERR_INVALID_ARGUMENT, "camera/params/light_sampling is NULL");
     if (ls->heuristic != RT_MIS_POWER && ls->heuristic != RT_MIS_BALANCE)
         return fail(RT_ERR_INVALID_ARGUMENT, "light_sampling->heuristic is not an RtMisHeuristic");
@@ -31,10 +35,33 @@ int check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p,
         return fail(RT_ERR_INVALID_ARGUMENT, "light_sampling->max_lights must be in 0..64");
     for (int32_t r : ls->_reserved)
         if (r != 0) return fail(RT_ERR_INVALID_ARGUMENT, "light_sampling->_reserved must be 0");
-    if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_frame_nee renders whole frames: params->strip_* is not supported");
-    if (p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_frame_nee renders full-resolution frames: params->scale must be 0 or 1");
+    if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, std::string(what) + " renders whole frames: params->strip_* is not supported");
+    if (p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, std::string(what) + " renders full-resolution frames: params->scale must be 0 or 1");
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     return rtapi::check_params(camera, p);
+}
+
+namespace {
+using rtapi::check_nee;
+
+// The argument blocks of a k_nee_f64 / k_nee_pass_f64 launch over the whole frame's samples
+int fill_nee_args(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, rtdev::TraceArgs &a,
+                  rtdev::NeeArgs &nee) {
+    // the render's own argument block (tables, tree, camera, grid); its fixed-point sums are the pooled kernel's, and this
+    // kernel sums in f64, so they are sized for one sample (which no bound refuses) and not read
+    RtRenderParams one = *p;
+    one.samples = 1;
+    const int rc = rtapi::fill_trace_args(s, camera, &one, a);
+    if (rc != RT_OK) return rc;
+    a.samples = p->samples;
+    a.sample_begin = 0;
+    a.sample_end = p->samples;
+    if (!s->use_bvh) a.n_bvh_nodes = 0;
+    nee.slot = s->nee_slot.ptr;
+    nee.prim = s->nee_prim.ptr;
+    nee.n_lights = std::min(ls->max_lights, (int32_t)s->lights.size());
+    nee.heuristic = ls->heuristic;
+    return RT_OK;
 }
 
 // One launch of k_nee_f64 over the whole frame into the scene's accumulator, then the resolve pass into out_device
@@ -42,25 +69,13 @@ int enqueue_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, con
                 hipStream_t stream) {
     RT_HIP(hipSetDevice(s->device));
     rtdev::TraceArgs a;
-    // the render's own argument block (tables, tree, camera, grid); its fixed-point sums are the pooled kernel's, and this
-    // kernel sums in f64, so they are sized for one sample (which no bound refuses) and not read
-    RtRenderParams one = *p;
-    one.samples = 1;
-    int rc = rtapi::fill_trace_args(s, camera, &one, a);
+    rtdev::NeeArgs nee;
+    int rc = fill_nee_args(s, camera, p, ls, a, nee);
     if (rc != RT_OK) return rc;
-    a.samples = p->samples;
-    a.sample_begin = 0;
-    a.sample_end = p->samples;
-    if (!s->use_bvh) a.n_bvh_nodes = 0;
     rtapi::RenderBuffers &b = s->buf;
     const size_t n = (size_t)p->width * (size_t)p->height * 3;
     if (b.accum.count < n) RT_HIP(b.accum.alloc(n));
     a.accum = b.accum.ptr;
-    rtdev::NeeArgs nee;
-    nee.slot = s->nee_slot.ptr;
-    nee.prim = s->nee_prim.ptr;
-    nee.n_lights = std::min(ls->max_lights, (int32_t)s->lights.size());
-    nee.heuristic = ls->heuristic;
     RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
     RT_HIP(hipEventRecord(b.ev_begin, stream));
     RT_HIP((s->exact ? rtdev_launch_nee_exact : rtdev_launch_nee)(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh,
@@ -105,6 +120,58 @@ int scene_lights(const RtScene *s, int32_t *out, int32_t capacity, int32_t *coun
 }
 
 } // namespace
+
+int rtapi::begin_nee_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                            hipStream_t stream, bool cancellable, NeePasses &np) {
+    RT_HIP(hipSetDevice(s->device));
+    rtdev::TraceArgs &a = np.args;
+    const int rc = fill_nee_args(s, camera, p, ls, a, np.nee);
+    if (rc != RT_OK) return rc;
+    rtapi::RenderBuffers &b = s->buf;
+    const size_t n = (size_t)p->width * (size_t)p->height * 3;
+    if (b.accum.count < n || b.squares.count < n || b.partial.count < n) return fail(RT_ERR_INVALID_ARGUMENT, "begin_nee_passes: the running sums are not reserved");
+    a.accum = b.accum.ptr;
+    np.starts = rtapi::chunk_starts(p->samples);
+    const int total_chunks = (int)np.starts.size() - 1;
+    for (int c = 0; c <= total_chunks; ++c) a.chunk_start[c] = np.starts[(size_t)c];
+    a.total_chunks = total_chunks;
+    a.chunk_samples = np.starts[1] - np.starts[0];
+    a.tiles_x = (p->width + 7) / 8;
+    a.n_tiles = a.tiles_x * ((p->height + 7) / 8);
+    if (cancellable) { // the waves read the scene's cancel word at their start and at chunk boundaries
+        b.host_flags[rtdev::RT_MAX_REGIONS] = 0u;
+        a.cancel_flag = b.host_flags + rtdev::RT_MAX_REGIONS;
+    }
+    RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
+    RT_HIP(hipEventRecord(b.ev_begin, stream));
+    s->has_stats = true;
+    s->last_launches = 0;
+    s->summed_times = false;
+    return RT_OK;
+}
+
+int rtapi::enqueue_nee_pass(RtScene *s, NeePasses &np, int c0, int c1, hipStream_t stream, const uint32_t *tile_list, uint32_t n_list) {
+    rtdev::TraceArgs &a = np.args;
+    if (c0 < 0 || c1 <= c0 || c1 > a.total_chunks || (tile_list && n_list > (uint32_t)a.n_tiles))
+        return fail(RT_ERR_INVALID_ARGUMENT, "enqueue_nee_pass: chunk range or tile list out of range");
+    a.tile_list = tile_list;
+    a.n_list = tile_list ? n_list : 0u;
+    a.n_items = tile_list ? n_list : (uint32_t)a.n_tiles;
+    a.n_chunks = 1;
+    rtapi::RenderBuffers &b = s->buf;
+    const size_t n = (size_t)a.width * (size_t)a.height * 3;
+    for (int c = c0; c < c1; ++c) { // one launch per chunk: the kernel's header says why
+        a.chunk_base = c;
+        a.sample_begin = np.starts[(size_t)c];
+        a.sample_end = np.starts[(size_t)c + 1];
+        RT_HIP((s->exact ? rtdev_launch_nee_pass_exact : rtdev_launch_nee_pass)(&a, &np.nee, s->prims_class, s->textured, s->specular,
+                                                                                s->use_bvh, stream));
+        RT_HIP((s->exact ? rtdev_launch_nee_chunk_exact : rtdev_launch_nee_chunk)(b.accum.ptr, b.partial.ptr, b.squares.ptr, n,
+                                                                                  a.sample_end - a.sample_begin, stream));
+    }
+    ++s->last_launches;
+    return RT_OK;
+}
 
 int rtapi::build_light_list(RtScene *s, const RtSceneDesc *d, const std::vector<int32_t> &order) {
     s->lights.clear();

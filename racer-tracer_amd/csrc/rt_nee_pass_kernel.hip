@@ -1,0 +1,220 @@
+// rt_nee_pass_kernel.hip — the next-event estimator in passes, behind rt_render_progressive_nee and
+// rt_render_adaptive_nee: k_nee_pass_f64 traces the samples of one pass for a list of 8x8 tiles on top of the running
+// per-pixel sums, k_nee_decide_f64 then writes the pass's frame, measures every running tile and stops it or lists it for
+// the next pass.  The estimator itself is rt_nee_common.h's nee_samples, the loop k_nee_f64 runs: a pixel's samples are
+// added in sample order to a sum that travels from launch to launch in TraceArgs.accum, so after any pass the sums are
+// the ones k_nee_f64 forms with that many samples, bit for bit.
+#include "rt_nee_common.h"
+
+namespace RT_KNS {
+
+// 256 threads = 4 waves; wave w of block b traces item 4 b + w: tile tile_list[item] of the 8x8 tile grid (tiles_x wide),
+// or tile `item` itself without a list; lane = pixel.  A launch traces ONE chunk of the frame's chunk plan, samples
+// [sample_begin, sample_end); the host launches a pass's chunks one behind the other (rt_nee.hip: enqueue_nee_pass).
+// That keeps the kernel k_nee_f64 with a prologue and an epilogue — same path loop, entered once, nothing more alive in
+// it — where a loop over the pass's chunks around the path loop cost every variant 4 to 9 VGPRs and six of them their
+// occupancy step.
+//
+// BATCH MEANS.  The error of rt_render_adaptive_nee needs Q = sum_j S_j^2 / n_j over the chunks, S_j being what chunk j
+// added to the pixel.  The trace kernel knows nothing of it: k_nee_chunk_f64 runs behind every chunk's launch, takes S_j as
+// the difference of the running sum and its copy from the last boundary and adds S_j^2 / n_j to Q.  (Updating Q in the
+// trace kernel's epilogue left ten of its variants with a stack frame; elementwise over the frame it costs 0.1 ms.)
+//
+// CANCEL.  The host's cancel word (TraceArgs.cancel_flag, pinned host memory) is read by lane 0 of every wave when it
+// starts, i.e. at every chunk boundary of a pass; when it is up the wave leaves at once.  What a cancelled pass leaves in
+// accum / squares is not read again: the host delivers nothing of it and the next call starts its sums afresh.
+template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH>
+__global__ __launch_bounds__(256) void k_nee_pass_f64(const TraceArgs A, const NeeArgs N) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const uint32_t item = 4u * blockIdx.x + (uint32_t)wave; // wave-uniform
+    // (a wave without work — beyond the list, or cancelled — runs through with no pixel in the image rather than return
+    // early: with the early exits the compiler gave the twelve linear-loop variants a 68- or 132-byte stack frame that
+    // no instruction touches, and a private segment has to be set up for every wave of a launch)
+    unsigned int up = item >= A.n_items;
+    if (A.cancel_flag != nullptr && lane == 0) up |= __hip_atomic_load(A.cancel_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    up = __builtin_amdgcn_readfirstlane(up);
+    uint32_t tile = item;
+    if (A.tile_list != nullptr) tile = __builtin_amdgcn_readfirstlane(A.tile_list[up ? 0u : item]);
+    const bool idle = up != 0u || tile >= (uint32_t)A.n_tiles; // (a list holds tiles of the grid only)
+    const int px = (int)(tile % (uint32_t)A.tiles_x) * 8 + (lane & 7);
+    const int py = (int)(tile / (uint32_t)A.tiles_x) * 8 + (lane >> 3);
+    const bool in_image = !idle && px < A.width && py < A.height;
+
+    PathRng rng;
+    rng.pixel = (uint32_t)py * (uint32_t)A.width + (uint32_t)px;
+    rng.k0 = A.seed_lo;
+    rng.k1 = A.seed_hi;
+
+    // cpu.rs:35-36: one horizontal jitter per pixel
+    rng.sample = RT_RNG_SAMPLE_PIXEL;
+    const u4 bj = rng.block(0, RT_RNG_PIXEL, 0);
+    const double u = ((double)px + u53(bj.a, bj.b)) / (double)(A.width - 1);
+
+    d3 sum = mk(0.0, 0.0, 0.0); // the pixel's running sum (+0.0 before the first chunk: the host cleared accum)
+    if (in_image) {
+        const double *px_sum = A.accum + 3 * (size_t)rng.pixel;
+        sum = mk(px_sum[0], px_sum[1], px_sum[2]);
+    }
+    unsigned int n_segments = 0, n_started = 0;
+    nee_samples<PRIMS, TEXTURED, SPECULAR, BVH>(A, N, rng, px, py, u, in_image ? A.sample_begin : A.sample_end, A.sample_end, sum,
+                                                n_segments, n_started);
+    if (in_image) {
+        double *px_sum = A.accum + 3 * (size_t)rng.pixel;
+        px_sum[0] = sum.x;
+        px_sum[1] = sum.y;
+        px_sum[2] = sum.z;
+    }
+    // one atomic per wave for each statistic: path segments (shadow rays excluded) and primary rays
+    unsigned long long total = n_segments;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
+    if (lane == 0 && total) atomicAdd(A.segments + RT_STAT_SEGMENTS, total);
+    unsigned long long started = n_started;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) started += __shfl_down(started, off, 64);
+    if (lane == 0 && started) atomicAdd(A.segments + RT_STAT_SAMPLES, started);
+}
+
+// Behind every chunk: per pixel and channel S_j = running - boundary, squares += S_j^2 / n_j, boundary = running.  A
+// stopped tile's sums no longer move: S_j = 0 there, so the whole frame is swept.
+__global__ __launch_bounds__(256) void k_nee_chunk_f64(const double *__restrict__ running, double *__restrict__ boundary,
+                                                       double *__restrict__ squares, size_t n, double inv_samples) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const double now = running[i], s = now - boundary[i];
+        squares[i] += s * s * inv_samples;
+        boundary[i] = now;
+    }
+}
+
+// The decision step of a pass (rtdev::NeeDecide), a kernel of its own behind k_nee_pass_f64: one wave per 8x8 tile of the
+// WHOLE frame, one lane per pixel, 16 tiles to a block — k_fold_adaptive_f64 (rt_trace_pool_kernel.hip) without the fold,
+// the sums and Q being where the trace kernel left them.  Every tile writes its pixels into the pass's frame slot,
+// sqrt(scale * S) with the pass's scale while it runs and with its own once it has stopped (the same bits as at its stop:
+// its sums are no longer touched), so the slot is whole.  A running tile's error is the largest over its pixels and
+// channels of e = sigma / (sqrt(m + sigma) + sqrt(m)), m = S / s, V = max(0, Q - S m) / (k - 1), sigma = sqrt(V / s)
+// (include/rt_abi.h: rt_render_adaptive); it stops (eligible, error <= threshold) or is appended to the next pass's list,
+// with ONE atomic per block of 16 tiles.  next_list NULL (rt_render_progressive_nee): nothing stops, nothing is listed.
+__global__ __launch_bounds__(1024) void k_nee_decide_f64(const NeeDecide F) {
+    __shared__ uint32_t keep_of[16];
+    __shared__ uint32_t list_base;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = (int)blockIdx.x * 16 + wave; // wave-uniform
+    uint32_t keep = 0; // (lane 0) this wave's tile runs on
+    if (t < F.n_tiles) {
+        const int tx = t % F.tiles_x, ty = t / F.tiles_x;
+        const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
+        const bool valid = px < F.width && py < F.height;
+        const size_t i = valid ? ((size_t)py * (size_t)F.width + (size_t)px) * 3 : 0;
+        double acc[3] = {0.0, 0.0, 0.0};
+        if (valid)
+            for (int ch = 0; ch < 3; ++ch) acc[ch] = F.running[i + ch];
+        const int stop = __builtin_amdgcn_readfirstlane(F.tile_stop[t]);
+        if (stop != 0) {
+            const double scale = F.tile_scale[t];
+            if (valid)
+                for (int ch = 0; ch < 3; ++ch) F.out[i + ch] = sqrt(scale * acc[ch]);
+            if (lane == 0) F.err[t] = F.err_prev[t];
+        } else {
+            double e_max = 0.0;
+            if (valid) {
+                for (int ch = 0; ch < 3; ++ch) {
+                    F.out[i + ch] = sqrt(F.scale * acc[ch]);
+                    if (F.chunks_done >= 2) { // (the error is compared to a threshold, not bit for bit: reciprocals from the host)
+                        const double q = F.squares[i + ch];
+                        const double m = acc[ch] * F.scale;
+                        const double var = fmax(0.0, q - acc[ch] * m) * F.inv_batches;
+                        const double sigma = sqrt(var * F.scale);
+                        const double e = sigma > 0.0 ? sigma / (sqrt(m + sigma) + sqrt(m)) : 0.0;
+                        e_max = e > e_max ? e : e_max;
+                    }
+                }
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                const double o = __shfl_xor(e_max, off, 64);
+                e_max = o > e_max ? o : e_max;
+            }
+            if (lane == 0) {
+                const double err = F.chunks_done >= 2 ? e_max : -1.0;
+                F.err[t] = err;
+                if (F.eligible && err <= F.threshold) {
+                    F.tile_stop[t] = F.samples_done;
+                    F.tile_scale[t] = F.scale;
+                } else {
+                    keep = 1u;
+                }
+            }
+        }
+    }
+    if (F.next_list == nullptr) return; // (uniform over the grid)
+    if (lane == 0) keep_of[wave] = keep;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t total = 0;
+        for (int w = 0; w < 16; ++w) total += keep_of[w];
+        list_base = total ? atomicAdd(F.next_count, total) : 0u;
+    }
+    __syncthreads();
+    if (lane == 0 && keep) {
+        uint32_t at = list_base;
+        for (int w = 0; w < wave; ++w) at += keep_of[w];
+        F.next_list[at] = (uint32_t)t;
+    }
+}
+
+} // namespace RT_KNS
+
+namespace {
+template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH>
+void launch_pass_variant(const rtdev::TraceArgs &a, const rtdev::NeeArgs &n, unsigned blocks,
+                         hipStream_t stream) {
+    hipLaunchKernelGGL((RT_KNS::k_nee_pass_f64<PRIMS, TEXTURED, SPECULAR, BVH>), dim3(blocks), dim3(256), 0, stream, a, n);
+}
+template <int PRIMS, bool BVH>
+void launch_pass_prims(const rtdev::TraceArgs &a, const rtdev::NeeArgs &n, bool textured, bool specular,
+                       unsigned blocks, hipStream_t stream) {
+    if (textured) {
+        if (specular) launch_pass_variant<PRIMS, true, true, BVH>(a, n, blocks, stream);
+        else launch_pass_variant<PRIMS, true, false, BVH>(a, n, blocks, stream);
+    } else {
+        if (specular) launch_pass_variant<PRIMS, false, true, BVH>(a, n, blocks, stream);
+        else launch_pass_variant<PRIMS, false, false, BVH>(a, n, blocks, stream);
+    }
+}
+} // namespace
+
+// Samples [sample_begin, sample_end), one chunk, of args->n_items tiles (args->tile_list, or every tile of the grid in order)
+// added to args->accum.  prims_class: rtdev::PRIMS_*; bvh: closest hits through args'
+// tree (then PRIMS_ANY).
+extern "C" hipError_t RT_LAUNCHER(rtdev_launch_nee_pass)(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee,
+                                                         int prims_class, int textured, int specular, int bvh,
+                                                         hipStream_t stream) {
+    if (args->n_items == 0 || args->sample_end <= args->sample_begin) return hipSuccess;
+    const unsigned blocks = (args->n_items + 3u) / 4u;
+    if (bvh) {
+        launch_pass_prims<rtdev::PRIMS_ANY, true>(*args, *nee, textured != 0, specular != 0, blocks, stream);
+    } else {
+        switch (prims_class) {
+        case rtdev::PRIMS_RECTS: launch_pass_prims<rtdev::PRIMS_RECTS, false>(*args, *nee, textured != 0, specular != 0, blocks, stream); break;
+        case rtdev::PRIMS_SPHERES: launch_pass_prims<rtdev::PRIMS_SPHERES, false>(*args, *nee, textured != 0, specular != 0, blocks, stream); break;
+        default: launch_pass_prims<rtdev::PRIMS_ANY, false>(*args, *nee, textured != 0, specular != 0, blocks, stream); break;
+        }
+    }
+    return hipGetLastError();
+}
+
+// n = W*H*3 elements; samples: those of the chunk just traced
+extern "C" hipError_t RT_LAUNCHER(rtdev_launch_nee_chunk)(const double *running, double *boundary, double *squares, size_t n,
+                                                          int samples, hipStream_t stream) {
+    unsigned blocks = (unsigned)((n + 255) / 256);
+    if (blocks > 4096u) blocks = 4096u;
+    if (blocks == 0 || samples <= 0) return hipSuccess;
+    hipLaunchKernelGGL(RT_KNS::k_nee_chunk_f64, dim3(blocks), dim3(256), 0, stream, running, boundary, squares, n, 1.0 / (double)samples);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t RT_LAUNCHER(rtdev_launch_nee_decide)(const rtdev::NeeDecide *f, hipStream_t stream) {
+    if (f->n_tiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(RT_KNS::k_nee_decide_f64, dim3((unsigned)(f->n_tiles + 15) / 16), dim3(1024), 0, stream, *f);
+    return hipGetLastError();
+}

@@ -20,6 +20,11 @@
 // fold k - 1 left running (TraceArgs.tile_list), k_fold_adaptive_f64 folds, measures every running tile's error and
 // stops it or lists it for pass k + 1, and the count of running tiles travels to the host ahead of the frame.
 //
+// rt_render_progressive_nee and rt_render_adaptive_nee are the same loop with the next-event
+// estimator: a pass is one launch of k_nee_pass_f64 (rt_nee_pass_kernel.hip), which adds the pass's samples to the running
+// sums itself — there are no slices and no fold — and k_nee_decide_f64 behind it writes the frame slot and, adaptive,
+// decides every running tile.  Slots, events, cancel polling and the count-ahead-of-frame hand-off are unchanged.
+//
 // Host code only.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -73,11 +78,13 @@ int check_adaptive(const RtRenderParams *p, const RtAdaptiveParams *a, const dou
 // Everything the call needs, allocated before its first launch (a hipMalloc between passes would wait for the running
 // kernels): slices, one item counter per pass, the running sums, `slots` device and pinned frame slots, the copy stream and
 // the events of the slots; adaptive (n_tiles > 0): the sums of squares and the per-tile state, lists and counts.
-int reserve_passes(RtScene *s, const RtRenderParams *p, int passes, size_t n, int slots, size_t n_tiles) {
-    int rc = rtapi::reserve_render_buffers(s, p, false);
+// nee: the NEE passes keep no slices and no item counters (their per-tile state is the adaptive one: n_tiles > 0).
+int reserve_passes(RtScene *s, const RtRenderParams *p, int passes, size_t n, int slots, size_t n_tiles, bool nee) {
+    int rc = nee ? RT_OK : rtapi::reserve_render_buffers(s, p, false);
     if (rc != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
-    if (b.queue.count < (size_t)passes) RT_HIP(b.queue.alloc((size_t)passes));
+    if (!nee && b.queue.count < (size_t)passes) RT_HIP(b.queue.alloc((size_t)passes));
+    if (nee && b.partial.count < n) RT_HIP(b.partial.alloc(n)); // (here: the running sums at the last chunk boundary)
     if (b.accum.count < n) RT_HIP(b.accum.alloc(n));
     if (b.frame.count < (size_t)slots * n) RT_HIP(b.frame.alloc((size_t)slots * n));
     if ((rc = rtapi::ensure_host_frame(s, (size_t)slots * n)) != RT_OK) return rc;
@@ -105,8 +112,11 @@ int reserve_passes(RtScene *s, const RtRenderParams *p, int passes, size_t n, in
 // The adaptive form keeps three frame slots and enqueues pass k + 1 as soon as pass k's running-tile count has arrived —
 // before callback k, and only if a tile still runs — so that a cancel seen while pass k + 1 waits still finds the slots
 // of pass k whole (pass k + 2 may be enqueued by then).
+// nee: the light sampling of rt_render_progressive_nee / rt_render_adaptive_nee (checked by the caller), or NULL: the plain
+// estimator.
 int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams *p, int pass_samples, RtFrameCallback callback,
-                       void *user, const Cancel &cancel, const RtDenoiseParams *dn = nullptr, const Adaptive *ad = nullptr) {
+                       void *user, const Cancel &cancel, const RtDenoiseParams *dn = nullptr, const Adaptive *ad = nullptr,
+                       const RtLightSamplingParams *nee = nullptr) {
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     if (!callback && !ad) return fail(RT_ERR_INVALID_ARGUMENT, "callback is NULL");
     if (pass_samples <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "pass_samples must be positive");
@@ -115,7 +125,7 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "progressive frames are whole frames: params->strip_* is not supported here");
     if (p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "progressive frames are full-resolution frames: params->scale must be 0 or 1");
     if (dn && (rc = rtapi::check_denoise(p, dn)) != RT_OK) return rc;
-    if (s->use_v1) return fail(RT_ERR_UNSUPPORTED, "rt_render_progressive needs the pooled kernel (the v1 kernel has no sample chunks)");
+    if (s->use_v1 && !nee) return fail(RT_ERR_UNSUPPORTED, "rt_render_progressive needs the pooled kernel (the v1 kernel has no sample chunks)");
     if (cancel.raised()) return RT_ERR_CANCEL_EVENT; // cpu.rs:82-85, as rt_render_ex
     RT_HIP(hipSetDevice(s->device));
     const std::vector<int> starts = rtapi::chunk_starts(p->samples);
@@ -124,8 +134,8 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     const size_t n = (size_t)p->width * (size_t)p->height * 3; // a frame, and a slice (whole-frame slices: slice_rows = height)
     const int slots = ad ? 3 : 2;
     const int tiles_x = (p->width + 7) / 8;
-    const size_t n_tiles = ad ? (size_t)tiles_x * (size_t)((p->height + 7) / 8) : 0;
-    if ((rc = reserve_passes(s, p, passes, n, slots, n_tiles)) != RT_OK) return rc;
+    const size_t n_tiles = ad || nee ? (size_t)tiles_x * (size_t)((p->height + 7) / 8) : 0;
+    if ((rc = reserve_passes(s, p, passes, n, slots, n_tiles, nee != nullptr)) != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     // denoised: the guides, the filter's scratch and a third device frame slot, the filter's output
     if (dn && (rc = rtapi::reserve_denoise(s, n / 3, true)) != RT_OK) return rc;
@@ -133,6 +143,7 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     const RtGuides guides = dn ? rtapi::scene_guides(s, n / 3) : RtGuides();
     const hipStream_t stream = b.stream, copy = b.stream_copy;
     rtapi::PoolPasses pp;
+    rtapi::NeePasses np;
     double kernel_ms = 0.0, fold_ms = 0.0;
     uint32_t running = (uint32_t)n_tiles; // adaptive: the tiles the next pass traces
     int delivered = -1;                    // the last pass whose callback has run
@@ -143,11 +154,35 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
         RT_HIP(hipEventRecord(b.ev_pass_begin[slot], stream));
         // adaptive: pass 0 traces every tile, pass k the list fold k - 1 wrote
         const uint32_t *list = ad && k > 0 ? b.tile_lists.ptr + (size_t)(k & 1) * n_tiles : nullptr;
-        const int rc2 = rtapi::enqueue_chunks(s, pp, c0, c1, stream, list, running);
+        const int rc2 = nee ? rtapi::enqueue_nee_pass(s, np, c0, c1, stream, list, running)
+                            : rtapi::enqueue_chunks(s, pp, c0, c1, stream, list, running);
         if (rc2 != RT_OK) return rc2;
         RT_HIP(hipEventRecord(b.ev_pass_traced[slot], stream));
         if (k >= slots) RT_HIP(hipStreamWaitEvent(stream, b.ev_copied[slot], 0)); // device slot k % slots held pass k - slots's frame
-        if (ad) {
+        if (nee) { // the sums are where the pass left them: the frame slot and, adaptive, the tiles' decisions
+            rtdev::NeeDecide f;
+            memset(&f, 0, sizeof f);
+            f.running = b.accum.ptr;
+            f.squares = b.squares.ptr;
+            f.out = dev;
+            f.tile_stop = b.tile_stop.ptr;
+            f.tile_scale = b.tile_scale.ptr;
+            f.err_prev = b.tile_err.ptr + (size_t)((k + slots - 1) % slots) * n_tiles;
+            f.err = b.tile_err.ptr + (size_t)slot * n_tiles;
+            f.next_list = ad ? b.tile_lists.ptr + (size_t)((k + 1) & 1) * n_tiles : nullptr;
+            f.next_count = b.tile_counts.ptr + k;
+            f.width = p->width;
+            f.height = p->height;
+            f.tiles_x = tiles_x;
+            f.n_tiles = (int32_t)n_tiles;
+            f.chunks_done = c1;
+            f.samples_done = starts[(size_t)c1];
+            f.eligible = ad && c1 >= 4 && f.samples_done >= ad->params->min_samples && ad->params->threshold > 0.0;
+            f.scale = 1.0 / (double)f.samples_done; // what rtdev_launch_resolve passes for rt_render_frame_nee
+            f.inv_batches = c1 >= 2 ? 1.0 / (double)(c1 - 1) : 0.0;
+            f.threshold = ad ? ad->params->threshold : 0.0;
+            RT_HIP((s->exact ? rtdev_launch_nee_decide_exact : rtdev_launch_nee_decide)(&f, stream));
+        } else if (ad) {
             rtdev::AdaptiveFold f;
             memset(&f, 0, sizeof f);
             f.partial = b.partial.ptr;
@@ -196,12 +231,15 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     bool begun = false;
     auto run = [&]() -> int {
         // (fill_args inside refuses what rt_render_frame refuses at this sample count, before anything is enqueued)
-        int rc2 = rtapi::begin_passes(s, camera, p, stream, passes, cancel.armed(), pp);
+        int rc2 = nee ? rtapi::begin_nee_passes(s, camera, p, nee, stream, cancel.armed(), np)
+                      : rtapi::begin_passes(s, camera, p, stream, passes, cancel.armed(), pp);
         if (rc2 != RT_OK) return rc2;
         begun = true;
-        if (ad && pp.args.n_tiles != (int)n_tiles) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive: tile grid mismatch");
+        if (ad && (nee ? np.args.n_tiles : pp.args.n_tiles) != (int)n_tiles)
+            return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive: tile grid mismatch");
         RT_HIP(hipMemsetAsync(b.accum.ptr, 0, n * sizeof(double), stream)); // the running sums start at +0.0
-        if (ad) { // ... and so do the squares; every tile runs, no tile has been counted
+        if (nee) RT_HIP(hipMemsetAsync(b.partial.ptr, 0, n * sizeof(double), stream)); // ... and their copy at the last boundary
+        if (n_tiles) { // ... and so do the squares; every tile runs, no tile has been counted
             RT_HIP(hipMemsetAsync(b.squares.ptr, 0, n * sizeof(double), stream));
             RT_HIP(hipMemsetAsync(b.tile_stop.ptr, 0, n_tiles * sizeof(int32_t), stream));
             RT_HIP(hipMemsetAsync(b.tile_counts.ptr, 0, (size_t)passes * sizeof(uint32_t), stream));
@@ -312,6 +350,33 @@ int rt_render_adaptive(RtScene *s, const RtCamera *camera, const RtRenderParams 
         if (rc != RT_OK) return rc;
         const Adaptive ad{adaptive, out_rgb, out_samples, out_tile_error};
         return render_progressive(s, camera, p, adaptive->pass_samples, callback, user, c, nullptr, &ad);
+    });
+}
+
+int rt_render_progressive_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *light_sampling,
+                              int32_t pass_samples, RtFrameCallback callback, void *user, RtCancelCallback cancelled,
+                              void *cancel_user) {
+    const Cancel c{nullptr, cancelled, cancel_user};
+    return rtapi::guarded("rt_render_progressive_nee", [&]() -> int {
+        // (before the scene: these refusals need no device)
+        if (pass_samples <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "pass_samples must be positive");
+        if (!callback) return fail(RT_ERR_INVALID_ARGUMENT, "callback is NULL");
+        const int rc = rtapi::check_nee(s, camera, p, light_sampling, "rt_render_progressive_nee");
+        if (rc != RT_OK) return rc;
+        return render_progressive(s, camera, p, pass_samples, callback, user, c, nullptr, nullptr, light_sampling);
+    });
+}
+
+int rt_render_adaptive_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *light_sampling,
+                           const RtAdaptiveParams *adaptive, double *out_rgb, int32_t *out_samples, double *out_tile_error,
+                           RtFrameCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user) {
+    const Cancel c{nullptr, cancelled, cancel_user};
+    return rtapi::guarded("rt_render_adaptive_nee", [&]() -> int {
+        int rc = check_adaptive(p, adaptive, out_rgb); // (before the scene: these refusals need no device)
+        if (rc != RT_OK) return rc;
+        if ((rc = rtapi::check_nee(s, camera, p, light_sampling, "rt_render_adaptive_nee")) != RT_OK) return rc;
+        const Adaptive ad{adaptive, out_rgb, out_samples, out_tile_error};
+        return render_progressive(s, camera, p, adaptive->pass_samples, callback, user, c, nullptr, &ad, light_sampling);
     });
 }
 

@@ -204,6 +204,18 @@ extern "C" hipError_t rtdev_launch_nee(const rtdev::TraceArgs *args, const rtdev
                                        int specular, int bvh, hipStream_t stream);
 extern "C" hipError_t rtdev_launch_nee_exact(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class,
                                              int textured, int specular, int bvh, hipStream_t stream);
+// The launchers of rt_nee_pass_kernel.hip (both arithmetic flavours): one chunk of the NEE estimator over listed tiles on top
+// of args->accum, the batch-means update behind it and the decision step behind a pass.
+extern "C" hipError_t rtdev_launch_nee_pass(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class, int textured,
+                                            int specular, int bvh, hipStream_t stream);
+extern "C" hipError_t rtdev_launch_nee_pass_exact(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class,
+                                                  int textured, int specular, int bvh, hipStream_t stream);
+extern "C" hipError_t rtdev_launch_nee_chunk(const double *running, double *boundary, double *squares, size_t n, int samples,
+                                             hipStream_t stream);
+extern "C" hipError_t rtdev_launch_nee_chunk_exact(const double *running, double *boundary, double *squares, size_t n, int samples,
+                                                   hipStream_t stream);
+extern "C" hipError_t rtdev_launch_nee_decide(const rtdev::NeeDecide *f, hipStream_t stream);
+extern "C" hipError_t rtdev_launch_nee_decide_exact(const rtdev::NeeDecide *f, hipStream_t stream);
 
 struct RtScene {
     int device = 0;
@@ -351,6 +363,24 @@ int enqueue_denoise(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *
 // The scene's light list (rt_nee.hip), made by rt_scene_create once the device table's order is final: order[j] is the
 // description index of device primitive j.
 int build_light_list(RtScene *s, const RtSceneDesc *d, const std::vector<int32_t> &order);
+// What every NEE entry point refuses before a device is touched (rt_nee.hip), the scene last so that each refusal names
+// its own cause; `what` is the entry point's name in the messages about whole frames.
+int check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+              const char *what = "rt_render_frame_nee");
+// A whole NEE frame enqueued pass by pass (rt_progressive.hip), the NEE form of begin_passes / enqueue_chunks:
+// begin_nee_passes fills the argument blocks and enqueues what precedes the first launch — statistics cleared, the cancel
+// word armed when `cancellable`, ev_begin — and enqueue_nee_pass launches, chunk by chunk of [c0, c1), k_nee_pass_f64 for
+// the listed tiles on top of the scene's running sums and k_nee_chunk_f64 behind it (RenderBuffers.accum, .squares and
+// .partial — here the sums at the last chunk boundary, W*H*3 —, all cleared by the caller before pass 0).
+struct NeePasses {
+    rtdev::TraceArgs args;
+    rtdev::NeeArgs nee;
+    std::vector<int> starts; // chunk_starts(samples)
+};
+int begin_nee_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                     hipStream_t stream, bool cancellable, NeePasses &np);
+int enqueue_nee_pass(RtScene *s, NeePasses &np, int c0, int c1, hipStream_t stream, const uint32_t *tile_list = nullptr,
+                     uint32_t n_list = 0);
 // The pinned host frame of the host-output entry points, at least `doubles` long (rt_deliver.hip).
 int ensure_host_frame(RtScene *s, size_t doubles);
 // Rows of the owned-row grid of a render with these parameters (a multiple of strip_rows with strips).

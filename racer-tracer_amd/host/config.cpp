@@ -205,13 +205,13 @@ Args Args::parse(int argc, const char *const *argv) {
         else if (s == "--devices") a.devices = std::atoi(val().c_str());
         else if (s == "--denoise" && !has_inline) a.denoise = true;
         else if (s == "--nee" && !has_inline) a.nee = true;
-        else if (s == "--adaptive") {
+        else if (s == "--adaptive" || s == "--nee-adaptive") {
             const std::string v = val();
             char *end = nullptr;
             const double t = std::strtod(v.c_str(), &end);
             if (v.empty() || end == nullptr || *end != '\0' || !std::isfinite(t) || !(t > 0.0))
-                throw TracerError::ArgumentParsingError("--adaptive needs a positive threshold, not '" + v + "'");
-            a.adaptive = t;
+                throw TracerError::ArgumentParsingError(s + " needs a positive threshold, not '" + v + "'");
+            (s == "--adaptive" ? a.adaptive : a.nee_adaptive) = t;
         }
         else if (s == "-h" || s == "--help") a.help = true;
         else throw TracerError::ArgumentParsingError("unknown argument " + s);
@@ -220,6 +220,10 @@ Args Args::parse(int argc, const char *const *argv) {
         throw TracerError::ArgumentParsingError("--adaptive renders on one device: it does not combine with --devices > 1");
     if (a.nee && a.adaptive > 0.0)
         throw TracerError::ArgumentParsingError("--nee and --adaptive are two estimators: pick one");
+    if (a.nee_adaptive > 0.0 && a.adaptive > 0.0)
+        throw TracerError::ArgumentParsingError("--nee-adaptive and --adaptive are two estimators: pick one");
+    if (a.nee_adaptive > 0.0 && a.devices > 1)
+        throw TracerError::ArgumentParsingError("--nee-adaptive renders on one device: it does not combine with --devices > 1");
     if (a.nee && a.devices > 1)
         throw TracerError::ArgumentParsingError("--nee renders on one device: it does not combine with --devices > 1");
     return a;

@@ -65,6 +65,7 @@ struct Args { // config.rs:12-28
     bool denoise = false; // --denoise: filter the assembled frame (rt_denoise_frame) before tone map and PNG
     bool nee = false; // --nee: one device renders the frame through rt_render_frame_nee (next-event estimation)
     double adaptive = 0.0; // --adaptive T (T > 0): render through rt_render_adaptive with threshold T, one device only
+    double nee_adaptive = 0.0; // --nee-adaptive T (T > 0): render through rt_render_adaptive_nee with threshold T, one device only
     bool help = false;
 
     static Args parse(int argc, const char *const *argv);

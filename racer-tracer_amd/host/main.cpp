@@ -7,7 +7,8 @@
 // process the way the reference shards it over its rayon pool, cpu.rs:118-131) and --denoise (the assembled frame goes
 // through rt_denoise_frame on the first device before the tone map and the PNG) and --adaptive T (one device renders the
 // frame through rt_render_adaptive, a tile stopping once its error is at most T; --denoise filters that frame) and --nee (one
-// device renders the frame through rt_render_frame_nee, next-event estimation; --denoise filters that frame).
+// device renders the frame through rt_render_frame_nee, next-event estimation; --denoise filters that frame) and
+// --nee-adaptive T (--adaptive's stop rule with the next-event estimator: rt_render_adaptive_nee).
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -52,7 +53,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee] [--nee-adaptive T]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -86,7 +87,7 @@ int main(int argc, char **argv) {
         scenes.push_back(scene);
     }
     const size_t n_rgb = (size_t)params.width * (size_t)params.height * 3;
-    ScreenBuffer sb{session, params.width, params.height, std::vector<double>(n_rgb, 0.0), std::vector<double>(args.denoise || args.adaptive > 0.0 || args.nee ? n_rgb : 0, 0.0)};
+    ScreenBuffer sb{session, params.width, params.height, std::vector<double>(n_rgb, 0.0), std::vector<double>(args.denoise || args.adaptive > 0.0 || args.nee || args.nee_adaptive > 0.0 ? n_rgb : 0, 0.0)};
     fprintf(stderr, "Rendering image...\n"); // interactive.rs:229
     auto t0 = std::chrono::steady_clock::now();
     double traced = 1.0; // --adaptive: the fraction of the frame's samples traced
@@ -97,6 +98,19 @@ int main(int argc, char **argv) {
         std::vector<int32_t> counts(n_rgb / 3);
         rc = rt_render_adaptive(scenes[0], rth_session_camera(session), &params, &ap, sb.raw.data(), counts.data(), nullptr, nullptr,
                                 nullptr, nullptr, nullptr);
+        double sum = 0.0;
+        for (int32_t c : counts) sum += (double)c;
+        traced = sum / ((double)counts.size() * (double)params.samples);
+        if (rc == RT_OK && !args.denoise) rth_tone_map(session, sb.raw.data(), sb.buffer.data(), n_rgb / 3);
+    } else if (args.nee_adaptive > 0.0) { // as --adaptive, with the next-event estimator
+        RtAdaptiveParams ap;
+        rt_adaptive_params_default(&ap);
+        ap.threshold = args.nee_adaptive;
+        RtLightSamplingParams ls;
+        rt_light_sampling_params_default(&ls);
+        std::vector<int32_t> counts(n_rgb / 3);
+        rc = rt_render_adaptive_nee(scenes[0], rth_session_camera(session), &params, &ls, &ap, sb.raw.data(), counts.data(), nullptr,
+                                    nullptr, nullptr, nullptr, nullptr);
         double sum = 0.0;
         for (int32_t c : counts) sum += (double)c;
         traced = sum / ((double)counts.size() * (double)params.samples);
@@ -132,9 +146,9 @@ int main(int argc, char **argv) {
             st.segments += one.segments;
             st.kernel_ms = one.kernel_ms > st.kernel_ms ? one.kernel_ms : st.kernel_ms;
         }
-        if (args.adaptive > 0.0)
-            fprintf(stderr, "Adaptive sampling (threshold %g) traced %.1f %% of the %d samples per pixel.\n", args.adaptive,
-                    100.0 * traced, params.samples);
+        if (args.adaptive > 0.0 || args.nee_adaptive > 0.0)
+            fprintf(stderr, "Adaptive sampling (threshold %g) traced %.1f %% of the %d samples per pixel.\n",
+                    args.adaptive > 0.0 ? args.adaptive : args.nee_adaptive, 100.0 * traced, params.samples);
         fprintf(stderr, "It took %.3f seconds to render the image. (%.1f Msamples/s, %.2f segments/sample, kernel %.1f ms)\n",
                 secs, (double)st.samples / secs / 1e6, st.samples ? (double)st.segments / (double)st.samples : 0.0, st.kernel_ms);
         if (rth_session_image_action(session) == RTH_IMAGE_ACTION_SAVE_PNG) { // main.rs:153-156
