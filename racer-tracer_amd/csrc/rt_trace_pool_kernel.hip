@@ -189,6 +189,11 @@ __device__ __forceinline__ void move_masked(const d3 &p, uint64_t mask, d3 &v) {
                  : [mask] "s"(mask), [px] "v"(p.x), [py] "v"(p.y), [pz] "v"(p.z)
                  : "scc");
 }
+// v += 1 in the lanes of `mask` (wave-uniform), as one add with the mask as its carry-in; written in C++ it is a select of
+// 0 / 1 (v_cndmask_b32) and an add.
+__device__ __forceinline__ void increment_masked(uint32_t &v, uint64_t mask) {
+    asm("v_addc_co_u32 %[v], vcc, 0, %[v], %[mask]" : [v] "+v"(v) : [mask] "s"(mask) : "vcc");
+}
 // The lowest set bit of every group of 2^lg bits of x (1 <= lg <= 6), in the scalar unit: x & -x within each group, the
 // negation done per group as (~x without the groups' top bits) + 1 in every group, whose carry stops at the group's top
 // bit, XOR the top bits of ~x
@@ -249,10 +254,11 @@ template <bool TEXTURED, int NBUF, bool OVERLAP> struct WaveLds {
     double ulc[3];
 };
 
-// vec3.rs:424-430 for every lane with `need`, evaluated by the whole wave.
+// vec3.rs:424-430 for every lane of `pending` (a wave-uniform lane mask, like the one it returns: the lanes
+// that got their sample), evaluated by the whole wave.
 // Must be called by all 64 lanes (wave-uniform control flow).  Runs at most
-// MAX_ROUNDS rounds: a lane whose request is still open afterwards returns
-// false and keeps `base` (its first untested candidate), so the search resumes
+// MAX_ROUNDS rounds: a lane whose request is still open afterwards is not in the
+// returned mask and keeps `base` (its first untested candidate), so the search resumes
 // at the same stream position in the next call.
 // The round count is a template constant: two rounds (the plain variants) are unrolled into straight-line code.  The
 // first round writes `result` in EVERY lane (no lane holds a sample yet), so only the later rounds write it under the
@@ -262,11 +268,10 @@ template <bool TEXTURED, int NBUF, bool OVERLAP> struct WaveLds {
 // call, and a grouped round posts it, so a candidate costs 10 multiplies instead of 14.  A grouped round's answer comes
 // back through the request's slot, not through lane shuffles.
 template <int MAX_ROUNDS>
-__device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t pixel, uint32_t sample, uint32_t seg,
+__device__ __forceinline__ uint64_t coop_random_in_unit_sphere(uint64_t pending, uint32_t pixel, uint32_t sample, uint32_t seg,
                                                            uint32_t &base, uint32_t k0, uint32_t k1, int lane,
                                                            SphereSlot *slot, d3 &result) {
-    bool have = false;
-    uint64_t pending = ballot(need);
+    uint64_t have = 0;
     const ScatterPrefix own = scatter_prefix(pixel, sample, seg, k0, k1);
     for (int round = 0; round < MAX_ROUNDS && pending != 0; ++round) {
         const int n = __popcll(pending);
@@ -277,25 +282,20 @@ __device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t p
         // group size q = 2^lg, the largest power of two with n * q <= 64
         const int lg = n > 32 ? 0 : (n > 16 ? 1 : (n > 8 ? 2 : (n > 4 ? 3 : (n > 2 ? 4 : (n > 1 ? 5 : 6)))));
         // what `result` takes: in every lane in the first round, in the lanes of `take` in the later ones.  `result` only
-        // means something to a lane that returns true, so a lane that still needs a sample may take whatever its round
+        // means something to a lane of the returned mask, so a lane that still needs a sample may take whatever its round
         // left it, a rejected candidate included.
         d3 cand;
         uint64_t take;
         if (lg == 0) { // more than 32 requests: one candidate each, so every lane tests its OWN (no LDS)
             const d3 p = sphere_candidate(philox_from_prefix(own, base, k0, k1));
             cand = p;
-            take = pending; // ballot(need)
-            const bool inside = len2(p) < 1.0;
-            if (need) {
-                if (inside) {
-                    need = false;
-                    have = true;
-                } else {
-                    base += 1u;
-                }
-            }
-            pending &= ~ballot(inside); // (the comparison's own lane mask: see `pending` below)
+            take = pending;
+            const uint64_t inside = ballot(len2(p) < 1.0); // (the comparison's own lane mask)
+            have |= pending & inside;
+            pending &= ~inside;
+            if (__builtin_amdgcn_inverse_ballot_w64(pending)) base += 1u;
         } else {
+            const bool need = __builtin_amdgcn_inverse_ballot_w64(pending);
             const int rank = lane_rank(pending);
             if (need) post_request(slot + rank, own, base);
             const int j = lane >> lg;              // request served by this lane
@@ -327,13 +327,9 @@ __device__ __forceinline__ bool coop_random_in_unit_sphere(bool need, uint32_t p
             const double *const answer = reinterpret_cast<const double *>(slot + (need ? rank : 0));
             cand = mk(answer[0], answer[1], answer[2]);
             take = got;
-            if (__builtin_amdgcn_inverse_ballot_w64(got)) {
-                need = false;
-                have = true;
-            } else if (need) {
-                base += 1u << lg;
-            }
+            have |= got;
             pending &= ~got; // the lanes still searching
+            if (__builtin_amdgcn_inverse_ballot_w64(pending)) base += 1u << lg;
         }
         if (round == 0) {
             result = cand;
@@ -861,7 +857,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
     };
 
     // ---- path state of this lane (it outlives the items: a lane's path may belong to either slot)
-    bool alive = false;
+    uint64_t alive_m = 0;
     int spix = 0;         // slot of the item the current path belongs to << 6 | its pixel of that item's tile (lane order)
     PathRng rng{0, 0, A.seed_lo, A.seed_hi};
     d3 o = mk(0, 0, 0), d = o, T = o;
@@ -870,9 +866,9 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
     // A lane whose hit needs a random_in_unit_sphere sample that the wave has not
     // found yet stays `waiting` (it keeps its hit below and skips tracing) until a
     // later iteration's sampler rounds reach its accepted candidate.
-    bool waiting = false;
+    uint64_t waiting_m = 0;
     uint32_t cand_base = 0;   // first untested candidate of the open request
-    bool is_lambert = false;  // material of the open hit (else Metal)
+    uint64_t lambert_m = 0;   // material of the open hit (else Metal)
     // the open hit: its point takes the ray origin's place (`o` is dead once the hit record exists) and its
     // attenuation goes into T at once, so neither is carried as extra state while the lane waits
     d3 hit_normal = o;
@@ -889,7 +885,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             batch_due = ~0u;
         }
         // (without OVERLAP there is one slot, and whatever is in flight belongs to the draining item)
-        if ((state & DRAINING) != 0u && ballot(alive && (!OVERLAP || (((uint32_t)spix ^ state) & CUR) != 0u)) == 0) { // the last path of the draining item has ended
+        if ((state & DRAINING) != 0u && (OVERLAP ? alive_m & ballot((((uint32_t)spix ^ state) & CUR) != 0u) : alive_m) == 0) { // the last path of the draining item has ended
             finish_item(OVERLAP ? (int)((state ^ CUR) >> 6) & 1 : 0);
             state &= ~DRAINING;
         }
@@ -903,9 +899,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             // one item at a time: no path is in flight here.  Saying so — every lane's path state is set anew — ends the
             // state's live ranges at the loop's exit: across the item code above they would otherwise hold their registers
             // (the plain variants: 77 -> 80 VGPRs and 64 bytes of scratch).
-            alive = false;
-            waiting = false;
-            is_lambert = false;
+            alive_m = waiting_m = lambert_m = 0;
             spix = 0;
             rng.pixel = rng.sample = 0;
             o = d = T = hit_normal = mk(0, 0, 0);
@@ -922,7 +916,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         RT_REGION(1); // batches
         // ---- hand pool entries to the lanes without a path (ballot + prefix count)
         if (next < total) {
-            const uint64_t idle = ballot(!alive);
+            const uint64_t idle = ~alive_m;
             const uint32_t w = next + (uint32_t)lane_rank(idle);
             // entries whose camera samples are in LDS: all of them with two buffers, the current batch with one
             const uint32_t ready = NBUF == 2 ? total : min(total, batches_done << 6);
@@ -940,7 +934,8 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 pix_new = L.pix_of[w - (uint32_t)s_off * (uint32_t)n_valid];
             }
             const uint32_t pixel_new = (uint32_t)shfl_i((int)my_pixel, pix_new);
-            if (!alive && w < ready) { // cpu.rs:39-40 + camera.rs:326-337
+            const uint64_t taking = idle & ballot(w < ready);
+            if (__builtin_amdgcn_inverse_ballot_w64(taking)) { // cpu.rs:39-40 + camera.rs:326-337
                 spix = (int)(state & CUR) | pix_new;
                 rng.pixel = pixel_new;
                 rng.sample = (uint32_t)(smp0 + s_off);
@@ -960,31 +955,40 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 if (PRIMS == PRIMS_ANY && ray_times != nullptr) ray_time = ray_times[buf][slot];
                 T = mk(1.0, 1.0, 1.0);
                 seg = 0;
-                alive = true;
                 ++n_started;
             }
+            alive_m |= taking;
         }
         RT_REGION(2); // hand-out + primary ray
         // (one item at a time: the loop ends when the pool is dry and nothing is in flight — a scalar test on a ballot.
         // The OVERLAP variants leave at the bottom instead.)
-        if (!OVERLAP && ballot(alive) == 0) break;
+        if (!OVERLAP && alive_m == 0) break;
         // ---- one ray_color level for every lane with a path
         // A path that ends here adds its throughput T (times what it ran into) to its pixel: T is dead
         // afterwards, so the product is formed in place.
-        bool ended = false;
-        bool scattered = false;  // the path got a new ray this iteration (depth check below)
-        bool finish = false;     // Lambertian / Metal hit whose direction can be completed now
+        uint64_t ended_m = 0;
+        uint64_t scattered_m = 0;  // the path got a new ray this iteration (depth check below)
+        uint64_t finish_m = 0;     // Lambertian / Metal hit whose direction can be completed now
+        const uint64_t tracing = alive_m & ~waiting_m;
         int noise_tex = -1;      // Noise texture this lane's hit wants (evaluated by the whole wave below)
-        RT_LANES(__popcll(ballot(alive && !waiting)), next >= total);
-        if (alive && !waiting) {
-            int max_depth = A.max_depth;
-            asm volatile("" : "+s"(max_depth)); // (opaque: hoisted out of the loop the test lives in a lane mask that is spilled)
-            if (max_depth <= 0) { // renderer.rs:48-55 with max_depth 0
-                ended = true;
-            } else {
+        RT_LANES(__popcll(tracing), next >= total);
+        // A scalar mask assigned inside a divergent branch meets its old value in a phi that the compiler takes for
+        // divergent (a VGPR pair).  So the branches below leave per-lane DATA behind them (`best`, `kind`, `fuzz`), and the
+        // masks are ballots of comparisons of that data, taken where all 64 lanes are back together.
+        int max_depth = A.max_depth;
+        asm volatile("" : "+s"(max_depth)); // (opaque: hoisted out of the loop the test lives in a lane mask that is spilled)
+        const uint64_t shooting = max_depth <= 0 ? 0ull : tracing; // renderer.rs:48-55 with max_depth 0: the path ends
+        ended_m = tracing & ~shooting;
+        double best_t = __builtin_inf(); // closest hit, t in [0.001, inf) (renderer.rs:58)
+        int best = -1, best_aux = 0;
+        // material of the hit: set by the lanes that hit and read under their mask, so it starts as whatever its register
+        // holds (an empty asm "defines" it: no move).  Opaque after the branch that sets it, or the comparison moves back
+        // into the branch and comes out as a bool.
+        int kind;
+        asm volatile("" : "=v"(kind));
+        {
+            if (__builtin_amdgcn_inverse_ballot_w64(shooting)) {
                 ++n_segments;
-                double best_t = __builtin_inf(); // closest hit, t in [0.001, inf) (renderer.rs:58)
-                int best = -1, best_aux = 0;
                 const d3 inv_d = rcp3(d);
                 const double inv_a = PRIMS == PRIMS_RECTS ? 0.0 : rcp_f64(len2(d));
                 if (BVH) {
@@ -1091,7 +1095,11 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                     }
                 }
                 RT_REGION(3); // closest hit
-                if (best < 0) { // background_color.rs:27-33 / :45-48
+            }
+            const uint64_t miss_m = shooting & ballot(best < 0), hit_m = shooting & ~miss_m;
+            ended_m |= miss_m;
+            {
+                if (__builtin_amdgcn_inverse_ballot_w64(miss_m)) { // background_color.rs:27-33 / :45-48
                     const RT_CONSTANT TraceArgs *K = kernargs_here();
                     d3 bgc = ld3(K->bg.top);
                     if (K->bg.kind == RT_BG_SKY) {
@@ -1099,12 +1107,12 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                         bgc = (1.0 - t) * bgc + t * ld3(K->bg.bottom);
                     }
                     T = T * bgc;
-                    ended = true;
-                } else {
+                }
+                if (__builtin_amdgcn_inverse_ballot_w64(hit_m)) {
                     const Prim &P = BVH ? A.prims[best] : lds_prims[best];
                     const Material &M = P.mat;
                     const Hit h = prim_hit_record<PRIMS, TEXTURED, true>(P, o, d, ray_time, best_t, best_aux, M.needs_uv != 0);
-                    const int kind = M.kind;
+                    kind = M.kind;
                     RT_REGION(8); // hit record
 #ifdef RT_PROFILE_REGIONS
                     { // how many lanes of an iteration look up a Noise texture together?
@@ -1140,23 +1148,18 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                         hit_normal = h.normal;
                         fuzz = M.fuzz;
                     }
-                    if (kind == RT_MAT_DIFFUSE_LIGHT) { // diffuse_light.rs:25-37
-                        ended = true;
-                        if (!SPECULAR && TEXTURED) o = h.point;
-                    } else if (!SPECULAR || kind == RT_MAT_LAMBERTIAN) { // lambertian.rs:26-38 (direction below)
-                        if (!SPECULAR) {
-                            o = h.point;
-                            cand_base = 0;
-                        }
+                    if (!SPECULAR) {
+                        // a light (diffuse_light.rs:25-37) ends the path, anything else is a Lambertian (lambertian.rs:26-38,
+                        // direction below); what a Lambertian hit sets is dead in a path that has ended
+                        o = h.point;
+                        cand_base = 0;
                         d = h.normal; // the incoming direction is dead: lambertian.rs:27 starts from the normal
-                        is_lambert = true;
-                        waiting = true;
-                    } else if (SPECULAR && kind == RT_MAT_METAL) { // metal.rs:26-43
+                    } else if (kind == RT_MAT_DIFFUSE_LIGHT) {
+                    } else if (kind == RT_MAT_LAMBERTIAN) {
+                        d = h.normal;
+                    } else if (kind == RT_MAT_METAL) { // metal.rs:26-43
                         const d3 ud = unit_fast(d_in);
                         d = ud - (2.0 * dot(ud, h.normal)) * h.normal; // metal.rs:30 reflect(); the fuzz term follows below
-                        is_lambert = false;
-                        waiting = fuzz != 0.0; // fuzz 0 multiplies the sample by 0: its draws are dead
-                        finish = !waiting;
                     } else { // dialectric.rs:25-55
                         const double ratio = h.front ? M.color[0] : M.ior; // 1 / ior, divided at upload
                         const d3 ud = unit_fast(d_in);
@@ -1177,9 +1180,23 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                             const d3 perp = ratio * (ud + cos_theta * h.normal);
                             d = perp + (-sqrt_fast(fabs(1.0 - len2(perp)))) * h.normal;
                         }
-                        scattered = true;
                     }
                 }
+            }
+            // what the hit's material decided, from its kind: a light ends the path, a Lambertian and a Metal with fuzz
+            // (fuzz 0 multiplies the sample by 0: its draws are dead) wait for a sample, glass has its new ray already
+            asm volatile("" : "+v"(kind));
+            const uint64_t light_m = hit_m & ballot(kind == RT_MAT_DIFFUSE_LIGHT);
+            ended_m |= light_m;
+            if (!SPECULAR) {
+                waiting_m |= hit_m & ~light_m;
+            } else {
+                const uint64_t lambertian = hit_m & ballot(kind == RT_MAT_LAMBERTIAN), metal = hit_m & ballot(kind == RT_MAT_METAL);
+                const uint64_t fuzzy = metal & ballot(fuzz != 0.0);
+                lambert_m = (lambert_m & ~metal) | lambertian;
+                waiting_m |= lambertian | fuzzy;
+                finish_m = metal & ~fuzzy;
+                scattered_m = hit_m & ~(light_m | lambertian | metal);
             }
         }
 
@@ -1192,7 +1209,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         RT_REGION(4); // miss / material
         if constexpr (TEXTURED) { // the Noise lookups of this iteration, by the whole wave (all 64 lanes arrive here)
             const bool lookup = noise_tex >= 0;
-            if (ballot(lookup) != 0) {
+            if (ballot(noise_tex >= 0) != 0) {
                 const Texture *tt = BVH ? A.textures : lds_textures;
                 const double turb = coop_noise_turbulence(lookup, o, lookup ? tt[noise_tex].depth : 0,
                                                           lookup ? tt[noise_tex].perlin : 0, A, lds_perlin, lane, L.scratch.noise);
@@ -1204,15 +1221,17 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         }
         RT_REGION(10); // Noise rounds
         d3 sph = mk(0.0, 0.0, 0.0); // (left uninitialised, three moves fewer per iteration cost the plain variants 16 bytes of scratch)
-        if (coop_random_in_unit_sphere<(TEXTURED || SPECULAR) ? 4 : 2>(waiting, rng.pixel, rng.sample, seg, cand_base, A.seed_lo,
-                                                                       A.seed_hi, lane, L.scratch.sphere, sph)) {
-            waiting = false;
-            finish = true;
+        {
+            const uint64_t got = coop_random_in_unit_sphere<(TEXTURED || SPECULAR) ? 4 : 2>(waiting_m, rng.pixel, rng.sample, seg, cand_base, A.seed_lo,
+                                                                                           A.seed_hi, lane, L.scratch.sphere, sph);
+            waiting_m &= ~got;
+            finish_m |= got;
         }
 
         RT_REGION(5); // sampler
-        if (finish) {
-            if (!SPECULAR || is_lambert) { // lambertian.rs:27-33 (without SPECULAR every open hit is a Lambertian one)
+        double facing = 0.0; // Metal: the new direction against the normal
+        if (__builtin_amdgcn_inverse_ballot_w64(finish_m)) {
+            if (!SPECULAR || __builtin_amdgcn_inverse_ballot_w64(lambert_m)) { // lambertian.rs:27-33 (without SPECULAR every open hit is a Lambertian one)
                 const d3 dir = d + unit_fast(sph); // d holds the normal since the hit
                 // vec3.rs:127-130 near_zero keeps the normal: once in 10^23 samples, so the wave branches
                 // around the six selects it would otherwise issue every time.  (The ballots of the three comparisons,
@@ -1242,20 +1261,24 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                         if ((near_zero >> lane) & 1ull) d = normal;
                     }
                 }
-                scattered = true;
             } else if (SPECULAR) { // metal.rs:31-42: d holds the reflected direction since the hit
                 if (fuzz != 0.0) d = d + fuzz * sph;
-                if (dot(d, hit_normal) < 0.0) {
-                    T = mk(0.0, 0.0, 0.0);
-                    ended = true;
-                } else {
-                    scattered = true;
-                }
+                facing = dot(d, hit_normal);
+                if (facing < 0.0) T = mk(0.0, 0.0, 0.0);
             }
         }
+        if (!SPECULAR) {
+            scattered_m = finish_m;
+        } else {
+            const uint64_t absorbed = finish_m & ~lambert_m & ballot(facing < 0.0);
+            ended_m |= absorbed;
+            scattered_m |= finish_m & ~absorbed;
+        }
         // renderer.rs:48-55: the recursion's next level has depth 0 -> white
-        if (scattered && (int)++seg >= A.max_depth) ended = true;
-        if (alive && ended) { // vec3.rs:38-42 Color::add into the pixel's sum
+        increment_masked(seg, scattered_m);
+        ended_m |= scattered_m & ballot((int)seg >= A.max_depth);
+        ended_m &= alive_m;
+        if (__builtin_amdgcn_inverse_ballot_w64(ended_m)) { // vec3.rs:38-42 Color::add into the pixel's sum
             // (the scale is a power of two: its upper half lives in ONE scalar register across the loop — a scalar load and its
             // wait here, in every iteration, showed in the frame time)
             if (FIXED_SUMS) {
@@ -1272,8 +1295,8 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 atomicAdd(&L.sum[spix][1], T.y);
                 atomicAdd(&L.sum[spix][2], T.z);
             }
-            alive = false;
         }
+        alive_m &= ~ended_m;
         RT_REGION(6); // scatter + accumulate
         // ---- ONE way out of the path loop, down here (a second `break`, or one inside an else-arm of the hand-out, had the
         // compiler merge the lanes' alive / waiting / material masks under the exec mask at two more joins: +20 scalar
@@ -1285,7 +1308,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             asm volatile("" : "+s"(st)); // (opaque: `state` does not change in this loop)
             if ((st & (DRAINING | POOL_DRY)) != 0u) { // (one scalar test in the usual iteration)
                 uint64_t go = 0ull; // (a scalar 64-bit value, not a bool: see the flags above)
-                if ((st & DRAINING) != 0u) go = ballot(alive && (((uint32_t)spix ^ st) & CUR) != 0u);
+                if ((st & DRAINING) != 0u) go = alive_m & ballot((((uint32_t)spix ^ st) & CUR) != 0u);
                 if (go == 0ull) break;
             }
         }

@@ -37,7 +37,8 @@ F64_TRANS = {"v_rcp_f64_e32", "v_rsq_f64_e32", "v_sqrt_f64_e32", "v_rcp_f64_e64"
 def unit_of(op):
     if op.startswith("v_"):
         return "valu"
-    if op.startswith(("s_load", "s_buffer_load", "s_memtime", "s_memrealtime", "s_dcache", "s_store", "s_atomic")):
+    # (scalar loads, clocks and cache invalidates; the kernels hold no scalar memory write of any kind)
+    if op.startswith(("s_load", "s_buffer_load", "s_memtime", "s_memrealtime", "s_dcache_inv")):
         return "smem"
     if op.startswith(("s_branch", "s_cbranch", "s_setpc", "s_swappc", "s_endpgm", "s_call")):
         return "branch"   # SQ_INSTS_BRANCH, not SQ_INSTS_SALU
