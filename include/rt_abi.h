@@ -609,6 +609,33 @@ int rt_render_adaptive_nee(RtScene *scene, const RtCamera *camera, const RtRende
                            double *out_tile_error, /* HOST, ceil(W/8)*ceil(H/8), row-major tiles; may be NULL */
                            RtFrameCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
 
+/* rt_render_ex's contract with rt_render_frame_nee's estimator: the tile stream of ONE next-event-estimation frame, delivered
+ * while it renders, with a cancel hook that stops it quickly.  One device; no `volatile int` form.
+ *  - Tiles: the tiles_w x tiles_h grid, column-major, the last row / column absorbing the remainders, ONE callback per tile
+ *    (an empty tile included), on the calling thread, while the launch is still running.  For the same `params` the sequence
+ *    of (r, c, width, height) is exactly rt_render_ex's.
+ *  - Pixels: every delivered pixel equals rt_render_frame_nee's pixel for the same scene, camera, params and
+ *    light_sampling, bit for bit: a pixel's samples are added in sample order to an f64 sum that starts at +0.0, and the
+ *    value written is sqrt((1 / samples) * sum) with the same reciprocal.  The tile grid changes no pixel.
+ *  - One persistent launch traces 8x8 pixel tiles, queued tile column by tile column, and writes finished pixels straight
+ *    into pinned host memory; no resolve launch.  Where that launch does not apply (a tile grid wider than the image) the
+ *    frame is rt_render_frame_nee's launch and the tiles are cut from it: same pixels, same sequence.
+ *  - cancelled / cancel_user as rt_render_ex's (polled on the calling thread; NULL: none).  Raised on entry:
+ *    RT_ERR_CANCEL_EVENT, no callback.  Raised later: RT_OK, nothing further is delivered, tiles already delivered stay
+ *    delivered.  On the device a wave reads the cancel word at every hand-out of a tile and between the sample chunks of
+ *    its tile, so a cancel does not wait for a tile's full sample count.  A later render on the same scene, through any
+ *    entry point, sees nothing stale.
+ *  - Refused with RT_ERR_INVALID_ARGUMENT before a device is touched: everything rt_render_frame_nee refuses (NULL scene,
+ *    camera, params or light_sampling, an unknown heuristic, max_lights outside 0..64, a non-zero _reserved,
+ *    params->strip_count > 1, params->scale > 1) and a NULL callback.  A scene created with RT_KERNEL_V1 is NOT refused
+ *    (the NEE kernels are their own).  max_lights = 0, or a scene without a listed light: the plain estimator's paths.
+ *  - rt_scene_last_stats afterwards: samples = W*H*N, segments exactly rt_render_frame_nee's count for the same inputs,
+ *    kernel_ms spans the launch, kernel_launches = 1.
+ * A binding detects this entry point by symbol lookup (RT_ABI_VERSION is unchanged by it). */
+int rt_render_nee(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                  const RtLightSamplingParams *light_sampling,
+                  RtTileCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
+
 /* What the reference does to a finished tile downstream of the renderer, on
  * the device: ScreenBuffer::update's tone map (image_buffer.rs:147-153) and
  * SavePng's packing `(c * 255.0) as u32 -> (r << 24 | g << 16 | b << 8 | 255)`

@@ -112,6 +112,12 @@ def progressive_passes(samples, pass_samples):
     return list(out[:n.value])
 
 
+def nee_stream_chunk(arithmetic=abi.RT_ARITH_FAST):
+    """rtdev_nee_stream_chunk: the samples rt_render_nee's kernel traces between two looks at the cancel word (a tuning
+    constant of the build; no pixel depends on it).  No device needed."""
+    return lib().rtdev_nee_stream_chunk_exact() if arithmetic == abi.RT_ARITH_REFERENCE else lib().rtdev_nee_stream_chunk()
+
+
 def denoise_params(**overrides):
     """rt_denoise_params_default, with fields overridden by keyword (iterations, flags, sigma_color, sigma_normal,
     sigma_plane) -> abi.RtDenoiseParams.  No device needed."""
@@ -382,6 +388,28 @@ class Scene:
                                                tile_error.ctypes.data_as(C.POINTER(C.c_double)), cb, None, hook, None),
               "rt_render_adaptive_nee", self._lib)
         return frame, samples, tile_error, frames
+
+    def render_tiles_nee(self, camera, params, heuristic=None, max_lights=None, cancel=None, on_tile=None):
+        """rt_render_nee -> (frame float64 [H, W, 3] assembled from the tiles that arrived (zero elsewhere), list of
+        (r, c, width, height) in arrival order).  Every tile equals render_frame_nee's pixels.  heuristic and max_lights as
+        render_frame_nee's; cancel: None or a callable returning True once the render should stop; on_tile: None or a
+        callable(r, c, width, height) run inside each callback."""
+        ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
+        frame = np.zeros((params.height, params.width, 3), dtype=np.float64)
+        order = []
+
+        def on_update(_user, rgb, r, c, w, h):
+            if w > 0 and h > 0:  # `rgb` is only valid during the callback
+                frame[r:r + h, c:c + w] = np.ctypeslib.as_array(rgb, shape=(h, w, 3))
+            order.append((r, c, w, h))
+            if on_tile is not None:
+                on_tile(r, c, w, h)
+
+        cb = abi.RtTileCallback(on_update)
+        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        check(self._lib.rt_render_nee(self._h, C.byref(camera), C.byref(params), C.byref(ls), cb, None, hook, None),
+              "rt_render_nee", self._lib)
+        return frame, order
 
     def render_guides(self, camera, params):
         """rt_render_guides_device on device buffers of torch, copied back -> dict of numpy planes: normal, position,

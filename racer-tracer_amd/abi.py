@@ -192,6 +192,8 @@ PROTOTYPES = {
                                          C.POINTER(RtLightSamplingParams), C.POINTER(RtAdaptiveParams), C.POINTER(C.c_double),
                                          C.POINTER(C.c_int32), C.POINTER(C.c_double), RtFrameCallback, C.c_void_p,
                                          RtCancelCallback, C.c_void_p]),
+    "rt_render_nee": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.POINTER(RtLightSamplingParams),
+                                RtTileCallback, C.c_void_p, RtCancelCallback, C.c_void_p]),
     "rt_post_rgba8_device": (C.c_int, [C.c_void_p, C.POINTER(RtToneMap), C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rt_render_frame_rgba8": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
@@ -216,6 +218,8 @@ DEV_PROTOTYPES = {
     "rtdev_scene_radiance_bound": (C.c_int, [C.POINTER(RtSceneDesc), C.POINTER(C.c_double)]),
     "rtdev_sum_exponent": (C.c_int, [C.c_double, C.c_int32, C.POINTER(C.c_int32)]),
     "rtdev_progressive_passes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
+    "rtdev_nee_stream_chunk": (C.c_int, []),
+    "rtdev_nee_stream_chunk_exact": (C.c_int, []),
 }
 
 

@@ -501,8 +501,10 @@ std::vector<Launch> plan_launches(const std::vector<int> &starts, int batch) {
     return plan;
 }
 
+} // namespace
+
 // A delivering launch (rt_deliver.hip): its items queued region by region, its counters cleared where they must be.
-int setup_delivery(RtScene *s, rtdev::TraceArgs &a, const Delivery &delivery, int total_chunks, hipStream_t stream) {
+int rtapi::setup_delivery(RtScene *s, rtdev::TraceArgs &a, const Delivery &delivery, int total_chunks, hipStream_t stream) {
     if (delivery.regions.empty() || (int)delivery.regions.size() > rtdev::RT_MAX_REGIONS)
         return fail(RT_ERR_INVALID_ARGUMENT, "bad region list");
     rtapi::RenderBuffers &b = s->buf;
@@ -534,6 +536,9 @@ int setup_delivery(RtScene *s, rtdev::TraceArgs &a, const Delivery &delivery, in
     a.deliver_cols = delivery.cols;
     return RT_OK;
 }
+
+namespace {
+using rtapi::setup_delivery;
 
 // A tree that lives in LDS is walked in ONE fixed child order: the order that suits the rays starting at this camera
 // (rt_bvh.h: order_bvh_for_origin).  Re-emitted when the camera has moved — microseconds for the few hundred nodes LDS

@@ -1,5 +1,6 @@
 // rt_deliver.hip — the entry points that hand finished pixels to the HOST: rt_render_frame, rt_render /
-// rt_render_ex (the reference's tile stream) and their several-device forms rt_render_frame_multi / rt_render_multi.
+// rt_render_ex (the reference's tile stream), their several-device forms rt_render_frame_multi / rt_render_multi, and
+// rt_render_nee (the tile stream of the next-event estimator).
 //
 // What the reference does here: CpuRenderer::render shards the frame into tiles, every tile is traced on a rayon
 // worker and sent to the writer the moment it is finished (racer-tracer/src/renderer/cpu.rs:64-70,118-131), with
@@ -126,7 +127,7 @@ int make_shares(RtScene *const *scenes, int n, const RtRenderParams *p, int stri
 
 int launch_shares(std::vector<Share> &shares, const RtCamera *camera, bool cancellable = false) {
     for (Share &sh : shares) { // every allocation of the call before its first launch (rt_api.hip: reserve_render_buffers)
-        if (sh.delivery.regions.empty()) continue;
+        if (sh.delivery.regions.empty() || sh.delivery.nee) continue; // (rt_render_nee: one share; enqueue_nee_stream allocates what it needs ahead of its launch)
         const int rc = rtapi::reserve_render_buffers(sh.scene, &sh.params, true);
         if (rc != RT_OK) return rc;
     }
@@ -138,7 +139,8 @@ int launch_shares(std::vector<Share> &shares, const RtCamera *camera, bool cance
         if (sh.delivery.regions.empty()) continue;
         sh.delivery.serial = ++sh.scene->buf.deliver_serial;
         if (sh.delivery.serial == 0) sh.delivery.serial = ++sh.scene->buf.deliver_serial; // 0 is the flags' idle value
-        const int rc = rtapi::enqueue_render(sh.scene, camera, &sh.params, nullptr, sh.scene->buf.stream, 0, Cancel(), &sh.delivery);
+        const int rc = sh.delivery.nee ? rtapi::enqueue_nee_stream(sh.scene, camera, &sh.params, sh.delivery.nee, sh.delivery)
+                                       : rtapi::enqueue_render(sh.scene, camera, &sh.params, nullptr, sh.scene->buf.stream, 0, Cancel(), &sh.delivery);
         if (rc != RT_OK) return rc;
         sh.launched = true;
     }
@@ -215,8 +217,9 @@ int deliver_frame(RtScene *const *scenes, int n, const RtCamera *camera, const R
 }
 
 // ------------------------------------------------------------------------------------------------- tile stream
+// nee: NULL, or rt_render_nee's light sampling — the same stream from k_nee_stream_f64's launch (one scene)
 int deliver_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p, int strip_rows,
-                  RtTileCallback callback, void *user, const Cancel &cancel) {
+                  RtTileCallback callback, void *user, const Cancel &cancel, const RtLightSamplingParams *nee = nullptr) {
     std::vector<Share> shares;
     int rc = make_shares(scenes, n, p, strip_rows, shares);
     if (rc != RT_OK) return rc;
@@ -281,6 +284,7 @@ int deliver_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const R
         sh.delivery.out = scenes[0]->buf.host_frame;
         sh.delivery.col_step = width_step;
         sh.delivery.cols = p->tiles_w;
+        sh.delivery.nee = nee;
     }
     rc = launch_shares(shares, camera, cancel.armed());
     bool cancelled = false;
@@ -394,6 +398,38 @@ int frame_two_pass(RtScene *s, const RtCamera *camera, const RtRenderParams *p, 
     return RT_OK;
 }
 
+// rt_render_nee: render_tiles with rt_render_frame_nee's estimator, on one scene.  The delivering launch is
+// k_nee_stream_f64's (the NEE kernels are their own: a scene made with RT_KERNEL_V1 streams too); where it does not apply —
+// a tile grid wider than the image — the frame is rt_render_frame_nee's launch and the tiles are cut from it on the host,
+// the hook being looked at before the launch and before every tile.
+int render_tiles_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                     RtTileCallback callback, void *user, const Cancel &cancel) {
+    if (!callback) return fail(RT_ERR_INVALID_ARGUMENT, "callback is NULL");
+    int rc = rtapi::check_nee(s, camera, p, ls, "rt_render_nee");
+    if (rc != RT_OK) return rc;
+    if (p->tiles_w <= 0 || p->tiles_h <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "tile grid must be positive");
+    if (cancel.raised()) return RT_ERR_CANCEL_EVENT; // cpu.rs:82-85
+    RT_HIP(hipSetDevice(s->device));
+    const int width_step = p->width / p->tiles_w, height_step = p->height / p->tiles_h;
+    if (width_step > 0) {
+        RtScene *scenes[1] = {s};
+        return deliver_tiles(scenes, 1, camera, p, 0, callback, user, cancel, ls);
+    }
+    std::vector<double> frame((size_t)p->width * (size_t)p->height * 3);
+    if ((rc = rtapi::nee_frame_to_host(s, camera, p, ls, frame.data())) != RT_OK) return rc;
+    std::vector<double> column;
+    for (int ws = 0; ws < p->tiles_w; ++ws) { // width_step == 0: empty columns, the last one is the whole frame
+        const int x = width_step * ws, w = ws == p->tiles_w - 1 ? p->width - x : width_step;
+        for (int hs = 0; hs < p->tiles_h; ++hs) {
+            if (cancel.raised()) return RT_OK; // cpu.rs:55-62
+            const int y = height_step * hs;
+            const int h = hs == p->tiles_h - 1 ? p->height - y : height_step;
+            callback(user, frame.data() + (size_t)y * (size_t)(w > 0 ? w : 0) * 3, y, x, w > 0 ? w : 0, h > 0 ? h : 0);
+        }
+    }
+    return RT_OK;
+}
+
 int render_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p, int strip_rows,
                  RtTileCallback callback, void *user, const Cancel &cancel) {
     int rc = rtapi::check_scenes(scenes, n);
@@ -481,6 +517,13 @@ int rt_render_ex(RtScene *s, const RtCamera *camera, const RtRenderParams *p, Rt
     RtScene *scenes[1] = {s};
     return rtapi::guarded("rt_render_ex",
                           [&] { return render_tiles(scenes, 1, camera, p, 0, callback, user, Cancel{nullptr, cancelled, cancel_user}); });
+}
+
+int rt_render_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *light_sampling,
+                  RtTileCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user) {
+    return rtapi::guarded("rt_render_nee", [&] {
+        return render_tiles_nee(s, camera, p, light_sampling, callback, user, Cancel{nullptr, cancelled, cancel_user});
+    });
 }
 
 int rt_render_multi(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *p, int strip_rows,

@@ -261,6 +261,9 @@ struct NeeArgs {
     const int32_t *prim;
     int32_t n_lights;
     int32_t heuristic; // RtMisHeuristic: 0 power (beta = 2), 1 balance (beta = 1)
+    // 1.0 / samples as the host forms it for k_resolve_f64: k_nee_stream_f64 (rt_nee_stream_kernel.hip), which resolves its
+    // own pixels, multiplies by the same bits.  (Last, so that no other field moves; the other kernels do not read it.)
+    double inv_samples;
 };
 
 // The decision step behind a pass (rt_nee_pass_kernel.hip: k_nee_decide_f64), one wave per 8x8 tile of the whole frame:

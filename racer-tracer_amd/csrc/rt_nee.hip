@@ -61,6 +61,7 @@ int fill_nee_args(RtScene *s, const RtCamera *camera, const RtRenderParams *p, c
     nee.prim = s->nee_prim.ptr;
     nee.n_lights = std::min(ls->max_lights, (int32_t)s->lights.size());
     nee.heuristic = ls->heuristic;
+    nee.inv_samples = 1.0 / (double)p->samples; // what rtdev_launch_resolve forms
     return RT_OK;
 }
 
@@ -93,14 +94,7 @@ int render_frame_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p
     int rc = check_nee(s, camera, p, ls);
     if (rc != RT_OK) return rc;
     if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgb is NULL");
-    RT_HIP(hipSetDevice(s->device));
-    rtapi::RenderBuffers &b = s->buf;
-    const size_t n = (size_t)p->width * (size_t)p->height * 3;
-    if (b.frame.count < n) RT_HIP(b.frame.alloc(n));
-    if ((rc = enqueue_nee(s, camera, p, ls, b.frame.ptr, b.stream)) != RT_OK) return rc;
-    RT_HIP(hipStreamSynchronize(b.stream));
-    RT_HIP(hipMemcpy(out, b.frame.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return rtapi::nee_frame_to_host(s, camera, p, ls, out);
 }
 
 int render_frame_nee_device(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
@@ -120,6 +114,57 @@ int scene_lights(const RtScene *s, int32_t *out, int32_t capacity, int32_t *coun
 }
 
 } // namespace
+
+// rt_render_nee's delivering launch: k_nee_stream_f64 as one persistent grid over the delivery's regions, ONE item per tile
+int rtapi::enqueue_nee_stream(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                              const Delivery &delivery) {
+    RT_HIP(hipSetDevice(s->device));
+    rtdev::TraceArgs a;
+    rtdev::NeeArgs nee;
+    int rc = fill_nee_args(s, camera, p, ls, a, nee);
+    if (rc != RT_OK) return rc;
+    rtapi::RenderBuffers &b = s->buf;
+    hipStream_t stream = b.stream;
+    a.tiles_x = (p->width + 7) / 8;
+    a.n_tiles = a.tiles_x * ((p->height + 7) / 8);
+    a.n_items = (uint32_t)a.n_tiles;
+    a.total_chunks = a.n_chunks = 1;
+    if (b.queue.count < 1) RT_HIP(b.queue.alloc(1)); // (allocations, here and in fill_nee_args / setup_delivery, may follow earlier work of the
+                                                     // stream; nothing of THIS call is in flight before the launch below)
+    if ((rc = rtapi::setup_delivery(s, a, delivery, 1, stream)) != RT_OK) return rc;
+    a.queue = b.queue.ptr;
+    if (delivery.cancellable) { // the waves read the scene's cancel word at every hand-out and chunk boundary
+        b.host_flags[rtdev::RT_MAX_REGIONS] = 0u;
+        a.cancel_flag = b.host_flags + rtdev::RT_MAX_REGIONS;
+    }
+    const int per_cu = (s->exact ? rtdev_nee_stream_blocks_per_cu_exact : rtdev_nee_stream_blocks_per_cu)(s->prims_class, s->textured,
+                                                                                                         s->specular, s->use_bvh);
+    const unsigned resident = (unsigned)(s->num_cus > 0 ? s->num_cus : 1) * (unsigned)per_cu;
+    const unsigned blocks = std::min(resident, (a.n_items + 3u) / 4u);
+    RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
+    RT_HIP(hipMemsetAsync(b.queue.ptr, 0, sizeof(unsigned int) * b.queue.count, stream));
+    RT_HIP(hipEventRecord(b.ev_begin, stream)); // (behind the clearing of the counter: poison_queue waits for it)
+    RT_HIP((s->exact ? rtdev_launch_nee_stream_exact : rtdev_launch_nee_stream)(&a, &nee, s->prims_class, s->textured, s->specular,
+                                                                                s->use_bvh, blocks, stream));
+    RT_HIP(hipEventRecord(b.ev_traced, stream));
+    RT_HIP(hipEventRecord(b.ev_resolved, stream)); // no resolve launch: the waves finish their own pixels
+    s->has_stats = true;
+    s->last_launches = 1;
+    s->summed_times = false;
+    return RT_OK;
+}
+
+int rtapi::nee_frame_to_host(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, double *out) {
+    RT_HIP(hipSetDevice(s->device));
+    rtapi::RenderBuffers &b = s->buf;
+    const size_t n = (size_t)p->width * (size_t)p->height * 3;
+    if (b.frame.count < n) RT_HIP(b.frame.alloc(n));
+    const int rc = enqueue_nee(s, camera, p, ls, b.frame.ptr, b.stream);
+    if (rc != RT_OK) return rc;
+    RT_HIP(hipStreamSynchronize(b.stream));
+    RT_HIP(hipMemcpy(out, b.frame.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
 
 int rtapi::begin_nee_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
                             hipStream_t stream, bool cancellable, NeePasses &np) {

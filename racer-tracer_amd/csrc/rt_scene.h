@@ -109,6 +109,8 @@ struct Delivery {
     std::vector<rtdev::Region> regions; // non-empty rectangles of item tiles in queue order (item_begin is filled in)
     uint32_t serial = 0;                // value published in the scene's host_flags[region]
     bool cancellable = false;           // the caller polls a cancel hook while this launch runs: the waves read the scene's cancel word
+    // rt_render_nee: the launch is k_nee_stream_f64's with this light sampling (rt_nee.hip: enqueue_nee_stream), not the pooled kernel's
+    const RtLightSamplingParams *nee = nullptr;
 };
 
 // Everything a render allocates on first use — slices, the v1 accumulator, frames, the packed RGBA, counters, the pinned
@@ -216,6 +218,17 @@ extern "C" hipError_t rtdev_launch_nee_chunk_exact(const double *running, double
                                                    hipStream_t stream);
 extern "C" hipError_t rtdev_launch_nee_decide(const rtdev::NeeDecide *f, hipStream_t stream);
 extern "C" hipError_t rtdev_launch_nee_decide_exact(const rtdev::NeeDecide *f, hipStream_t stream);
+// The launchers of rt_nee_stream_kernel.hip (both arithmetic flavours): the NEE estimator as ONE persistent launch of `blocks`
+// blocks over args' region-ordered tile queue, every tile delivered into args->deliver_out; the variant's resident blocks
+// per CU (the runtime's occupancy query); the chunk length the flavour was compiled with.
+extern "C" hipError_t rtdev_launch_nee_stream(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class, int textured,
+                                              int specular, int bvh, unsigned blocks, hipStream_t stream);
+extern "C" hipError_t rtdev_launch_nee_stream_exact(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class,
+                                                    int textured, int specular, int bvh, unsigned blocks, hipStream_t stream);
+extern "C" int rtdev_nee_stream_blocks_per_cu(int prims_class, int textured, int specular, int bvh);
+extern "C" int rtdev_nee_stream_blocks_per_cu_exact(int prims_class, int textured, int specular, int bvh);
+extern "C" int rtdev_nee_stream_chunk(void);
+extern "C" int rtdev_nee_stream_chunk_exact(void);
 
 struct RtScene {
     int device = 0;
@@ -381,6 +394,16 @@ int begin_nee_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p
                      hipStream_t stream, bool cancellable, NeePasses &np);
 int enqueue_nee_pass(RtScene *s, NeePasses &np, int c0, int c1, hipStream_t stream, const uint32_t *tile_list = nullptr,
                      uint32_t n_list = 0);
+// rt_render_nee's delivering launch (rt_nee.hip): k_nee_stream_f64 as one persistent grid over delivery.regions (one item per
+// tile), finishing its own pixels in delivery.out; everything it needs is allocated first, ev_begin / ev_traced /
+// ev_resolved span it.  ... and the frame behind its fallback: rt_render_frame_nee's launch and resolve into the scene's
+// device frame, copied into `out` (host memory, W*H*3), arguments checked by the caller.
+int enqueue_nee_stream(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                       const Delivery &delivery);
+int nee_frame_to_host(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, double *out);
+// A delivering launch's regions and counters in its argument block (rt_api.hip): item_begin of every region for
+// `chunks_per_tile` items per tile, the counters cleared where a launch was cut short, TraceArgs.deliver_*.
+int setup_delivery(RtScene *s, rtdev::TraceArgs &a, const Delivery &delivery, int chunks_per_tile, hipStream_t stream);
 // The pinned host frame of the host-output entry points, at least `doubles` long (rt_deliver.hip).
 int ensure_host_frame(RtScene *s, size_t doubles);
 // Rows of the owned-row grid of a render with these parameters (a multiple of strip_rows with strips).

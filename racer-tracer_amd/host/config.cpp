@@ -205,6 +205,7 @@ Args Args::parse(int argc, const char *const *argv) {
         else if (s == "--devices") a.devices = std::atoi(val().c_str());
         else if (s == "--denoise" && !has_inline) a.denoise = true;
         else if (s == "--nee" && !has_inline) a.nee = true;
+        else if (s == "--nee-stream" && !has_inline) a.nee_stream = true;
         else if (s == "--adaptive" || s == "--nee-adaptive") {
             const std::string v = val();
             char *end = nullptr;
@@ -218,6 +219,10 @@ Args Args::parse(int argc, const char *const *argv) {
     }
     if (a.adaptive > 0.0 && a.devices > 1)
         throw TracerError::ArgumentParsingError("--adaptive renders on one device: it does not combine with --devices > 1");
+    if (a.nee_stream && (a.nee || a.adaptive > 0.0 || a.nee_adaptive > 0.0))
+        throw TracerError::ArgumentParsingError("--nee-stream is a render mode of its own: it does not combine with --nee, --adaptive or --nee-adaptive");
+    if (a.nee_stream && a.devices > 1)
+        throw TracerError::ArgumentParsingError("--nee-stream renders on one device: it does not combine with --devices > 1");
     if (a.nee && a.adaptive > 0.0)
         throw TracerError::ArgumentParsingError("--nee and --adaptive are two estimators: pick one");
     if (a.nee_adaptive > 0.0 && a.adaptive > 0.0)

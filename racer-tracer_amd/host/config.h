@@ -64,6 +64,7 @@ struct Args { // config.rs:12-28
     int devices = 1; // --devices N: render the frame on devices device .. device+N-1 (rt_render_frame_multi)
     bool denoise = false; // --denoise: filter the assembled frame (rt_denoise_frame) before tone map and PNG
     bool nee = false; // --nee: one device renders the frame through rt_render_frame_nee (next-event estimation)
+    bool nee_stream = false; // --nee-stream: the same frame through rt_render_nee, tile by tile into the screen buffer, one device only
     double adaptive = 0.0; // --adaptive T (T > 0): render through rt_render_adaptive with threshold T, one device only
     double nee_adaptive = 0.0; // --nee-adaptive T (T > 0): render through rt_render_adaptive_nee with threshold T, one device only
     bool help = false;

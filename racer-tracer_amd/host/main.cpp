@@ -8,7 +8,8 @@
 // through rt_denoise_frame on the first device before the tone map and the PNG) and --adaptive T (one device renders the
 // frame through rt_render_adaptive, a tile stopping once its error is at most T; --denoise filters that frame) and --nee (one
 // device renders the frame through rt_render_frame_nee, next-event estimation; --denoise filters that frame) and
-// --nee-adaptive T (--adaptive's stop rule with the next-event estimator: rt_render_adaptive_nee).
+// --nee-adaptive T (--adaptive's stop rule with the next-event estimator: rt_render_adaptive_nee) and --nee-stream (--nee's
+// frame through rt_render_nee, tile by tile into the screen buffer; the PNG has --nee's bytes).
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -53,7 +54,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee] [--nee-adaptive T]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee] [--nee-stream] [--nee-adaptive T]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -120,6 +121,10 @@ int main(int argc, char **argv) {
         rt_light_sampling_params_default(&ls);
         rc = rt_render_frame_nee(scenes[0], rth_session_camera(session), &params, &ls, sb.raw.data());
         if (rc == RT_OK && !args.denoise) rth_tone_map(session, sb.raw.data(), sb.buffer.data(), n_rgb / 3);
+    } else if (args.nee_stream) { // --nee's frame as a tile stream: every finished tile goes through the tone map as it arrives
+        RtLightSamplingParams ls;
+        rt_light_sampling_params_default(&ls);
+        rc = rt_render_nee(scenes[0], rth_session_camera(session), &params, &ls, on_tile, &sb, nullptr, nullptr);
     } else if (scenes.size() == 1) {
         // the reference's tile stream (cpu.rs:64-70): every finished tile goes through ScreenBuffer::update's tone map;
         // with several devices a tile column arrives once every device has finished its strips of it
