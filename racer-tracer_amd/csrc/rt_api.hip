@@ -25,13 +25,12 @@ extern "C" hipError_t rtdev_launch_post_rgba8(const RtToneMap *tm, const double 
                                               double *mapped, hipStream_t stream);
 
 namespace {
-const rtapi::Launchers kFastLaunchers = {rtdev_launch_trace,      rtdev_launch_resolve,    rtdev_pool_blocks_per_cu,
-                                         rtdev_pool_static_lds,   rtdev_launch_trace_pool, rtdev_launch_resolve_chunks,
-                                         rtdev_launch_fold_chunks, rtdev_launch_fold_adaptive};
-const rtapi::Launchers kExactLaunchers = {rtdev_launch_trace_exact,      rtdev_launch_resolve_exact,
-                                          rtdev_pool_blocks_per_cu_exact, rtdev_pool_static_lds_exact,
-                                          rtdev_launch_trace_pool_exact,  rtdev_launch_resolve_chunks_exact,
-                                          rtdev_launch_fold_chunks_exact, rtdev_launch_fold_adaptive_exact};
+#define RT_FAST_LAUNCHER(member, name, ret, params) name,
+#define RT_EXACT_LAUNCHER(member, name, ret, params) name##_exact,
+const rtapi::Launchers kFastLaunchers = {RT_LAUNCHER_LIST(RT_FAST_LAUNCHER)};
+const rtapi::Launchers kExactLaunchers = {RT_LAUNCHER_LIST(RT_EXACT_LAUNCHER)};
+#undef RT_FAST_LAUNCHER
+#undef RT_EXACT_LAUNCHER
 
 thread_local char g_last_error[1024]; // a fixed buffer: setting it cannot throw (rtapi::guarded's handlers use it)
 } // namespace
@@ -585,10 +584,7 @@ int setup_pool_grid(const RtScene *s, rtdev::TraceArgs &a, const RtRenderParams 
 int pool_prologue(RtScene *s, rtdev::TraceArgs &a, const RtCamera *camera, const RtRenderParams *p, size_t n_launches,
                   bool cancellable, hipStream_t stream) {
     rtapi::RenderBuffers &b = s->buf;
-    if (cancellable) {
-        b.host_flags[rtdev::RT_MAX_REGIONS] = 0u;
-        a.cancel_flag = b.host_flags + rtdev::RT_MAX_REGIONS;
-    }
+    if (cancellable) rtapi::arm_cancel_word(s, a);
     // slices hold the launch's owned rows only (the kernel compacts rows: owned_rows, tile_py0)
     a.slice_rows = a.owned_rows;
     const size_t slice_elems = (size_t)p->width * (size_t)a.slice_rows * 3;
@@ -684,9 +680,7 @@ int rtapi::enqueue_render(RtScene *s, const RtCamera *camera, const RtRenderPara
         rc = enqueue_pool(s, a, camera, p, out_device, stream, batch, cancel, delivery, out_col_step, out_cols, launches);
     }
     if (rc != RT_OK) return rc;
-    s->has_stats = true;
-    s->last_launches = launches;
-    s->summed_times = false;
+    note_launches(s, launches);
     return RT_OK;
 }
 using rtapi::enqueue_render;
@@ -702,9 +696,7 @@ int rtapi::begin_passes(RtScene *s, const RtCamera *camera, const RtRenderParams
     if ((rc = pool_prologue(s, pp.args, camera, p, (size_t)max_launches, cancellable, stream)) != RT_OK) return rc;
     pp.launches = 0;
     pp.max_launches = max_launches;
-    s->has_stats = true;
-    s->last_launches = 0;
-    s->summed_times = false;
+    note_launches(s, 0);
     return RT_OK;
 }
 
@@ -1425,7 +1417,7 @@ int rtdev_scene_variant(const RtScene *s, int32_t *out, int32_t n_out) {
     return rtapi::guarded("rtdev_scene_variant", [&]() -> int {
         if (!s || (!out && n_out > 0) || n_out < 0) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out is NULL or n_out is negative");
         const int32_t v[RTDEV_VARIANT_FIELDS] = {
-            s->use_v1 ? 1 : 0, s->prims_class, s->textured, s->specular, s->use_bvh, s->exact ? 1 : 0, s->bvh_nodes_in_lds ? 1 : 0,
+            s->use_v1 ? 1 : 0, s->prims_class, s->textured, s->specular, s->use_bvh, (int32_t)s->exact, s->bvh_nodes_in_lds ? 1 : 0,
             s->has_moving, (s->textured && s->n_perlins > 0 && s->perlin_identity) ? 1 : 0,
             s->use_v1 ? 0 : s->pool_static_lds, s->use_v1 ? 0 : (int32_t)s->pool_dyn_lds, s->use_v1 ? 0 : (int32_t)s->pool_dyn_lds_lens,
             s->pool_blocks_per_cu, s->pool_blocks_per_cu_lens};

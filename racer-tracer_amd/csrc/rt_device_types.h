@@ -134,6 +134,10 @@ enum {
     RT_STAT_SLOTS = 60
 };
 
+// What a scene's primitive table holds, the PRIMS argument of the kernel variants (rt_variant_dispatch.h): untransformed
+// rects only, untransformed spheres only, anything
+enum { PRIMS_RECTS = 0, PRIMS_SPHERES = 1, PRIMS_ANY = 2 };
+
 enum { RT_MAX_CHUNKS = 64 }; // a frame's samples are cut into at most this many chunks (slices of `partial`)
 enum { RT_MAX_REGIONS = 32 }; // a launch's items are queued region by region (TraceArgs.regions)
 

@@ -1,6 +1,6 @@
 // rt_nee.hip — next-event estimation: the scene's light list and the entry points rt_render_frame_nee,
 // rt_render_frame_nee_device, rt_scene_lights and rt_light_sampling_params_default (include/rt_abi.h).  The kernel is
-// rt_nee_kernel.hip's k_nee_f64, compiled in both arithmetic flavours; a scene uses its own (RtScene.exact).
+// rt_nee_kernel.hip's k_nee_f64, compiled in both arithmetic flavours; a scene uses its own (RtScene.kernels).
 #include "rt_scene.h"
 
 #include <algorithm>
@@ -65,6 +65,22 @@ int fill_nee_args(RtScene *s, const RtCamera *camera, const RtRenderParams *p, c
     return RT_OK;
 }
 
+// The grid of 8x8 tiles that k_nee_pass_f64 and k_nee_stream_f64 draw their work from
+void set_tile_grid(rtdev::TraceArgs &a, const RtRenderParams *p) {
+    a.tiles_x = (p->width + 7) / 8;
+    a.n_tiles = a.tiles_x * ((p->height + 7) / 8);
+}
+
+// What precedes the first launch of a call on `stream`: the statistics slots cleared, the item counter of a persistent
+// grid (`clear_queue`) cleared, then ev_begin — behind the clearing of the counter: poison_queue waits for it
+int open_launches(RtScene *s, hipStream_t stream, bool clear_queue = false) {
+    rtapi::RenderBuffers &b = s->buf;
+    RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
+    if (clear_queue) RT_HIP(hipMemsetAsync(b.queue.ptr, 0, sizeof(unsigned int) * b.queue.count, stream));
+    RT_HIP(hipEventRecord(b.ev_begin, stream));
+    return RT_OK;
+}
+
 // One launch of k_nee_f64 over the whole frame into the scene's accumulator, then the resolve pass into out_device
 int enqueue_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, double *out_device,
                 hipStream_t stream) {
@@ -77,16 +93,12 @@ int enqueue_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, con
     const size_t n = (size_t)p->width * (size_t)p->height * 3;
     if (b.accum.count < n) RT_HIP(b.accum.alloc(n));
     a.accum = b.accum.ptr;
-    RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
-    RT_HIP(hipEventRecord(b.ev_begin, stream));
-    RT_HIP((s->exact ? rtdev_launch_nee_exact : rtdev_launch_nee)(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh,
-                                                                  stream));
+    if ((rc = open_launches(s, stream)) != RT_OK) return rc;
+    RT_HIP(s->kernels->nee(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh, stream));
     RT_HIP(hipEventRecord(b.ev_traced, stream));
     RT_HIP(s->kernels->resolve(b.accum.ptr, out_device, p->width, p->height, p->height, 1, 0, p->samples, stream));
     RT_HIP(hipEventRecord(b.ev_resolved, stream));
-    s->has_stats = true;
-    s->last_launches = 1;
-    s->summed_times = false;
+    rtapi::note_launches(s, 1);
     return RT_OK;
 }
 
@@ -125,32 +137,22 @@ int rtapi::enqueue_nee_stream(RtScene *s, const RtCamera *camera, const RtRender
     if (rc != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     hipStream_t stream = b.stream;
-    a.tiles_x = (p->width + 7) / 8;
-    a.n_tiles = a.tiles_x * ((p->height + 7) / 8);
+    set_tile_grid(a, p);
     a.n_items = (uint32_t)a.n_tiles;
     a.total_chunks = a.n_chunks = 1;
     if (b.queue.count < 1) RT_HIP(b.queue.alloc(1)); // (allocations, here and in fill_nee_args / setup_delivery, may follow earlier work of the
                                                      // stream; nothing of THIS call is in flight before the launch below)
     if ((rc = rtapi::setup_delivery(s, a, delivery, 1, stream)) != RT_OK) return rc;
     a.queue = b.queue.ptr;
-    if (delivery.cancellable) { // the waves read the scene's cancel word at every hand-out and chunk boundary
-        b.host_flags[rtdev::RT_MAX_REGIONS] = 0u;
-        a.cancel_flag = b.host_flags + rtdev::RT_MAX_REGIONS;
-    }
-    const int per_cu = (s->exact ? rtdev_nee_stream_blocks_per_cu_exact : rtdev_nee_stream_blocks_per_cu)(s->prims_class, s->textured,
-                                                                                                         s->specular, s->use_bvh);
+    if (delivery.cancellable) rtapi::arm_cancel_word(s, a); // the waves read it at every hand-out and chunk boundary
+    const int per_cu = s->kernels->nee_stream_blocks_per_cu(s->prims_class, s->textured, s->specular, s->use_bvh);
     const unsigned resident = (unsigned)(s->num_cus > 0 ? s->num_cus : 1) * (unsigned)per_cu;
     const unsigned blocks = std::min(resident, (a.n_items + 3u) / 4u);
-    RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
-    RT_HIP(hipMemsetAsync(b.queue.ptr, 0, sizeof(unsigned int) * b.queue.count, stream));
-    RT_HIP(hipEventRecord(b.ev_begin, stream)); // (behind the clearing of the counter: poison_queue waits for it)
-    RT_HIP((s->exact ? rtdev_launch_nee_stream_exact : rtdev_launch_nee_stream)(&a, &nee, s->prims_class, s->textured, s->specular,
-                                                                                s->use_bvh, blocks, stream));
+    if ((rc = open_launches(s, stream, /*clear_queue=*/true)) != RT_OK) return rc;
+    RT_HIP(s->kernels->nee_stream(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh, blocks, stream));
     RT_HIP(hipEventRecord(b.ev_traced, stream));
     RT_HIP(hipEventRecord(b.ev_resolved, stream)); // no resolve launch: the waves finish their own pixels
-    s->has_stats = true;
-    s->last_launches = 1;
-    s->summed_times = false;
+    rtapi::note_launches(s, 1);
     return RT_OK;
 }
 
@@ -170,7 +172,7 @@ int rtapi::begin_nee_passes(RtScene *s, const RtCamera *camera, const RtRenderPa
                             hipStream_t stream, bool cancellable, NeePasses &np) {
     RT_HIP(hipSetDevice(s->device));
     rtdev::TraceArgs &a = np.args;
-    const int rc = fill_nee_args(s, camera, p, ls, a, np.nee);
+    int rc = fill_nee_args(s, camera, p, ls, a, np.nee);
     if (rc != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     const size_t n = (size_t)p->width * (size_t)p->height * 3;
@@ -181,17 +183,10 @@ int rtapi::begin_nee_passes(RtScene *s, const RtCamera *camera, const RtRenderPa
     for (int c = 0; c <= total_chunks; ++c) a.chunk_start[c] = np.starts[(size_t)c];
     a.total_chunks = total_chunks;
     a.chunk_samples = np.starts[1] - np.starts[0];
-    a.tiles_x = (p->width + 7) / 8;
-    a.n_tiles = a.tiles_x * ((p->height + 7) / 8);
-    if (cancellable) { // the waves read the scene's cancel word at their start and at chunk boundaries
-        b.host_flags[rtdev::RT_MAX_REGIONS] = 0u;
-        a.cancel_flag = b.host_flags + rtdev::RT_MAX_REGIONS;
-    }
-    RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
-    RT_HIP(hipEventRecord(b.ev_begin, stream));
-    s->has_stats = true;
-    s->last_launches = 0;
-    s->summed_times = false;
+    set_tile_grid(a, p);
+    if (cancellable) rtapi::arm_cancel_word(s, a); // the waves read it at their start and at chunk boundaries
+    if ((rc = open_launches(s, stream)) != RT_OK) return rc;
+    rtapi::note_launches(s, 0);
     return RT_OK;
 }
 
@@ -209,10 +204,8 @@ int rtapi::enqueue_nee_pass(RtScene *s, NeePasses &np, int c0, int c1, hipStream
         a.chunk_base = c;
         a.sample_begin = np.starts[(size_t)c];
         a.sample_end = np.starts[(size_t)c + 1];
-        RT_HIP((s->exact ? rtdev_launch_nee_pass_exact : rtdev_launch_nee_pass)(&a, &np.nee, s->prims_class, s->textured, s->specular,
-                                                                                s->use_bvh, stream));
-        RT_HIP((s->exact ? rtdev_launch_nee_chunk_exact : rtdev_launch_nee_chunk)(b.accum.ptr, b.partial.ptr, b.squares.ptr, n,
-                                                                                  a.sample_end - a.sample_begin, stream));
+        RT_HIP(s->kernels->nee_pass(&a, &np.nee, s->prims_class, s->textured, s->specular, s->use_bvh, stream));
+        RT_HIP(s->kernels->nee_chunk(b.accum.ptr, b.partial.ptr, b.squares.ptr, n, a.sample_end - a.sample_begin, stream));
     }
     ++s->last_launches;
     return RT_OK;

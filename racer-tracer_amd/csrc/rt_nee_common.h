@@ -231,7 +231,16 @@ __device__ __forceinline__ void nee_samples(const TraceArgs &A, const NeeArgs &N
                     const double cos_theta = fmin(dot(-ud, h.normal), 1.0);
                     const double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
                     bool reflect_it = ratio * sin_theta > 1.0;
+#ifdef RT_EXACT_DIV
+                    // RT_ARITH_REFERENCE forms the Fresnel term on every lane, not under `if (!reflect_it)` (the draw is
+                    // addressed, so an unused one changes nothing).  With the nested branch the compiler's code for the
+                    // <PRIMS_RECTS, plain, SPECULAR> kernels lost `o = h.point` on the lanes that reflect by the draw:
+                    // LABNOTES 10 has the instructions; tests/test_gpu_nee.py holds every variant to the oracle.
+                    const bool total_reflection = reflect_it;
+                    {
+#else
                     if (!reflect_it) { // the draw happens only when refraction is possible
+#endif
                         double r0 = (1.0 - ratio) / (1.0 + ratio);
                         r0 = r0 * r0;
                         const double m = 1.0 - cos_theta;
@@ -240,6 +249,9 @@ __device__ __forceinline__ void nee_samples(const TraceArgs &A, const NeeArgs &N
                         const u4 b = rng.block(seg, RT_RNG_DIELECTRIC, 0);
                         reflect_it = refl > u53(b.a, b.b);
                     }
+#ifdef RT_EXACT_DIV
+                    reflect_it = reflect_it || total_reflection;
+#endif
                     d3 dir;
                     if (reflect_it) {
                         dir = ud - (2.0 * dot(ud, h.normal)) * h.normal;

@@ -9,6 +9,7 @@
 // and then continues with the bounce ray it drew.  (Two trace calls per iteration would leave every lane that has no
 // shadow ray idle through the second one.)
 #include "rt_nee_common.h"
+#include "rt_variant_dispatch.h"
 
 namespace RT_KNS {
 
@@ -61,21 +62,11 @@ __global__ __launch_bounds__(256) void k_nee_f64(const TraceArgs A, const NeeArg
 } // namespace RT_KNS
 
 namespace {
-template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH>
-void launch_nee_variant(const rtdev::TraceArgs &a, const rtdev::NeeArgs &n, unsigned blocks, hipStream_t stream) {
-    hipLaunchKernelGGL((RT_KNS::k_nee_f64<PRIMS, TEXTURED, SPECULAR, BVH>), dim3(blocks), dim3(256), 0, stream, a, n);
-}
-template <int PRIMS, bool BVH>
-void launch_nee_prims(const rtdev::TraceArgs &a, const rtdev::NeeArgs &n, bool textured, bool specular, unsigned blocks,
-                      hipStream_t stream) {
-    if (textured) {
-        if (specular) launch_nee_variant<PRIMS, true, true, BVH>(a, n, blocks, stream);
-        else launch_nee_variant<PRIMS, true, false, BVH>(a, n, blocks, stream);
-    } else {
-        if (specular) launch_nee_variant<PRIMS, false, true, BVH>(a, n, blocks, stream);
-        else launch_nee_variant<PRIMS, false, false, BVH>(a, n, blocks, stream);
+template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH> struct NeeVariant {
+    static void launch(const rtdev::TraceArgs &a, const rtdev::NeeArgs &n, unsigned blocks, hipStream_t stream) {
+        hipLaunchKernelGGL((RT_KNS::k_nee_f64<PRIMS, TEXTURED, SPECULAR, BVH>), dim3(blocks), dim3(256), 0, stream, a, n);
     }
-}
+};
 } // namespace
 
 // The whole frame's samples [sample_begin, sample_end) into args->accum (written, not added to).  prims_class:
@@ -86,14 +77,8 @@ extern "C" hipError_t RT_LAUNCHER(rtdev_launch_nee)(const rtdev::TraceArgs *args
     const int tiles_y = (args->height + 15) / 16;
     if (tiles_x <= 0 || tiles_y <= 0) return hipSuccess;
     const unsigned blocks = (unsigned)(tiles_x * tiles_y);
-    if (bvh) {
-        launch_nee_prims<rtdev::PRIMS_ANY, true>(*args, *nee, textured != 0, specular != 0, blocks, stream);
-    } else {
-        switch (prims_class) {
-        case rtdev::PRIMS_RECTS: launch_nee_prims<rtdev::PRIMS_RECTS, false>(*args, *nee, textured != 0, specular != 0, blocks, stream); break;
-        case rtdev::PRIMS_SPHERES: launch_nee_prims<rtdev::PRIMS_SPHERES, false>(*args, *nee, textured != 0, specular != 0, blocks, stream); break;
-        default: launch_nee_prims<rtdev::PRIMS_ANY, false>(*args, *nee, textured != 0, specular != 0, blocks, stream); break;
-        }
-    }
+    rtdev::dispatch_variant<NeeVariant>(prims_class, textured != 0, specular != 0, bvh != 0, [&](auto v) {
+        decltype(v)::launch(*args, *nee, blocks, stream);
+    });
     return hipGetLastError();
 }

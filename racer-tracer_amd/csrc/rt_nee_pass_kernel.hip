@@ -5,6 +5,7 @@
 // added in sample order to a sum that travels from launch to launch in TraceArgs.accum, so after any pass the sums are
 // the ones k_nee_f64 forms with that many samples, bit for bit.
 #include "rt_nee_common.h"
+#include "rt_variant_dispatch.h"
 
 namespace RT_KNS {
 
@@ -165,22 +166,11 @@ __global__ __launch_bounds__(1024) void k_nee_decide_f64(const NeeDecide F) {
 } // namespace RT_KNS
 
 namespace {
-template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH>
-void launch_pass_variant(const rtdev::TraceArgs &a, const rtdev::NeeArgs &n, unsigned blocks,
-                         hipStream_t stream) {
-    hipLaunchKernelGGL((RT_KNS::k_nee_pass_f64<PRIMS, TEXTURED, SPECULAR, BVH>), dim3(blocks), dim3(256), 0, stream, a, n);
-}
-template <int PRIMS, bool BVH>
-void launch_pass_prims(const rtdev::TraceArgs &a, const rtdev::NeeArgs &n, bool textured, bool specular,
-                       unsigned blocks, hipStream_t stream) {
-    if (textured) {
-        if (specular) launch_pass_variant<PRIMS, true, true, BVH>(a, n, blocks, stream);
-        else launch_pass_variant<PRIMS, true, false, BVH>(a, n, blocks, stream);
-    } else {
-        if (specular) launch_pass_variant<PRIMS, false, true, BVH>(a, n, blocks, stream);
-        else launch_pass_variant<PRIMS, false, false, BVH>(a, n, blocks, stream);
+template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH> struct PassVariant {
+    static void launch(const rtdev::TraceArgs &a, const rtdev::NeeArgs &n, unsigned blocks, hipStream_t stream) {
+        hipLaunchKernelGGL((RT_KNS::k_nee_pass_f64<PRIMS, TEXTURED, SPECULAR, BVH>), dim3(blocks), dim3(256), 0, stream, a, n);
     }
-}
+};
 } // namespace
 
 // Samples [sample_begin, sample_end), one chunk, of args->n_items tiles (args->tile_list, or every tile of the grid in order)
@@ -191,15 +181,9 @@ extern "C" hipError_t RT_LAUNCHER(rtdev_launch_nee_pass)(const rtdev::TraceArgs 
                                                          hipStream_t stream) {
     if (args->n_items == 0 || args->sample_end <= args->sample_begin) return hipSuccess;
     const unsigned blocks = (args->n_items + 3u) / 4u;
-    if (bvh) {
-        launch_pass_prims<rtdev::PRIMS_ANY, true>(*args, *nee, textured != 0, specular != 0, blocks, stream);
-    } else {
-        switch (prims_class) {
-        case rtdev::PRIMS_RECTS: launch_pass_prims<rtdev::PRIMS_RECTS, false>(*args, *nee, textured != 0, specular != 0, blocks, stream); break;
-        case rtdev::PRIMS_SPHERES: launch_pass_prims<rtdev::PRIMS_SPHERES, false>(*args, *nee, textured != 0, specular != 0, blocks, stream); break;
-        default: launch_pass_prims<rtdev::PRIMS_ANY, false>(*args, *nee, textured != 0, specular != 0, blocks, stream); break;
-        }
-    }
+    rtdev::dispatch_variant<PassVariant>(prims_class, textured != 0, specular != 0, bvh != 0, [&](auto v) {
+        decltype(v)::launch(*args, *nee, blocks, stream);
+    });
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 // tile-column frame.  The wave that finishes a region's last tile publishes the region to the host.  A pixel is therefore
 // rt_render_frame_nee's pixel, bit for bit, whatever the tile grid, the grid size or the order the waves run in.
 #include "rt_nee_common.h"
+#include "rt_variant_dispatch.h"
 
 // Samples a wave traces between two looks at the host's cancel word.  A tuning constant: the sum is carried from chunk to
 // chunk in registers, in sample order, so no pixel depends on it.  Small = a cancel lands sooner (a wave runs out its
@@ -196,23 +197,12 @@ template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH> struct StreamVarian
         return n < 1 ? 1 : (n > 8 ? 8 : n);
     }
 };
-
-template <class F> auto dispatch_stream(int prims_class, bool textured, bool specular, bool bvh, F f) {
-    using namespace rtdev;
-#define RT_PICK(P, B)                                                                                   \
-    (textured ? (specular ? f(StreamVariant<P, true, true, B>()) : f(StreamVariant<P, true, false, B>())) \
-              : (specular ? f(StreamVariant<P, false, true, B>()) : f(StreamVariant<P, false, false, B>())))
-    if (bvh) return RT_PICK(PRIMS_ANY, true);
-    if (prims_class == PRIMS_RECTS) return RT_PICK(PRIMS_RECTS, false);
-    if (prims_class == PRIMS_SPHERES) return RT_PICK(PRIMS_SPHERES, false);
-    return RT_PICK(PRIMS_ANY, false);
-#undef RT_PICK
-}
 } // namespace
 
 // Resident blocks per CU of the variant (the persistent grid is CUs x this).
 extern "C" int RT_LAUNCHER(rtdev_nee_stream_blocks_per_cu)(int prims_class, int textured, int specular, int bvh) {
-    return dispatch_stream(prims_class, textured != 0, specular != 0, bvh != 0, [](auto v) { return decltype(v)::blocks_per_cu(); });
+    return rtdev::dispatch_variant<StreamVariant>(prims_class, textured != 0, specular != 0, bvh != 0,
+                                                  [](auto v) { return decltype(v)::blocks_per_cu(); });
 }
 
 // The chunk length this flavour was compiled with (the tests size their sample counts by it).
@@ -223,9 +213,8 @@ extern "C" int RT_LAUNCHER(rtdev_nee_stream_chunk)(void) { return RT_KNS::kNeeSt
 extern "C" hipError_t RT_LAUNCHER(rtdev_launch_nee_stream)(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class,
                                                            int textured, int specular, int bvh, unsigned blocks, hipStream_t stream) {
     if (blocks == 0 || args->n_items == 0 || args->samples <= 0) return hipSuccess;
-    dispatch_stream(prims_class, textured != 0, specular != 0, bvh != 0, [&](auto v) {
+    rtdev::dispatch_variant<StreamVariant>(prims_class, textured != 0, specular != 0, bvh != 0, [&](auto v) {
         decltype(v)::launch(*args, *nee, blocks, stream);
-        return 0;
     });
     return hipGetLastError();
 }

@@ -13,39 +13,65 @@
 #include "../../include/rt_abi.h"
 
 // The trace kernels exist twice (rt_trace_common.h: ARITHMETIC): RT_ARITH_FAST, and RT_ARITH_REFERENCE behind *_exact.
-#define RT_DECLARE_LAUNCHERS(SUFFIX)                                                                                       \
-    extern "C" hipError_t rtdev_launch_trace##SUFFIX(const rtdev::TraceArgs *args, int prims_class, int textured,         \
-                                                     int specular, hipStream_t stream);                                   \
-    extern "C" hipError_t rtdev_launch_resolve##SUFFIX(const double *accum, double *out, int width, int height,           \
-                                                       int strip_rows, int strip_count, int strip_index, int samples,     \
-                                                       hipStream_t stream);                                               \
-    extern "C" int rtdev_pool_blocks_per_cu##SUFFIX(int prims_class, int textured, int specular, int bvh, size_t dyn_lds); \
-    extern "C" int rtdev_pool_static_lds##SUFFIX(int prims_class, int textured, int specular, int bvh);                 \
-    extern "C" hipError_t rtdev_launch_trace_pool##SUFFIX(const rtdev::TraceArgs *args, int prims_class, int textured,    \
-                                                          int specular, int bvh, unsigned blocks, hipStream_t stream);    \
-    extern "C" hipError_t rtdev_launch_resolve_chunks##SUFFIX(const double *partial, double *out, int width, int height,  \
-                                                              int n_chunks, int slice_rows, int strip_rows, int strip_count, \
-                                                              int strip_index, int step_x, int step_y, int cover_w,       \
-                                                              int cover_h, int out_col_step, int out_cols, int samples,   \
-                                                              hipStream_t stream);                                        \
-    extern "C" hipError_t rtdev_launch_fold_chunks##SUFFIX(const double *partial, double *running, double *out, size_t n,   \
-                                                           int c0, int c1, int samples_done, hipStream_t stream);    \
-    extern "C" hipError_t rtdev_launch_fold_adaptive##SUFFIX(const rtdev::AdaptiveFold *f, hipStream_t stream);
-RT_DECLARE_LAUNCHERS()
-RT_DECLARE_LAUNCHERS(_exact)
+// Every launcher that has both flavours, ONCE: X(member of rtapi::Launchers, exported name, return type, parameters).  The
+// declarations of both flavours, the struct and its two tables (rt_api.hip) are all expanded from this list.
+//   trace, resolve (rt_trace_kernel.hip): the v1 kernel and its resolve pass.
+//   pool_*, trace_pool, resolve_chunks, fold_* (rt_trace_pool_kernel.hip): the pooled kernel, the variant's resident blocks
+//     per CU and static LDS, the resolve and fold passes over its slices.
+//   nee (rt_nee_kernel.hip): the whole frame's NEE samples into args->accum.
+//   nee_pass, nee_chunk, nee_decide (rt_nee_pass_kernel.hip): one chunk of the NEE estimator over listed tiles on top of
+//     args->accum, the batch-means update behind it and the decision step behind a pass.
+//   nee_stream* (rt_nee_stream_kernel.hip): the NEE estimator as ONE persistent launch of `blocks` blocks over args'
+//     region-ordered tile queue, every tile delivered into args->deliver_out; the variant's resident blocks per CU (the
+//     runtime's occupancy query); the chunk length the flavour was compiled with.
+#define RT_LAUNCHER_LIST(X)                                                                                                \
+    X(trace, rtdev_launch_trace, hipError_t,                                                                               \
+      (const rtdev::TraceArgs *args, int prims_class, int textured, int specular, hipStream_t stream))                     \
+    X(resolve, rtdev_launch_resolve, hipError_t,                                                                           \
+      (const double *accum, double *out, int width, int height, int strip_rows, int strip_count, int strip_index,         \
+       int samples, hipStream_t stream))                                                                                   \
+    X(pool_blocks_per_cu, rtdev_pool_blocks_per_cu, int,                                                                   \
+      (int prims_class, int textured, int specular, int bvh, size_t dyn_lds))                                              \
+    X(pool_static_lds, rtdev_pool_static_lds, int, (int prims_class, int textured, int specular, int bvh))                 \
+    X(trace_pool, rtdev_launch_trace_pool, hipError_t,                                                                     \
+      (const rtdev::TraceArgs *args, int prims_class, int textured, int specular, int bvh, unsigned blocks,               \
+       hipStream_t stream))                                                                                                \
+    X(resolve_chunks, rtdev_launch_resolve_chunks, hipError_t,                                                             \
+      (const double *partial, double *out, int width, int height, int n_chunks, int slice_rows, int strip_rows,           \
+       int strip_count, int strip_index, int step_x, int step_y, int cover_w, int cover_h, int out_col_step, int out_cols, \
+       int samples, hipStream_t stream))                                                                                   \
+    X(fold_chunks, rtdev_launch_fold_chunks, hipError_t,                                                                   \
+      (const double *partial, double *running, double *out, size_t n, int c0, int c1, int samples_done,                   \
+       hipStream_t stream))                                                                                                \
+    X(fold_adaptive, rtdev_launch_fold_adaptive, hipError_t, (const rtdev::AdaptiveFold *f, hipStream_t stream))           \
+    X(nee, rtdev_launch_nee, hipError_t,                                                                                   \
+      (const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class, int textured, int specular, int bvh,     \
+       hipStream_t stream))                                                                                                \
+    X(nee_pass, rtdev_launch_nee_pass, hipError_t,                                                                         \
+      (const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class, int textured, int specular, int bvh,     \
+       hipStream_t stream))                                                                                                \
+    X(nee_chunk, rtdev_launch_nee_chunk, hipError_t,                                                                       \
+      (const double *running, double *boundary, double *squares, size_t n, int samples, hipStream_t stream))              \
+    X(nee_decide, rtdev_launch_nee_decide, hipError_t, (const rtdev::NeeDecide *f, hipStream_t stream))                    \
+    X(nee_stream, rtdev_launch_nee_stream, hipError_t,                                                                     \
+      (const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class, int textured, int specular, int bvh,     \
+       unsigned blocks, hipStream_t stream))                                                                               \
+    X(nee_stream_blocks_per_cu, rtdev_nee_stream_blocks_per_cu, int,                                                       \
+      (int prims_class, int textured, int specular, int bvh))                                                              \
+    X(nee_stream_chunk, rtdev_nee_stream_chunk, int, (void))
+#define RT_DECLARE_LAUNCHER(member, name, ret, params) \
+    extern "C" ret name params;                        \
+    extern "C" ret name##_exact params;
+RT_LAUNCHER_LIST(RT_DECLARE_LAUNCHER)
+#undef RT_DECLARE_LAUNCHER
 
 namespace rtapi {
 
 // The launchers of one arithmetic flavour (rt_api.hip: kFastLaunchers, kExactLaunchers); a scene points to its own.
 struct Launchers {
-    decltype(&rtdev_launch_trace) trace;
-    decltype(&rtdev_launch_resolve) resolve;
-    decltype(&rtdev_pool_blocks_per_cu) pool_blocks_per_cu;
-    decltype(&rtdev_pool_static_lds) pool_static_lds;
-    decltype(&rtdev_launch_trace_pool) trace_pool;
-    decltype(&rtdev_launch_resolve_chunks) resolve_chunks;
-    decltype(&rtdev_launch_fold_chunks) fold_chunks;
-    decltype(&rtdev_launch_fold_adaptive) fold_adaptive;
+#define RT_LAUNCHER_MEMBER(member, name, ret, params) ret(*member) params;
+    RT_LAUNCHER_LIST(RT_LAUNCHER_MEMBER)
+#undef RT_LAUNCHER_MEMBER
 };
 
 // set the thread-local text behind rt_last_error_message (truncated, never throws) and return `code`
@@ -201,35 +227,6 @@ extern "C" hipError_t rtdev_launch_guides(const rtdev::TraceArgs *args, const Rt
 extern "C" hipError_t rtdev_launch_denoise_step(const RtDenoiseParams *d, int step, int width, int height, const double *in,
                                                 const RtGuides *guides, double *out, hipStream_t stream);
 
-// The launchers of rt_nee_kernel.hip (both arithmetic flavours): the whole frame's NEE samples into args->accum.
-extern "C" hipError_t rtdev_launch_nee(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class, int textured,
-                                       int specular, int bvh, hipStream_t stream);
-extern "C" hipError_t rtdev_launch_nee_exact(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class,
-                                             int textured, int specular, int bvh, hipStream_t stream);
-// The launchers of rt_nee_pass_kernel.hip (both arithmetic flavours): one chunk of the NEE estimator over listed tiles on top
-// of args->accum, the batch-means update behind it and the decision step behind a pass.
-extern "C" hipError_t rtdev_launch_nee_pass(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class, int textured,
-                                            int specular, int bvh, hipStream_t stream);
-extern "C" hipError_t rtdev_launch_nee_pass_exact(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class,
-                                                  int textured, int specular, int bvh, hipStream_t stream);
-extern "C" hipError_t rtdev_launch_nee_chunk(const double *running, double *boundary, double *squares, size_t n, int samples,
-                                             hipStream_t stream);
-extern "C" hipError_t rtdev_launch_nee_chunk_exact(const double *running, double *boundary, double *squares, size_t n, int samples,
-                                                   hipStream_t stream);
-extern "C" hipError_t rtdev_launch_nee_decide(const rtdev::NeeDecide *f, hipStream_t stream);
-extern "C" hipError_t rtdev_launch_nee_decide_exact(const rtdev::NeeDecide *f, hipStream_t stream);
-// The launchers of rt_nee_stream_kernel.hip (both arithmetic flavours): the NEE estimator as ONE persistent launch of `blocks`
-// blocks over args' region-ordered tile queue, every tile delivered into args->deliver_out; the variant's resident blocks
-// per CU (the runtime's occupancy query); the chunk length the flavour was compiled with.
-extern "C" hipError_t rtdev_launch_nee_stream(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class, int textured,
-                                              int specular, int bvh, unsigned blocks, hipStream_t stream);
-extern "C" hipError_t rtdev_launch_nee_stream_exact(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class,
-                                                    int textured, int specular, int bvh, unsigned blocks, hipStream_t stream);
-extern "C" int rtdev_nee_stream_blocks_per_cu(int prims_class, int textured, int specular, int bvh);
-extern "C" int rtdev_nee_stream_blocks_per_cu_exact(int prims_class, int textured, int specular, int bvh);
-extern "C" int rtdev_nee_stream_chunk(void);
-extern "C" int rtdev_nee_stream_chunk_exact(void);
-
 struct RtScene {
     int device = 0;
     rtapi::DevBuf<rtdev::Prim> prims;
@@ -293,6 +290,20 @@ struct RtScene {
     bool summed_times = false;
     double summed_kernel_ms = 0.0, summed_resolve_ms = 0.0;
 };
+
+namespace rtapi {
+// A launch whose waves read the scene's cancel word (the slot behind the region flags): lowered, and named in its arguments
+inline void arm_cancel_word(RtScene *s, rtdev::TraceArgs &a) {
+    s->buf.host_flags[rtdev::RT_MAX_REGIONS] = 0u;
+    a.cancel_flag = s->buf.host_flags + rtdev::RT_MAX_REGIONS;
+}
+// A call has enqueued its (first) launches: rt_scene_last_stats reads the counters and the event spans of this call
+inline void note_launches(RtScene *s, int launches) {
+    s->has_stats = true;
+    s->last_launches = launches;
+    s->summed_times = false;
+}
+} // namespace rtapi
 
 // Internal exports for the tests (not part of rt_abi.h; the ABI version does not cover them).
 //   rtdev_progressive_passes: the samples_done of every pass of rt_render_progressive(samples, pass_samples), in order, into

@@ -26,10 +26,6 @@
 #define RT_LAUNCHER(name) name
 #endif
 
-namespace rtdev {
-enum { PRIMS_RECTS = 0, PRIMS_SPHERES = 1, PRIMS_ANY = 2 };
-}
-
 namespace RT_KNS {
 using namespace rtdev;
 

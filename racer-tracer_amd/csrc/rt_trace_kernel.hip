@@ -5,6 +5,7 @@
 // measurements against the pooled kernel of rt_trace_pool_kernel.hip, which is
 // the default.  Selected with RtSceneOptions.kernel = RT_KERNEL_V1 (rt_scene_create_ex).
 #include "rt_trace_common.h"
+#include "rt_variant_dispatch.h"
 
 namespace RT_KNS {
 
@@ -217,20 +218,14 @@ __global__ __launch_bounds__(256) void k_resolve_f64(const double *__restrict__ 
 } // namespace RT_KNS
 
 namespace {
-template <int PRIMS, bool TEXTURED, bool SPECULAR>
-void launch_variant(const rtdev::TraceArgs &a, unsigned blocks, hipStream_t stream) {
-    hipLaunchKernelGGL((RT_KNS::k_trace_f64<PRIMS, TEXTURED, SPECULAR>), dim3(blocks), dim3(256), 0, stream, a);
-}
-template <int PRIMS>
-void launch_prims(const rtdev::TraceArgs &a, bool textured, bool specular, unsigned blocks, hipStream_t stream) {
-    if (textured) {
-        if (specular) launch_variant<PRIMS, true, true>(a, blocks, stream);
-        else launch_variant<PRIMS, true, false>(a, blocks, stream);
-    } else {
-        if (specular) launch_variant<PRIMS, false, true>(a, blocks, stream);
-        else launch_variant<PRIMS, false, false>(a, blocks, stream);
+// k_trace_f64 has no BVH form and the launcher below never asks for one: the BVH column of the variant table is empty
+// (it names no kernel, so the twelve instantiations are the linear loop's, in the order of their classes)
+template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH> struct TraceVariant {
+    static void launch(const rtdev::TraceArgs &a, unsigned blocks, hipStream_t stream) {
+        if constexpr (!BVH)
+            hipLaunchKernelGGL((RT_KNS::k_trace_f64<PRIMS, TEXTURED, SPECULAR>), dim3(blocks), dim3(256), 0, stream, a);
     }
-}
+};
 } // namespace
 
 // prims_class: rtdev::PRIMS_*; textured/specular: scene feature flags (see k_trace_f64)
@@ -240,11 +235,9 @@ extern "C" hipError_t RT_LAUNCHER(rtdev_launch_trace)(const rtdev::TraceArgs *ar
     int tiles_y = (args->owned_rows + 15) / 16;
     if (tiles_x <= 0 || tiles_y <= 0) return hipSuccess;
     unsigned blocks = (unsigned)(tiles_x * tiles_y);
-    switch (prims_class) {
-    case rtdev::PRIMS_RECTS: launch_prims<rtdev::PRIMS_RECTS>(*args, textured != 0, specular != 0, blocks, stream); break;
-    case rtdev::PRIMS_SPHERES: launch_prims<rtdev::PRIMS_SPHERES>(*args, textured != 0, specular != 0, blocks, stream); break;
-    default: launch_prims<rtdev::PRIMS_ANY>(*args, textured != 0, specular != 0, blocks, stream); break;
-    }
+    rtdev::dispatch_variant<TraceVariant>(prims_class, textured != 0, specular != 0, false, [&](auto v) {
+        decltype(v)::launch(*args, blocks, stream);
+    });
     return hipGetLastError();
 }
 

@@ -66,6 +66,7 @@
 #include <cstddef>
 #include <type_traits>
 #include "rt_trace_common.h"
+#include "rt_variant_dispatch.h"
 
 #ifndef RT_OCC_TEX
 #define RT_OCC_TEX 4 // textured spheres-only / rects-only variants: 40 KB of LDS per block still fits four (C4 +3 %)
@@ -1524,38 +1525,25 @@ template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH> struct PoolVariant 
         return (int)attr.sharedSizeBytes;
     }
 };
-
-// Calls F::template run<Variant>() for the variant the flags select.
-template <class F> auto dispatch_variant(int prims_class, bool textured, bool specular, bool bvh, F f) {
-    using namespace rtdev;
-#define RT_PICK(P, B)                                                                           \
-    (textured ? (specular ? f(PoolVariant<P, true, true, B>()) : f(PoolVariant<P, true, false, B>())) \
-              : (specular ? f(PoolVariant<P, false, true, B>()) : f(PoolVariant<P, false, false, B>())))
-    if (bvh) return RT_PICK(PRIMS_ANY, true);
-    if (prims_class == PRIMS_RECTS) return RT_PICK(PRIMS_RECTS, false);
-    if (prims_class == PRIMS_SPHERES) return RT_PICK(PRIMS_SPHERES, false);
-    return RT_PICK(PRIMS_ANY, false);
-#undef RT_PICK
-}
 } // namespace
 
 // Resident blocks per CU of the variant (the persistent grid is CUs x this).
 extern "C" int RT_LAUNCHER(rtdev_pool_blocks_per_cu)(int prims_class, int textured, int specular, int bvh, size_t dyn_lds) {
-    return dispatch_variant(prims_class, textured != 0, specular != 0, bvh != 0,
-                            [dyn_lds](auto v) { return decltype(v)::blocks_per_cu(dyn_lds); });
+    return rtdev::dispatch_variant<PoolVariant>(prims_class, textured != 0, specular != 0, bvh != 0,
+                                                [dyn_lds](auto v) { return decltype(v)::blocks_per_cu(dyn_lds); });
 }
 
 // Static LDS of the variant's kernel (its WaveLds), -1 when the runtime cannot say.
 extern "C" int RT_LAUNCHER(rtdev_pool_static_lds)(int prims_class, int textured, int specular, int bvh) {
-    return dispatch_variant(prims_class, textured != 0, specular != 0, bvh != 0, [](auto v) { return decltype(v)::static_lds(); });
+    return rtdev::dispatch_variant<PoolVariant>(prims_class, textured != 0, specular != 0, bvh != 0,
+                                                [](auto v) { return decltype(v)::static_lds(); });
 }
 
 extern "C" hipError_t RT_LAUNCHER(rtdev_launch_trace_pool)(const rtdev::TraceArgs *args, int prims_class, int textured, int specular,
                                               int bvh, unsigned blocks, hipStream_t stream) {
     if (blocks == 0 || args->n_items == 0) return hipSuccess;
-    dispatch_variant(prims_class, textured != 0, specular != 0, bvh != 0, [&](auto v) {
+    rtdev::dispatch_variant<PoolVariant>(prims_class, textured != 0, specular != 0, bvh != 0, [&](auto v) {
         decltype(v)::launch(*args, blocks, stream);
-        return 0;
     });
     return hipGetLastError();
 }

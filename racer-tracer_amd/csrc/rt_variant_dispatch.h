@@ -1,0 +1,28 @@
+// rt_variant_dispatch.h — the one place where a scene's runtime flags become the template arguments of a kernel variant.
+// The trace kernels are compiled as PRIMS x TEXTURED x SPECULAR with the linear closest-hit loop plus PRIMS_ANY x
+// TEXTURED x SPECULAR with the BVH; each kernel file wraps its kernel in a struct V<PRIMS, TEXTURED, SPECULAR, BVH> of
+// static functions (launch, occupancy queries) and calls dispatch_variant<V>.  Plain C++: no HIP header is needed, so the
+// mapping is tested with the host compiler alone (tests/test_variant_dispatch.py).
+#pragma once
+#include "rt_device_types.h"
+
+namespace rtdev {
+
+template <template <int, bool, bool, bool> class V, int PRIMS, bool BVH, class F>
+auto dispatch_features(bool textured, bool specular, F &f) {
+    if (textured) return specular ? f(V<PRIMS, true, true, BVH>()) : f(V<PRIMS, true, false, BVH>());
+    return specular ? f(V<PRIMS, false, true, BVH>()) : f(V<PRIMS, false, false, BVH>());
+}
+
+// f(V<P, T, S, B>()) for the variant the flags select: with `bvh` the tree's <PRIMS_ANY, t, s, true>, whatever the class;
+// otherwise the linear loop of the scene's class, any value other than PRIMS_RECTS / PRIMS_SPHERES being PRIMS_ANY.
+// f is a generic callable (`[](auto v) { return decltype(v)::...; }`) with one return type for every variant.
+template <template <int, bool, bool, bool> class V, class F>
+auto dispatch_variant(int prims_class, bool textured, bool specular, bool bvh, F f) {
+    if (bvh) return dispatch_features<V, PRIMS_ANY, true>(textured, specular, f);
+    if (prims_class == PRIMS_RECTS) return dispatch_features<V, PRIMS_RECTS, false>(textured, specular, f);
+    if (prims_class == PRIMS_SPHERES) return dispatch_features<V, PRIMS_SPHERES, false>(textured, specular, f);
+    return dispatch_features<V, PRIMS_ANY, false>(textured, specular, f);
+}
+
+} // namespace rtdev

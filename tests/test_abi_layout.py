@@ -100,6 +100,19 @@ def test_both_arithmetics_are_in_the_one_library(rt):
     symbols = subprocess.check_output(["nm", "-D", "--defined-only", so]).decode()
     for name in ("rtdev_launch_trace_pool", "rtdev_launch_trace_pool_exact", "rtdev_pool_blocks_per_cu_exact"):
         assert re.search(r"\b%s\b" % name, symbols), name
+    # every exported rtdev_* function comes as a pair, <name> and <name>_exact (rt_scene.h: RT_LAUNCHER_LIST), except the
+    # ones that exist once: post-processing, guides and the denoiser's step (RT_ARITH_FAST only), the host-side helpers
+    exported = {line.split()[-1] for line in symbols.splitlines() if line.split()[-1].startswith("rtdev_")}
+    single = {"rtdev_launch_post_rgba8", "rtdev_launch_guides", "rtdev_launch_denoise_step", "rtdev_scene_variant",
+              "rtdev_scene_classify", "rtdev_scene_radiance_bound", "rtdev_sum_exponent", "rtdev_progressive_passes"}
+    assert single <= exported, sorted(single - exported)
+    for name in single:     # (the list cannot rot: a name on it has no twin)
+        assert not name.endswith("_exact") and name + "_exact" not in exported, name
+    paired = exported - single
+    assert len(paired) >= 2 * 15
+    for name in paired:
+        twin = name[:-len("_exact")] if name.endswith("_exact") else name + "_exact"
+        assert twin in exported, "%s is exported without %s" % (name, twin)
 
 
 def test_multi_device_entry_points_validate_before_touching_a_device(rt, abi):

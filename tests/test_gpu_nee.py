@@ -11,6 +11,7 @@ import pytest
 
 import nee_model as NM
 import scenes_py as S
+import variant_scenes as V
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -194,3 +195,52 @@ def test_cli_nee_writes_the_nee_frame(rt, host, gpu):
     for bad in (["--nee", "--adaptive", "0.01"], ["--nee", "--devices", "2"]):
         r = subprocess.run([exe, "-c", config, "-s", scene_yml] + bad, capture_output=True, text=True, cwd=out, timeout=60)
         assert r.returncode != 0 and "--nee" in r.stderr
+
+
+# ---- k_nee_f64's own dispatch ----------------------------------------------------------------------------------------------
+# k_nee_pass_f64 and k_nee_stream_f64 are compared with k_nee_f64, and all three pick their instantiation through one
+# dispatcher (rt_variant_dispatch.h): a wrong pick would agree with itself.  So every form of the variant matrix, in both
+# flavours, renders the plain estimator through rtdev_launch_nee (max_lights = 0) against the oracle, under the conditions
+# tests/test_gpu_variants.py applies to these scenes.
+
+_ORACLE_FRAMES = {}   # form -> (frame, segments): one oracle render serves both flavours
+
+
+def _oracle_frame(orc, form, bundle, camera, params):
+    if form not in _ORACLE_FRAMES:
+        _ORACLE_FRAMES[form] = orc.render(bundle.desc, camera, params, use_bvh=V.oracle_use_bvh(bundle))
+    return _ORACLE_FRAMES[form]
+
+
+@pytest.mark.parametrize("flavour", ["fast", "exact"])
+@pytest.mark.parametrize("form", list(V.SPECS), ids=lambda f: "%s%s%s%s" % ("RSA"[f[0]], "t" * f[1], "s" * f[2], "-bvh" * f[3]))
+def test_every_variant_of_the_nee_kernel_matches_the_oracle(rt, orc, abi, gpu, form, flavour):
+    """Each form's scene selects its form, and the plain estimator through k_nee_f64 (no light listed) is the oracle's frame:
+    every linear value within 1e-3, fewer than 1e-3 of them beyond 1e-9 (the oracle against itself: none), a picture and
+    not a flat background, and the oracle's path segments to within 4.  (This is the test that found the reference
+    arithmetic's <PRIMS_RECTS, plain, SPECULAR> kernels continuing from a wrong origin behind a Fresnel reflection:
+    rt_nee_common.h, LABNOTES 10.)"""
+    prims_class, textured, specular, bvh = form
+    bundle, cam = V.build(form)
+    camera = S.camera_for(cam, V.W, V.H)
+    params = abi.render_params(V.W, V.H, V.SPP, max_depth=V.DEPTH)
+    scene = rt.Scene(bundle, closest_hit=abi.RT_HIT_BVH if bvh else abi.RT_HIT_LINEAR,
+                     arithmetic=abi.RT_ARITH_REFERENCE if flavour == "exact" else abi.RT_ARITH_FAST)
+    try:
+        variant = scene.variant()
+        got = scene.render_frame_nee(camera, params, max_lights=0)
+        segments = int(scene.last_stats().segments)
+    finally:
+        scene.close()
+    want = dict(prims_class=prims_class, textured=textured, specular=specular, use_bvh=bvh, exact=int(flavour == "exact"))
+    assert {k: variant[k] for k in want} == want
+    ref, ref_segments = _oracle_frame(orc, form, bundle, camera, params)
+    d = np.abs(got - ref)
+    share = float((d > 1e-9).mean())
+    print("%s %s: max |delta| = %.3g, share beyond 1e-9 = %.3g, std = %.3g, segments %d (oracle %d)"
+          % (form, flavour, d.max(), share, got.std(), segments, ref_segments))
+    assert np.isfinite(got).all()
+    assert d.max() < 1e-3, "max |delta| = %g" % d.max()
+    assert share < 1e-3, "share of values beyond 1e-9: %g" % share   # (a cap: the oracle against itself has share 0)
+    assert got.std() > 0.05   # a picture, not a flat background
+    assert abs(segments - ref_segments) <= 4, (segments, ref_segments)

@@ -1,7 +1,7 @@
 """Every compiled trace-kernel instantiation against the oracle.
 
-rt_scene_create_ex picks one of many kernels from what a scene holds (rt_api.hip: select_variant, dispatch_variant in
-rt_trace_pool_kernel.hip): k_trace_pool_f64<PRIMS, TEXTURED, SPECULAR, BVH> (12 linear-loop forms + 4 BVH forms) and
+rt_scene_create_ex picks one of many kernels from what a scene holds (rt_api.hip: select_variant; rt_variant_dispatch.h:
+dispatch_variant, which every kernel file's launcher goes through): k_trace_pool_f64<PRIMS, TEXTURED, SPECULAR, BVH> (12 linear-loop forms + 4 BVH forms) and
 k_trace_f64<PRIMS, TEXTURED, SPECULAR> (12 forms), each compiled twice — RT_ARITH_FAST and RT_ARITH_REFERENCE.  Template
 flags add or remove whole material arms, LDS layouts, NBUF and the fixed-point sums, so each is separate code: every
 one renders a scene built to reach it (tests/variant_scenes.py), after the test has checked that the scene selects it.

@@ -19,8 +19,8 @@ import variant_scenes as V
 
 abi = S.abi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# what dispatch_variant (rt_trace_pool_kernel.hip) and the v1 launcher (rt_trace_kernel.hip) can select: the BVH forms
-# exist for PRIMS_ANY only
+# what dispatch_variant (rt_variant_dispatch.h) can select for the pooled kernel and for the v1 launcher
+# (rt_trace_kernel.hip), which never asks for a tree: the BVH forms exist for PRIMS_ANY only
 REACHABLE = {
     "pool": {(p, t, s, 0) for p in (0, 1, 2) for t in (0, 1) for s in (0, 1)} | {(2, t, s, 1) for t in (0, 1) for s in (0, 1)},
     "v1": {(p, t, s, 0) for p in (0, 1, 2) for t in (0, 1) for s in (0, 1)},
@@ -43,11 +43,14 @@ def test_the_gpu_matrix_covers_every_compiled_instantiation(hipcc, kernel, flavo
 
 
 def test_dispatch_sends_only_prims_any_to_the_bvh_forms():
-    src = open(os.path.join(ROOT, "racer-tracer_amd", "csrc", "rt_trace_pool_kernel.hip")).read()
+    """The text of the one dispatcher (tests/test_variant_dispatch.py runs it), and that the pooled kernel goes through it."""
+    csrc = os.path.join(ROOT, "racer-tracer_amd", "csrc")
+    src = open(os.path.join(csrc, "rt_variant_dispatch.h")).read()
     body = src[src.index("auto dispatch_variant("):]
-    body = body[:body.index("#undef RT_PICK")]
-    assert re.search(r"if \(bvh\) return RT_PICK\(PRIMS_ANY, true\);", body)
-    assert len(re.findall(r"RT_PICK\(PRIMS_\w+, (?:true|false)\)", body)) == 4
+    assert re.search(r"if \(bvh\) return dispatch_features<V, PRIMS_ANY, true>\(", body)
+    assert len(re.findall(r"dispatch_features<V, PRIMS_\w+, (?:true|false)>\(", body)) == 4
+    pool = open(os.path.join(csrc, "rt_trace_pool_kernel.hip")).read()
+    assert "RT_PICK" not in pool and len(re.findall(r"rtdev::dispatch_variant<PoolVariant>\(", pool)) == 3
 
 
 def test_static_lds_of_the_linear_forms(hipcc):
