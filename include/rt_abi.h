@@ -486,6 +486,75 @@ int rt_render_progressive_denoised(RtScene *scene, const RtCamera *camera, const
  * sigmas, non-zero _reserved, strips, scale > 1 and rgb == out (RT_ERR_INVALID_ARGUMENT) before they touch a device.  A binding detects them by symbol lookup (RT_ABI_VERSION is
  * unchanged by them). */
 
+/* ---------------------------------------------------------------- temporal accumulation
+ * The history the reference's renderer/denoised.rs plans ("Implement SVGF", `temporal()`): radiance carried from one
+ * camera to the next by re-projecting the first hits, per-pixel luminance moments, and an a-trous filter whose luminance
+ * stop is scaled by the local standard deviation (Schied et al. 2017).  DESIGN.md section 4.11 has the definition; all of
+ * it is f64 in linear (demodulated) radiance.
+ *  - A history is six planes over W*H pixels in DEVICE memory: radiance (3 f64, accumulated and UNFILTERED), moments
+ *    (2 f64: the running means of the luminance and of its square), length (1 f64), and the normal (3 f64), position
+ *    (3 f64) and obj_id (int32) of the frame that wrote it.  The camera of that frame is kept by the caller.
+ *  - rt_temporal_accumulate_device blends a gamma-encoded frame (what rt_render_frame_device writes) into out_history:
+ *    each hit pixel's position is re-projected through prev_camera, the four bilinear taps of prev_history that agree in
+ *    obj_id, normal (|n - n'|^2 <= normal_tolerance^2) and plane (|n . (x' - x)| <= plane_tolerance * footprint) are
+ *    blended with a = max(1 / (length + 1), alpha); a pixel without a valid tap, a miss, or prev_history == NULL starts
+ *    afresh with length 1.  prev_camera and prev_history are both NULL or neither is; out_history must not alias
+ *    prev_history.  denoise->flags decides the demodulation, as in rt_denoise_device.  Enqueued on `hip_stream` without
+ *    synchronising.
+ *  - rt_denoise_history_device filters a history's radiance into out_device (gamma-encoded): the per-pixel variance of the
+ *    luminance (from the moments where length >= 4, else from a 7x7 neighbourhood), denoise->iterations a-trous levels with
+ *    the extra stop exp(-|l_p - l_q| / (sigma_luminance * sqrt(var) + 1e-10)), and the re-modulation
+ *    sqrt(max(radiance * albedo, 0)), which is all that iterations == 0 does.  With sigma_luminance <= 0 the levels are
+ *    rt_denoise_device's own.  guides_device are the guides of the frame that wrote the history.  The history is not
+ *    written: no filtered colour is ever fed back.  Scratch memory is the scene's.
+ *  - RtTemporal keeps two histories, the guides and the last camera for a W x H stream of frames on one device.
+ *    rt_render_temporal does, in order: rt_render_frame_device's frame for (camera, params), its guides, the accumulation
+ *    against the stored history and camera, the filter, the download into out_rgb_host (and of the history's length into
+ *    out_length_host, W*H f64, when not NULL), and the swap of the histories.  The caller advances params->seed from frame
+ *    to frame: equal seeds trace equal samples, and accumulating those adds nothing.  rt_temporal_reset forgets the
+ *    history (a moved object keeps its obj_id, so the caller resets).  Calls on one RtTemporal, and on the scene it
+ *    renders, are serialised by the caller.
+ *  - Refused with RT_ERR_INVALID_ARGUMENT before a device is touched: NULL pointers, what rt_denoise_device refuses about
+ *    params and denoise, non-finite temporal parameters, an alpha outside [0, 1], max_history < 1, a non-zero _reserved;
+ *    for rt_render_temporal also a width, height or device that is not the RtTemporal's.  RT_ERR_UNSUPPORTED for
+ *    rt_render_temporal on a scene of the v1 kernel, as rt_render_progressive_denoised.
+ * A binding detects these entry points by symbol lookup (RT_ABI_VERSION is unchanged by them). */
+typedef struct RtTemporalParams {
+    double alpha;            /* floor of the radiance blend factor, 0..1 (0: the running mean up to max_history) */
+    double alpha_moments;    /* ... of the moments' */
+    double max_history;      /* the history length stops growing here (>= 1) */
+    double normal_tolerance; /* a tap is valid while |n - n'| <= this */
+    double plane_tolerance;  /* ... and its distance from the pixel's tangent plane <= this many pixel footprints */
+    double sigma_luminance;  /* luminance stop in standard deviations; <= 0 switches it off */
+    int32_t _reserved[4];    /* must be 0 */
+} RtTemporalParams;
+typedef struct RtHistory {
+    double *radiance;  /* W*H*3 */
+    double *moments;   /* W*H*2 */
+    double *length;    /* W*H   */
+    double *normal;    /* W*H*3 */
+    double *position;  /* W*H*3 */
+    int32_t *obj_id;   /* W*H   */
+} RtHistory;
+typedef struct RtTemporal RtTemporal; /* opaque; owned by the library */
+
+/* The defaults: alpha = alpha_moments = 0.2, max_history 32, the tolerances and sigma_luminance as DESIGN.md 4.11
+ * records.  A NULL is ignored. */
+void rt_temporal_params_default(RtTemporalParams *out);
+int rt_temporal_accumulate_device(RtScene *scene, const RtRenderParams *params, const RtTemporalParams *temporal,
+                                  const RtDenoiseParams *denoise, const double *rgb_device, const RtGuides *guides_device,
+                                  const RtCamera *prev_camera, const RtHistory *prev_history, const RtHistory *out_history,
+                                  void *hip_stream);
+int rt_denoise_history_device(RtScene *scene, const RtRenderParams *params, const RtDenoiseParams *denoise,
+                              const RtTemporalParams *temporal, const RtHistory *history, const RtGuides *guides_device,
+                              double *out_device, void *hip_stream);
+int rt_temporal_create(int device, int32_t width, int32_t height, RtTemporal **out);
+void rt_temporal_destroy(RtTemporal *temporal_state);
+int rt_temporal_reset(RtTemporal *temporal_state);
+int rt_render_temporal(RtScene *scene, RtTemporal *temporal_state, const RtCamera *camera, const RtRenderParams *params,
+                       const RtTemporalParams *temporal, const RtDenoiseParams *denoise, double *out_rgb_host,
+                       double *out_length_host /* may be NULL */);
+
 /* ---------------------------------------------------------------- adaptive sampling
  * rt_render_progressive's passes, with the 8x8 tiles that have converged left out of the passes after it (DESIGN.md
  * section 4.7).

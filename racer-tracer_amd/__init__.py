@@ -148,6 +148,24 @@ def light_sampling_params(**overrides):
     return ls
 
 
+def temporal_params(**overrides):
+    """rt_temporal_params_default, with fields overridden by keyword (alpha, alpha_moments, max_history, normal_tolerance,
+    plane_tolerance, sigma_luminance) -> abi.RtTemporalParams.  No device needed."""
+    tp = abi.RtTemporalParams()
+    lib().rt_temporal_params_default(C.byref(tp))
+    for k, v in overrides.items():
+        setattr(tp, k, v)
+    return tp
+
+
+HISTORY_PLANES = ("radiance", "moments", "length", "normal", "position", "obj_id")
+
+
+def history_struct(planes):
+    """abi.RtHistory over device tensors (a dict with radiance, moments, length, normal, position, obj_id)."""
+    return abi.RtHistory(*[planes[k].data_ptr() for k in HISTORY_PLANES])
+
+
 def guides_struct(planes):
     """abi.RtGuides over device tensors (a dict with normal, position, albedo, footprint, obj_id)."""
     return abi.RtGuides(*[planes[k].data_ptr() for k in ("normal", "position", "albedo", "footprint", "obj_id")])
@@ -448,6 +466,28 @@ class Scene:
               "rt_denoise_frame", self._lib)
         return out
 
+    def temporal_accumulate_device(self, params, rgb_ptr, guides, out_history, prev_camera=None, prev_history=None,
+                                   tparams=None, dparams=None, stream=None):
+        """rt_temporal_accumulate_device: rgb_ptr = device address (int) of a gamma-encoded frame; guides an abi.RtGuides,
+        out_history / prev_history abi.RtHistory of device addresses; prev_camera and prev_history both None: a first frame.
+        dparams decides the demodulation (None: the defaults).  Enqueued on `stream`, not synchronised."""
+        tp = tparams if tparams is not None else temporal_params()
+        dp = dparams if dparams is not None else denoise_params()
+        check(self._lib.rt_temporal_accumulate_device(
+            self._h, C.byref(params), C.byref(tp), C.byref(dp), C.c_void_p(rgb_ptr), C.byref(guides),
+            C.byref(prev_camera) if prev_camera is not None else None,
+            C.byref(prev_history) if prev_history is not None else None, C.byref(out_history), C.c_void_p(stream or 0)),
+            "rt_temporal_accumulate_device", self._lib)
+
+    def denoise_history_device(self, params, history, guides, out_ptr, dparams=None, tparams=None, stream=None):
+        """rt_denoise_history_device: the variance-guided filter of a history's radiance into out_ptr (device address),
+        gamma-encoded.  Enqueued on `stream`, not synchronised."""
+        tp = tparams if tparams is not None else temporal_params()
+        dp = dparams if dparams is not None else denoise_params()
+        check(self._lib.rt_denoise_history_device(self._h, C.byref(params), C.byref(dp), C.byref(tp), C.byref(history),
+                                                  C.byref(guides), C.c_void_p(out_ptr), C.c_void_p(stream or 0)),
+              "rt_denoise_history_device", self._lib)
+
     def variant(self):
         """rtdev_scene_variant: which trace kernel rt_scene_create_ex chose -> dict of abi.VARIANT_FIELDS."""
         out = (C.c_int32 * len(abi.VARIANT_FIELDS))()
@@ -460,3 +500,42 @@ class Scene:
         st = abi.RtRenderStats()
         check(self._lib.rt_scene_last_stats(self._h, C.byref(st)), "rt_scene_last_stats", self._lib)
         return st
+
+
+class Temporal:
+    """RtTemporal handle: the history of a width x height stream of frames on one device (rt_temporal_create)."""
+
+    def __init__(self, width, height, device=0, library=None):
+        self._lib = library or lib()
+        self._h = C.c_void_p()
+        check(self._lib.rt_temporal_create(device, width, height, C.byref(self._h)), "rt_temporal_create", self._lib)
+        self.width, self.height, self.device = width, height, device
+
+    def render(self, scene, camera, params, tparams=None, dparams=None, with_length=False):
+        """rt_render_temporal: the frame of (camera, params) accumulated into the history and filtered -> float64 [H, W, 3],
+        or (frame, history length float64 [H, W]) with with_length.  The caller advances params.seed from frame to frame:
+        equal seeds trace equal samples."""
+        tp = tparams if tparams is not None else temporal_params()
+        dp = dparams if dparams is not None else denoise_params()
+        out = np.zeros((params.height, params.width, 3), dtype=np.float64)
+        length = np.zeros((params.height, params.width), dtype=np.float64) if with_length else None
+        check(self._lib.rt_render_temporal(scene._h, self._h, C.byref(camera), C.byref(params), C.byref(tp), C.byref(dp),
+                                           out.ctypes.data_as(C.POINTER(C.c_double)),
+                                           length.ctypes.data_as(C.POINTER(C.c_double)) if with_length else None),
+              "rt_render_temporal", self._lib)
+        return (out, length) if with_length else out
+
+    def reset(self):
+        """rt_temporal_reset: the next frame starts a new history."""
+        check(self._lib.rt_temporal_reset(self._h), "rt_temporal_reset", self._lib)
+
+    def close(self):
+        if self._h:
+            self._lib.rt_temporal_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

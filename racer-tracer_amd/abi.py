@@ -120,6 +120,17 @@ class RtDenoiseParams(C.Structure):
                 ("sigma_plane", C.c_double), ("_reserved", C.c_int32 * 4)]
 
 
+class RtTemporalParams(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("alpha_moments", C.c_double), ("max_history", C.c_double),
+                ("normal_tolerance", C.c_double), ("plane_tolerance", C.c_double), ("sigma_luminance", C.c_double),
+                ("_reserved", C.c_int32 * 4)]
+
+
+class RtHistory(C.Structure):
+    _fields_ = [("radiance", C.c_void_p), ("moments", C.c_void_p), ("length", C.c_void_p), ("normal", C.c_void_p),
+                ("position", C.c_void_p), ("obj_id", C.c_void_p)]
+
+
 class RtAdaptiveParams(C.Structure):
     _fields_ = [("threshold", C.c_double), ("pass_samples", C.c_int32), ("min_samples", C.c_int32),
                 ("_reserved", C.c_int32 * 4)]
@@ -175,6 +186,19 @@ PROTOTYPES = {
     "rt_render_progressive_denoised": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.c_int32,
                                                  C.POINTER(RtDenoiseParams), RtFrameCallback, C.c_void_p, RtCancelCallback,
                                                  C.c_void_p]),
+    "rt_temporal_params_default": (None, [C.POINTER(RtTemporalParams)]),
+    "rt_temporal_accumulate_device": (C.c_int, [C.c_void_p, C.POINTER(RtRenderParams), C.POINTER(RtTemporalParams),
+                                                C.POINTER(RtDenoiseParams), C.c_void_p, C.POINTER(RtGuides),
+                                                C.POINTER(RtCamera), C.POINTER(RtHistory), C.POINTER(RtHistory), C.c_void_p]),
+    "rt_denoise_history_device": (C.c_int, [C.c_void_p, C.POINTER(RtRenderParams), C.POINTER(RtDenoiseParams),
+                                            C.POINTER(RtTemporalParams), C.POINTER(RtHistory), C.POINTER(RtGuides),
+                                            C.c_void_p, C.c_void_p]),
+    "rt_temporal_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "rt_temporal_destroy": (None, [C.c_void_p]),
+    "rt_temporal_reset": (C.c_int, [C.c_void_p]),
+    "rt_render_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
+                                     C.POINTER(RtTemporalParams), C.POINTER(RtDenoiseParams), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double)]),
     "rt_adaptive_params_default": (None, [C.POINTER(RtAdaptiveParams)]),
     "rt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.POINTER(RtAdaptiveParams),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), RtFrameCallback,

@@ -1,0 +1,578 @@
+// rt_temporal.hip — temporal accumulation and the variance-guided a-trous filter behind rt_temporal_accumulate_device,
+// rt_denoise_history_device and rt_render_temporal (include/rt_abi.h), defined in DESIGN.md section 4.11.
+//
+// The reference's renderer/denoised.rs plans "Implement SVGF" with a temporal() blend; rt_denoise.hip is the spatial half
+// of that plan, this is the other: a history of demodulated linear radiance and luminance moments that follows the camera
+// by re-projecting the first hits of the guides, and a luminance stop scaled by the local standard deviation.
+//   accumulate  C = g^2 (/ max(albedo, 1e-3)); the hit point through the PREVIOUS camera's pinhole (Cramer's rule), four
+//               bilinear taps (j, then i) that agree in id, normal and plane; a = max(1 / (L + 1), alpha)
+//   variance    (m2 - m1^2) / length where length >= 4, else the 7x7 neighbourhood's (dy, then dx)
+//   a-trous     rt_denoise.hip's level with the factor exp(-|l_p - l_q| / (sigma_l sqrt(vbar_p) + 1e-10)); the variance is
+//               filtered alongside with the squared weights
+// With sigma_luminance <= 0 the levels are rt_denoise.hip's own launches, and the re-modulation always is.
+//
+// Compiled once, with the fast arithmetic, as rt_denoise.hip.  Lane = pixel, 16x16 pixels per block, taps straight from
+// global memory.  The launchers have internal linkage: nothing outside this file starts these kernels.
+#include "rt_trace_common.h"
+#include "rt_scene.h"
+
+#include <cmath>
+#include <cstring>
+#include <utility>
+
+namespace RT_KNS {
+
+struct AccumulateArgs {
+    int width, height;
+    int has_prev, demodulate;
+    double o[3], ulc[3], hor[3], ver[3]; // the previous camera
+    double alpha, alpha_moments, max_history;
+    double normal_tol2;                  // normal_tolerance^2
+    double plane_tol;
+};
+
+__device__ __forceinline__ d3 cross3(d3 a, d3 b) {
+    return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+__device__ __forceinline__ double luminance(d3 c) { return 0.2126 * c.x + 0.7152 * c.y + 0.0722 * c.z; }
+
+// One pixel of the accumulation.  Whether a history tap exists is decided on doubles: no index is formed, and nothing
+// of the previous history is loaded, before the re-projected position is known to be finite and within one pixel of the
+// previous image, and every tap is bounds-checked on its own.
+__global__ __launch_bounds__(256) void k_temporal_accumulate(const AccumulateArgs P, const double *__restrict__ g,
+                                                             const RtGuides G, const RtHistory prev, const RtHistory out) {
+    const int px = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int py = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (px >= P.width || py >= P.height) return;
+    const size_t p = (size_t)py * (size_t)P.width + (size_t)px;
+
+    // the demodulation of rt_denoise.hip (k_denoise_demod), operation for operation
+    double c[3];
+    for (int k = 0; k < 3; ++k) {
+        const double v = g[3 * p + k];
+        const double L = v * v;
+        c[k] = P.demodulate ? L / fmax(G.albedo[3 * p + k], 1e-3) : L;
+    }
+    const d3 cp = mk(c[0], c[1], c[2]);
+    const double lp = luminance(cp);
+    const int id = G.obj_id[p];
+    const d3 np = ld3(G.normal + 3 * p), xp = ld3(G.position + 3 * p);
+
+    d3 rad = cp;
+    double m1 = lp, m2 = lp * lp, len = 1.0;
+    if (P.has_prev && id >= 0) {
+        // ulc + u hor - v ver - o = s (x - o): columns hor, -ver, -(x - o) against o - ulc
+        const d3 o = ld3(P.o);
+        const d3 a = ld3(P.hor), b = -ld3(P.ver), cc = -(xp - o), r = o - ld3(P.ulc);
+        const d3 bxc = cross3(b, cc);
+        const double det = dot(a, bxc);
+        const double u = dot(r, bxc) / det;
+        const double v = dot(a, cross3(r, cc)) / det;
+        const double s = dot(a, cross3(b, r)) / det;
+        const double fx = u * (double)(P.width - 1) - 0.5;
+        const double fy = v * (double)(P.height - 1) - 0.5;
+        // (a NaN fails every comparison below)
+        const bool inside = det != 0.0 && s > 0.0 && fx >= -1.0 && fx <= (double)P.width && fy >= -1.0 && fy <= (double)P.height;
+        if (inside) {
+            const double flx = floor(fx), fly = floor(fy);
+            const int x0 = (int)flx, y0 = (int)fly; // in [-1, W] and [-1, H]
+            const double tx = fx - flx, ty = fy - fly;
+            const double fp = G.footprint[p];
+            d3 ch = mk(0.0, 0.0, 0.0);
+            double mh1 = 0.0, mh2 = 0.0, lh = 0.0, wsum = 0.0;
+            for (int j = 0; j < 2; ++j) {
+                const int qy = y0 + j;
+                if (qy < 0 || qy >= P.height) continue;
+                for (int i = 0; i < 2; ++i) {
+                    const int qx = x0 + i;
+                    if (qx < 0 || qx >= P.width) continue;
+                    const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
+                    if (prev.obj_id[q] != id) continue;
+                    const d3 dn = np - ld3(prev.normal + 3 * q);
+                    if (!(len2(dn) <= P.normal_tol2)) continue;
+                    const double dist = dot(np, ld3(prev.position + 3 * q) - xp);
+                    if (!(fabs(dist) <= P.plane_tol * fp)) continue;
+                    const double w = (i ? tx : 1.0 - tx) * (j ? ty : 1.0 - ty);
+                    ch = ch + w * ld3(prev.radiance + 3 * q);
+                    mh1 += w * prev.moments[2 * q + 0];
+                    mh2 += w * prev.moments[2 * q + 1];
+                    lh += w * prev.length[q];
+                    wsum += w;
+                }
+            }
+            if (wsum >= 1e-3) {
+                const double inv = 1.0 / wsum;
+                const double N = lh * inv + 1.0;
+                const double al = fmax(1.0 / N, P.alpha), am = fmax(1.0 / N, P.alpha_moments);
+                rad = (1.0 - al) * (ch * inv) + al * cp;
+                m1 = (1.0 - am) * (mh1 * inv) + am * lp;
+                m2 = (1.0 - am) * (mh2 * inv) + am * (lp * lp);
+                len = fmin(N, P.max_history);
+            }
+        }
+    }
+    out.radiance[3 * p + 0] = rad.x;
+    out.radiance[3 * p + 1] = rad.y;
+    out.radiance[3 * p + 2] = rad.z;
+    out.moments[2 * p + 0] = m1;
+    out.moments[2 * p + 1] = m2;
+    out.length[p] = len;
+    out.normal[3 * p + 0] = np.x;
+    out.normal[3 * p + 1] = np.y;
+    out.normal[3 * p + 2] = np.z;
+    out.position[3 * p + 0] = xp.x;
+    out.position[3 * p + 1] = xp.y;
+    out.position[3 * p + 2] = xp.z;
+    out.obj_id[p] = id;
+}
+
+struct VarianceArgs {
+    int width, height;
+    double inv_sn2; // 1 / sigma_n^2, or 0: the normal stop is off
+    double inv_sx;  // 1 / sigma_x (step 1), or 0: the plane stop is off
+};
+
+// The variance of the accumulated luminance: the moments' where the history is long enough, else the neighbourhood's.
+__global__ __launch_bounds__(256) void k_temporal_variance(const VarianceArgs P, const double *__restrict__ radiance,
+                                                           const double *__restrict__ moments,
+                                                           const double *__restrict__ length, const RtGuides G,
+                                                           double *__restrict__ var) {
+    const int px = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int py = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (px >= P.width || py >= P.height) return;
+    const size_t p = (size_t)py * (size_t)P.width + (size_t)px;
+    const int id = G.obj_id[p];
+    if (id < 0) {
+        var[p] = 0.0;
+        return;
+    }
+    const double len = length[p];
+    if (len >= 4.0) {
+        const double m1 = moments[2 * p + 0], m2 = moments[2 * p + 1];
+        var[p] = fmax(0.0, m2 - __dmul_rn(m1, m1)) / len; // the square rounded on its own: m2 == m1^2 gives exactly 0
+        return;
+    }
+    const d3 np = ld3(G.normal + 3 * p), xp = ld3(G.position + 3 * p);
+    const double inv_fx = P.inv_sx / G.footprint[p];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int dy = -3; dy <= 3; ++dy) {
+        const int qy = py + dy;
+        if (qy < 0 || qy >= P.height) continue;
+        for (int dx = -3; dx <= 3; ++dx) {
+            const int qx = px + dx;
+            if (qx < 0 || qx >= P.width) continue;
+            const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
+            if (G.obj_id[q] != id) continue;
+            double w = 1.0;
+            if (P.inv_sn2 > 0.0) {
+                const d3 dn = np - ld3(G.normal + 3 * q);
+                w *= exp(-len2(dn) * P.inv_sn2);
+            }
+            if (P.inv_sx > 0.0) {
+                const double dist = dot(np, ld3(G.position + 3 * q) - xp) * inv_fx;
+                w *= exp(-(dist * dist));
+            }
+            const double lq = luminance(ld3(radiance + 3 * q));
+            s0 += w;
+            s1 += w * lq;
+            s2 += w * __dmul_rn(lq, lq);
+        }
+    }
+    const double mean = s1 / s0; // the centre tap weighs 1
+    var[p] = fmax(0.0, s2 / s0 - __dmul_rn(mean, mean)); // ... and a pixel alone in its window likewise
+}
+
+struct AtrousVarArgs {
+    int width, height, step;
+    double inv_sn2, inv_sx, inv_sc2; // rt_denoise.hip: AtrousArgs
+    double sigma_l;                  // > 0
+};
+
+// One variance-guided level: k_denoise_atrous's taps, weights and order with the luminance factor, the variance filtered
+// alongside with the squared weights.
+__global__ __launch_bounds__(256) void k_temporal_atrous(const AtrousVarArgs P, const double *__restrict__ I,
+                                                         const double *__restrict__ var, const RtGuides G,
+                                                         double *__restrict__ out, double *__restrict__ var_out) {
+    const int px = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int py = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (px >= P.width || py >= P.height) return;
+    const size_t p = (size_t)py * (size_t)P.width + (size_t)px;
+    const d3 ip = ld3(I + 3 * p);
+    const int id = G.obj_id[p];
+    if (id < 0) { // a guide miss passes through
+        out[3 * p + 0] = ip.x;
+        out[3 * p + 1] = ip.y;
+        out[3 * p + 2] = ip.z;
+        var_out[p] = var[p];
+        return;
+    }
+    // vbar: the 3x3 Gaussian of the variance around the centre, at step 1, over the taps inside the image
+    double vs = 0.0, vw = 0.0;
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int qy = py + dy;
+        if (qy < 0 || qy >= P.height) continue;
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = px + dx;
+            if (qx < 0 || qx >= P.width) continue;
+            const double k = (dx == 0 ? 0.5 : 0.25) * (dy == 0 ? 0.5 : 0.25); // 1/4, 1/8, 1/16
+            vs += k * var[(size_t)qy * (size_t)P.width + (size_t)qx];
+            vw += k;
+        }
+    }
+    const double inv_sl = 1.0 / (P.sigma_l * sqrt(vs / vw) + 1e-10);
+    const double lp = luminance(ip);
+
+    const double kh[5] = {1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0};
+    const d3 np = ld3(G.normal + 3 * p), xp = ld3(G.position + 3 * p);
+    const d3 sp = mk(sqrt(ip.x), sqrt(ip.y), sqrt(ip.z));
+    const double inv_fx = P.inv_sx / G.footprint[p];
+    d3 sum = mk(0.0, 0.0, 0.0);
+    double wsum = 0.0, vsum = 0.0;
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = py + dy * P.step;
+        if (qy < 0 || qy >= P.height) continue;
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = px + dx * P.step;
+            if (qx < 0 || qx >= P.width) continue;
+            const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
+            if (G.obj_id[q] != id) continue;
+            const d3 iq = ld3(I + 3 * q);
+            double w = kh[dx + 2] * kh[dy + 2];
+            if (P.inv_sn2 > 0.0) {
+                const d3 dn = np - ld3(G.normal + 3 * q);
+                w *= exp(-len2(dn) * P.inv_sn2);
+            }
+            if (P.inv_sx > 0.0) {
+                const double dist = dot(np, ld3(G.position + 3 * q) - xp) * inv_fx;
+                w *= exp(-(dist * dist));
+            }
+            if (P.inv_sc2 > 0.0) {
+                const d3 dc = sp - mk(sqrt(iq.x), sqrt(iq.y), sqrt(iq.z));
+                w *= exp(-len2(dc) * P.inv_sc2);
+            }
+            w *= exp(-fabs(lp - luminance(iq)) * inv_sl);
+            sum = sum + w * iq;
+            wsum += w;
+            vsum += (w * w) * var[q];
+        }
+    }
+    const double inv = 1.0 / wsum; // the centre tap alone weighs 9/64
+    out[3 * p + 0] = sum.x * inv;
+    out[3 * p + 1] = sum.y * inv;
+    out[3 * p + 2] = sum.z * inv;
+    var_out[p] = vsum * (inv * inv);
+}
+
+} // namespace RT_KNS
+
+// ------------------------------------------------------------------------------------------------------------ host side
+using rtapi::fail;
+
+struct RtTemporal {
+    int device = 0;
+    int width = 0, height = 0;
+    rtapi::DevBuf<double> planes; // two histories of 12 doubles per pixel, the guides' 10, the frame's 3 and the output's 3
+    rtapi::DevBuf<int32_t> ids;   // the histories' and the guides' obj_id
+    double *host_length = nullptr; // pinned, W*H
+    bool has_prev = false;
+    int current = 0; // the history the next frame reads
+    RtCamera camera;
+};
+
+namespace {
+
+dim3 pixel_grid(int width, int height) { return dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)); }
+
+hipError_t launch_accumulate(const RtRenderParams *p, const RtTemporalParams *t, int demodulate, const double *rgb,
+                             const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out,
+                             hipStream_t stream) {
+    RT_KNS::AccumulateArgs a;
+    memset(&a, 0, sizeof a);
+    a.width = p->width;
+    a.height = p->height;
+    a.has_prev = prev != nullptr;
+    a.demodulate = demodulate;
+    if (prev_camera) {
+        memcpy(a.o, prev_camera->origin, sizeof a.o);
+        memcpy(a.ulc, prev_camera->upper_left_corner, sizeof a.ulc);
+        memcpy(a.hor, prev_camera->horizontal, sizeof a.hor);
+        memcpy(a.ver, prev_camera->vertical, sizeof a.ver);
+    }
+    a.alpha = t->alpha;
+    a.alpha_moments = t->alpha_moments;
+    a.max_history = t->max_history;
+    a.normal_tol2 = t->normal_tolerance * t->normal_tolerance;
+    a.plane_tol = t->plane_tolerance;
+    hipLaunchKernelGGL(RT_KNS::k_temporal_accumulate, pixel_grid(p->width, p->height), dim3(256), 0, stream, a, rgb, *g,
+                       prev ? *prev : *out, *out);
+    return hipGetLastError();
+}
+
+hipError_t launch_variance(const RtRenderParams *p, const RtDenoiseParams *d, const RtHistory *h, const RtGuides *g, double *var,
+                           hipStream_t stream) {
+    RT_KNS::VarianceArgs a;
+    a.width = p->width;
+    a.height = p->height;
+    a.inv_sn2 = d->sigma_normal > 0.0 ? 1.0 / (d->sigma_normal * d->sigma_normal) : 0.0;
+    a.inv_sx = d->sigma_plane > 0.0 ? 1.0 / d->sigma_plane : 0.0;
+    hipLaunchKernelGGL(RT_KNS::k_temporal_variance, pixel_grid(p->width, p->height), dim3(256), 0, stream, a, h->radiance,
+                       h->moments, h->length, *g, var);
+    return hipGetLastError();
+}
+
+// level `step` of the variance-guided filter: the parameters of rtdev_launch_denoise_step (rt_denoise.hip) and sigma_l
+hipError_t launch_atrous_var(const RtRenderParams *p, const RtDenoiseParams *d, double sigma_l, int step, const double *in,
+                             const double *var, const RtGuides *g, double *out, double *var_out, hipStream_t stream) {
+    RT_KNS::AtrousVarArgs a;
+    a.width = p->width;
+    a.height = p->height;
+    a.step = 1 << step;
+    a.inv_sn2 = d->sigma_normal > 0.0 ? 1.0 / (d->sigma_normal * d->sigma_normal) : 0.0;
+    a.inv_sx = d->sigma_plane > 0.0 ? 1.0 / (d->sigma_plane * (double)a.step) : 0.0;
+    const double sc = d->sigma_color > 0.0 ? ldexp(d->sigma_color, -step) : 0.0;
+    a.inv_sc2 = sc > 0.0 ? 1.0 / (sc * sc) : 0.0;
+    a.sigma_l = sigma_l;
+    hipLaunchKernelGGL(RT_KNS::k_temporal_atrous, pixel_grid(p->width, p->height), dim3(256), 0, stream, a, in, var, *g, out,
+                       var_out);
+    return hipGetLastError();
+}
+
+// calibrated on tests/temporal_model.py (cornell_box_boxes, eight 4-spp frames on a 1-degree orbit)
+constexpr double kAlpha = 0.2, kMaxHistory = 32.0;
+constexpr double kNormalTolerance = 0.25, kPlaneTolerance = 2.0, kSigmaLuminance = 4.0;
+
+bool guides_complete(const RtGuides *g) { return g && g->normal && g->position && g->albedo && g->footprint && g->obj_id; }
+bool history_complete(const RtHistory *h) {
+    return h && h->radiance && h->moments && h->length && h->normal && h->position && h->obj_id;
+}
+
+int check_temporal(const RtTemporalParams *t) {
+    if (!t) return fail(RT_ERR_INVALID_ARGUMENT, "temporal is NULL");
+    for (double v : {t->alpha, t->alpha_moments, t->max_history, t->normal_tolerance, t->plane_tolerance, t->sigma_luminance})
+        if (!std::isfinite(v)) return fail(RT_ERR_INVALID_ARGUMENT, "temporal parameters must be finite");
+    if (t->alpha < 0.0 || t->alpha > 1.0 || t->alpha_moments < 0.0 || t->alpha_moments > 1.0)
+        return fail(RT_ERR_INVALID_ARGUMENT, "temporal->alpha and alpha_moments must be in 0..1");
+    if (t->max_history < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, "temporal->max_history must be at least 1");
+    for (int32_t r : t->_reserved)
+        if (r != 0) return fail(RT_ERR_INVALID_ARGUMENT, "temporal->_reserved must be 0");
+    return RT_OK;
+}
+
+int enqueue_accumulate(const RtRenderParams *p, const RtTemporalParams *t, const RtDenoiseParams *d, const double *rgb,
+                       const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out,
+                       hipStream_t stream) {
+    RT_HIP(launch_accumulate(p, t, (d->flags & RT_DENOISE_DEMODULATE) != 0, rgb, g, prev_camera, prev, out, stream));
+    return RT_OK;
+}
+
+// the filter of a history into `out`; the scene's scratch holds two colour buffers and, behind them, two variance planes
+int enqueue_denoise_history(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, const RtTemporalParams *t,
+                            const RtHistory *h, const RtGuides *g, double *out, hipStream_t stream) {
+    const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
+    rtapi::RenderBuffers &b = s->buf;
+    if (b.denoise_scratch.count < 8 * pixels) RT_HIP(b.denoise_scratch.alloc(8 * pixels));
+    const double *in = h->radiance;
+    double *ping = b.denoise_scratch.ptr, *pong = ping + n;
+    if (t->sigma_luminance > 0.0 && d->iterations > 0) {
+        double *var = ping + 2 * n, *var_next = var + pixels;
+        RT_HIP(launch_variance(p, d, h, g, var, stream));
+        for (int i = 0; i < d->iterations; ++i) {
+            RT_HIP(launch_atrous_var(p, d, t->sigma_luminance, i, in, var, g, ping, var_next, stream));
+            in = ping;
+            std::swap(ping, pong);
+            std::swap(var, var_next);
+        }
+    } else {
+        for (int i = 0; i < d->iterations; ++i) { // rt_denoise_device's own levels
+            RT_HIP(rtdev_launch_denoise_step(d, i, p->width, p->height, in, g, ping, stream));
+            in = ping;
+            std::swap(ping, pong);
+        }
+    }
+    RT_HIP(rtdev_launch_denoise_step(d, d->iterations, p->width, p->height, in, g, out, stream)); // re-modulation
+    return RT_OK;
+}
+
+int accumulate_device(RtScene *s, const RtRenderParams *p, const RtTemporalParams *t, const RtDenoiseParams *d, const double *rgb,
+                      const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out, void *stream) {
+    int rc = rtapi::check_denoise(p, d);
+    if (rc != RT_OK) return rc;
+    if ((rc = check_temporal(t)) != RT_OK) return rc;
+    if (!rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device is NULL");
+    if (!guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
+    if (!history_complete(out)) return fail(RT_ERR_INVALID_ARGUMENT, "out_history or one of its planes is NULL");
+    if ((prev_camera == nullptr) != (prev == nullptr))
+        return fail(RT_ERR_INVALID_ARGUMENT, "prev_camera and prev_history are both NULL or neither is");
+    if (prev) {
+        if (!history_complete(prev)) return fail(RT_ERR_INVALID_ARGUMENT, "prev_history has a NULL plane");
+        if (prev->radiance == out->radiance || prev->moments == out->moments || prev->length == out->length ||
+            prev->normal == out->normal || prev->position == out->position || prev->obj_id == out->obj_id)
+            return fail(RT_ERR_INVALID_ARGUMENT, "out_history and prev_history must differ");
+    }
+    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    RT_HIP(hipSetDevice(s->device));
+    return enqueue_accumulate(p, t, d, rgb, g, prev_camera, prev, out, (hipStream_t)stream);
+}
+
+int denoise_history_device(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, const RtTemporalParams *t,
+                           const RtHistory *h, const RtGuides *g, double *out, void *stream) {
+    int rc = rtapi::check_denoise(p, d);
+    if (rc != RT_OK) return rc;
+    if ((rc = check_temporal(t)) != RT_OK) return rc;
+    if (!history_complete(h)) return fail(RT_ERR_INVALID_ARGUMENT, "history or one of its planes is NULL");
+    if (!guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out_device is NULL");
+    if (out == h->radiance) return fail(RT_ERR_INVALID_ARGUMENT, "out_device and the history's radiance must differ");
+    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    RT_HIP(hipSetDevice(s->device));
+    return enqueue_denoise_history(s, p, d, t, h, g, out, (hipStream_t)stream);
+}
+
+// the planes of an RtTemporal: [history 0 | history 1 | guides | frame | output]
+constexpr size_t kHistoryDoubles = 12, kStateDoubles = 2 * kHistoryDoubles + 10 + 3 + 3;
+
+RtHistory state_history(RtTemporal *t, int k) {
+    const size_t pixels = (size_t)t->width * (size_t)t->height;
+    double *base = t->planes.ptr + (size_t)k * kHistoryDoubles * pixels;
+    RtHistory h;
+    h.radiance = base;
+    h.moments = base + 3 * pixels;
+    h.length = base + 5 * pixels;
+    h.normal = base + 6 * pixels;
+    h.position = base + 9 * pixels;
+    h.obj_id = t->ids.ptr + (size_t)k * pixels;
+    return h;
+}
+
+RtGuides state_guides(RtTemporal *t) {
+    const size_t pixels = (size_t)t->width * (size_t)t->height;
+    double *base = t->planes.ptr + 2 * kHistoryDoubles * pixels;
+    RtGuides g;
+    g.normal = base;
+    g.position = base + 3 * pixels;
+    g.albedo = base + 6 * pixels;
+    g.footprint = base + 9 * pixels;
+    g.obj_id = t->ids.ptr + 2 * pixels;
+    return g;
+}
+
+void temporal_free(RtTemporal *t) {
+    (void)hipSetDevice(t->device);
+    t->planes.release();
+    t->ids.release();
+    if (t->host_length) (void)hipHostFree(t->host_length);
+    delete t;
+}
+
+int temporal_create(int device, int32_t width, int32_t height, RtTemporal **out) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    if (width < 2 || height < 2) return fail(RT_ERR_INVALID_ARGUMENT, "width and height must be at least 2");
+    if ((uint64_t)width * (uint64_t)height > 0xFFFFFFFFull) return fail(RT_ERR_INVALID_ARGUMENT, "image too large for the pixel counter");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(RT_ERR_NO_DEVICE, "no HIP device");
+    if (device < 0 || device >= count) return fail(RT_ERR_INVALID_ARGUMENT, "device out of range");
+    RT_HIP(hipSetDevice(device));
+    RtTemporal *t = new RtTemporal();
+    t->device = device;
+    t->width = width;
+    t->height = height;
+    const size_t pixels = (size_t)width * (size_t)height;
+    hipError_t e = t->planes.alloc(kStateDoubles * pixels);
+    if (e == hipSuccess) e = t->ids.alloc(3 * pixels);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&t->host_length, pixels * sizeof(double), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        temporal_free(t);
+        return fail(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_HIP, std::string("rt_temporal_create: ") + hipGetErrorString(e));
+    }
+    *out = t;
+    return RT_OK;
+}
+
+int render_temporal(RtScene *s, RtTemporal *t, const RtCamera *camera, const RtRenderParams *p, const RtTemporalParams *tp,
+                    const RtDenoiseParams *d, double *out_rgb, double *out_length) {
+    int rc = rtapi::check_denoise(p, d);
+    if (rc != RT_OK) return rc;
+    if ((rc = check_temporal(tp)) != RT_OK) return rc;
+    if ((rc = rtapi::check_params(camera, p)) != RT_OK) return rc;
+    if (!out_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgb_host is NULL");
+    if (!t) return fail(RT_ERR_INVALID_ARGUMENT, "temporal_state is NULL");
+    if (p->width != t->width || p->height != t->height)
+        return fail(RT_ERR_INVALID_ARGUMENT, "params->width and height must be the RtTemporal's");
+    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (s->device != t->device) return fail(RT_ERR_INVALID_ARGUMENT, "the scene and the RtTemporal must be on the same device");
+    if (s->use_v1) return fail(RT_ERR_UNSUPPORTED, "rt_render_temporal needs the pooled kernel");
+    RT_HIP(hipSetDevice(s->device));
+    const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
+    const hipStream_t stream = s->buf.stream;
+    double *frame = t->planes.ptr + (2 * kHistoryDoubles + 10) * pixels, *filtered = frame + n;
+    const RtGuides g = state_guides(t);
+    const RtHistory prev = state_history(t, t->current), next = state_history(t, t->current ^ 1);
+    if ((rc = rtapi::enqueue_render(s, camera, p, frame, stream, 0, rtapi::Cancel())) != RT_OK) return rc;
+    if ((rc = rtapi::enqueue_guides(s, camera, p, g, stream)) != RT_OK) return rc;
+    if ((rc = enqueue_accumulate(p, tp, d, frame, &g, t->has_prev ? &t->camera : nullptr, t->has_prev ? &prev : nullptr, &next,
+                                 stream)) != RT_OK)
+        return rc;
+    if ((rc = enqueue_denoise_history(s, p, d, tp, &next, &g, filtered, stream)) != RT_OK) return rc;
+    RT_HIP(hipMemcpyAsync(out_rgb, filtered, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (out_length) RT_HIP(hipMemcpyAsync(t->host_length, next.length, pixels * sizeof(double), hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    if (out_length) memcpy(out_length, t->host_length, pixels * sizeof(double));
+    t->current ^= 1;
+    t->has_prev = true;
+    t->camera = *camera;
+    return RT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void rt_temporal_params_default(RtTemporalParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof *out);
+    out->alpha = kAlpha;
+    out->alpha_moments = kAlpha;
+    out->max_history = kMaxHistory;
+    out->normal_tolerance = kNormalTolerance;
+    out->plane_tolerance = kPlaneTolerance;
+    out->sigma_luminance = kSigmaLuminance;
+}
+
+int rt_temporal_accumulate_device(RtScene *s, const RtRenderParams *p, const RtTemporalParams *t, const RtDenoiseParams *d,
+                                  const double *rgb_device, const RtGuides *guides_device, const RtCamera *prev_camera,
+                                  const RtHistory *prev_history, const RtHistory *out_history, void *hip_stream) {
+    return rtapi::guarded("rt_temporal_accumulate_device", [&] {
+        return accumulate_device(s, p, t, d, rgb_device, guides_device, prev_camera, prev_history, out_history, hip_stream);
+    });
+}
+
+int rt_denoise_history_device(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, const RtTemporalParams *t,
+                              const RtHistory *history, const RtGuides *guides_device, double *out_device, void *hip_stream) {
+    return rtapi::guarded("rt_denoise_history_device",
+                          [&] { return denoise_history_device(s, p, d, t, history, guides_device, out_device, hip_stream); });
+}
+
+int rt_temporal_create(int device, int32_t width, int32_t height, RtTemporal **out) {
+    return rtapi::guarded("rt_temporal_create", [&] { return temporal_create(device, width, height, out); });
+}
+
+void rt_temporal_destroy(RtTemporal *t) {
+    if (!t) return;
+    (void)rtapi::guarded("rt_temporal_destroy", [&] { temporal_free(t); return RT_OK; });
+}
+
+int rt_temporal_reset(RtTemporal *t) {
+    return rtapi::guarded("rt_temporal_reset", [&]() -> int {
+        if (!t) return fail(RT_ERR_INVALID_ARGUMENT, "temporal_state is NULL");
+        t->has_prev = false;
+        return RT_OK;
+    });
+}
+
+int rt_render_temporal(RtScene *s, RtTemporal *t, const RtCamera *camera, const RtRenderParams *p, const RtTemporalParams *tp,
+                       const RtDenoiseParams *d, double *out_rgb_host, double *out_length_host) {
+    return rtapi::guarded("rt_render_temporal", [&] { return render_temporal(s, t, camera, p, tp, d, out_rgb_host, out_length_host); });
+}
+
+} // extern "C"

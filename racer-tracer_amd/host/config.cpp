@@ -214,6 +214,14 @@ Args Args::parse(int argc, const char *const *argv) {
                 throw TracerError::ArgumentParsingError(s + " needs a positive threshold, not '" + v + "'");
             (s == "--adaptive" ? a.adaptive : a.nee_adaptive) = t;
         }
+        else if (s == "--temporal") {
+            const std::string v = val();
+            char *end = nullptr;
+            const long k = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || end == nullptr || *end != '\0' || k < 1 || k > 1000000)
+                throw TracerError::ArgumentParsingError("--temporal needs a positive number of frames, not '" + v + "'");
+            a.temporal = (int)k;
+        }
         else if (s == "-h" || s == "--help") a.help = true;
         else throw TracerError::ArgumentParsingError("unknown argument " + s);
     }
@@ -229,6 +237,10 @@ Args Args::parse(int argc, const char *const *argv) {
         throw TracerError::ArgumentParsingError("--nee-adaptive and --adaptive are two estimators: pick one");
     if (a.nee_adaptive > 0.0 && a.devices > 1)
         throw TracerError::ArgumentParsingError("--nee-adaptive renders on one device: it does not combine with --devices > 1");
+    if (a.temporal > 0 && (a.nee || a.nee_stream || a.adaptive > 0.0 || a.nee_adaptive > 0.0))
+        throw TracerError::ArgumentParsingError("--temporal is a render mode of its own: it does not combine with --nee, --nee-stream, --adaptive or --nee-adaptive");
+    if (a.temporal > 0 && a.devices > 1)
+        throw TracerError::ArgumentParsingError("--temporal renders on one device: it does not combine with --devices > 1");
     if (a.nee && a.devices > 1)
         throw TracerError::ArgumentParsingError("--nee renders on one device: it does not combine with --devices > 1");
     return a;

@@ -67,6 +67,7 @@ struct Args { // config.rs:12-28
     bool nee_stream = false; // --nee-stream: the same frame through rt_render_nee, tile by tile into the screen buffer, one device only
     double adaptive = 0.0; // --adaptive T (T > 0): render through rt_render_adaptive with threshold T, one device only
     double nee_adaptive = 0.0; // --nee-adaptive T (T > 0): render through rt_render_adaptive_nee with threshold T, one device only
+    int temporal = 0; // --temporal K (K >= 1): K frames at seeds seed .. seed + K - 1 through rt_render_temporal, the last one written; one device only
     bool help = false;
 
     static Args parse(int argc, const char *const *argv);

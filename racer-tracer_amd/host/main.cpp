@@ -9,7 +9,9 @@
 // frame through rt_render_adaptive, a tile stopping once its error is at most T; --denoise filters that frame) and --nee (one
 // device renders the frame through rt_render_frame_nee, next-event estimation; --denoise filters that frame) and
 // --nee-adaptive T (--adaptive's stop rule with the next-event estimator: rt_render_adaptive_nee) and --nee-stream (--nee's
-// frame through rt_render_nee, tile by tile into the screen buffer; the PNG has --nee's bytes).
+// frame through rt_render_nee, tile by tile into the screen buffer; the PNG has --nee's bytes) and --temporal K (one device
+// renders K frames of the configured sample count at seeds seed .. seed + K - 1 from the configured camera through
+// rt_render_temporal and writes the last; --denoise gives the filter its levels, without it the history alone is shown).
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -54,7 +56,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee] [--nee-stream] [--nee-adaptive T]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee] [--nee-stream] [--nee-adaptive T] [--temporal K]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -92,7 +94,26 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Rendering image...\n"); // interactive.rs:229
     auto t0 = std::chrono::steady_clock::now();
     double traced = 1.0; // --adaptive: the fraction of the frame's samples traced
-    if (args.adaptive > 0.0) { // the whole frame at once; tone-mapped below (after the filter, with --denoise)
+    double mean_length = 0.0; // --temporal: the mean history length behind the last frame
+    if (args.temporal > 0) { // K frames into one history; the last one, filtered inside the call, is tone-mapped here
+        RtTemporalParams tp;
+        rt_temporal_params_default(&tp);
+        RtDenoiseParams dp;
+        rt_denoise_params_default(&dp);
+        if (!args.denoise) dp.iterations = 0;
+        RtTemporal *history = nullptr;
+        rc = rt_temporal_create(args.device, params.width, params.height, &history);
+        std::vector<double> frame(n_rgb), length(n_rgb / 3);
+        RtRenderParams one = params;
+        for (int k = 0; rc == RT_OK && k < args.temporal; ++k) {
+            one.seed = params.seed + (uint64_t)k; // equal seeds would trace equal samples
+            rc = rt_render_temporal(scenes[0], history, rth_session_camera(session), &one, &tp, &dp, frame.data(), length.data());
+        }
+        rt_temporal_destroy(history);
+        for (double l : length) mean_length += l;
+        mean_length /= (double)length.size();
+        if (rc == RT_OK) rth_tone_map(session, frame.data(), sb.buffer.data(), n_rgb / 3);
+    } else if (args.adaptive > 0.0) { // the whole frame at once; tone-mapped below (after the filter, with --denoise)
         RtAdaptiveParams ap;
         rt_adaptive_params_default(&ap);
         ap.threshold = args.adaptive;
@@ -132,7 +153,7 @@ int main(int argc, char **argv) {
     } else {
         rc = rt_render_multi(scenes.data(), (int)scenes.size(), rth_session_camera(session), &params, 0, on_tile, &sb, nullptr, nullptr);
     }
-    if (rc == RT_OK && args.denoise) { // the whole frame, filtered, then tone-mapped like the tiles were
+    if (rc == RT_OK && args.denoise && args.temporal == 0) { // the whole frame, filtered, then tone-mapped like the tiles were
         RtDenoiseParams dp;
         rt_denoise_params_default(&dp);
         std::vector<double> filtered(n_rgb);
@@ -154,6 +175,8 @@ int main(int argc, char **argv) {
         if (args.adaptive > 0.0 || args.nee_adaptive > 0.0)
             fprintf(stderr, "Adaptive sampling (threshold %g) traced %.1f %% of the %d samples per pixel.\n",
                     args.adaptive > 0.0 ? args.adaptive : args.nee_adaptive, 100.0 * traced, params.samples);
+        if (args.temporal > 0)
+            fprintf(stderr, "Temporal accumulation over %d frames: mean history length %.2f.\n", args.temporal, mean_length);
         fprintf(stderr, "It took %.3f seconds to render the image. (%.1f Msamples/s, %.2f segments/sample, kernel %.1f ms)\n",
                 secs, (double)st.samples / secs / 1e6, st.samples ? (double)st.segments / (double)st.samples : 0.0, st.kernel_ms);
         if (rth_session_image_action(session) == RTH_IMAGE_ACTION_SAVE_PNG) { // main.rs:153-156
