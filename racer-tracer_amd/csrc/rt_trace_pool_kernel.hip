@@ -59,6 +59,15 @@
 //    start the NEXT item's paths; per-pixel sums are 64-bit fixed-point integers, so the order in which samples arrive —
 //    which now depends on what else the wave traces — cannot change a bit of the frame (SUMS AND OVERLAPPED ITEMS below).
 //
+// 10. PRIMARY SEGMENTS ARE TRACED IN THE CAMERA BATCHES (the rects-only plain variant, C3's, in both arithmetic flavours).
+//    The batch of idea 4 forms the rays of its 64 entries and runs the closest-hit loop on them, all lanes busy and the
+//    rays coherent; an entry whose path ends on that segment (a miss, a light, max_depth <= 1) adds its contribution there
+//    and never takes a lane, the others wait in a ring of 92 slots in LDS with their hit (22 bytes each).  The path loop of
+//    that variant is ROTATED: hand-out from the ring, shade the pending hits, sampler, new direction, trace, ends — so a
+//    lane that takes an entry traces the path's SECOND segment in the same iteration.  Every sample keeps its bits; the
+//    order in which an item's samples reach its sums changes (spp 1 and 2 frames are bit-identical to the old loop's).
+//    C3 59.6 -> 56.4 ms (LABNOTES R10.1).  The other variants keep the loop of ideas 1 - 9.
+//
 // The launch is VALU-throughput bound with the CU's one scalar ALU close behind (scalar_busy 0.60 on C3: count scalar
 // instructions before vector ones; DESIGN.md 4.2 / 6 and LABNOTES.md have the counters, the per-region cycle profile of the
 // -DRT_PROFILE_REGIONS build — which adds 1.8 KB of LDS per block and can cost a variant at a granule edge a block per CU —
@@ -254,6 +263,76 @@ template <bool TEXTURED, int NBUF, bool OVERLAP> struct WaveLds {
     // one vector has to come from vector registers — copied there with six v_mov_b32 per iteration, or read from here
     double ulc[3];
 };
+
+// Survivors a camera batch of the PRETRACE variant may park (see PRIMARY SEGMENTS IN THE BATCHES in the kernel): a batch
+// adds up to 64 and runs when at most RING_SLOTS - 64 are waiting.
+enum : uint32_t { RING_SLOTS = 92u };
+// Per-wave scratch of the PRETRACE variant (rects only, no textures, no specular materials): the members of WaveLds that
+// variant reads, under the same names, and the ring of pool entries whose primary segment a batch has traced and that
+// live on.  An entry keeps what its ray is formed from (v; the pixel's u stays in `u`) and its first hit: 22 bytes, where
+// the ray itself would take 48.  WaveLds' `base` and `v` have no counterpart (the ray is formed from u and the ring's v);
+// with them gone the block has 20 096 bytes of static LDS, 64 fewer than before, and seven blocks still fit a CU beside
+// C3's primitive table (the seven-block edge is 23 040 bytes).  The lens samples of the ring's entries sit in the dynamic
+// LDS that holds the two batches' in the other variants (128 slots per wave).
+struct PretraceLds {
+    // camera.origin and background.top, for the same reason as `ulc` below: a rect test and an LDS add take their
+    // operands from vector registers, and an LDS read puts them there without a vector instruction
+    double cam_origin[3], bg_top[3];
+    double u[64];      // per pixel of the tile: (px + ju) / (W - 1)
+    double sum[64][3]; // per-pixel radiance sums (doubles)
+    SamplerScratch<false> scratch;
+    uint8_t pix_of[64];
+    double ring_v[RING_SLOTS];     // (py + jv) / (H - 1) of the entry
+    double ring_t[RING_SLOTS];     // its primary hit: ray parameter ...
+    uint32_t ring_w[RING_SLOTS];   // (its index in the item's pool)
+    uint16_t ring_best[RING_SLOTS]; // ... and primitive (the table is staged in LDS, 192 bytes a record: under 1 000 records)
+    uint32_t n_started;            // paths this wave has started (RtRenderStats.samples): every entry of every batch
+    ItemInfo info[1]; // (one item at a time)
+    double ulc[3];
+};
+
+// The closest-hit loop of the rects-only variants over the grouped table (XY, XZ, YZ rects, in that order: record order,
+// strict `t < best_t`), one straight-line test per group with the plane a compile-time constant.  PAIRS: two records per
+// scalar-load wait (what the path loop runs); without, one test site per plane (the camera batches: every site is a copy
+// of the rect test in the kernel's text).
+template <bool PAIRS>
+__device__ __forceinline__ void closest_hit_rects(const Prim *table, const d3 &o, const d3 &d, const d3 &inv_d, double &best_t, int &best) {
+    auto test_plane = [&](auto axis, const Prim &P, int i) {
+#ifndef RT_EXACT_DIV
+        rect_closest_update<decltype(axis)::value>(P.p[0], P.p[1], P.p[2], P.p[3], P.p[4], o, d, inv_d, 0.001, best_t, best, i);
+        return;
+#endif
+        double t;
+        if (rect_t<true>(decltype(axis)::value, P.p[0], P.p[1], P.p[2], P.p[3], P.p[4], o, d, inv_d, 0.001, best_t, t)) {
+            best_t = t;
+            best = i;
+        }
+    };
+    const Prim *rec = table; // ONE pointer runs through the groups (they follow each other in the table)
+    int i = 0;
+    auto group = [&](auto axis, int end) {
+        if (PAIRS) {
+            for (; i + 1 < end; i += 2, rec += 2) {
+                const Prim pa = load_prim_uniform(rec, 0), pb = load_prim_uniform(rec, 1);
+                test_plane(axis, pa, i);
+                test_plane(axis, pb, i + 1);
+            }
+            if (i < end) {
+                test_plane(axis, load_prim_uniform(rec, 0), i);
+                ++i;
+                ++rec;
+            }
+        } else {
+            for (; i < end; ++i, ++rec) test_plane(axis, load_prim_uniform(rec, 0), i);
+        }
+    };
+    // (the group bounds are re-read from the kernel arguments here: see the path loop of the other variants)
+    const RT_CONSTANT TraceArgs *KB = kernargs_here();
+    const int end_xy = KB->rect_end[0], end_xz = KB->rect_end[1], end_yz = KB->rect_end[2];
+    group(std::integral_constant<int, 2>(), end_xy); // XY
+    group(std::integral_constant<int, 1>(), end_xz); // XZ
+    group(std::integral_constant<int, 0>(), end_yz); // YZ
+}
 
 // vec3.rs:424-430 for every lane of `pending` (a wave-uniform lane mask, like the one it returns: the lanes
 // that got their sample), evaluated by the whole wave.
@@ -551,7 +630,14 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
 #else
     constexpr bool OVERLAP = BVH || PRIMS == PRIMS_ANY;
 #endif
-    __shared__ WaveLds<TEXTURED, NBUF, OVERLAP> lds_all[4];
+    // PRIMARY SEGMENTS IN THE BATCHES (the rects-only plain variant, both arithmetic flavours): see the path loop below.
+#ifdef RT_NO_PRETRACE
+    constexpr bool PRETRACE = false;
+#else
+    constexpr bool PRETRACE = PRIMS == PRIMS_RECTS && !TEXTURED && !SPECULAR && !BVH;
+#endif
+    using Lds = std::conditional_t<PRETRACE, PretraceLds, WaveLds<TEXTURED, NBUF, OVERLAP>>;
+    __shared__ Lds lds_all[4];
     // Dynamic LDS of a block: [BVH nodes | primitive table + texture table][Perlin gradients][lens samples][ray times];
     // the host sizes it (rt_device_types.h: pool_lds_layout, whose order the offsets below follow) and says what is in it.
     extern __shared__ __align__(16) unsigned char dyn_lds[];
@@ -628,9 +714,16 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
     }
     const int lane = threadIdx.x & 63;
     const int lane_of_wave = lane;
-    WaveLds<TEXTURED, NBUF, OVERLAP> &L = lds_all[threadIdx.x >> 6];
+    Lds &L = lds_all[threadIdx.x >> 6];
     unsigned int n_segments = 0, n_started = 0;
-    if (OVERLAP && lane < 3) L.ulc[lane] = A.cam.ulc[lane];
+    if ((OVERLAP || PRETRACE) && lane < 3) L.ulc[lane] = A.cam.ulc[lane];
+    if constexpr (PRETRACE) {
+        if (lane < 3) {
+            L.cam_origin[lane] = A.cam.origin[lane];
+            L.bg_top[lane] = A.bg.top[lane];
+        }
+        L.n_started = 0u; // (every lane: a `lane == 0` here is kept, as a lane mask, for the kernel's last lines)
+    }
 
     // SUMS AND OVERLAPPED ITEMS.  When the pool of an item is dry its last paths still take a dozen iterations to end, with
     // ever fewer lanes tracing (`random`: 14 % of a wave's iterations ran at 14 lanes, cornell_box_boxes 13 % at 19, C4
@@ -666,6 +759,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
     // `next` at which the next batch of camera samples is due (batch b when next >= (b - (NBUF - 1)) * 64: NBUF batches stay
     // ahead of the hand-out), or ~0 when the item's batches are all drawn: ONE scalar compare per iteration decides
     uint32_t batch_due = ~0u;
+    uint32_t ring_head = 0; // PRETRACE: slot of the ring's oldest entry
     uint32_t my_pixel = 0; // image index of this lane's pixel of the current item's tile
 
     RT_REGION_DECL
@@ -695,7 +789,21 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         // item -> (region, chunk, tile): regions in queue order, chunk-major inside a region (rt_device_types.h: Region)
         int region = 0, reg_tx0 = 0, reg_ty0 = 0, reg_ntx = A.tiles_x;
         uint32_t reg_tiles = (uint32_t)A.n_tiles, local = item;
-        if (A.n_regions > 1) {
+        if constexpr (PRETRACE) {
+            // (the region count opaque, where the path loop leaves no scalar register to spare: n_regions - 1 would be formed
+            // in front of the loops and parked in a VGPR lane across them)
+            int n_regions = A.n_regions;
+            asm volatile("" : "+s"(n_regions));
+            if (n_regions > 1) {
+                const RT_CONSTANT TraceArgs *K = kernargs_here();
+                while (region + 1 < n_regions && item >= K->regions[region + 1].item_begin) ++region;
+                local = item - K->regions[region].item_begin;
+                reg_tx0 = K->regions[region].tx0;
+                reg_ntx = K->regions[region].ntx;
+                reg_ty0 = K->regions[region].ty0;
+                reg_tiles = (uint32_t)reg_ntx * (uint32_t)K->regions[region].nty;
+            }
+        } else if (A.n_regions > 1) {
             const RT_CONSTANT TraceArgs *K = kernargs_here();
             while (region + 1 < A.n_regions && item >= K->regions[region + 1].item_begin) ++region;
             local = item - K->regions[region].item_begin;
@@ -742,11 +850,15 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         const uint64_t valid_mask = ballot(my_valid);
         n_valid = __popcll(valid_mask);
         {
-            PathRng prng{my_pixel, RT_RNG_SAMPLE_PIXEL, A.seed_lo, A.seed_hi};
+            uint32_t pixel_stream = RT_RNG_SAMPLE_PIXEL;
+            // (opaque where the path loop leaves no register to spare: the products of the block's constant words would
+            // otherwise be formed in front of the loops and parked in scratch memory across them)
+            if constexpr (PRETRACE) asm volatile("" : "+s"(pixel_stream));
+            PathRng prng{my_pixel, pixel_stream, A.seed_lo, A.seed_hi};
             u4 bj = prng.block(0, RT_RNG_PIXEL, 0);
             const RT_CONSTANT TraceArgs *K = kernargs_here();
             const double u = div_by((double)my_px + u53(bj.a, bj.b), (double)(A.width - 1), K->inv_width_m1); // cpu.rs:35-36
-            if (OVERLAP) {
+            if constexpr (OVERLAP || PRETRACE) {
                 L.u[lane] = u;
             } else {
                 const d3 base = ld3(K->cam.ulc) + u * ld3(K->cam.horizontal); // camera.rs:331, first two terms
@@ -756,7 +868,8 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             }
             // fixed-point sums: a sample arrives as the bit pattern of (T * scale + 2^52), i.e. 0x433 << 52 plus the
             // integer; the n_smp patterns' exponent fields are taken off here, once, instead of masked off every sample
-            const unsigned long long zero = FIXED_SUMS ? 0ull - (unsigned long long)n_smp * 0x4330000000000000ull : 0ull;
+            unsigned long long zero = FIXED_SUMS ? 0ull - (unsigned long long)n_smp * 0x4330000000000000ull : 0ull;
+            if constexpr (PRETRACE) asm volatile("" : "+v"(zero)); // (as above)
             unsigned long long *sum = reinterpret_cast<unsigned long long *>(L.sum[cur * 64 + lane]);
             sum[0] = zero;
             sum[1] = zero;
@@ -770,6 +883,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         n_batches = (total + 63u) >> 6;
         batches_done = 0;
         batch_due = n_batches > 0u ? 0u : ~0u;
+        ring_head = 0;
         return true;
     };
     // The item of slot `s` has no path left: its sums go to its own slice of `partial` (or the launch finishes the tile's
@@ -808,8 +922,8 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         }
     };
     // Pool entry w of the current item = (pixel w % n_valid of the tile, sample smp0 + w / n_valid).
-    auto entry_of = [&](uint32_t w, int &py_out, uint32_t &pixel_out, uint32_t &sample_out) { // (all 64 lanes: a lane shuffle)
-        int s_off, pix;
+    auto entry_of = [&](uint32_t w, int &py_out, uint32_t &pixel_out, uint32_t &sample_out, int &pix) { // (all 64 lanes: a lane shuffle)
+        int s_off;
         if (n_valid == 64) {
             pix = (int)(w & 63u);
             s_off = (int)(w >> 6);
@@ -835,6 +949,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
     // once — every lane busy — into LDS, two batches ahead of `next`.  (The buffers belong to the current item: an item
     // that still has paths in flight when the next one starts has handed out all its entries.)
     auto prepare_batch = [&](uint32_t b) {
+        if constexpr (!PRETRACE) {
         int lane = lane_of_wave; // (opaque, like start_item's)
         asm volatile("" : "+v"(lane));
         const RT_CONSTANT TraceArgs *K = kernargs_here();
@@ -842,7 +957,8 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         const bool in_pool = w < total;
         int py_b = 0;
         uint32_t pixel_b = 0, sample_b = 0;
-        entry_of(w, py_b, pixel_b, sample_b); // (entries behind the pool's end: values nobody reads)
+        int pix_b = 0;
+        entry_of(w, py_b, pixel_b, sample_b, pix_b); // (entries behind the pool's end: values nobody reads)
         const u4 bc = philox4x32(pixel_b, sample_b, RT_RNG_CAMERA, 0u, A.seed_lo, A.seed_hi);
         const int buf = (int)(b & (uint32_t)(NBUF - 1));
         L.v[buf][lane] = div_by((double)py_b + u53(bc.a, bc.b), (double)(A.height - 1), K->inv_height_m1); // cpu.rs:39-40
@@ -854,6 +970,138 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             coop_random_in_unit_disk(in_pool, pixel_b, sample_b, A.seed_lo, A.seed_hi, lane, L.scratch.req, lx, ly);
             lens[buf][lane][0] = lx * K->cam.lens_radius; // camera.rs:327 `lens_radius * random_in_unit_disk()`: formed here, by all
             lens[buf][lane][1] = ly * K->cam.lens_radius; // 64 lanes, not at the hand-out by the quarter of them that start a path
+        }
+        }
+    };
+
+    // PRIMARY SEGMENTS IN THE BATCHES (PRETRACE).  A path's first segment needs nothing a lane carries: its ray is a
+    // function of the pool entry.  So the batch that draws the camera samples of 64 consecutive entries — all lanes busy,
+    // rays of neighbouring pixels from one origin, so the rect tests' early outs fire — also forms their rays and runs
+    // the closest-hit loop on them, with the expressions and the order of the path loop (a value never depends on where
+    // it was computed).  An entry whose path ENDS on that segment (a miss, a light, or a depth limit of 0 or 1) adds its
+    // contribution to the tile's sums right here and never takes a lane: on C3, whose camera looks at the box from
+    // outside, that is half the paths.  The others go to a ring in LDS (PretraceLds) with their hit, and the hand-out gives
+    // lanes ring entries instead of pool entries.
+    // The camera ray of pixel `pix` of the tile (camera.rs:326-337), for the batch and for the hand-out: ONE expression,
+    // so both get the same bits (upper_left_corner + u * horizontal, the vector the other variants keep per pixel, is
+    // formed here as the two-item variants do).
+    // (TraceArgs.lens_lds is set exactly when the camera has an aperture: an integer the scalar unit can test)
+    auto camera_ray = [&](int pix, double v, double lens_x, double lens_y, d3 &ro, d3 &rd) {
+        if constexpr (PRETRACE) {
+        const RT_CONSTANT TraceArgs *K = kernargs_here();
+        ro = ld3(L.cam_origin);
+        rd = (ld3(L.ulc) + L.u[pix] * ld3(K->cam.horizontal)) - v * ld3(K->cam.vertical) - ld3(K->cam.origin); // camera.rs:331
+        if (kernargs_here()->lens_lds != 0) { // (lens_x, lens_y mean something only here; both rays are updated in place)
+            const d3 offset = ld3(K->cam.right) * lens_x + ld3(K->cam.up) * lens_y;
+            ro = ro + offset;
+            rd = rd - offset;
+        }
+        }
+    };
+    double (*const lens_ring)[2] = reinterpret_cast<double (*)[2]>(lens); // lens samples of the ring's entries, by slot
+    static_assert(RING_SLOTS <= 2 * 64, "the ring's lens samples take the LDS of two batches'");
+    auto pretrace_batch = [&](uint32_t b) {
+        if constexpr (PRETRACE) {
+        int lane = lane_of_wave; // (opaque, like start_item's)
+        asm volatile("" : "+v"(lane));
+        const RT_CONSTANT TraceArgs *K = kernargs_here();
+        const uint32_t w = b * 64u + (uint32_t)lane;
+        const uint64_t in_pool = ballot(w < total);
+        int py_b = 0, pix_b = 0;
+        uint32_t pixel_b = 0, sample_b = 0;
+        entry_of(w, py_b, pixel_b, sample_b, pix_b); // (entries behind the pool's end: values nobody reads)
+        const int max_depth = K->max_depth;
+        if (max_depth <= 0) { // renderer.rs:48-55: no segment at all, every path of the batch is white and ends here
+            double one = 1.0;
+            asm volatile("" : "+v"(one));
+            if (__builtin_amdgcn_inverse_ballot_w64(in_pool)) {
+                atomicAdd(&L.sum[pix_b][0], one);
+                atomicAdd(&L.sum[pix_b][1], one);
+                atomicAdd(&L.sum[pix_b][2], one);
+            }
+            if (lane == 0) L.n_started += (uint32_t)__popcll(in_pool);
+            next += (uint32_t)__popcll(in_pool);
+            return;
+        }
+        const u4 bc = philox4x32(pixel_b, sample_b, RT_RNG_CAMERA, 0u, A.seed_lo, A.seed_hi);
+        // The 64 slots behind the ring's entries are free (the path loop sees to that: at most RING_SLOTS - 64 entries wait
+        // when a batch runs).  Lane l parks its camera sample in the l-th of them while the segment is traced — the registers
+        // are wanted there — and an entry that lives on moves it down to its place in the queue afterwards.
+        const uint32_t in_ring = min(b << 6, total) - next;
+        uint32_t park = ring_head + in_ring + (uint32_t)lane; // (head < RING_SLOTS, in_ring + lane < RING_SLOTS)
+        if (park >= RING_SLOTS) park -= RING_SLOTS;
+        d3 bo, bd;
+        {
+            const double v = div_by((double)py_b + u53(bc.a, bc.b), (double)(A.height - 1), K->inv_height_m1); // cpu.rs:39-40
+            double lx, ly; // (set and read with an aperture only; the empty asm "defines" them without a move)
+            asm volatile("" : "=v"(lx), "=v"(ly));
+            if (kernargs_here()->lens_lds != 0) { // camera.rs:327
+                lx = ly = 0.0;
+                uint32_t w_here = w;
+                asm volatile("" : "+v"(w_here)); // (the comparison anew: kept from above it is a bool turned back into a mask)
+                coop_random_in_unit_disk(w_here < total, pixel_b, sample_b, A.seed_lo, A.seed_hi, lane, L.scratch.req, lx, ly);
+                lx = lx * K->cam.lens_radius;
+                ly = ly * K->cam.lens_radius;
+                lens_ring[park][0] = lx;
+                lens_ring[park][1] = ly;
+            }
+            L.ring_v[park] = v;
+            camera_ray(pix_b, v, lx, ly, bo, bd);
+        }
+        // ---- the primary segment (renderer.rs:56-58)
+        double best_t = __builtin_inf();
+        int best = -1;
+        increment_masked(n_segments, in_pool);
+        closest_hit_rects<false>(A.prims, bo, bd, rcp3(bd), best_t, best);
+        // what the path adds to its pixel if it ends here (its throughput is 1): the background
+        // (background_color.rs:27-33 / :45-48), or what it hit
+        d3 C = ld3(L.bg_top);
+        if (kernargs_here()->bg.kind == RT_BG_SKY) {
+            const double t = 0.5 * (unit_fast(bd).y + 1.0);
+            C = (1.0 - t) * C + t * ld3(kernargs_here()->bg.bottom);
+        }
+        const uint64_t hit = in_pool & ballot(best >= 0);
+        int kind; // (set and read under `hit`)
+        asm volatile("" : "=v"(kind));
+        if (__builtin_amdgcn_inverse_ballot_w64(hit)) { // a light's emission, or a Lambertian's attenuation (which is all a path of depth 1 adds)
+            const Material &M = lds_prims[best].mat;
+            kind = M.kind;
+            C = ld3(M.color);
+        }
+        asm volatile("" : "+v"(kind));
+        // ends here: a miss, a light, or no depth left for a second segment (the scattered ray would come back white)
+        const uint64_t light = hit & ballot(kind == RT_MAT_DIFFUSE_LIGHT);
+        const uint64_t ends = kernargs_here()->max_depth <= 1 ? in_pool : (in_pool & ~hit) | light;
+        const uint64_t lives = in_pool & ~ends;
+        if (__builtin_amdgcn_inverse_ballot_w64(ends)) { // vec3.rs:38-42 Color::add into the pixel's sum
+            atomicAdd(&L.sum[pix_b][0], C.x);
+            atomicAdd(&L.sum[pix_b][1], C.y);
+            atomicAdd(&L.sum[pix_b][2], C.z);
+        }
+        if (lane == 0) L.n_started += (uint32_t)__popcll(in_pool);
+        // ---- the others queue up behind the ring's entries, in pool order: an entry's place is at or below where its
+        // lane parked (rank <= lane), and one wave's LDS accesses complete in order — every read below before any write
+        uint32_t slot = ring_head + in_ring + (uint32_t)lane_rank(lives);
+        if (slot >= RING_SLOTS) slot -= RING_SLOTS;
+        if (__builtin_amdgcn_inverse_ballot_w64(lives)) {
+            const double v = L.ring_v[park];
+            double lx, ly;
+            asm volatile("" : "=v"(lx), "=v"(ly));
+            if (kernargs_here()->lens_lds != 0) {
+                lx = lens_ring[park][0];
+                ly = lens_ring[park][1];
+            }
+            asm volatile("" ::: "memory"); // (the compiler keeps the reads above the writes)
+            L.ring_v[slot] = v;
+            L.ring_t[slot] = best_t;
+            L.ring_w[slot] = w;
+            L.ring_best[slot] = (uint16_t)best;
+            if (kernargs_here()->lens_lds != 0) {
+                lens_ring[slot][0] = lx;
+                lens_ring[slot][1] = ly;
+            }
+        }
+        next += (uint32_t)__popcll(ends); // `next` counts the entries that have left the pool: ended here, or handed out
         }
     };
 
@@ -907,6 +1155,152 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             seg = cand_base = 0;
             ray_time = fuzz = 0.0;
         }
+        // ---- the path loop of the PRETRACE variant, ROTATED: hand-out, shade the pending hits, sampler, new direction,
+        // trace, ends.  A lane leaves the trace block with its hit (`best`, `best_t`) or ended; the back edge sits between
+        // the trace block and the shading.  A lane that takes a ring entry gets the entry's primary hit in the same two
+        // registers, so it is shaded with the others, gets its sample and traces its SECOND segment in the iteration that
+        // hands it out: the loop traces no primary segment at all.  Across the sampler a lane holds what it holds in the
+        // other variants (`waiting`: o = the hit's point, d = its normal).
+        if constexpr (PRETRACE) {
+            double best_t = __builtin_inf(); // the pending hit of a lane with a path that is not `waiting`
+            int best = -1;
+            for (;;) {
+                // ---- camera batches: keep more than RING_SLOTS - 64 entries in the ring while the pool has any (a batch
+                // needs 64 free slots; the hand-out goes short only where more lanes are idle than that, at an item's start)
+                while (batches_done < n_batches && min(batches_done << 6, total) - next <= RING_SLOTS - 64u) pretrace_batch(batches_done++);
+                RT_REGION(1); // batches
+                // ---- hand ring entries to the lanes without a path (ballot + prefix count)
+                const uint32_t in_ring = min(batches_done << 6, total) - next;
+                if (in_ring != 0u) {
+                    const uint64_t idle = ~alive_m;
+                    const uint32_t r = (uint32_t)lane_rank(idle);
+                    uint32_t slot = ring_head + r; // (every lane reads a slot: the pixel comes by a lane shuffle)
+                    if (slot >= RING_SLOTS) slot -= RING_SLOTS;
+                    const uint32_t w = L.ring_w[slot];
+                    int s_off, pix_new;
+                    if (n_valid == 64) {
+                        pix_new = (int)(w & 63u);
+                        s_off = (int)(w >> 6);
+                    } else {
+                        s_off = (int)(w / (uint32_t)n_valid);
+                        pix_new = L.pix_of[(w - (uint32_t)s_off * (uint32_t)n_valid) & 63u];
+                    }
+                    const uint32_t pixel_new = (uint32_t)shfl_i((int)my_pixel, pix_new);
+                    const uint64_t taking = idle & ballot(r < in_ring);
+                    const uint32_t n_take = min((uint32_t)__popcll(idle), in_ring);
+                    next += n_take;
+                    ring_head += n_take;
+                    if (ring_head >= RING_SLOTS) ring_head -= RING_SLOTS;
+                    if (__builtin_amdgcn_inverse_ballot_w64(taking)) { // cpu.rs:39-40 + camera.rs:326-337, and the hit the batch found
+                        spix = pix_new;
+                        rng.pixel = pixel_new;
+                        rng.sample = (uint32_t)(smp0 + s_off);
+                        double lens_x, lens_y;
+                        asm volatile("" : "=v"(lens_x), "=v"(lens_y));
+                        if (kernargs_here()->lens_lds != 0) {
+                            lens_x = lens_ring[slot][0];
+                            lens_y = lens_ring[slot][1];
+                        }
+                        camera_ray(pix_new, L.ring_v[slot], lens_x, lens_y, o, d);
+                        best_t = L.ring_t[slot];
+                        best = (int)L.ring_best[slot];
+                        T = mk(1.0, 1.0, 1.0);
+                        seg = 0;
+                    }
+                    alive_m |= taking;
+                }
+                RT_REGION(2); // hand-out + primary ray
+                // (the loop ends when nothing is in flight: the ring is then empty and every batch drawn, so the pool is dry)
+                if (alive_m == 0) break;
+                uint64_t ended_m = 0;
+                // ---- shade the pending hits.  (The masks are ballots of per-lane data taken where the lanes are together: a
+                // mask assigned inside a divergent branch would live in a VGPR pair.)
+                const uint64_t hit_m = alive_m & ~waiting_m;
+                int kind; // material of the hit: set and read under hit_m
+                asm volatile("" : "=v"(kind));
+                if (__builtin_amdgcn_inverse_ballot_w64(hit_m)) {
+                    const Prim &P = lds_prims[best];
+                    const Material &M = P.mat;
+                    const Hit h = prim_hit_record<PRIMS, TEXTURED, true>(P, o, d, ray_time, best_t, 0, false);
+                    kind = M.kind;
+                    RT_REGION(8); // hit record
+                    T = T * ld3(M.color); // emission (the path ends) or attenuation: solid_color.rs:24-28
+                    RT_REGION(9); // texture, step 1
+                    // a light (diffuse_light.rs:25-37) ends the path, anything else is a Lambertian (lambertian.rs:26-38,
+                    // direction below); what a Lambertian hit sets is dead in a path that has ended
+                    o = h.point;
+                    cand_base = 0;
+                    d = h.normal; // the incoming direction is dead: lambertian.rs:27 starts from the normal
+                }
+                asm volatile("" : "+v"(kind));
+                const uint64_t light_m = hit_m & ballot(kind == RT_MAT_DIFFUSE_LIGHT);
+                ended_m |= light_m;
+                waiting_m |= hit_m & ~light_m;
+                RT_REGION(4); // material
+                // ---- the wave evaluates the open rejection loops together (all 64 lanes arrive here)
+                d3 sph = mk(0.0, 0.0, 0.0);
+                const uint64_t finish_m = coop_random_in_unit_sphere<2>(waiting_m, rng.pixel, rng.sample, seg, cand_base, A.seed_lo, A.seed_hi, lane,
+                                                                        L.scratch.sphere, sph);
+                waiting_m &= ~finish_m;
+                RT_REGION(5); // sampler
+                if (__builtin_amdgcn_inverse_ballot_w64(finish_m)) { // lambertian.rs:27-33
+                    const d3 dir = d + unit_fast(sph); // d holds the normal since the hit
+                    // vec3.rs:127-130 near_zero keeps the normal: once in 10^23 samples, so the wave branches around it
+                    const uint64_t near_zero = ballot(fabs(dir.x) < 1e-8) & ballot(fabs(dir.y) < 1e-8) & ballot(fabs(dir.z) < 1e-8);
+#ifndef RT_EXACT_DIV
+                    // (a rect's normal is +-1 on its axis and +0 on the others: rounding the negated unit sample to integers
+                    // gives it back exactly, so d takes the new direction in place — see the other variants' loop)
+                    d = dir;
+                    if (near_zero != 0) {
+                        asm volatile("; near_zero (keeps the compiler from turning the branch back into selects)");
+                        if ((near_zero >> lane) & 1ull) {
+                            const d3 u = unit_fast(sph);
+                            d = mk(rint(-u.x) + 0.0, rint(-u.y) + 0.0, rint(-u.z) + 0.0);
+                        }
+                    }
+#else
+                    const d3 normal = d;
+                    d = dir;
+                    if (near_zero != 0) {
+                        asm volatile("; near_zero (keeps the compiler from turning the branch back into selects)");
+                        if ((near_zero >> lane) & 1ull) d = normal;
+                    }
+#endif
+                }
+                // renderer.rs:48-55: the recursion's next level has depth 0 -> white
+                increment_masked(seg, finish_m);
+                const uint64_t deep_m = finish_m & ballot((int)seg >= A.max_depth);
+                ended_m |= deep_m;
+                // ---- the next segment of every lane that has its new ray
+                const uint64_t shooting = finish_m & ~deep_m;
+                RT_LANES(__popcll(shooting), next >= total);
+                best_t = __builtin_inf(); // closest hit, t in [0.001, inf) (renderer.rs:58)
+                best = -1;
+                if (__builtin_amdgcn_inverse_ballot_w64(shooting)) {
+                    ++n_segments;
+                    closest_hit_rects<true>(A.prims, o, d, rcp3(d), best_t, best);
+                    RT_REGION(3); // closest hit
+                }
+                const uint64_t miss_m = shooting & ballot(best < 0);
+                ended_m |= miss_m;
+                if (__builtin_amdgcn_inverse_ballot_w64(miss_m)) { // background_color.rs:27-33 / :45-48
+                    const RT_CONSTANT TraceArgs *K = kernargs_here();
+                    d3 bgc = ld3(K->bg.top);
+                    if (K->bg.kind == RT_BG_SKY) {
+                        const double t = 0.5 * (unit_fast(d).y + 1.0);
+                        bgc = (1.0 - t) * bgc + t * ld3(K->bg.bottom);
+                    }
+                    T = T * bgc;
+                }
+                if (__builtin_amdgcn_inverse_ballot_w64(ended_m)) { // vec3.rs:38-42 Color::add into the pixel's sum
+                    atomicAdd(&L.sum[spix][0], T.x);
+                    atomicAdd(&L.sum[spix][1], T.y);
+                    atomicAdd(&L.sum[spix][2], T.z);
+                }
+                alive_m &= ~ended_m;
+                RT_REGION(6); // scatter + accumulate
+            }
+        } else
         // ---- the path loop: until the pool runs dry or the draining item's last path ends
         for (;;) {
         // ---- camera samples for the entries about to leave the pool (whole wave, see above)
@@ -1321,6 +1715,11 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) total_segments += __shfl_down(total_segments, off, 64);
     if (lane == 0 && total_segments) atomicAdd(A.segments + RT_STAT_SEGMENTS, total_segments);
+    if constexpr (PRETRACE) {
+        int first = lane_of_wave;
+        asm volatile("" : "+v"(first));
+        n_started = first == 0 ? L.n_started : 0u;
+    }
     unsigned long long started = n_started; // primary rays (RtRenderStats.samples)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) started += __shfl_down(started, off, 64);
