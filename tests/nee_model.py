@@ -6,9 +6,13 @@ orc_rng_double, orc_rng_triple): with no light listed the model IS the plain est
 to orc.render.  On top of that it takes the light sample of the contract at every eligible Lambertian vertex and
 weights both terms by multiple importance sampling.
 
-Scope: untransformed rects and spheres, moving spheres, Lambertian, Metal, Dielectric and DiffuseLight, any texture the
-oracle evaluates.  The hit primitive is found by its obj_id, so a scene given to the model has unique obj_ids.  Scalar
-Python over (pixel, sample): meant for frames of a few thousand samples.
+Scope: whatever the oracle's linear closest hit takes (rects, spheres, moving spheres, boxes, Translate and RotateY
+wrappers, the lens, any texture it evaluates, on a light too), Lambertian, Metal, Dielectric and DiffuseLight; listed
+lights are plain spheres and rects of any axis.  tests/test_nee_cpu.py verifies it on cornell_box, three_balls,
+mixed_scene and the scene of every kernel form (tests/variant_scenes.py), with and without `light2`: lights off it is
+orc.render to 1e-12 with the same segments, and with several lights of every kind its mean is the plain mean.  The hit
+primitive is found by its obj_id, so a scene given to the model has unique obj_ids.  Scalar Python over (pixel, sample):
+meant for frames of a few thousand samples.
 """
 import ctypes as C
 import math

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import nee_model as NM
+import nee_variant_frames as F
 import scenes_py as S
 import variant_scenes as V
 
@@ -244,3 +245,44 @@ def test_every_variant_of_the_nee_kernel_matches_the_oracle(rt, orc, abi, gpu, f
     assert share < 1e-3, "share of values beyond 1e-9: %g" % share   # (a cap: the oracle against itself has share 0)
     assert got.std() > 0.05   # a picture, not a flat background
     assert abs(segments - ref_segments) <= 4, (segments, ref_segments)
+
+
+# ---- ... and with lights listed ------------------------------------------------------------------------------------------
+# Listing a light makes other branches of the same function live: the pick among several lights, the pdf and the sample of
+# every rect axis and of a sphere, the shadow ray, both MIS heuristics.  tests/nee_model.py is verified on these scenes by
+# tests/test_nee_cpu.py (lights off it is the oracle, its mean is the plain mean, and the frames below move with the lights).
+
+@pytest.mark.parametrize("flavour", ["fast", "exact"])
+@pytest.mark.parametrize("form", list(V.SPECS), ids=lambda f: "%s%s%s%s" % ("RSA"[f[0]], "t" * f[1], "s" * f[2], "-bvh" * f[3]))
+def test_every_variant_of_the_nee_kernel_matches_the_model(rt, orc, abi, gpu, form, flavour):
+    """Each form's scene with `light2` (XZ, YZ and XY rect lights, two sphere lights, as the class allows) still selects
+    its form, lists the model's lights, and k_nee_f64 renders the model's frame under the power heuristic, under the
+    balance heuristic, and with the list capped at one light at max_depth 2 (only the first vertex samples a light): the
+    parity tolerance each time, a picture, and the model's path segments to within 4 (shadow rays are not counted)."""
+    prims_class, textured, specular, bvh = form
+    bundle, camera = F.case(abi, form)
+    scene = rt.Scene(bundle, closest_hit=abi.RT_HIT_BVH if bvh else abi.RT_HIT_LINEAR,
+                     arithmetic=abi.RT_ARITH_REFERENCE if flavour == "exact" else abi.RT_ARITH_FAST)
+    got = []
+    try:
+        variant = scene.variant()
+        lights = scene.lights()
+        for heuristic, max_lights, depth in F.RENDERS:
+            frame = scene.render_frame_nee(camera, F.params(abi, depth), max_lights=max_lights, heuristic=heuristic)
+            got.append((frame, int(scene.last_stats().segments)))
+    finally:
+        scene.close()
+    want = dict(prims_class=prims_class, textured=textured, specular=specular, use_bvh=bvh, exact=int(flavour == "exact"))
+    assert {k: variant[k] for k in want} == want
+    assert lights == NM.light_list(bundle.desc) and len(lights) == F.N_LIGHTS[prims_class]
+    refs = [F.model_frame(orc, abi, form, *r) for r in F.RENDERS]
+    for (heuristic, max_lights, depth), (frame, segments), (ref, ref_segments) in zip(F.RENDERS, got, refs):
+        d = np.abs(frame - ref)
+        print("%s %s %s max_lights %d depth %d: max |delta| = %.3g, share beyond 1e-9 = %.3g, std = %.3g, segments %d (model %d)"
+              % (form, flavour, "balance" if heuristic == NM.BALANCE else "power", max_lights, depth, d.max(),
+                 float((d.max(axis=2) > 1e-9).mean()), frame.std(), segments, ref_segments))
+    for (frame, segments), (ref, ref_segments) in zip(got, refs):
+        assert np.isfinite(frame).all()
+        _parity(frame, ref)
+        assert frame.std() > 0.05   # a picture, not a flat background
+        assert abs(segments - ref_segments) <= 4, (segments, ref_segments)

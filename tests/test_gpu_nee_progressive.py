@@ -87,21 +87,24 @@ def test_nothing_listed_is_the_plain_estimator_in_passes(rt, orc, abi, gpu):
 @pytest.mark.parametrize("flavour", ["fast", "exact"])
 @pytest.mark.parametrize("form", sorted(V.SPECS), ids=lambda f: "p%d-t%d-s%d-b%d" % f)
 def test_every_variant_ends_on_the_one_shot_frame(rt, abi, gpu, form, flavour):
-    # (the forms' scenes list no light: the estimator's plain branch through every instantiation of the pass kernel; the
-    # light-sampling branch of the rect, sphere, any-primitive and BVH forms is section 1's)
-    bundle, cam = V.build(form)
-    c = S.camera_for(cam, V.W, V.H)
-    p = abi.render_params(V.W, V.H, 48, max_depth=V.DEPTH)
-    scene = rt.Scene(bundle, closest_hit=abi.RT_HIT_BVH if form[3] else abi.RT_HIT_LINEAR,
-                     arithmetic=abi.RT_ARITH_REFERENCE if flavour == "exact" else abi.RT_ARITH_FAST)
-    try:
-        v = scene.variant()
-        assert (v["prims_class"], v["textured"], v["specular"], v["use_bvh"]) == form
-        want = scene.render_frame_nee(c, p)
-        frames = scene.render_progressive_nee(c, p, 10)
-        assert len(frames) > 1 and np.array_equal(frames[-1][1], want)
-    finally:
-        scene.close()
+    # (every form's scene lists a light, so the light-sampling branch runs in every instantiation of the pass kernel; with
+    # `light2` it lists several, of every rect axis and of spheres as the class allows.  The one-shot frame itself is held
+    # to the model in tests/test_gpu_nee.py)
+    for light2 in (False, True):
+        bundle, cam = V.build(form, light2=light2)
+        c = S.camera_for(cam, V.W, V.H)
+        p = abi.render_params(V.W, V.H, 48, max_depth=V.DEPTH)
+        scene = rt.Scene(bundle, closest_hit=abi.RT_HIT_BVH if form[3] else abi.RT_HIT_LINEAR,
+                         arithmetic=abi.RT_ARITH_REFERENCE if flavour == "exact" else abi.RT_ARITH_FAST)
+        try:
+            v = scene.variant()
+            assert (v["prims_class"], v["textured"], v["specular"], v["use_bvh"]) == form
+            assert scene.lights() and (len(scene.lights()) > 1) == light2
+            want = scene.render_frame_nee(c, p)
+            frames = scene.render_progressive_nee(c, p, 10)
+            assert len(frames) > 1 and np.array_equal(frames[-1][1], want)
+        finally:
+            scene.close()
 
 
 # ---- 3. / 4. adaptive off, and a huge threshold ----------------------------------------------------------------------

@@ -125,17 +125,20 @@ def test_sample_counts_around_the_chunk_length(rt, abi, gpu, flavour):
 @pytest.mark.parametrize("flavour", ["fast", "exact"])
 @pytest.mark.parametrize("form", sorted(V.SPECS), ids=lambda f: "p%d-t%d-s%d-b%d" % f)
 def test_every_variant_streams_the_one_shot_frame(rt, abi, gpu, form, flavour):
-    bundle, cam = V.build(form)
-    c = S.camera_for(cam, V.W, V.H)
-    p = abi.render_params(V.W, V.H, 40, max_depth=V.DEPTH, tiles_w=3, tiles_h=2)
-    scene = rt.Scene(bundle, closest_hit=abi.RT_HIT_BVH if form[3] else abi.RT_HIT_LINEAR,
-                     arithmetic=abi.RT_ARITH_REFERENCE if flavour == "exact" else abi.RT_ARITH_FAST)
-    try:
-        v = scene.variant()
-        assert (v["prims_class"], v["textured"], v["specular"], v["use_bvh"]) == form
-        _check_stream(scene, c, p)
-    finally:
-        scene.close()
+    # (the plain scene lists one light; with `light2` several, of every rect axis and of spheres as the class allows)
+    for light2 in (False, True):
+        bundle, cam = V.build(form, light2=light2)
+        c = S.camera_for(cam, V.W, V.H)
+        p = abi.render_params(V.W, V.H, 40, max_depth=V.DEPTH, tiles_w=3, tiles_h=2)
+        scene = rt.Scene(bundle, closest_hit=abi.RT_HIT_BVH if form[3] else abi.RT_HIT_LINEAR,
+                         arithmetic=abi.RT_ARITH_REFERENCE if flavour == "exact" else abi.RT_ARITH_FAST)
+        try:
+            v = scene.variant()
+            assert (v["prims_class"], v["textured"], v["specular"], v["use_bvh"]) == form
+            assert scene.lights() and (len(scene.lights()) > 1) == light2
+            _check_stream(scene, c, p)
+        finally:
+            scene.close()
 
 
 # ---- 5. determinism ----------------------------------------------------------------------------------------------------------

@@ -12,6 +12,8 @@ code for it (a pairwise design, not a full product):
   metal fuzz   0 / > 0, a Dielectric (on spheres with a negative-radius shell)
   wrappers     Translate and RotateY on a sphere and on a rect (the `flags` that send a rect to PRIMS_ANY)
   background   sky / solid
+  light2       off in every spec; build(form, light2=True) adds plain YZ and XY rect lights and a second sphere light,
+               for the next-event-estimation tests (a pick among several lights, every rect axis)
 `probes` names the features a scene is there to exercise and the value that turns each off: the oracle must see the
 difference (test_variant_matrix.py: sensitivity), so a GPU case would fail if the kernel's arm for it were wrong.
 """
@@ -105,7 +107,7 @@ def build(form, **override):
     """-> (SceneBundle, camera dict) of the form's spec, with `override` applied to the spec's features."""
     prims_class, textured, specular, bvh = form
     f = dict(lens=False, bg="sky", moving=False, perlin=None, image=False, noise_light=False,
-             fuzz=None, shell=False, wrap=False, metal=True, dielectric=True)
+             fuzz=None, shell=False, wrap=False, metal=True, dielectric=True, light2=False)
     f.update({k: v for k, v in SPECS[form].items() if k != "probes"})
     f.update(override)
     T = _Tables()
@@ -182,6 +184,17 @@ def build(form, **override):
             for i in range(12):  # a few more, so that the tree has some depth
                 a = 2.0 * math.pi * i / 12
                 prims.append(abi.sphere((3.2 * math.cos(a), 0.2, -1.0 + 2.2 * math.sin(a)), 0.2, (mat_red, mat_blue, mat_grey)[i % 3]))
+    if f["light2"]:
+        # more listed lights, plain and unwrapped so that the form stays its own: the YZ and XY arms of the rect
+        # light's pdf and sample (the scenes' own rect light is XZ), and a pick among several (p_pick < 1)
+        if prims_class == RECTS:
+            prims += [abi.rect(abi.RT_PRIM_YZ_RECT, 0.4, 1.6, -0.6, 0.6, 2.4, mat_light),
+                      abi.rect(abi.RT_PRIM_XY_RECT, -2.4, -1.4, 0.3, 1.3, -1.9, mat_light)]
+        if prims_class == ANY:
+            prims += [abi.rect(abi.RT_PRIM_YZ_RECT, 0.4, 1.6, -0.6, 0.6, 3.4, mat_light),
+                      abi.rect(abi.RT_PRIM_XY_RECT, -2.4, -1.4, 0.3, 1.3, -2.4, mat_light)]
+        if prims_class != RECTS:
+            prims.append(abi.sphere((-2.4, 1.8, 0.6), 0.3, mat_light))
     for i, p in enumerate(prims):
         p.obj_id = i + 1
     bg = abi.sky() if f["bg"] == "sky" else abi.solid_background((0.35, 0.3, 0.4))
