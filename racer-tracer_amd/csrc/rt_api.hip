@@ -19,6 +19,7 @@
 #include <thread>
 #include <chrono>
 #include "rt_bvh.h"
+#include "rt_primary_bounds.h"
 #include "rt_scene.h"
 
 extern "C" hipError_t rtdev_launch_post_rgba8(const RtToneMap *tm, const double *rgb, size_t n_pixels, uint8_t *rgba,
@@ -394,6 +395,13 @@ int fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtde
         a.sum_scale = ldexp(1.0, 52 - e);
         a.sum_unscale = ldexp(1.0, e - 52);
     }
+    // the pixels whose camera rays can hit anything (rt_primary_bounds.h), from this call's camera: nothing is kept between calls
+    const rtdev::PixelRect seen = rtdev::primary_bounds(a.cam.origin, a.cam.ulc, a.cam.horizontal, a.cam.vertical, a.cam.lens_radius,
+                                                        a.width, a.height, s->box_mn, s->box_mx);
+    a.cull_px0 = seen.px0;
+    a.cull_px1 = seen.px1;
+    a.cull_py0 = seen.py0;
+    a.cull_py1 = seen.py1;
 #ifdef RT_DEVELOPER_KNOBS // throw-away kernel knobs of the developer build (tools/perf_ab.sh)
     for (int k = 0; k < 4; ++k) {
         char name[16];
@@ -1127,6 +1135,14 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
     s->textured = sel.textured;
     s->specular = sel.specular;
     s->has_moving = sel.has_moving;
+    for (int i = 0; i < d->n_primitives; ++i) { // the scene's box (RtScene.box_mn; a NaN bound stays: it turns the cull off)
+        double mn[3], mx[3];
+        rtdev::primitive_bounds(d->primitives[i], mn, mx);
+        for (int k = 0; k < 3; ++k) { // (std::fmin would drop a NaN)
+            if (i == 0 || std::isnan(mn[k]) || mn[k] < s->box_mn[k]) s->box_mn[k] = std::isnan(s->box_mn[k]) && i > 0 ? s->box_mn[k] : mn[k];
+            if (i == 0 || std::isnan(mx[k]) || mx[k] > s->box_mx[k]) s->box_mx[k] = std::isnan(s->box_mx[k]) && i > 0 ? s->box_mx[k] : mx[k];
+        }
+    }
     // The linear loop costs ~35 VALU instructions per primitive with scalar loads and
     // no divergence; the BVH walk ~25 node visits plus leaf tests with per-lane loads.
     // They cross at a few dozen primitives (clown.yml, 23 spheres, is still linear).

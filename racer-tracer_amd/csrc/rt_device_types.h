@@ -254,8 +254,12 @@ struct TraceArgs {
     int32_t dbg[4];        // developer knobs (env RT_DBG0..3), 0 in production
     // TILE LIST (rt_render_adaptive, one-region launches only): NULL — every launch but the adaptive passes — or the
     // n_list tiles (indices into the tiles_x-wide grid) this launch traces, in any order: item = chunk * n_list + slot,
-    // tile = tile_list[slot].  (Last in the block, so that no other field moves.)
+    // tile = tile_list[slot].  (Behind everything older, so that no other field moves.)
     const uint32_t *tile_list;
+    // PRIMARY BOUNDS (rt_primary_bounds.h; rt_api.hip: fill_args, on every render): a pixel outside the inclusive rectangle
+    // [cull_px0, cull_px1] x [cull_py0, cull_py1] has no camera ray that can hit a primitive.  The whole frame when the host
+    // cannot tell.  (Appended, for the same reason.)
+    int32_t cull_px0, cull_px1, cull_py0, cull_py1;
 };
 
 // The light list of an NEE launch (rt_nee.hip; rt_nee_kernel.hip: k_nee_f64, rt_nee_pass_kernel.hip: k_nee_pass_f64): slot[i] = the list index of

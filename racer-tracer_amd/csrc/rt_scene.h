@@ -249,6 +249,9 @@ struct RtScene {
     double radiance_bound = 0.0;
     int specular = 0; // some material is Metal or Dielectric
     int has_moving = 0; // some primitive is a MovingSphere (the only reader of a ray's time)
+    // union of the primitives' bounds (rt_bvh.h: primitive_bounds), for the pixel rectangle camera rays can hit anything
+    // in (rt_primary_bounds.h); empty (mn > mx) for a scene without primitives
+    double box_mn[3] = {1.0, 1.0, 1.0}, box_mx[3] = {-1.0, -1.0, -1.0};
 
     // closest hit: linear loop for small scenes, skip-link BVH (rt_bvh.h) above kBvhThreshold primitives
     int use_bvh = 0;

@@ -849,22 +849,40 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         my_pixel = (uint32_t)my_py * (uint32_t)A.width + (uint32_t)my_px;
         const uint64_t valid_mask = ballot(my_valid);
         n_valid = __popcll(valid_mask);
-        {
-            uint32_t pixel_stream = RT_RNG_SAMPLE_PIXEL;
-            // (opaque where the path loop leaves no register to spare: the products of the block's constant words would
-            // otherwise be formed in front of the loops and parked in scratch memory across them)
-            if constexpr (PRETRACE) asm volatile("" : "+s"(pixel_stream));
-            PathRng prng{my_pixel, pixel_stream, A.seed_lo, A.seed_hi};
-            u4 bj = prng.block(0, RT_RNG_PIXEL, 0);
+        // ITEMS NO CAMERA RAY CAN HIT (PRETRACE).  The host bounds the pixels whose camera rays can reach a primitive
+        // (TraceArgs.cull_px0..; rt_primary_bounds.h).  In an item without such a pixel every path is one segment that misses:
+        // with a solid background each of its n_smp samples adds `top` to its pixel, which is all the item's batches would
+        // do — a Philox block, a ray, six rect tests and three LDS adds per sample.  So the item takes none of them: its sums
+        // are formed below by the batches' own LDS additions (n_smp equal terms onto +0.0: no order to keep; NOT a
+        // multiplication, which rounds once), the counters grow as the batches count, and its pool is empty, like that of an
+        // item without a pixel: the outer loop goes from here to finish_item.
+        // A sky background depends on the ray, and max_depth <= 0 ends every path white without a segment: the batches.
+        bool culled = false;
+        if constexpr (PRETRACE) {
             const RT_CONSTANT TraceArgs *K = kernargs_here();
-            const double u = div_by((double)my_px + u53(bj.a, bj.b), (double)(A.width - 1), K->inv_width_m1); // cpu.rs:35-36
-            if constexpr (OVERLAP || PRETRACE) {
-                L.u[lane] = u;
-            } else {
-                const d3 base = ld3(K->cam.ulc) + u * ld3(K->cam.horizontal); // camera.rs:331, first two terms
-                L.base[lane][0] = base.x;
-                L.base[lane][1] = base.y;
-                L.base[lane][2] = base.z;
+            // (four comparisons ANDed in the scalar unit: written with && they are four nested branches)
+            const int x0 = K->cull_px0, x1 = K->cull_px1, y0 = K->cull_py0, y1 = K->cull_py1;
+            const uint64_t seen = valid_mask & ballot(my_px >= x0) & ballot(my_px <= x1) & ballot(my_py >= y0) & ballot(my_py <= y1);
+            culled = seen == 0ull && K->bg.kind != RT_BG_SKY && K->max_depth >= 1;
+        }
+        {
+            if (!culled) { // (a culled item forms no ray)
+                uint32_t pixel_stream = RT_RNG_SAMPLE_PIXEL;
+                // (opaque where the path loop leaves no register to spare: the products of the block's constant words would
+                // otherwise be formed in front of the loops and parked in scratch memory across them)
+                if constexpr (PRETRACE) asm volatile("" : "+s"(pixel_stream));
+                PathRng prng{my_pixel, pixel_stream, A.seed_lo, A.seed_hi};
+                u4 bj = prng.block(0, RT_RNG_PIXEL, 0);
+                const RT_CONSTANT TraceArgs *K = kernargs_here();
+                const double u = div_by((double)my_px + u53(bj.a, bj.b), (double)(A.width - 1), K->inv_width_m1); // cpu.rs:35-36
+                if constexpr (OVERLAP || PRETRACE) {
+                    L.u[lane] = u;
+                } else {
+                    const d3 base = ld3(K->cam.ulc) + u * ld3(K->cam.horizontal); // camera.rs:331, first two terms
+                    L.base[lane][0] = base.x;
+                    L.base[lane][1] = base.y;
+                    L.base[lane][2] = base.z;
+                }
             }
             // fixed-point sums: a sample arrives as the bit pattern of (T * scale + 2^52), i.e. 0x433 << 52 plus the
             // integer; the n_smp patterns' exponent fields are taken off here, once, instead of masked off every sample
@@ -877,8 +895,22 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             if (my_valid) L.pix_of[lane_rank(valid_mask)] = lane;
             if (lane == 0) L.info[cur] = ItemInfo{(int)chunk, tx, ty, tile_py0, region, (int)reg_tiles, rows_aligned ? 1 : 0, 0};
         }
+        if constexpr (PRETRACE) {
+            if (culled) {
+                const d3 bg = ld3(L.bg_top);
+                if (bg.x != 0.0 || bg.y != 0.0 || bg.z != 0.0) // (wave-uniform; a black background leaves the sums at +0.0)
+                    // (addressed by the kernel's own lane index: by the opaque copy, the zero stores above got a 64-bit address)
+                    for (int k = 0; k < n_smp; ++k) { // vec3.rs:38-42 Color::add, once per sample
+                        atomicAdd(&L.sum[lane_of_wave][0], bg.x);
+                        atomicAdd(&L.sum[lane_of_wave][1], bg.y);
+                        atomicAdd(&L.sum[lane_of_wave][2], bg.z);
+                    }
+                if (__builtin_amdgcn_inverse_ballot_w64(valid_mask)) n_segments += (unsigned int)n_smp; // one primary segment per path
+                if (lane == 0) L.n_started += (uint32_t)n_valid * (uint32_t)n_smp;
+            }
+        }
         if (!rows_aligned) tile_py0 = -1;
-        total = (uint32_t)n_valid * (uint32_t)n_smp; // paths in this item's pool
+        total = culled ? 0u : (uint32_t)n_valid * (uint32_t)n_smp; // paths in this item's pool
         next = 0;
         n_batches = (total + 63u) >> 6;
         batches_done = 0;
