@@ -402,6 +402,8 @@ int fill_args(const RtScene *s, const RtCamera *c, const RtRenderParams *p, rtde
     a.cull_px1 = seen.px1;
     a.cull_py0 = seen.py0;
     a.cull_py1 = seen.py1;
+    a.bg_black = rtdev::background_is_black(a.bg);
+    static_assert(RT_BG_SOLID == 1, "rt_device_types.h: background_is_black");
 #ifdef RT_DEVELOPER_KNOBS // throw-away kernel knobs of the developer build (tools/perf_ab.sh)
     for (int k = 0; k < 4; ++k) {
         char name[16];

@@ -260,7 +260,17 @@ struct TraceArgs {
     // [cull_px0, cull_px1] x [cull_py0, cull_py1] has no camera ray that can hit a primitive.  The whole frame when the host
     // cannot tell.  (Appended, for the same reason.)
     int32_t cull_px0, cull_px1, cull_py0, cull_py1;
+    // BLACK BACKGROUND (background_is_black below; fill_args, on every render): the background is solid and its three
+    // components compare equal to 0.0.  A path that leaves the scene then adds +-0.0 to its pixel, which changes no sum:
+    // the path loop of the rects-only plain variant leaves that addition out.  (Appended, for the same reason.)
+    int32_t bg_black;
 };
+
+// TraceArgs.bg_black of a background: solid (include/rt_abi.h: RT_BG_SOLID = 1), and every component of its colour
+// compares equal to 0.0 (+0.0 or -0.0; a denormal, a NaN or a sky does not).
+inline int32_t background_is_black(const Background &bg) {
+    return bg.kind == 1 && bg.top[0] == 0.0 && bg.top[1] == 0.0 && bg.top[2] == 0.0 ? 1 : 0;
+}
 
 // The light list of an NEE launch (rt_nee.hip; rt_nee_kernel.hip: k_nee_f64, rt_nee_pass_kernel.hip: k_nee_pass_f64): slot[i] = the list index of
 // device primitive i, or -1; prim[k] = the device primitive of light k.  Light k is sampled when k < n_lights.

@@ -1262,7 +1262,28 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                     // direction below); what a Lambertian hit sets is dead in a path that has ended
                     o = h.point;
                     cand_base = 0;
-                    d = h.normal; // the incoming direction is dead: lambertian.rs:27 starts from the normal
+                    // the incoming direction is dead: lambertian.rs:27 starts from the normal
+#ifndef RT_EXACT_DIV
+                    // h.normal (set_face_normal_axis: +-1.0 against the ray on the rect's axis, +0.0 on the others), formed IN
+                    // d's registers.  Its three low words are zeros, and given one zero the compiler keeps it in a register of
+                    // its own across the loop and pairs it with each high word somewhere else: two v_mov_b64 per iteration to
+                    // bring the pairs to d.  Three opaque zeros are three v_mov_b32 into d's own low words.
+                    {
+                        const int axis = P.kind == RT_PRIM_XY_RECT ? 2 : (P.kind == RT_PRIM_XZ_RECT ? 1 : 0); // (prim_hit_record's)
+                        auto against = [](double dk, bool on_axis) { // on the axis +1.0 for dk < 0, -1.0 for dk > 0; else +0.0
+                            uint32_t lo = 0u;
+                            asm volatile("" : "+v"(lo));
+                            const uint32_t hi = on_axis ? 0xBFF00000u ^ ((uint32_t)((unsigned long long)__double_as_longlong(dk) >> 32) & 0x80000000u) : 0u;
+                            return __longlong_as_double((long long)((unsigned long long)hi << 32 | lo));
+                        };
+                        // (two comparisons: a rect that is neither XY nor XZ is YZ, which the scalar unit works out of the two masks)
+                        const uint64_t xy_m = ballot(axis == 2), xz_m = ballot(axis == 1);
+                        d = mk(against(d.x, __builtin_amdgcn_inverse_ballot_w64(~(xy_m | xz_m))), against(d.y, __builtin_amdgcn_inverse_ballot_w64(xz_m)),
+                               against(d.z, __builtin_amdgcn_inverse_ballot_w64(xy_m)));
+                    }
+#else
+                    d = h.normal;
+#endif
                 }
                 asm volatile("" : "+v"(kind));
                 const uint64_t light_m = hit_m & ballot(kind == RT_MAT_DIFFUSE_LIGHT);
@@ -1306,25 +1327,42 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 // ---- the next segment of every lane that has its new ray
                 const uint64_t shooting = finish_m & ~deep_m;
                 RT_LANES(__popcll(shooting), next >= total);
-                best_t = __builtin_inf(); // closest hit, t in [0.001, inf) (renderer.rs:58)
-                best = -1;
+                // (the pending hit is dead here — a lane that does not shoot is `waiting`, ended or idle, and none of those reads
+                // it before it is set again — and saying so costs no instruction: set to "no hit" out here, for every lane,
+                // the three moves were issued twice, here and again in front of the closest-hit loop)
+                asm volatile("" : "=v"(best_t), "=v"(best));
                 if (__builtin_amdgcn_inverse_ballot_w64(shooting)) {
+                    best_t = __builtin_inf(); // closest hit, t in [0.001, inf) (renderer.rs:58)
+                    best = -1;
                     ++n_segments;
                     closest_hit_rects<true>(A.prims, o, d, rcp3(d), best_t, best);
                     RT_REGION(3); // closest hit
                 }
                 const uint64_t miss_m = shooting & ballot(best < 0);
+                // A BLACK BACKGROUND (TraceArgs.bg_black: solid, every component == 0.0) costs the loop nothing: a lane that
+                // leaves the scene ends, and its segment is counted, but it forms no product and takes no part in the
+                // additions below.  Exact: its terms would be T * (+-0.0) = +-0.0 (T is finite: a product of colours), a sum
+                // starts at +0.0, and round-to-nearest never makes -0.0 of +0.0 plus anything — so a sum is never -0.0, and
+                // x + (+-0.0) is x for every x a sum can hold.
+                uint64_t adding_m = ended_m; // the ended lanes that have something to add
                 ended_m |= miss_m;
-                if (__builtin_amdgcn_inverse_ballot_w64(miss_m)) { // background_color.rs:27-33 / :45-48
+                if (kernargs_here()->bg_black == 0) {
+                    adding_m = ended_m;
                     const RT_CONSTANT TraceArgs *K = kernargs_here();
-                    d3 bgc = ld3(K->bg.top);
-                    if (K->bg.kind == RT_BG_SKY) {
-                        const double t = 0.5 * (unit_fast(d).y + 1.0);
-                        bgc = (1.0 - t) * bgc + t * ld3(K->bg.bottom);
+                    // (the two kinds as two lane masks, one of them empty: as the arms of a wave-uniform if / else they meet in
+                    // temporaries, with copies in front of either arm and behind both)
+                    const uint64_t sky_m = K->bg.kind == RT_BG_SKY ? miss_m : 0ull;
+                    if (__builtin_amdgcn_inverse_ballot_w64(miss_m & ~sky_m)) { // background_color.rs:45-48
+                        T.x = T.x * K->bg.top[0]; // (the colour as the scalar operand of each product: no copy of it is made)
+                        T.y = T.y * K->bg.top[1];
+                        T.z = T.z * K->bg.top[2];
                     }
-                    T = T * bgc;
+                    if (__builtin_amdgcn_inverse_ballot_w64(sky_m)) { // background_color.rs:27-33
+                        const double t = 0.5 * (unit_fast(d).y + 1.0);
+                        T = T * ((1.0 - t) * ld3(K->bg.top) + t * ld3(K->bg.bottom));
+                    }
                 }
-                if (__builtin_amdgcn_inverse_ballot_w64(ended_m)) { // vec3.rs:38-42 Color::add into the pixel's sum
+                if (__builtin_amdgcn_inverse_ballot_w64(adding_m)) { // vec3.rs:38-42 Color::add into the pixel's sum
                     atomicAdd(&L.sum[spix][0], T.x);
                     atomicAdd(&L.sum[spix][1], T.y);
                     atomicAdd(&L.sum[spix][2], T.z);
