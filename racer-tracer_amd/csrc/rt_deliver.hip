@@ -461,21 +461,6 @@ int rtapi::check_scenes(RtScene *const *scenes, int n) {
     return RT_OK;
 }
 
-int rtapi::deal_strips(const RtRenderParams *p, int n, int &strip_rows, std::vector<RtRenderParams> &params) {
-    if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "params->strip_* must be unset: the call assigns strips itself");
-    if (p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, "the preview scale cannot be combined with strips");
-    if (strip_rows < 0) return fail(RT_ERR_INVALID_ARGUMENT, "strip_rows must not be negative");
-    if (strip_rows == 0) strip_rows = 8;
-    params.assign((size_t)n, *p);
-    if (n > 1)
-        for (int i = 0; i < n; ++i) {
-            params[(size_t)i].strip_rows = strip_rows;
-            params[(size_t)i].strip_count = n;
-            params[(size_t)i].strip_index = i;
-        }
-    return RT_OK;
-}
-
 extern "C" {
 
 int rt_render_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p, double *out_rgb) {

@@ -188,7 +188,7 @@ struct TraceArgs {
     int32_t chunk_base;          // index of this launch's first chunk in `partial`
     int32_t chunk_samples;       // samples per full-length chunk (informational; the kernel reads chunk_start)
     // Chunk c of the frame covers the samples [chunk_start[c], chunk_start[c + 1]): full-length chunks first, then a
-    // taper of ever shorter ones, so that the last items of a launch are small (rt_api.hip: chunk_plan).
+    // taper of ever shorter ones, so that the last items of a launch are small (rt_plan.cpp: chunk_plan).
     int32_t chunk_start[RT_MAX_CHUNKS + 1];
     int32_t tiles_x, n_tiles;    // 8x8 tiles over width x owned_rows
     // cpu.rs:36,40 divide by (W-1) and (H-1); the pooled kernel multiplies by these
@@ -245,7 +245,7 @@ struct TraceArgs {
     // price is an ABSOLUTE quantum of 2^-k per sample where a double has a relative one: a pixel whose radiance is of that
     // order — black, for every purpose — comes out up to sqrt(2^-(k+1)) (4e-8 for E = 15: k = 48) from the f64 sum's
     // value.  So the host uses these sums only while that stays within half the 1e-3 tolerance: k = 52 - e with
-    // E < 2^30 and e <= 31 (rt_api.hip: sum_exponent; 4.9e-4).  A brighter scene is rendered by the RT_ARITH_REFERENCE
+    // E < 2^30 and e <= 31 (rt_plan.cpp: sum_exponent; 4.9e-4).  A brighter scene is rendered by the RT_ARITH_REFERENCE
     // copy, and a render whose chunks would take e past 31 is refused (RT_ERR_UNSUPPORTED).
     // The other variants, and every RT_ARITH_REFERENCE kernel, add doubles in the order the samples finish, one item at a time.
     double sum_scale, sum_unscale;

@@ -1,6 +1,7 @@
-// rt_nee.hip — next-event estimation: the scene's light list and the entry points rt_render_frame_nee,
-// rt_render_frame_nee_device, rt_scene_lights and rt_light_sampling_params_default (include/rt_abi.h).  The kernel is
-// rt_nee_kernel.hip's k_nee_f64, compiled in both arithmetic flavours; a scene uses its own (RtScene.kernels).
+// rt_nee.hip — next-event estimation: the upload of the scene's light list (rt_plan.cpp: light_tables) and
+// the entry points rt_render_frame_nee, rt_render_frame_nee_device, rt_scene_lights and rt_light_sampling_params_default
+// (include/rt_abi.h).  The kernel is rt_nee_kernel.hip's k_nee_f64, compiled in both arithmetic flavours; a scene uses its
+// own (RtScene.kernels).
 #include "rt_scene.h"
 
 #include <algorithm>
@@ -8,22 +9,7 @@
 #include <string>
 
 using rtapi::fail;
-
-namespace {
-
-constexpr int kMaxLights = 64;
-
-// Listed: an unwrapped Sphere of positive radius or an unwrapped rect of non-zero area, made of DiffuseLight
-bool listed(const RtSceneDesc *d, const RtPrimitive &p) {
-    if (p.flags != 0 || p.material < 0 || p.material >= d->n_materials) return false;
-    if (d->materials[p.material].kind != RT_MAT_DIFFUSE_LIGHT) return false;
-    if (p.kind == RT_PRIM_SPHERE) return p.p[3] > 0.0;
-    if (p.kind == RT_PRIM_XY_RECT || p.kind == RT_PRIM_XZ_RECT || p.kind == RT_PRIM_YZ_RECT)
-        return (p.p[1] - p.p[0]) * (p.p[3] - p.p[2]) != 0.0;
-    return false;
-}
-
-} // namespace
+using rtapi::kMaxLights;
 
 // Everything that is refused before a device is touched; the scene last, so that each refusal names its own cause
 int rtapi::check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
@@ -63,12 +49,6 @@ int fill_nee_args(RtScene *s, const RtCamera *camera, const RtRenderParams *p, c
     nee.heuristic = ls->heuristic;
     nee.inv_samples = 1.0 / (double)p->samples; // what rtdev_launch_resolve forms
     return RT_OK;
-}
-
-// The grid of 8x8 tiles that k_nee_pass_f64 and k_nee_stream_f64 draw their work from
-void set_tile_grid(rtdev::TraceArgs &a, const RtRenderParams *p) {
-    a.tiles_x = (p->width + 7) / 8;
-    a.n_tiles = a.tiles_x * ((p->height + 7) / 8);
 }
 
 // What precedes the first launch of a call on `stream`: the statistics slots cleared, the item counter of a persistent
@@ -137,7 +117,7 @@ int rtapi::enqueue_nee_stream(RtScene *s, const RtCamera *camera, const RtRender
     if (rc != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     hipStream_t stream = b.stream;
-    set_tile_grid(a, p);
+    rtapi::set_tile_grid(a, p->width, p->height); // the tiles k_nee_stream_f64 draws its work from
     a.n_items = (uint32_t)a.n_tiles;
     a.total_chunks = a.n_chunks = 1;
     if (b.queue.count < 1) RT_HIP(b.queue.alloc(1)); // (allocations, here and in fill_nee_args / setup_delivery, may follow earlier work of the
@@ -178,12 +158,9 @@ int rtapi::begin_nee_passes(RtScene *s, const RtCamera *camera, const RtRenderPa
     const size_t n = (size_t)p->width * (size_t)p->height * 3;
     if (b.accum.count < n || b.squares.count < n || b.partial.count < n) return fail(RT_ERR_INVALID_ARGUMENT, "begin_nee_passes: the running sums are not reserved");
     a.accum = b.accum.ptr;
-    np.starts = rtapi::chunk_starts(p->samples);
-    const int total_chunks = (int)np.starts.size() - 1;
-    for (int c = 0; c <= total_chunks; ++c) a.chunk_start[c] = np.starts[(size_t)c];
-    a.total_chunks = total_chunks;
-    a.chunk_samples = np.starts[1] - np.starts[0];
-    set_tile_grid(a, p);
+    np.starts = rtapi::chunk_plan(p->samples);
+    rtapi::set_chunk_table(a, np.starts);
+    rtapi::set_tile_grid(a, p->width, p->height); // the tiles k_nee_pass_f64 draws its work from
     if (cancellable) rtapi::arm_cancel_word(s, a); // the waves read it at their start and at chunk boundaries
     if ((rc = open_launches(s, stream)) != RT_OK) return rc;
     rtapi::note_launches(s, 0);
@@ -211,21 +188,12 @@ int rtapi::enqueue_nee_pass(RtScene *s, NeePasses &np, int c0, int c1, hipStream
     return RT_OK;
 }
 
-int rtapi::build_light_list(RtScene *s, const RtSceneDesc *d, const std::vector<int32_t> &order) {
-    s->lights.clear();
-    for (int32_t i = 0; i < d->n_primitives && (int)s->lights.size() < kMaxLights; ++i)
-        if (listed(d, d->primitives[i])) s->lights.push_back(i);
-    std::vector<int32_t> device_of(order.size(), -1);
-    for (size_t j = 0; j < order.size(); ++j) device_of[(size_t)order[j]] = (int32_t)j;
-    std::vector<int32_t> slot(order.size(), -1), prim(s->lights.size());
-    for (size_t k = 0; k < s->lights.size(); ++k) {
-        prim[k] = device_of[(size_t)s->lights[k]];
-        slot[(size_t)prim[k]] = (int32_t)k;
-    }
-    RT_HIP(s->nee_slot.alloc(slot.size()));
-    if (!slot.empty()) RT_HIP(hipMemcpy(s->nee_slot.ptr, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    RT_HIP(s->nee_prim.alloc(prim.size()));
-    if (!prim.empty()) RT_HIP(hipMemcpy(s->nee_prim.ptr, prim.data(), prim.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+int rtapi::build_light_list(RtScene *s, const LightTables &t) {
+    s->lights = t.lights;
+    RT_HIP(s->nee_slot.alloc(t.slot.size()));
+    if (!t.slot.empty()) RT_HIP(hipMemcpy(s->nee_slot.ptr, t.slot.data(), t.slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    RT_HIP(s->nee_prim.alloc(t.prim.size()));
+    if (!t.prim.empty()) RT_HIP(hipMemcpy(s->nee_prim.ptr, t.prim.data(), t.prim.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     return RT_OK;
 }
 

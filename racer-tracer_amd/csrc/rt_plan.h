@@ -1,0 +1,123 @@
+// rt_plan.h — the rules that turn a scene description and render parameters into plain numbers and tables: what a
+// description may hold, which kernel it selects, its radiance bound, the device records and their order, the light list,
+// the sample chunks and launches of a render, its pixel grid and strips.  Nothing here needs a device or the runtime, and
+// nothing takes an RtScene: rt_scene_create.hip and rt_api.hip upload and enqueue what these functions return, and
+// tests/plan_driver.cpp runs them as they are.  Private to the library.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+#include "../../include/rt_abi.h"
+#include "rt_device_types.h"
+#include "rt_bvh.h"
+#include "rt_primary_bounds.h"
+#include "rt_error.h"
+
+namespace rtapi {
+
+// ------------------------------------------------------------------------------------------------------------ a scene
+// The linear loop costs ~35 VALU instructions per primitive with scalar loads and
+// no divergence; the BVH walk ~25 node visits plus leaf tests with per-lane loads.
+// They cross at a few dozen primitives (clown.yml, 23 spheres, is still linear).
+constexpr int kBvhThreshold = 48;
+constexpr size_t kBvhLdsBytes = 32 * 1024;       // a node array up to this size is staged in dynamic LDS
+constexpr size_t kLinearTableBytes = 120 * 1024; // the linear-loop variants keep the whole primitive table in LDS
+constexpr int kMaxLights = 64;                   // listed lights of a scene (RtLightSamplingParams.max_lights)
+
+// What rt_scene_create refuses about a description, with the error code and text of each refusal.
+int validate_desc(const RtSceneDesc *d);
+// The options as given, or all zero; refused when a field is out of range.
+int check_options(const RtSceneOptions *options, RtSceneOptions &opt);
+
+// Which trace-kernel instantiation a (validated) description needs: the primitive class (rtdev::PRIMS_*: untransformed rects
+// only, untransformed spheres only, anything), whether some material reads a texture that is not a plain SolidColor (a
+// Dielectric reads none), whether some material is Metal or Dielectric, and whether a MovingSphere is present.
+struct Selection {
+    int prims_class, textured, specular, has_moving;
+};
+Selection select_variant(const RtSceneDesc *d);
+
+// What a finished sample can be at most (RtScene.radiance_bound), or 0: the scene has no bound (rt_plan.cpp).
+double scene_radiance_bound(const RtSceneDesc *d);
+
+// The union of the primitives' bounds (rt_bvh.h: primitive_bounds; a NaN bound stays: it turns the primary-ray cull off);
+// empty (mn > mx) for a scene without primitives.
+void scene_bounds(const RtSceneDesc *d, double mn[3], double mx[3]);
+
+// The device records of the primitives, each carrying its material (the only device copy of a material).
+std::vector<rtdev::Prim> pack_prims(const RtSceneDesc *d);
+// The device records of the textures; an image texture embeds its image's record (rt_device_types.h).
+std::vector<rtdev::Texture> pack_textures(const RtSceneDesc *d, const std::vector<rtdev::Image> &images);
+// The Perlin tables as they are; `identity` is cleared when some permutation is not the identity.
+std::vector<rtdev::Perlin> pack_perlins(const RtSceneDesc *d, int &identity);
+
+// Linear loop: group the table (rt_device_types.h: rect_end, sphere_end, box_end); the order inside a group is kept.
+// `order` (the description index of each record) is permuted alongside.  Returns where the groups end.
+struct LinearGroups {
+    int rect_end[3], sphere_end, box_end;
+};
+LinearGroups group_linear_table(std::vector<rtdev::Prim> &prims, std::vector<int32_t> &order);
+
+// The compact records the walk tests leaves with (rt_device_types.h: LeafGeo), of a table in leaf order; the first
+// MovingSphere with a finite interval sets the scene-wide one (TraceArgs.leaf_time_a, leaf_inv_dt).
+struct LeafTable {
+    std::vector<rtdev::LeafGeo> geo;
+    double time_a = 0.0, inv_dt = 1.0;
+};
+LeafTable leaf_geometry(const std::vector<rtdev::Prim> &prims);
+
+// Next-event estimation: the listed lights as description indices, in description order (at most max_lights), and what
+// rtdev::NeeArgs reads: the light slot of every device primitive (-1: none) and the device primitive of every light.
+// order[j] is the description index of device primitive j.
+struct LightTables {
+    std::vector<int32_t> lights, slot, prim;
+};
+LightTables light_tables(const RtSceneDesc *d, const std::vector<int32_t> &order, int max_lights);
+
+// ----------------------------------------------------------------------------------------------------------- a render
+int check_params(const RtCamera *camera, const RtRenderParams *p);
+
+// Sample chunks a frame of `samples` samples per pixel is cut into, a function of spp only: the start sample of every
+// chunk plus the total (chunks + 1 entries; rt_plan.cpp).
+std::vector<int> chunk_plan(int samples);
+inline int chunk_count(int samples) { return (int)chunk_plan(samples).size() - 1; }
+// ... in a render's argument block: chunk_start[], total_chunks, chunk_samples.
+void set_chunk_table(rtdev::TraceArgs &a, const std::vector<int> &starts);
+
+// The exponent e of the fixed-point sums (sum_scale = 2^(52-e)) for a radiance bound and a sample count, or 0: f64 sums.
+int sum_exponent(double bound, int samples, int *e_out);
+
+// One launch of the pooled kernel: chunks [first_chunk, first_chunk + n_chunks) of every tile.
+struct Launch {
+    int first_chunk, n_chunks;
+};
+// Sample batches are cut on chunk boundaries (chunk_plan), so batching changes no sum.
+std::vector<Launch> plan_launches(const std::vector<int> &starts, int batch);
+
+// Pass k ends at chunk boundary ends[k] (an index into chunk_plan): the first boundary at least pass_samples beyond the
+// one it starts at, or the end of the frame.
+std::vector<int> pass_ends(const std::vector<int> &starts, int pass_samples);
+
+// The render's pixel grid: sizes, samples, strips, the preview's coarser grid, the seed.
+void fill_grid(const RtRenderParams *p, rtdev::TraceArgs &a);
+// Rows of the owned-row grid of a render with these parameters (a multiple of strip_rows with strips).
+int owned_rows_of(const RtRenderParams *p);
+// Image row of row `vr` of the launch's owned-row grid (identity without strips).
+inline int owned_row_to_image_row(const RtRenderParams *p, int vr) {
+    if (p->strip_count <= 1) return vr;
+    return ((vr / p->strip_rows) * p->strip_count + p->strip_index) * p->strip_rows + vr % p->strip_rows;
+}
+// The strips of a several-device call: strip j of `strip_rows` rows (0: 8, written back) goes to share j % n; params[i] is
+// share i's (the caller's own with n == 1).  Refuses parameters that cannot be combined with strips dealt out by the call.
+int deal_strips(const RtRenderParams *p, int n, int &strip_rows, std::vector<RtRenderParams> &params);
+
+// Work is handed out in tiles of 8x8 cells: the tiles across `cells`, the tiles of a cols x rows grid, and that grid in a
+// render's argument block (tiles_x, n_tiles).
+inline int tiles_across(int cells) { return (cells + 7) / 8; }
+inline size_t tile_count(int cols, int rows) { return (size_t)tiles_across(cols) * (size_t)tiles_across(rows); }
+inline void set_tile_grid(rtdev::TraceArgs &a, int cols, int rows) {
+    a.tiles_x = tiles_across(cols);
+    a.n_tiles = a.tiles_x * tiles_across(rows);
+}
+
+} // namespace rtapi

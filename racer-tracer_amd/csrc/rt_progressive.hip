@@ -2,7 +2,7 @@
 // while it converges, the last pass's frame being rt_render_frame's.
 //
 // The reference's author wanted this shape: renderer/denoised.rs:291-331 renders the frame in passes and writes a
-// whole-frame BufferUpdate after each (:210-216).  Here a pass is a run of whole chunks of the frame's chunk plan (rt_api.hip:
+// whole-frame BufferUpdate after each (:210-216).  Here a pass is a run of whole chunks of the frame's chunk plan (rt_plan.cpp:
 // chunk_plan, a function of the TOTAL sample count), traced by one launch of the pooled kernel into the chunks' slices.  A
 // fold pass (k_fold_chunks_f64) then adds those slices to the running per-pixel sums (RenderBuffers.accum) in chunk order
 // and writes sqrt(sum / samples so far).  The running sums start at +0.0, so after the last pass they are
@@ -35,22 +35,9 @@
 
 using rtapi::Cancel;
 using rtapi::fail;
+using rtapi::pass_ends;
 
 namespace {
-
-// Pass k ends at chunk boundary ends[k] (an index into chunk_starts): the first boundary at least pass_samples beyond the
-// one it starts at, or the end of the frame.
-std::vector<int> pass_ends(const std::vector<int> &starts, int pass_samples) {
-    const int total = (int)starts.size() - 1;
-    std::vector<int> ends;
-    for (int c = 0; c < total;) {
-        int e = c + 1;
-        while (e < total && starts[(size_t)e] - starts[(size_t)c] < pass_samples) ++e;
-        ends.push_back(e);
-        c = e;
-    }
-    return ends;
-}
 
 // rt_render_adaptive's side of a call (rt_render_progressive and its denoised form have none): its parameters, checked,
 // and the caller's outputs.
@@ -128,13 +115,13 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     if (s->use_v1 && !nee) return fail(RT_ERR_UNSUPPORTED, "rt_render_progressive needs the pooled kernel (the v1 kernel has no sample chunks)");
     if (cancel.raised()) return RT_ERR_CANCEL_EVENT; // cpu.rs:82-85, as rt_render_ex
     RT_HIP(hipSetDevice(s->device));
-    const std::vector<int> starts = rtapi::chunk_starts(p->samples);
+    const std::vector<int> starts = rtapi::chunk_plan(p->samples);
     const std::vector<int> ends = pass_ends(starts, pass_samples);
     const int passes = (int)ends.size();
     const size_t n = (size_t)p->width * (size_t)p->height * 3; // a frame, and a slice (whole-frame slices: slice_rows = height)
     const int slots = ad ? 3 : 2;
-    const int tiles_x = (p->width + 7) / 8;
-    const size_t n_tiles = ad || nee ? (size_t)tiles_x * (size_t)((p->height + 7) / 8) : 0;
+    const int tiles_x = rtapi::tiles_across(p->width);
+    const size_t n_tiles = ad || nee ? rtapi::tile_count(p->width, p->height) : 0;
     if ((rc = reserve_passes(s, p, passes, n, slots, n_tiles, nee != nullptr)) != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     // denoised: the guides, the filter's scratch and a third device frame slot, the filter's output
@@ -371,7 +358,7 @@ int rtdev_progressive_passes(int32_t samples, int32_t pass_samples, int32_t *out
         if (!n_passes || n_out < 0 || (!out && n_out > 0)) return fail(RT_ERR_INVALID_ARGUMENT, "n_passes/out is NULL or n_out is negative");
         *n_passes = 0;
         if (samples <= 0 || pass_samples <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "samples and pass_samples must be positive");
-        const std::vector<int> starts = rtapi::chunk_starts(samples);
+        const std::vector<int> starts = rtapi::chunk_plan(samples);
         const std::vector<int> ends = pass_ends(starts, pass_samples);
         for (size_t k = 0; k < ends.size() && (int32_t)k < n_out; ++k) out[k] = starts[(size_t)ends[k]];
         *n_passes = (int32_t)ends.size();

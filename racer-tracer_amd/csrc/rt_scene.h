@@ -1,20 +1,21 @@
 // rt_scene.h — what the host-side translation units of the library share: the RtScene object
-// behind include/rt_abi.h's opaque handle, the guard and error helpers of the C entry points and the
-// one function that enqueues a render (rt_api.hip).  Private to the library.
+// behind include/rt_abi.h's opaque handle, the RT_HIP check of a runtime call and the one function
+// that enqueues a render (rt_api.hip).  The error helpers are rt_error.h's, the rules that need no
+// device rt_plan.h's.  Private to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <exception>
-#include <new>
 #include <string>
 #include <vector>
 #include "rt_device_types.h"
 #include "rt_bvh.h"
+#include "rt_error.h"
+#include "rt_plan.h"
 #include "../../include/rt_abi.h"
 
 // The trace kernels exist twice (rt_trace_common.h: ARITHMETIC): RT_ARITH_FAST, and RT_ARITH_REFERENCE behind *_exact.
 // Every launcher that has both flavours, ONCE: X(member of rtapi::Launchers, exported name, return type, parameters).  The
-// declarations of both flavours, the struct and its two tables (rt_api.hip) are all expanded from this list.
+// declarations of both flavours, the struct and its two tables (rt_scene_create.hip) are all expanded from this list.
 //   trace, resolve (rt_trace_kernel.hip): the v1 kernel and its resolve pass.
 //   pool_*, trace_pool, resolve_chunks, fold_* (rt_trace_pool_kernel.hip): the pooled kernel, the variant's resident blocks
 //     per CU and static LDS, the resolve and fold passes over its slices.
@@ -67,32 +68,12 @@ RT_LAUNCHER_LIST(RT_DECLARE_LAUNCHER)
 
 namespace rtapi {
 
-// The launchers of one arithmetic flavour (rt_api.hip: kFastLaunchers, kExactLaunchers); a scene points to its own.
+// The launchers of one arithmetic flavour (rt_scene_create.hip: kFastLaunchers, kExactLaunchers); a scene points to its own.
 struct Launchers {
 #define RT_LAUNCHER_MEMBER(member, name, ret, params) ret(*member) params;
     RT_LAUNCHER_LIST(RT_LAUNCHER_MEMBER)
 #undef RT_LAUNCHER_MEMBER
 };
-
-// set the thread-local text behind rt_last_error_message (truncated, never throws) and return `code`
-int fail(int code, const char *msg) noexcept;
-inline int fail(int code, const std::string &msg) { return fail(code, msg.c_str()); }
-// ... as "<what>: <msg>"
-int fail_in(int code, const char *what, const char *msg) noexcept;
-
-// Every exported function of the library runs its body through this: nothing unwinds into a C, Rust or ctypes caller.
-// std::bad_alloc is RT_ERR_OUT_OF_MEMORY, any other exception RT_ERR_INVALID_ARGUMENT; the message names the entry point.
-template <class F> int guarded(const char *what, F &&body) noexcept {
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        return fail_in(RT_ERR_OUT_OF_MEMORY, what, "host allocation failed");
-    } catch (const std::exception &e) {
-        return fail_in(RT_ERR_INVALID_ARGUMENT, what, e.what());
-    } catch (...) {
-        return fail_in(RT_ERR_INVALID_ARGUMENT, what, "unknown exception");
-    }
-}
 
 #define RT_HIP(call)                                                                            \
     do {                                                                                        \
@@ -140,7 +121,7 @@ struct Delivery {
 };
 
 // Everything a render allocates on first use — slices, the v1 accumulator, frames, the packed RGBA, counters, the pinned
-// frame and flags, streams, events — kept per device across rt_scene_destroy / rt_scene_create (rt_api.hip:
+// frame and flags, streams, events — kept per device across rt_scene_destroy / rt_scene_create (rt_scene_create.hip:
 // render_cache_put / render_cache_take), which move the whole set.
 struct RenderBuffers {
     DevBuf<double> partial;             // [chunks][owned rows][W][3] per-chunk sums (pooled kernel)
@@ -245,7 +226,7 @@ struct RtScene {
     int box_end = 0;             // ... and of the boxes (wrapped or not) behind those
     int textured = 0; // some material's texture is not a plain SolidColor
     // upper bound of a finished sample's radiance (every attenuation in [0, 1]; emission, background and the depth-0 white
-    // below it), or 0 when the scene has none (rt_api.hip: scene_create): what sizes the pooled kernel's fixed-point sums
+    // below it), or 0 when the scene has none (rt_plan.cpp: scene_radiance_bound): what sizes the pooled kernel's fixed-point sums
     double radiance_bound = 0.0;
     int specular = 0; // some material is Metal or Dielectric
     int has_moving = 0; // some primitive is a MovingSphere (the only reader of a ray's time)
@@ -274,7 +255,7 @@ struct RtScene {
     // pooled kernel (default): persistent grid = CUs x resident blocks of the variant
     bool use_v1 = false;   // RtSceneOptions.kernel == RT_KERNEL_V1: the lane-per-pixel kernel
     bool exact = false;    // RtSceneOptions.arithmetic == RT_ARITH_REFERENCE: the *_exact copy of the trace kernels
-    const rtapi::Launchers *kernels = nullptr; // ... and their launchers (rt_api.hip: scene_create)
+    const rtapi::Launchers *kernels = nullptr; // ... and their launchers (rt_scene_create.hip: scene_create)
     bool gather_staged = false; // RtSceneOptions.gather == RT_GATHER_STAGED (rt_multi.hip)
     int num_cus = 0, pool_blocks_per_cu = 1;
     int pool_blocks_per_cu_lens = 1; // ... when the camera has an aperture (its lens samples take dynamic LDS)
@@ -321,7 +302,7 @@ inline void note_launches(RtScene *s, int launches) {
 //     (RtScene.radiance_bound), or 0: none (f64 sums).  Returns the description's validation error, if any.
 //   rtdev_sum_exponent: the exponent e of the fixed-point sums (TraceArgs.sum_scale = 2^(52-e)) that a render of `samples`
 //     samples per pixel gets from a radiance bound, or e = 0: f64 sums; RT_ERR_UNSUPPORTED where the render is refused
-//     (rt_api.hip: sum_exponent).
+//     (rt_plan.cpp: sum_exponent).
 #define RTDEV_VARIANT_FIELDS 14
 extern "C" int rtdev_scene_variant(const RtScene *s, int32_t *out, int32_t n_out);
 extern "C" int rtdev_scene_classify(const RtSceneDesc *d, int32_t out[4]);
@@ -330,7 +311,6 @@ extern "C" int rtdev_sum_exponent(double bound, int32_t samples, int32_t *e);
 extern "C" int rtdev_progressive_passes(int32_t samples, int32_t pass_samples, int32_t *out, int32_t n_out, int32_t *n_passes);
 
 namespace rtapi {
-int check_params(const RtCamera *camera, const RtRenderParams *p);
 // Enqueue trace + resolve on `stream` (two-pass path: the resolve kernel writes out_device), or — with a Delivery —
 // ONE delivering launch that finishes its own pixels (out_device is ignored).  `cancel` is polled before every launch:
 // between the sample batches of the v1 kernel, between the chunk batches of the pooled one (whose waves also read the
@@ -350,15 +330,6 @@ int poison_queue(RtScene *s);
 // a share whose launch still waits behind another share's on the SAME device only reaches its ev_begin when that one ends,
 // and waiting for it before poisoning the next would let the next run to its end.
 int poison_queue_begin(RtScene *s);
-// Image row of row `vr` of the launch's owned-row grid (identity without strips).
-inline int owned_row_to_image_row(const RtRenderParams *p, int vr) {
-    if (p->strip_count <= 1) return vr;
-    return ((vr / p->strip_rows) * p->strip_count + p->strip_index) * p->strip_rows + vr % p->strip_rows;
-}
-// Sample chunks a frame of `samples` samples per pixel is cut into (a function of spp only: rt_api.hip: chunk_plan).
-int chunk_count(int samples);
-// ... and their boundaries: the start sample of every chunk plus the total (chunk_count + 1 entries).
-std::vector<int> chunk_starts(int samples);
 // A whole-frame render of the pooled kernel enqueued chunk range by chunk range (rt_progressive.hip): begin_passes checks the
 // render as enqueue_render does and enqueues what precedes its first launch — counters cleared (one item counter per
 // launch, max_launches of them), the cancel word armed when `cancellable`, the tree ordered for the camera, ev_begin —
@@ -366,7 +337,7 @@ std::vector<int> chunk_starts(int samples);
 // counters, so rt_scene_last_stats counts the whole call.  Buffers must be reserved first (reserve_render_buffers).
 struct PoolPasses {
     rtdev::TraceArgs args;
-    std::vector<int> starts; // chunk_starts(samples)
+    std::vector<int> starts; // chunk_plan(samples)
     unsigned max_blocks = 0; // resident blocks of the variant on the device
     int launches = 0, max_launches = 0;
 };
@@ -387,9 +358,9 @@ RtGuides scene_guides(RtScene *s, size_t pixels);
 int enqueue_guides(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtGuides &g, hipStream_t stream);
 int enqueue_denoise(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, const double *rgb, const RtGuides &g,
                     double *out, hipStream_t stream);
-// The scene's light list (rt_nee.hip), made by rt_scene_create once the device table's order is final: order[j] is the
-// description index of device primitive j.
-int build_light_list(RtScene *s, const RtSceneDesc *d, const std::vector<int32_t> &order);
+// The scene's light list (rt_nee.hip) on the device, made by rt_scene_create once the device table's order is final
+// (rt_plan.h: light_tables).
+int build_light_list(RtScene *s, const LightTables &t);
 // What every NEE entry point refuses before a device is touched (rt_nee.hip), the scene last so that each refusal names
 // its own cause; `what` is the entry point's name in the messages about whole frames.
 int check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
@@ -402,7 +373,7 @@ int check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p,
 struct NeePasses {
     rtdev::TraceArgs args;
     rtdev::NeeArgs nee;
-    std::vector<int> starts; // chunk_starts(samples)
+    std::vector<int> starts; // chunk_plan(samples)
 };
 int begin_nee_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
                      hipStream_t stream, bool cancellable, NeePasses &np);
@@ -420,11 +391,6 @@ int nee_frame_to_host(RtScene *s, const RtCamera *camera, const RtRenderParams *
 int setup_delivery(RtScene *s, rtdev::TraceArgs &a, const Delivery &delivery, int chunks_per_tile, hipStream_t stream);
 // The pinned host frame of the host-output entry points, at least `doubles` long (rt_deliver.hip).
 int ensure_host_frame(RtScene *s, size_t doubles);
-// Rows of the owned-row grid of a render with these parameters (a multiple of strip_rows with strips).
-int owned_rows_of(const RtRenderParams *p);
 // The several-device calls (rt_deliver.hip, rt_multi.hip): a non-empty list of distinct, non-NULL scenes.
 int check_scenes(RtScene *const *scenes, int n);
-// ... and their strips: strip j of `strip_rows` rows (0: 8, written back) goes to share j % n; params[i] is share i's
-// (the caller's own with n == 1).  Refuses parameters that cannot be combined with strips dealt out by the call.
-int deal_strips(const RtRenderParams *p, int n, int &strip_rows, std::vector<RtRenderParams> &params);
 } // namespace rtapi

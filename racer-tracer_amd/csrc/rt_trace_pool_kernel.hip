@@ -10,7 +10,7 @@
 // 1. PERSISTENT WAVES + ITEM QUEUE.  The grid is sized to what is resident
 //    (CUs x blocks per CU); every wave pulls items from one atomic counter
 //    until the queue is dry.  An item is a tile x a chunk of its samples; the
-//    chunk plan (rt_api.hip: chunk_plan, a function of spp only) has long chunks
+//    chunk plan (rt_plan.cpp: chunk_plan, a function of spp only) has long chunks
 //    first and a taper of short ones last, so a launch ends on small items.
 //
 // 2. LANES ARE NOT PIXELS.  Inside an item the 64 lanes share a pool of

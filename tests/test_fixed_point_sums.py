@@ -1,7 +1,7 @@
 """The fixed-point pixel sums of the pooled variants that keep two items in flight (rt_trace_pool_kernel.hip, OVERLAP;
 rt_device_types.h: sum_scale), checked on the host against the oracle's per-sample radiances — no device needed.
 
-The sums rest on two host rules (rt_api.hip): the scene's radiance bound E (rtdev_scene_radiance_bound) and the exponent e
+The sums rest on two host rules (rt_plan.cpp): the scene's radiance bound E (rtdev_scene_radiance_bound) and the exponent e
 it gives a render (rtdev_sum_exponent: sum_scale = 2^(52 - e)).  What has to hold:
   * the bound bounds every sample, so round(T 2^(52-e)) fits the kernel's 52-bit conversion and a chunk of such integers
     the 64-bit sum (a sample above the bound would turn the sum into garbage, not into a NaN);
@@ -31,7 +31,7 @@ MAX_CHUNKS = 64              # rt_device_types.h: RT_MAX_CHUNKS
 # ---- helpers -----------------------------------------------------------------------------------------------------------
 
 def chunk_plan(samples):
-    """rt_api.hip: chunk_plan of the product build -> the start sample of every chunk plus the total.  (Checked against
+    """rt_plan.cpp: chunk_plan of the product build -> the start sample of every chunk plus the total.  (Checked against
     the library's rule in test_chunk_plan_replica_matches_the_library.)"""
     full = max(24, ((samples + 15) // 16 + 3) // 4 * 4)
     starts, at = [], 0

@@ -64,7 +64,7 @@ def test_one_pixel_dimension_is_refused(rt, gpu, w, h):
 @pytest.mark.parametrize("spp", [1, 7, 8, 9, 31, 32, 33, 47, 48, 49, 64, 65, 200, 257, 1000, 2049])
 def test_sample_counts_around_chunk_boundaries(rt, orc, gpu, spp):
     """The pooled kernel sums a pixel's samples in chunks: full-length ones of spp / 16 (at least 24) samples,
-    then a taper of halving chunks down to 8 or fewer (rt_api.hip: chunk_plan); any count must give the
+    then a taper of halving chunks down to 8 or fewer (rt_plan.cpp: chunk_plan); any count must give the
     oracle's frame."""
     bundle, cam, _ = S.cornell_box()
     w, h = (16, 9) if spp > 100 else (48, 27)

@@ -1,7 +1,7 @@
 """The fixed-point pixel sums of the pooled variants that keep two items in flight (rt_trace_pool_kernel.hip, OVERLAP;
 rt_device_types.h: sum_scale) on the device, across the radiance range the host accepts for them and beyond it.
 
-The rule (rt_api.hip: scene_radiance_bound, sum_exponent; tests/test_fixed_point_sums.py checks it on the host): a scene
+The rule (rt_plan.cpp: scene_radiance_bound, sum_exponent; tests/test_fixed_point_sums.py checks it on the host): a scene
 whose radiance bound E is below 2^30 sums its samples as integers of 2^(e-52), e <= 31; a brighter one keeps the f64 sums
 of the RT_ARITH_REFERENCE copy.  Every fixed-sum path is run through that range — the mixed linear variant, the BVH with
 its nodes in LDS, the BVH with its nodes in global memory and the delivering launch of the tile stream — on a scene whose
@@ -17,7 +17,7 @@ from test_fixed_point_sums import dark_under_bright
 pytestmark = pytest.mark.gpu
 abi = S.abi
 TOL = 1e-3
-CAP = 2.0 ** 30      # rt_api.hip: kSumsBoundCap
+CAP = 2.0 ** 30      # rt_plan.cpp: kSumsBoundCap
 EMISSIONS = [2.0 ** 4, 2.0 ** 20, CAP * (1 - 1e-15), CAP, 2.0 ** 33, 2.0 ** 39]
 
 

@@ -1,6 +1,6 @@
 """Every compiled trace-kernel instantiation against the oracle.
 
-rt_scene_create_ex picks one of many kernels from what a scene holds (rt_api.hip: select_variant; rt_variant_dispatch.h:
+rt_scene_create_ex picks one of many kernels from what a scene holds (rt_plan.cpp: select_variant; rt_variant_dispatch.h:
 dispatch_variant, which every kernel file's launcher goes through): k_trace_pool_f64<PRIMS, TEXTURED, SPECULAR, BVH> (12 linear-loop forms + 4 BVH forms) and
 k_trace_f64<PRIMS, TEXTURED, SPECULAR> (12 forms), each compiled twice — RT_ARITH_FAST and RT_ARITH_REFERENCE.  Template
 flags add or remove whole material arms, LDS layouts, NBUF and the fixed-point sums, so each is separate code: every
@@ -107,7 +107,7 @@ def test_bvh_nodes_in_global_memory(rt, orc, gpu, flavour):
 @pytest.mark.parametrize("bvh", [0, 1])
 def test_scene_without_radiance_bound_renders_with_f64_sums(rt, orc, gpu, bvh):
     """A colour above 1 on a scattering material leaves the scene without a radiance bound: the two-item (OVERLAP) forms
-    with fixed-point sums cannot hold it, and RT_ARITH_FAST is rendered by the RT_ARITH_REFERENCE copy (rt_api.hip)."""
+    with fixed-point sums cannot hold it, and RT_ARITH_FAST is rendered by the RT_ARITH_REFERENCE copy (rt_scene_create.hip)."""
     bundle, cam = V.unbounded_scene()
     variant, got, stats, ref, ref_segs = _render(rt, orc, bundle, cam, "pool", "fast", abi.RT_HIT_BVH if bvh else abi.RT_HIT_LINEAR)
     assert (variant["prims_class"], variant["use_bvh"], variant["exact"]) == (V.ANY, bvh, 1)
@@ -116,7 +116,7 @@ def test_scene_without_radiance_bound_renders_with_f64_sums(rt, orc, gpu, bvh):
 
 # ---- the LDS bill ------------------------------------------------------------------------------------------------------
 
-MAX_LINEAR_PRIMS = 640   # rt_api.hip: the linear loop's table is at most 120 KiB of 192-byte records
+MAX_LINEAR_PRIMS = 640   # rt_plan.h: kLinearTableBytes, the linear loop's table is at most 120 KiB of 192-byte records
 
 
 def lds_scene(prims_class, n_extra_textures):

@@ -34,3 +34,25 @@ def test_host_layer_is_clean_under_asan_and_ubsan(tmp_path):
     assert 400 < n_random <= 488
     assert "missing config rc=3" in out and "missing scene rc=3" in out   # TracerError::Configuration (scene/yml.rs:153-170)
     assert "decode jpg rc=0 1024x512" in out and "decode garbage rc=21" in out
+
+
+def test_plan_rules_are_clean_under_asan_and_ubsan(host, tmp_path):
+    """The device-free scene and render rules (racer-tracer_amd/csrc/rt_plan.cpp: validation, packing, the permutations of
+    the primitive table, chunk plans, grids) as a stand-alone program — tests/plan_driver.cpp — over every command
+    tests/test_plan_cpu.py sends it."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    import test_plan_cpu as P
+    exe = str(tmp_path / "plan_sanitize")
+    build = P.build_driver(exe, ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"])
+    if build.returncode != 0 and ("asan" in build.stderr or "ubsan" in build.stderr):
+        pytest.skip("sanitizer runtimes not installed: " + build.stderr[-200:])
+    assert build.returncode == 0, build.stderr[-2000:]
+    commands = P.all_commands(tmp_path, host)
+    assert {c.split()[0] for c in commands} == set(P.LINES)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    run = subprocess.run([exe], input="\n".join(commands) + "\n", capture_output=True, text=True, env=env, timeout=300)
+    assert run.returncode == 0, (run.stdout[-500:], run.stderr[-3000:])
+    assert run.stderr == "", run.stderr[-3000:]
+    assert "runtime error" not in run.stdout and "Sanitizer" not in run.stdout
+    assert len(run.stdout.splitlines()) == sum(P.LINES[c.split()[0]] for c in commands)

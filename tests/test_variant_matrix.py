@@ -1,7 +1,7 @@
 """What keeps tests/test_gpu_variants.py honest, without a GPU:
   * the inventory: the trace-kernel instantiations in the compiled code (both arithmetic flavours) are exactly the cases
     the GPU module renders, and dispatch_variant can reach each of them;
-  * the selection rule (rt_api.hip: select_variant, exported as rtdev_scene_classify): every scene of the matrix selects
+  * the selection rule (rt_plan.cpp: select_variant, exported as rtdev_scene_classify): every scene of the matrix selects
     the form it is there for, and the edge descriptions select what the kernels expect;
   * sensitivity: turning off the feature a scene is there to exercise changes the oracle's picture, so a GPU case would
     fail if the kernel's arm for that feature were wrong."""

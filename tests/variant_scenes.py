@@ -230,7 +230,7 @@ def large_bvh_scene(n=3000):
 
 def unbounded_scene():
     """A Lambertian colour above 1: the scene has no radiance bound, so the fixed-point sums of the two-item (OVERLAP)
-    forms cannot hold it and rt_scene_create_ex sends it to the RT_ARITH_REFERENCE copy (rt_api.hip)."""
+    forms cannot hold it and rt_scene_create_ex sends it to the RT_ARITH_REFERENCE copy (rt_scene_create.hip)."""
     bundle, cam = build((ANY, 0, 1, 0))
     bundle.textures[0].color = abi.D3(1.3, 0.9, 0.9)
     return bundle, cam

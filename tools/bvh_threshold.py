@@ -1,4 +1,4 @@
-"""Developer probe: where does the BVH walk overtake the linear closest-hit loop?  (rt_api.hip: kBvhThreshold)
+"""Developer probe: where does the BVH walk overtake the linear closest-hit loop?  (rt_plan.h: kBvhThreshold)
 Scenes of N spheres (Lambertian / Metal / Dielectric mix on a ground sphere), 1920x1080 x 32 spp, both closest-hit routines."""
 import importlib, os, sys
 import numpy as np

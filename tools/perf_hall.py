@@ -1,6 +1,6 @@
 """Developer probe: the BVH variants on LARGE scenes — a hall of N spheres (Lambertian / Metal / Dielectric mixed), 1080p.
 Above 1023 nodes the node array (32 B per node) no longer fits the 32 KiB of LDS the walk stages it in and every descent
-step is two 128-bit reads from global memory instead (racer-tracer_amd/csrc/rt_api.hip: bvh_nodes_in_lds).
+step is two 128-bit reads from global memory instead (racer-tracer_amd/csrc/rt_scene_create.hip: bvh_nodes_in_lds).
 Usage: python3 tools/perf_hall.py [spp] [N ...]        (RACER_TRACER_AMD_LIB=.../libracer_tracer_amd_regions.so adds
 the walk's nodes / leaf primitives per segment)"""
 import importlib, os, sys, time
