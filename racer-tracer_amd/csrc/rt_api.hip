@@ -3,9 +3,9 @@
 // ones live in rt_deliver.hip and rt_multi.hip).  Scenes are made in rt_scene_create.hip; the rules that need no device —
 // the chunk plan, the pixel grid, the exponent of the fixed-point sums — are rt_plan.cpp's.
 //
-// Host code only (HIP runtime calls); the kernels live in rt_trace_kernel.hip (v1), rt_trace_pool_kernel.hip (pooled)
-// and rt_post_kernel.hip.  Nothing here falls back to a CPU renderer: without a usable HIP device every entry point
-// returns RT_ERR_NO_DEVICE.
+// Host code only (HIP runtime calls); the kernels live in rt_trace_kernel.hip (v1), rt_trace_pool_kernel.hip (pooled),
+// rt_frame_kernels.hip (resolve, folds) and rt_post_kernel.hip.  Nothing here falls back to a CPU renderer: without a
+// usable HIP device every entry point returns RT_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>

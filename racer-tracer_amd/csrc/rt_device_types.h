@@ -101,7 +101,7 @@ struct alignas(64) LeafGeo {
 static_assert(sizeof(LeafGeo) == 64, "LeafGeo must be 64 bytes");
 
 // dynamic LDS of the pooled kernel's lens-disk samples per block: 4 waves x NBUF batches x 64 entries x (x, y);
-// NBUF = 1 in the BVH variants, 2 elsewhere (rt_trace_pool_kernel.hip: WaveLds)
+// NBUF = 1 in the BVH variants, 2 elsewhere (rt_pool_lds.h: WaveLds)
 inline size_t pool_lens_lds_bytes(bool bvh) { return (size_t)4 * (bvh ? 1 : 2) * 64 * 2 * sizeof(double); }
 // ... and of the batches' ray times, when the scene has a MovingSphere: 4 waves x NBUF batches x 64 entries
 inline size_t pool_time_lds_bytes(bool bvh) { return (size_t)4 * (bvh ? 1 : 2) * 64 * sizeof(double); }
@@ -284,12 +284,12 @@ struct NeeArgs {
     double inv_samples;
 };
 
-// The decision step behind a pass (rt_nee_pass_kernel.hip: k_nee_decide_f64), one wave per 8x8 tile of the whole frame:
-// AdaptiveFold's second half.  A running tile (tile_stop 0) writes its pixels and its error and either stops or appends
-// itself to next_list; a stopped tile rewrites its pixels from its own scale and carries its error over.
-struct NeeDecide {
-    const double *running;   // S: the running sums (W*H*3)
-    const double *squares;   // Q: per pixel and channel the sum over the chunks done of S_j^2 / n_j (W*H*3)
+// The decision step of an adaptive pass (rt_tile_decide.h), one wave per 8x8 tile of the whole frame: what both estimators
+// tell it.  A running tile (tile_stop 0) writes its pixels and its error and either stops or appends itself to next_list;
+// a stopped tile rewrites its pixels from its own scale and carries its error over.
+struct TileDecision {
+    double *running;         // S: the running sums (W*H*3)
+    double *squares;         // Q: per pixel and channel the sum over the chunks done of S_j^2 / n_j (W*H*3)
     double *out;             // the pass's frame slot: sqrt(scale * S)
     int32_t *tile_stop;      // per tile: 0 while it runs, else the samples it stopped at
     double *tile_scale;      // per tile: the scale of the pass that stopped it (1 / those samples)
@@ -302,33 +302,26 @@ struct NeeDecide {
     int32_t samples_done;    // chunk_start[chunks_done]
     int32_t eligible;        // a tile may stop here: chunks_done >= 4, samples_done >= min_samples and threshold > 0
     int32_t _pad;
-    double scale;            // 1.0 / samples_done, as the host computes it for the resolve of rt_render_frame_nee
+    double scale;            // 1.0 / samples_done, as the host computes it for the resolve of rt_render_frame_nee and
+                             // for rt_render_progressive's fold
     double inv_batches;      // 1.0 / (chunks_done - 1), 0 when chunks_done < 2
     double threshold;
 };
 
-// One pass of rt_render_adaptive's fold (rt_trace_pool_kernel.hip: k_fold_adaptive_f64), one wave per 8x8 tile of the whole
-// frame.  Whole-frame slices, as rt_render_progressive's.  A running tile (tile_stop 0) folds the slices [c0, c1) into
-// `running` and their squares over their sample counts into `squares`, writes its pixels, its error and either stops or
-// appends itself to next_list; a stopped tile rewrites its pixels from its own scale and carries its error over.
+// The decision step behind an NEE pass (rt_nee_pass_kernel.hip: k_nee_decide_f64): the sums and Q are where the trace
+// kernel and k_nee_chunk_f64 left them.
+struct NeeDecide {
+    TileDecision d;
+};
+
+// One pass of rt_render_adaptive's fold (rt_frame_kernels.hip: k_fold_adaptive_f64).  Whole-frame slices, as
+// rt_render_progressive's.  A running tile folds the slices [c0, d.chunks_done) into `running` and their squares over
+// their sample counts into `squares` in front of its decision.
 struct AdaptiveFold {
+    TileDecision d;
     const double *partial;   // [chunk][H][W][3]
-    double *running;         // S: the running sums (W*H*3)
-    double *squares;         // Q: sum over the chunks done of S_j^2 / n_j (W*H*3)
-    double *out;             // the pass's frame slot: sqrt(scale * S)
-    int32_t *tile_stop;      // per tile: 0 while it runs, else the samples it stopped at
-    double *tile_scale;      // per tile: the scale of the pass that stopped it (1 / those samples)
-    const double *err_prev;  // per tile: error after the previous pass
-    double *err;             // ... after this one (-1: fewer than 2 chunks)
-    uint32_t *next_list;     // the tiles that run on, in any order ...
-    uint32_t *next_count;    // ... and their number (zero before the pass)
-    int32_t width, height, tiles_x, n_tiles;
-    int32_t c0, c1;          // chunks of this pass; c1 = the chunks done
-    int32_t samples_done;    // chunk_start[c1]
-    int32_t eligible;        // a tile may stop here: c1 >= 4, samples_done >= min_samples and threshold > 0
-    double scale;            // 1.0 / samples_done, as the host computes it for rt_render_progressive's fold
-    double inv_batches;      // 1.0 / (c1 - 1), 0 when c1 < 2
-    double threshold;
+    int32_t c0;              // first chunk of this pass (the last is d.chunks_done - 1)
+    int32_t _pad;
     double inv_chunk[RT_MAX_CHUNKS]; // 1.0 / the samples of each chunk
 };
 

@@ -5,6 +5,7 @@
 // added in sample order to a sum that travels from launch to launch in TraceArgs.accum, so after any pass the sums are
 // the ones k_nee_f64 forms with that many samples, bit for bit.
 #include "rt_nee_common.h"
+#include "rt_tile_decide.h"
 #include "rt_variant_dispatch.h"
 
 namespace RT_KNS {
@@ -88,79 +89,18 @@ __global__ __launch_bounds__(256) void k_nee_chunk_f64(const double *__restrict_
     }
 }
 
-// The decision step of a pass (rtdev::NeeDecide), a kernel of its own behind k_nee_pass_f64: one wave per 8x8 tile of the
-// WHOLE frame, one lane per pixel, 16 tiles to a block — k_fold_adaptive_f64 (rt_trace_pool_kernel.hip) without the fold,
-// the sums and Q being where the trace kernel left them.  Every tile writes its pixels into the pass's frame slot,
-// sqrt(scale * S) with the pass's scale while it runs and with its own once it has stopped (the same bits as at its stop:
-// its sums are no longer touched), so the slot is whole.  A running tile's error is the largest over its pixels and
-// channels of e = sigma / (sqrt(m + sigma) + sqrt(m)), m = S / s, V = max(0, Q - S m) / (k - 1), sigma = sqrt(V / s)
-// (include/rt_abi.h: rt_render_adaptive); it stops (eligible, error <= threshold) or is appended to the next pass's list,
-// with ONE atomic per block of 16 tiles.  next_list NULL (rt_render_progressive_nee): nothing stops, nothing is listed.
+// The decision step of a pass (rtdev::NeeDecide), a kernel of its own behind k_nee_pass_f64: rt_tile_decide.h's step with
+// nothing to fold — k_fold_adaptive_f64 (rt_frame_kernels.hip) without the fold, the sums and Q being where the trace
+// kernel and k_nee_chunk_f64 left them.  Every tile writes its pixels into the pass's frame slot; a running tile is
+// measured and stops or is appended to the next pass's list.  next_list NULL (rt_render_progressive_nee): nothing stops,
+// nothing is listed.
 __global__ __launch_bounds__(1024) void k_nee_decide_f64(const NeeDecide F) {
-    __shared__ uint32_t keep_of[16];
-    __shared__ uint32_t list_base;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int t = (int)blockIdx.x * 16 + wave; // wave-uniform
     uint32_t keep = 0; // (lane 0) this wave's tile runs on
-    if (t < F.n_tiles) {
-        const int tx = t % F.tiles_x, ty = t / F.tiles_x;
-        const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
-        const bool valid = px < F.width && py < F.height;
-        const size_t i = valid ? ((size_t)py * (size_t)F.width + (size_t)px) * 3 : 0;
-        double acc[3] = {0.0, 0.0, 0.0};
-        if (valid)
-            for (int ch = 0; ch < 3; ++ch) acc[ch] = F.running[i + ch];
-        const int stop = __builtin_amdgcn_readfirstlane(F.tile_stop[t]);
-        if (stop != 0) {
-            const double scale = F.tile_scale[t];
-            if (valid)
-                for (int ch = 0; ch < 3; ++ch) F.out[i + ch] = sqrt(scale * acc[ch]);
-            if (lane == 0) F.err[t] = F.err_prev[t];
-        } else {
-            double e_max = 0.0;
-            if (valid) {
-                for (int ch = 0; ch < 3; ++ch) {
-                    F.out[i + ch] = sqrt(F.scale * acc[ch]);
-                    if (F.chunks_done >= 2) { // (the error is compared to a threshold, not bit for bit: reciprocals from the host)
-                        const double q = F.squares[i + ch];
-                        const double m = acc[ch] * F.scale;
-                        const double var = fmax(0.0, q - acc[ch] * m) * F.inv_batches;
-                        const double sigma = sqrt(var * F.scale);
-                        const double e = sigma > 0.0 ? sigma / (sqrt(m + sigma) + sqrt(m)) : 0.0;
-                        e_max = e > e_max ? e : e_max;
-                    }
-                }
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                const double o = __shfl_xor(e_max, off, 64);
-                e_max = o > e_max ? o : e_max;
-            }
-            if (lane == 0) {
-                const double err = F.chunks_done >= 2 ? e_max : -1.0;
-                F.err[t] = err;
-                if (F.eligible && err <= F.threshold) {
-                    F.tile_stop[t] = F.samples_done;
-                    F.tile_scale[t] = F.scale;
-                } else {
-                    keep = 1u;
-                }
-            }
-        }
-    }
-    if (F.next_list == nullptr) return; // (uniform over the grid)
-    if (lane == 0) keep_of[wave] = keep;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t total = 0;
-        for (int w = 0; w < 16; ++w) total += keep_of[w];
-        list_base = total ? atomicAdd(F.next_count, total) : 0u;
-    }
-    __syncthreads();
-    if (lane == 0 && keep) {
-        uint32_t at = list_base;
-        for (int w = 0; w < wave; ++w) at += keep_of[w];
-        F.next_list[at] = (uint32_t)t;
-    }
+    if (t < F.d.n_tiles) keep = decide_tile(F.d, t, lane, [](size_t, double (&)[3], double (&)[3]) {});
+    if (F.d.next_list == nullptr) return; // (uniform over the grid)
+    append_running_tiles(F.d, t, lane, wave, keep);
 }
 
 } // namespace RT_KNS
@@ -198,7 +138,7 @@ extern "C" hipError_t RT_LAUNCHER(rtdev_launch_nee_chunk)(const double *running,
 }
 
 extern "C" hipError_t RT_LAUNCHER(rtdev_launch_nee_decide)(const rtdev::NeeDecide *f, hipStream_t stream) {
-    if (f->n_tiles <= 0) return hipSuccess;
-    hipLaunchKernelGGL(RT_KNS::k_nee_decide_f64, dim3((unsigned)(f->n_tiles + 15) / 16), dim3(1024), 0, stream, *f);
+    if (f->d.n_tiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(RT_KNS::k_nee_decide_f64, dim3((unsigned)(f->d.n_tiles + 15) / 16), dim3(1024), 0, stream, *f);
     return hipGetLastError();
 }

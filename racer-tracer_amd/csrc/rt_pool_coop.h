@@ -1,0 +1,289 @@
+// rt_pool_coop.h — what the 64 lanes of a wave of the pooled trace kernel (rt_trace_pool_kernel.hip) do together: lane
+// ranks and masked register updates, the closest-hit loop of the rects-only variants, and the wave-cooperative samplers
+// (unit sphere, lens disk, Perlin turbulence) over the request slots of rt_pool_lds.h.
+#pragma once
+#include "rt_pool_lds.h"
+
+namespace RT_KNS {
+
+__device__ __forceinline__ int lane_rank(uint64_t mask) { // set bits of `mask` below this lane
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// Posts a sphere sampler request as six 32-bit LDS stores.  Wider stores want the values in consecutive VGPRs: pixel,
+// sample and candidate were then copied into such a quad in every iteration (v_mov_b32 around every round), and the
+// stores cost the LDS pipe, which the path loop barely uses, instead of the vector one.  (Relaxed atomic stores: plain
+// ones are merged back into wider stores.)
+__device__ __forceinline__ void post_request(SphereSlot *slot, const ScatterPrefix &P, uint32_t base) {
+    __hip_atomic_store(&slot->b, P.b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->y, P.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->x, P.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->w, P.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->z, P.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __hip_atomic_store(&slot->base, base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+// v = p in the lanes of `mask`, in v's own registers.  Written in C++, a masked write of the sphere sampler's `result` is a
+// branch around it, and the compiler copied `result` on both sides of the branch and back at the join; this does the
+// masking itself, so to the compiler it is an unconditional update of `v` in place.
+__device__ __forceinline__ void move_masked(const d3 &p, uint64_t mask, d3 &v) {
+    uint64_t saved;
+    asm volatile("s_and_saveexec_b64 %[saved], %[mask]\n\t"
+                 "v_mov_b64 %[x], %[px]\n\t"
+                 "v_mov_b64 %[y], %[py]\n\t"
+                 "v_mov_b64 %[z], %[pz]\n\t"
+                 "s_mov_b64 exec, %[saved]"
+                 : [x] "+v"(v.x), [y] "+v"(v.y), [z] "+v"(v.z), [saved] "=&s"(saved)
+                 : [mask] "s"(mask), [px] "v"(p.x), [py] "v"(p.y), [pz] "v"(p.z)
+                 : "scc");
+}
+// v += 1 in the lanes of `mask` (wave-uniform), as one add with the mask as its carry-in; written in C++ it is a select of
+// 0 / 1 (v_cndmask_b32) and an add.
+__device__ __forceinline__ void increment_masked(uint32_t &v, uint64_t mask) {
+    asm("v_addc_co_u32 %[v], vcc, 0, %[v], %[mask]" : [v] "+v"(v) : [mask] "s"(mask) : "vcc");
+}
+// The lowest set bit of every group of 2^lg bits of x (1 <= lg <= 6), in the scalar unit: x & -x within each group, the
+// negation done per group as (~x without the groups' top bits) + 1 in every group, whose carry stops at the group's top
+// bit, XOR the top bits of ~x
+__device__ __forceinline__ uint64_t lowest_in_groups(uint64_t x, int lg) {
+    const int q = 1 << lg;
+    uint64_t low = 1; // bit 0 of every group, doubled out (a shift by 64 or more is one by 0, which adds nothing)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) low |= low << ((q << k) & 63);
+    const uint64_t top = low << (q - 1);
+    return x & (((~x & ~top) + low) ^ (~x & top));
+}
+
+// The closest-hit loop of the rects-only variants over the grouped table (XY, XZ, YZ rects, in that order: record order,
+// strict `t < best_t`), one straight-line test per group with the plane a compile-time constant.  PAIRS: two records per
+// scalar-load wait (what the path loop runs); without, one test site per plane (the camera batches: every site is a copy
+// of the rect test in the kernel's text).
+template <bool PAIRS>
+__device__ __forceinline__ void closest_hit_rects(const Prim *table, const d3 &o, const d3 &d, const d3 &inv_d, double &best_t, int &best) {
+    auto test_plane = [&](auto axis, const Prim &P, int i) {
+#ifndef RT_EXACT_DIV
+        rect_closest_update<decltype(axis)::value>(P.p[0], P.p[1], P.p[2], P.p[3], P.p[4], o, d, inv_d, 0.001, best_t, best, i);
+        return;
+#endif
+        double t;
+        if (rect_t<true>(decltype(axis)::value, P.p[0], P.p[1], P.p[2], P.p[3], P.p[4], o, d, inv_d, 0.001, best_t, t)) {
+            best_t = t;
+            best = i;
+        }
+    };
+    const Prim *rec = table; // ONE pointer runs through the groups (they follow each other in the table)
+    int i = 0;
+    auto group = [&](auto axis, int end) {
+        if (PAIRS) {
+            for (; i + 1 < end; i += 2, rec += 2) {
+                const Prim pa = load_prim_uniform(rec, 0), pb = load_prim_uniform(rec, 1);
+                test_plane(axis, pa, i);
+                test_plane(axis, pb, i + 1);
+            }
+            if (i < end) {
+                test_plane(axis, load_prim_uniform(rec, 0), i);
+                ++i;
+                ++rec;
+            }
+        } else {
+            for (; i < end; ++i, ++rec) test_plane(axis, load_prim_uniform(rec, 0), i);
+        }
+    };
+    // (the group bounds are re-read from the kernel arguments here: see the path loop of the other variants)
+    const RT_CONSTANT TraceArgs *KB = kernargs_here();
+    const int end_xy = KB->rect_end[0], end_xz = KB->rect_end[1], end_yz = KB->rect_end[2];
+    group(std::integral_constant<int, 2>(), end_xy); // XY
+    group(std::integral_constant<int, 1>(), end_xz); // XZ
+    group(std::integral_constant<int, 0>(), end_yz); // YZ
+}
+
+// vec3.rs:424-430 for every lane of `pending` (a wave-uniform lane mask, like the one it returns: the lanes
+// that got their sample), evaluated by the whole wave.
+// Must be called by all 64 lanes (wave-uniform control flow).  Runs at most
+// MAX_ROUNDS rounds: a lane whose request is still open afterwards is not in the
+// returned mask and keeps `base` (its first untested candidate), so the search resumes
+// at the same stream position in the next call.
+// The round count is a template constant: two rounds (the plain variants) are unrolled into straight-line code.  The
+// first round writes `result` in EVERY lane (no lane holds a sample yet), so only the later rounds write it under the
+// mask of the lanes still searching — a masked write is a copy of the old value at the join (C3 -0.8 %); both kinds of
+// round end in ONE such write (move_masked), after their branches have joined.
+// Every candidate is drawn from the scatter prefix of its request (philox_from_prefix): each lane forms its own once per
+// call, and a grouped round posts it, so a candidate costs 10 multiplies instead of 14.  A grouped round's answer comes
+// back through the request's slot, not through lane shuffles.
+template <int MAX_ROUNDS>
+__device__ __forceinline__ uint64_t coop_random_in_unit_sphere(uint64_t pending, uint32_t pixel, uint32_t sample, uint32_t seg,
+                                                           uint32_t &base, uint32_t k0, uint32_t k1, int lane,
+                                                           SphereSlot *slot, d3 &result) {
+    uint64_t have = 0;
+    const ScatterPrefix own = scatter_prefix(pixel, sample, seg, k0, k1);
+    for (int round = 0; round < MAX_ROUNDS && pending != 0; ++round) {
+        const int n = __popcll(pending);
+        // a round costs the whole wave ~70 instructions; past the first it only runs while enough requests are
+        // open to be worth that (the others resume next iteration): C2 +2.2 %, C3 +0.3 % (thresholds 2..16 and one to
+        // six rounds measured again with one-block candidates: 8 and two rounds stay)
+        if (round > 0 && n < 8) break;
+        // group size q = 2^lg, the largest power of two with n * q <= 64
+        const int lg = n > 32 ? 0 : (n > 16 ? 1 : (n > 8 ? 2 : (n > 4 ? 3 : (n > 2 ? 4 : (n > 1 ? 5 : 6)))));
+        // what `result` takes: in every lane in the first round, in the lanes of `take` in the later ones.  `result` only
+        // means something to a lane of the returned mask, so a lane that still needs a sample may take whatever its round
+        // left it, a rejected candidate included.
+        d3 cand;
+        uint64_t take;
+        if (lg == 0) { // more than 32 requests: one candidate each, so every lane tests its OWN (no LDS)
+            const d3 p = sphere_candidate(philox_from_prefix(own, base, k0, k1));
+            cand = p;
+            take = pending;
+            const uint64_t inside = ballot(len2(p) < 1.0); // (the comparison's own lane mask)
+            have |= pending & inside;
+            pending &= ~inside;
+            if (__builtin_amdgcn_inverse_ballot_w64(pending)) base += 1u;
+        } else {
+            const bool need = __builtin_amdgcn_inverse_ballot_w64(pending);
+            const int rank = lane_rank(pending);
+            if (need) post_request(slot + rank, own, base);
+            const int j = lane >> lg;              // request served by this lane
+            const int c = lane & ((1 << lg) - 1);  // candidate offset inside the group
+            const bool serving = j < n;
+            SphereSlot *const served = slot + (serving ? j : 0);
+            const ScatterPrefix r = {served->b, served->y, served->x, served->w, served->z};
+            const uint32_t i = served->base + (uint32_t)c; // candidate index = its block (rt_rng.h)
+            const d3 p = sphere_candidate(philox_from_prefix(r, i, k0, k1));
+            // (ballots of the two comparisons, ANDed as scalars: a ballot of `serving && ...` is a lane mask turned into an
+            // integer and back, v_cndmask_b32 + v_cmp_ne_u32)
+            const uint64_t accepted = ballot(serving) & ballot(len2(p) < 1.0);
+            // The first accepted candidate of every group, in stream order, answers its request in the slot it was read
+            // from (after that read: one wave's LDS accesses complete in order, and the empty asm keeps the compiler from
+            // moving the double stores above the word loads).
+            asm volatile("" ::: "memory");
+            if (__builtin_amdgcn_inverse_ballot_w64(lowest_in_groups(accepted, lg))) {
+                double *const answer = reinterpret_cast<double *>(served);
+                answer[0] = p.x;
+                answer[1] = p.y;
+                answer[2] = p.z;
+            }
+            asm volatile("" ::: "memory"); // (and the answers' loads below them)
+            // did my own request get one?  (a ballot of the comparison, ANDed with `pending` = ballot(need) as scalars)
+            const int first = need ? (rank << lg) : 0;
+            const uint64_t width_mask = lg == 6 ? ~0ull : ((1ull << (1 << lg)) - 1ull);
+            const uint64_t got = pending & ballot(((accepted >> first) & width_mask) != 0);
+            // every lane reads a slot: what it finds means nothing to a lane that got none
+            const double *const answer = reinterpret_cast<const double *>(slot + (need ? rank : 0));
+            cand = mk(answer[0], answer[1], answer[2]);
+            take = got;
+            have |= got;
+            pending &= ~got; // the lanes still searching
+            if (__builtin_amdgcn_inverse_ballot_w64(pending)) base += 1u << lg;
+        }
+        if (round == 0) {
+            result = cand;
+        } else {
+            move_masked(cand, take, result);
+        }
+    }
+    return have;
+}
+
+// util.rs:25-39 random_in_unit_disk for every lane with `need`, same scheme: one
+// Philox block per candidate (block i -> x, y), first accepted candidate in stream
+// order.  Runs until every request is settled (a fresh path needs its ray now).
+__device__ __forceinline__ void coop_random_in_unit_disk(bool need, uint32_t pixel, uint32_t sample, uint32_t k0,
+                                                         uint32_t k1, int lane, Req4 *req, double &out_x,
+                                                         double &out_y) {
+    uint32_t base = 0;
+    uint64_t pending = ballot(need);
+    while (pending != 0) {
+        const int n = __popcll(pending);
+        const int lg = n > 32 ? 0 : (n > 16 ? 1 : (n > 8 ? 2 : (n > 4 ? 3 : (n > 2 ? 4 : (n > 1 ? 5 : 6)))));
+        if (lg == 0) { // one candidate per request: every lane tests its own (the usual first round of a batch)
+            if (need) {
+                const u4 b = philox4x32(pixel, sample, RT_RNG_LENS, base, k0, k1);
+                const double x = sym53(b.a, b.b), y = sym53(b.c, b.d);
+                if (x * x + y * y < 1.0) {
+                    out_x = x;
+                    out_y = y;
+                    need = false;
+                } else {
+                    base += 1u;
+                }
+            }
+            pending = ballot(need);
+            continue;
+        }
+        const int rank = lane_rank(pending);
+        if (need) req[rank] = Req4{pixel, sample, 0u, base};
+        const int j = lane >> lg;
+        const int c = lane & ((1 << lg) - 1);
+        const bool serving = j < n;
+        const Req4 r = req[serving ? j : 0];
+        const u4 b = philox4x32(r.x, r.y, RT_RNG_LENS, r.w + (uint32_t)c, k0, k1);
+        const double x = sym53(b.a, b.b), y = sym53(b.c, b.d);
+        const uint64_t accepted = ballot(serving && x * x + y * y < 1.0);
+        const int first = need ? (rank << lg) : 0;
+        const uint64_t width_mask = lg == 6 ? ~0ull : ((1ull << (1 << lg)) - 1ull);
+        const uint64_t mine = need ? ((accepted >> first) & width_mask) : 0ull;
+        const bool got = mine != 0;
+        const int src = got ? first + __ffsll((unsigned long long)mine) - 1 : lane;
+        const double rx = shfl_d(x, src), ry = shfl_d(y, src);
+        if (got) {
+            out_x = rx;
+            out_y = ry;
+            need = false;
+        } else if (need) {
+            base += 1u << lg;
+        }
+        pending = ballot(need);
+    }
+}
+
+// SHADING SORTED BY COST: the one expensive texture.  A marble lookup (noise.rs:26-33, :98-109) is seven
+// octaves of eight gradient dots, ~900 VALU instructions, and in a wave of 64 paths it is typically wanted by
+// a handful of lanes at a time (noise_and_textures: <= 4 lanes in 60 % of the iterations that have one), so
+// evaluated where the hit is shaded it runs at ~6 % lane use.  Octaves are independent until they are
+// summed, so the wave evaluates them side by side instead: lanes note their lookup during shading
+// (texture_value_deferred), then — all 64 lanes, wave-uniform control flow — eight lookups per round take
+// eight lanes each, lane o of a group computes octave o (0.5^o * noise(2^o p), both scalings exact), and
+// the requester adds the terms in octave order like the reference's loop.  One round costs about what ONE
+// octave costs.  Every lookup goes through this code, so a value never depends on which lanes sat next to it.
+// Returns turb(p, depth) (noise.rs:98-109) to the lanes with `need`; must be called by the whole wave.
+__device__ __forceinline__ double coop_noise_turbulence(bool need, d3 p, int depth, int perlin, const TraceArgs &A,
+                                                        const Perlin *lds_perlin, int lane, NoiseSlots &S) {
+    double turb = 0.0;
+    const uint64_t pending = ballot(need);
+    const int n = __popcll(pending);
+    const int rank = lane_rank(pending);
+    const int j = lane >> 3, o8 = lane & 7; // this lane works on request j of the round, octave o8 (+ 8 per pass)
+    for (int r0 = 0; r0 < n; r0 += 8) {
+        const bool mine = need && rank >= r0 && rank < r0 + 8;
+        const int slot = rank - r0;
+        if (mine) {
+            S.p[slot][0] = p.x;
+            S.p[slot][1] = p.y;
+            S.p[slot][2] = p.z;
+            S.depth[slot] = depth;
+            S.perlin[slot] = perlin;
+        }
+        const bool serving = r0 + j < n;
+        const int dj = serving ? S.depth[j] : 0;
+        double accum = 0.0; // noise.rs:99
+        for (int ob = 0; ballot(serving && ob < dj) != 0; ob += 8) { // one pass unless a texture has more than 8 octaves
+            const int o = ob + o8;
+            double term = 0.0;
+            if (serving && o < dj) {
+                // noise.rs:103-106: temp_p doubles and weight halves per octave — powers of two, exact
+                const d3 q = mk(__builtin_ldexp(S.p[j][0], o), __builtin_ldexp(S.p[j][1], o), __builtin_ldexp(S.p[j][2], o));
+                const int pi = S.perlin[j];
+                const double nz = (lds_perlin != nullptr && pi == 0) ? perlin_noise<true>(*lds_perlin, q)
+                                                                     : perlin_noise<false>(A.perlins[pi], q);
+                term = __builtin_ldexp(nz, -o);
+            }
+            S.term[j][o8] = term;
+            if (mine) { // accum += weight * noise(temp_p), in octave order (absent octaves are +0.0)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) accum += S.term[slot][k];
+            }
+        }
+        if (mine) turb = fabs(accum); // noise.rs:108
+    }
+    return turb;
+}
+
+} // namespace RT_KNS

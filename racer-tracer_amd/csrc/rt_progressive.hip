@@ -146,40 +146,41 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
         if (rc2 != RT_OK) return rc2;
         RT_HIP(hipEventRecord(b.ev_pass_traced[slot], stream));
         if (k >= slots) RT_HIP(hipStreamWaitEvent(stream, b.ev_copied[slot], 0)); // device slot k % slots held pass k - slots's frame
-        // what the decision step of either estimator is told (rtdev::NeeDecide, rtdev::AdaptiveFold): the sums, the pass's
-        // frame slot, the tiles' state and lists, and where the pass ends in the chunk plan
-        auto fill_decision = [&](auto &f) {
-            memset(&f, 0, sizeof f);
-            f.running = b.accum.ptr;
-            f.squares = b.squares.ptr;
-            f.out = dev;
-            f.tile_stop = b.tile_stop.ptr;
-            f.tile_scale = b.tile_scale.ptr;
-            f.err_prev = b.tile_err.ptr + (size_t)((k + slots - 1) % slots) * n_tiles;
-            f.err = b.tile_err.ptr + (size_t)slot * n_tiles;
-            f.next_list = ad ? b.tile_lists.ptr + (size_t)((k + 1) & 1) * n_tiles : nullptr;
-            f.next_count = b.tile_counts.ptr + k;
-            f.width = p->width;
-            f.height = p->height;
-            f.tiles_x = tiles_x;
-            f.n_tiles = (int32_t)n_tiles;
-            f.samples_done = starts[(size_t)c1];
-            f.eligible = ad && c1 >= 4 && f.samples_done >= ad->params->min_samples && ad->params->threshold > 0.0;
-            f.scale = 1.0 / (double)f.samples_done; // what rtdev_launch_resolve (rt_render_frame_nee) and rtdev_launch_fold_chunks pass
-            f.inv_batches = c1 >= 2 ? 1.0 / (double)(c1 - 1) : 0.0;
-            f.threshold = ad ? ad->params->threshold : 0.0;
+        // what the decision step of either estimator is told (rtdev::TileDecision): the sums, the pass's frame slot, the
+        // tiles' state and lists, and where the pass ends in the chunk plan
+        auto decision = [&]() -> rtdev::TileDecision {
+            rtdev::TileDecision d;
+            memset(&d, 0, sizeof d);
+            d.running = b.accum.ptr;
+            d.squares = b.squares.ptr;
+            d.out = dev;
+            d.tile_stop = b.tile_stop.ptr;
+            d.tile_scale = b.tile_scale.ptr;
+            d.err_prev = b.tile_err.ptr + (size_t)((k + slots - 1) % slots) * n_tiles;
+            d.err = b.tile_err.ptr + (size_t)slot * n_tiles;
+            d.next_list = ad ? b.tile_lists.ptr + (size_t)((k + 1) & 1) * n_tiles : nullptr;
+            d.next_count = b.tile_counts.ptr + k;
+            d.width = p->width;
+            d.height = p->height;
+            d.tiles_x = tiles_x;
+            d.n_tiles = (int32_t)n_tiles;
+            d.chunks_done = c1;
+            d.samples_done = starts[(size_t)c1];
+            d.eligible = ad && c1 >= 4 && d.samples_done >= ad->params->min_samples && ad->params->threshold > 0.0;
+            d.scale = 1.0 / (double)d.samples_done; // what rtdev_launch_resolve (rt_render_frame_nee) and rtdev_launch_fold_chunks pass
+            d.inv_batches = c1 >= 2 ? 1.0 / (double)(c1 - 1) : 0.0;
+            d.threshold = ad ? ad->params->threshold : 0.0;
+            return d;
         };
         if (nee) { // the sums are where the pass left them: the frame slot and, adaptive, the tiles' decisions
-            rtdev::NeeDecide f;
-            fill_decision(f);
-            f.chunks_done = c1;
+            const rtdev::NeeDecide f = {decision()};
             RT_HIP(s->kernels->nee_decide(&f, stream));
         } else if (ad) {
             rtdev::AdaptiveFold f;
-            fill_decision(f);
+            memset(&f, 0, sizeof f);
+            f.d = decision();
             f.partial = b.partial.ptr;
             f.c0 = c0;
-            f.c1 = c1;
             for (size_t c = 0; c + 1 < starts.size(); ++c) f.inv_chunk[c] = 1.0 / (double)(starts[c + 1] - starts[c]);
             RT_HIP(s->kernels->fold_adaptive(&f, stream));
         } else {

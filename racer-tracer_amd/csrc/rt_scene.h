@@ -16,12 +16,13 @@
 // The trace kernels exist twice (rt_trace_common.h: ARITHMETIC): RT_ARITH_FAST, and RT_ARITH_REFERENCE behind *_exact.
 // Every launcher that has both flavours, ONCE: X(member of rtapi::Launchers, exported name, return type, parameters).  The
 // declarations of both flavours, the struct and its two tables (rt_scene_create.hip) are all expanded from this list.
-//   trace, resolve (rt_trace_kernel.hip): the v1 kernel and its resolve pass.
-//   pool_*, trace_pool, resolve_chunks, fold_* (rt_trace_pool_kernel.hip): the pooled kernel, the variant's resident blocks
-//     per CU and static LDS, the resolve and fold passes over its slices.
+//   trace (rt_trace_kernel.hip): the v1 kernel.
+//   pool_*, trace_pool (rt_trace_pool_kernel.hip): the pooled kernel, the variant's resident blocks per CU and static LDS.
+//   resolve, resolve_chunks, fold_* (rt_frame_kernels.hip): the resolve pass over per-pixel sums, the resolve and fold
+//     passes over the pooled kernel's slices (fold_adaptive with the tiles' decisions, rt_tile_decide.h).
 //   nee (rt_nee_kernel.hip): the whole frame's NEE samples into args->accum.
 //   nee_pass, nee_chunk, nee_decide (rt_nee_pass_kernel.hip): one chunk of the NEE estimator over listed tiles on top of
-//     args->accum, the batch-means update behind it and the decision step behind a pass.
+//     args->accum, the batch-means update behind it and the decision step behind a pass (rt_tile_decide.h).
 //   nee_stream* (rt_nee_stream_kernel.hip): the NEE estimator as ONE persistent launch of `blocks` blocks over args'
 //     region-ordered tile queue, every tile delivered into args->deliver_out; the variant's resident blocks per CU (the
 //     runtime's occupancy query); the chunk length the flavour was compiled with.
@@ -315,7 +316,7 @@ namespace rtapi {
 // ONE delivering launch that finishes its own pixels (out_device is ignored).  `cancel` is polled before every launch:
 // between the sample batches of the v1 kernel, between the chunk batches of the pooled one (whose waves also read the
 // scene's cancel word while `cancel` is armed).  Returns RT_ERR_CANCEL_EVENT when cancelled (callers map that to RT_OK).
-// out_col_step / out_cols: layout the RESOLVE pass of the two-pass path writes (rt_trace_pool_kernel.hip:
+// out_col_step / out_cols: layout the RESOLVE pass of the two-pass path writes (rt_frame_kernels.hip:
 // k_resolve_chunks_f64): the plain frame, or the tile stream's column layout.
 int enqueue_render(RtScene *s, const RtCamera *camera, const RtRenderParams *p, double *out_device,
                    hipStream_t stream, int batch, const Cancel &cancel, const Delivery *delivery = nullptr,

@@ -940,7 +940,7 @@ __device__ __forceinline__ d3 texture_value_full(const TraceArgs &A, const Perli
 // Texture::value in two steps for the pooled kernel.  Step 1 (per lane, inside the divergent shading
 // code): everything except the Perlin turbulence of a Noise texture; for a Noise texture the lane only
 // notes WHICH one (`noise_tex`, after a Checkered parent has picked its side) and returns zeros.
-// Step 2 (whole wave, coop_noise_turbulence in rt_trace_pool_kernel.hip) evaluates the turbulence of all
+// Step 2 (whole wave, coop_noise_turbulence in rt_pool_coop.h) evaluates the turbulence of all
 // noted lookups together, and noise_colour() finishes noise.rs:26-33.
 // texture/image.rs:28-51: the cell of a width x height grid that (u, v) selects (v flipped, both clamped)
 __device__ __forceinline__ void image_cell(double u, double v, int width, int height, uint32_t &xi, uint32_t &yj) {

@@ -3,7 +3,7 @@
 // (see DESIGN.md 4.2).  Kept as the simple, order-exact reference form of the
 // device path (per-pixel sums in the oracle's sample order) and for A/B
 // measurements against the pooled kernel of rt_trace_pool_kernel.hip, which is
-// the default.  Selected with RtSceneOptions.kernel = RT_KERNEL_V1 (rt_scene_create_ex).
+// the default (its resolve pass: rt_frame_kernels.hip).  Selected with RtSceneOptions.kernel = RT_KERNEL_V1 (rt_scene_create_ex).
 #include "rt_trace_common.h"
 #include "rt_variant_dispatch.h"
 
@@ -201,20 +201,6 @@ __global__ __launch_bounds__(256) void k_trace_f64(const TraceArgs A) {
     if (lane == 0 && started) atomicAdd(A.segments + RT_STAT_SAMPLES, started);
 }
 
-// vec3.rs:119-125 scale_sqrt over the owned rows: out = sqrt(accum / samples)
-__global__ __launch_bounds__(256) void k_resolve_f64(const double *__restrict__ accum, double *__restrict__ out,
-                                                     int width, int height, int strip_rows, int strip_count,
-                                                     int strip_index, double scale) {
-    size_t n = (size_t)width * (size_t)height * 3;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        if (strip_count > 1) {
-            int row = (int)(i / ((size_t)width * 3));
-            if ((row / strip_rows) % strip_count != strip_index) continue;
-        }
-        out[i] = sqrt(scale * accum[i]);
-    }
-}
-
 } // namespace RT_KNS
 
 namespace {
@@ -238,17 +224,5 @@ extern "C" hipError_t RT_LAUNCHER(rtdev_launch_trace)(const rtdev::TraceArgs *ar
     rtdev::dispatch_variant<TraceVariant>(prims_class, textured != 0, specular != 0, false, [&](auto v) {
         decltype(v)::launch(*args, blocks, stream);
     });
-    return hipGetLastError();
-}
-
-extern "C" hipError_t RT_LAUNCHER(rtdev_launch_resolve)(const double *accum, double *out, int width, int height,
-                                           int strip_rows, int strip_count, int strip_index, int samples,
-                                           hipStream_t stream) {
-    size_t n = (size_t)width * (size_t)height * 3;
-    unsigned blocks = (unsigned)((n + 255) / 256);
-    if (blocks > 2048u) blocks = 2048u;
-    if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(RT_KNS::k_resolve_f64, dim3(blocks), dim3(256), 0, stream, accum, out, width, height,
-                       strip_rows, strip_count, strip_index, 1.0 / (double)samples);
     return hipGetLastError();
 }

@@ -76,6 +76,10 @@
 #include <type_traits>
 #include "rt_trace_common.h"
 #include "rt_variant_dispatch.h"
+#include "rt_pool_profile.h"
+#include "rt_pool_lds.h"
+#include "rt_pool_coop.h"
+#include "rt_pool_deliver.h"
 
 #ifndef RT_OCC_TEX
 #define RT_OCC_TEX 4 // textured spheres-only / rects-only variants: 40 KB of LDS per block still fits four (C4 +3 %)
@@ -98,521 +102,6 @@
                        // items (its live ranges then end at the path loop's exit: 73); the bound keeps the allocator there.
 #endif
 namespace RT_KNS {
-
-// -DRT_PROFILE_REGIONS: developer build that accumulates the shader-clock cycles each wave
-// spends per region of the path loop into A.segments[RT_STAT_REGIONS..]; rt_scene_last_stats prints them
-// (tools/region_profile.sh).  Not part of the product build.
-#ifdef RT_PROFILE_REGIONS
-// rt_t_[0..15] region cycles, [16] the previous marker, [17..34] the two lane histograms, [35..36] noise counts
-#define RT_REGION_DECL                                                          \
-    __shared__ unsigned long long rt_t_all_[4][56];                             \
-    unsigned long long *rt_t_ = rt_t_all_[threadIdx.x >> 6];                    \
-    if ((threadIdx.x & 63) < 56) rt_t_[threadIdx.x & 63] = 0;                   \
-    if ((threadIdx.x & 63) == 16) rt_t_[16] = __builtin_readcyclecounter();   \
-    const unsigned long long rt_wave_start_ = wall_clock64();
-// usable inside divergent code: the first ACTIVE lane books the time since the previous marker
-#define RT_REGION(k)                                                            \
-    do {                                                                        \
-        const unsigned long long act_ = ballot(1);                            \
-        if (lane_rank(act_) == 0) {                                             \
-            const unsigned long long now_ = __builtin_readcyclecounter();       \
-            rt_t_[k] += now_ - rt_t_[16];                                       \
-            rt_t_[40 + (k)] += (now_ - rt_t_[16]) * (unsigned long long)__popcll(act_); \
-            rt_t_[16] = now_;                                                   \
-        }                                                                       \
-    } while (0)
-/* lanes tracing this iteration (wave-uniform n), booked while the pool has entries / in the item's tail */ \
-#define RT_LANES(n, tail)                                                       \
-    do {                                                                        \
-        const int n_ = (n); /* the ballot needs every lane */                   \
-        if (lane == 0) rt_t_[17 + ((tail) ? 9 : 0) + (n_ + 7) / 8] += 1;        \
-    } while (0)
-#define RT_REGION_FLUSH                                                         \
-    if (lane < 16) atomicAdd(A.segments + RT_STAT_REGIONS + lane, rt_t_[lane]); \
-    if (lane < 18) atomicAdd(A.segments + RT_STAT_LANES_BODY + lane, rt_t_[17 + lane]); \
-    if (lane < 4) atomicAdd(A.segments + RT_STAT_NOISE + lane, rt_t_[35 + lane]); \
-    if (lane < 16) atomicAdd(A.segments + RT_STAT_REGION_LANES + lane, rt_t_[40 + lane]); \
-    if (lane == 0) { /* wall clock (100 MHz) of the first/last wave start and end */ \
-        const unsigned long long end_ = wall_clock64();                         \
-        atomicMin(A.segments + RT_STAT_WALL + 0, rt_wave_start_);               \
-        atomicMax(A.segments + RT_STAT_WALL + 1, rt_wave_start_);               \
-        atomicMin(A.segments + RT_STAT_WALL + 2, end_);                         \
-        atomicMax(A.segments + RT_STAT_WALL + 3, end_);                         \
-    }
-#else
-#define RT_REGION_DECL
-#ifdef RT_ISA_MARKERS // `make isa`: the region boundaries as comments in the assembly listing (tools/isa_regions.py)
-#define RT_REGION(k) asm volatile("; ==== end of region " #k);
-#else
-#define RT_REGION(k)
-#endif
-#define RT_LANES(n, tail)
-#define RT_REGION_FLUSH
-#endif
-
-__device__ __forceinline__ int lane_rank(uint64_t mask) { // set bits of `mask` below this lane
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-// Request slots of the wave-cooperative Perlin turbulence (coop_noise_turbulence): eight lookups per
-// round, eight lanes each.
-struct NoiseSlots {
-    double p[8][3];    // hit point of the lookup
-    int depth[8];      // its texture's octave count (noise.rs:28)
-    int perlin[8];     // ... and gradient table
-    double term[8][8]; // 0.5^o * noise(2^o * p) of the round's octaves, summed in order by the requester
-};
-// A request of the lens-disk sampler: {pixel, sample, 0, next candidate}
-struct alignas(16) Req4 { // one 128-bit LDS access
-    uint32_t x, y, z, w;
-};
-// A request of the sphere sampler: the scatter prefix of (pixel, sample, segment) and the next candidate.  After the
-// round's ballot the same 24 bytes carry the answer back: the first accepted candidate of the group that served the slot
-// writes its three coordinates over the request, and the requester reads them from there.
-struct alignas(8) SphereSlot {
-    uint32_t b, y, x, w, z, base;
-};
-static_assert(sizeof(SphereSlot) == 3 * sizeof(double), "a slot holds the request or the sample");
-// Posts a sphere sampler request as six 32-bit LDS stores.  Wider stores want the values in consecutive VGPRs: pixel,
-// sample and candidate were then copied into such a quad in every iteration (v_mov_b32 around every round), and the
-// stores cost the LDS pipe, which the path loop barely uses, instead of the vector one.  (Relaxed atomic stores: plain
-// ones are merged back into wider stores.)
-__device__ __forceinline__ void post_request(SphereSlot *slot, const ScatterPrefix &P, uint32_t base) {
-    __hip_atomic_store(&slot->b, P.b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    __hip_atomic_store(&slot->y, P.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    __hip_atomic_store(&slot->x, P.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    __hip_atomic_store(&slot->w, P.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    __hip_atomic_store(&slot->z, P.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    __hip_atomic_store(&slot->base, base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-// v = p in the lanes of `mask`, in v's own registers.  Written in C++, a masked write of the sphere sampler's `result` is a
-// branch around it, and the compiler copied `result` on both sides of the branch and back at the join; this does the
-// masking itself, so to the compiler it is an unconditional update of `v` in place.
-__device__ __forceinline__ void move_masked(const d3 &p, uint64_t mask, d3 &v) {
-    uint64_t saved;
-    asm volatile("s_and_saveexec_b64 %[saved], %[mask]\n\t"
-                 "v_mov_b64 %[x], %[px]\n\t"
-                 "v_mov_b64 %[y], %[py]\n\t"
-                 "v_mov_b64 %[z], %[pz]\n\t"
-                 "s_mov_b64 exec, %[saved]"
-                 : [x] "+v"(v.x), [y] "+v"(v.y), [z] "+v"(v.z), [saved] "=&s"(saved)
-                 : [mask] "s"(mask), [px] "v"(p.x), [py] "v"(p.y), [pz] "v"(p.z)
-                 : "scc");
-}
-// v += 1 in the lanes of `mask` (wave-uniform), as one add with the mask as its carry-in; written in C++ it is a select of
-// 0 / 1 (v_cndmask_b32) and an add.
-__device__ __forceinline__ void increment_masked(uint32_t &v, uint64_t mask) {
-    asm("v_addc_co_u32 %[v], vcc, 0, %[v], %[mask]" : [v] "+v"(v) : [mask] "s"(mask) : "vcc");
-}
-// The lowest set bit of every group of 2^lg bits of x (1 <= lg <= 6), in the scalar unit: x & -x within each group, the
-// negation done per group as (~x without the groups' top bits) + 1 in every group, whose carry stops at the group's top
-// bit, XOR the top bits of ~x
-__device__ __forceinline__ uint64_t lowest_in_groups(uint64_t x, int lg) {
-    const int q = 1 << lg;
-    uint64_t low = 1; // bit 0 of every group, doubled out (a shift by 64 or more is one by 0, which adds nothing)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) low |= low << ((q << k) & 63);
-    const uint64_t top = low << (q - 1);
-    return x & (((~x & ~top) + low) ^ (~x & top));
-}
-// The sampler's request slots and the turbulence slots are never live at the same time (the Noise rounds of
-// an iteration end before its sampler rounds begin, and both finish with what they posted), so they share
-// their LDS: the textured variants — the BVH ones above all, whose node array already fills LDS to
-// three blocks per CU — cost no more LDS than the plain ones.
-// (A round of the samplers that has more than 32 requests open gives every lane its own candidate and touches no slot, so 32
-// slots are all they use; variants without textures have no Noise lookups to make room for.)
-template <bool TEXTURED> union SamplerScratch {
-    Req4 req[32];
-    SphereSlot sphere[32];
-    NoiseSlots noise;
-};
-template <> union SamplerScratch<false> {
-    Req4 req[32];
-    SphereSlot sphere[32];
-};
-
-// What the END of an item needs of it (finish_item), parked while the item's last paths are in flight and the wave already
-// hands out the next item's.
-struct alignas(16) ItemInfo {
-    int chunk, tx, ty, tile_py0, region, reg_tiles, rows_aligned, _pad;
-};
-
-// Per-wave scratch in LDS.  HAS_TIME: the scene has MovingSpheres (PRIMS_ANY variants).
-// NBUF: batches of camera samples kept (2, or 1 for the BVH variants, whose node array wants the LDS).
-// The lens-disk samples of a batch (16 B per entry) are NOT in here: only a camera with an aperture draws them, and
-// without their 8 KB per block the plain variants fit six blocks per CU instead of five (cornell 85.2 -> 82.1 ms).
-// They live behind everything else in DYNAMIC LDS, which the launch sizes by the camera (TraceArgs.lens_lds).
-// OVERLAP: the variant keeps two items in flight (see SUMS AND OVERLAPPED ITEMS in the kernel): two sets of sums, and — to pay
-// for them — the per-pixel `base` vector is replaced by the jitter it is made of.
-template <bool TEXTURED, int NBUF, bool OVERLAP> struct WaveLds {
-    // per pixel of the CURRENT item's tile (the one entries are handed out of): upper_left_corner + u * horizontal with the
-    // pixel's ONE horizontal jitter u = (px + ju) / (W - 1) (cpu.rs:35-36, camera.rs:331) — or, OVERLAP, just u: the
-    // hand-out then forms the vector (three fma and a read of `ulc` per iteration for 1 KB)
-    double base[OVERLAP ? 1 : 64][3];
-    double u[OVERLAP ? 64 : 1];
-    // per-pixel radiance sums: doubles — or, OVERLAP, 64-bit fixed-point integers (TraceArgs.sum_scale) of the (up to) two
-    // items in flight: slot s, pixel p at [s * 64 + p]
-    double sum[OVERLAP ? 128 : 64][3];
-    SamplerScratch<TEXTURED> scratch; // cooperative sampler requests / Noise lookups
-    uint8_t pix_of[64]; // pool slot -> lane-order pixel index, for tiles cut by the image edge (current item)
-    // Camera samples of the pool entries, drawn 64 entries at a time by the WHOLE wave
-    // (prepare_batch below): entry w sits in slot w & 63 of buffer (w >> 6) & (NBUF - 1).
-    double v[NBUF][64];        // (py + jv) / (H - 1)                      cpu.rs:39-40
-    ItemInfo info[2];
-    // camera.upper_left_corner, for the hand-out: v_fma_f64 reads ONE scalar operand, so of upper_left_corner + u * horizontal
-    // one vector has to come from vector registers — copied there with six v_mov_b32 per iteration, or read from here
-    double ulc[3];
-};
-
-// Survivors a camera batch of the PRETRACE variant may park (see PRIMARY SEGMENTS IN THE BATCHES in the kernel): a batch
-// adds up to 64 and runs when at most RING_SLOTS - 64 are waiting.
-enum : uint32_t { RING_SLOTS = 92u };
-// Per-wave scratch of the PRETRACE variant (rects only, no textures, no specular materials): the members of WaveLds that
-// variant reads, under the same names, and the ring of pool entries whose primary segment a batch has traced and that
-// live on.  An entry keeps what its ray is formed from (v; the pixel's u stays in `u`) and its first hit: 22 bytes, where
-// the ray itself would take 48.  WaveLds' `base` and `v` have no counterpart (the ray is formed from u and the ring's v);
-// with them gone the block has 20 096 bytes of static LDS, 64 fewer than before, and seven blocks still fit a CU beside
-// C3's primitive table (the seven-block edge is 23 040 bytes).  The lens samples of the ring's entries sit in the dynamic
-// LDS that holds the two batches' in the other variants (128 slots per wave).
-struct PretraceLds {
-    // camera.origin and background.top, for the same reason as `ulc` below: a rect test and an LDS add take their
-    // operands from vector registers, and an LDS read puts them there without a vector instruction
-    double cam_origin[3], bg_top[3];
-    double u[64];      // per pixel of the tile: (px + ju) / (W - 1)
-    double sum[64][3]; // per-pixel radiance sums (doubles)
-    SamplerScratch<false> scratch;
-    uint8_t pix_of[64];
-    double ring_v[RING_SLOTS];     // (py + jv) / (H - 1) of the entry
-    double ring_t[RING_SLOTS];     // its primary hit: ray parameter ...
-    uint32_t ring_w[RING_SLOTS];   // (its index in the item's pool)
-    uint16_t ring_best[RING_SLOTS]; // ... and primitive (the table is staged in LDS, 192 bytes a record: under 1 000 records)
-    uint32_t n_started;            // paths this wave has started (RtRenderStats.samples): every entry of every batch
-    ItemInfo info[1]; // (one item at a time)
-    double ulc[3];
-};
-
-// The closest-hit loop of the rects-only variants over the grouped table (XY, XZ, YZ rects, in that order: record order,
-// strict `t < best_t`), one straight-line test per group with the plane a compile-time constant.  PAIRS: two records per
-// scalar-load wait (what the path loop runs); without, one test site per plane (the camera batches: every site is a copy
-// of the rect test in the kernel's text).
-template <bool PAIRS>
-__device__ __forceinline__ void closest_hit_rects(const Prim *table, const d3 &o, const d3 &d, const d3 &inv_d, double &best_t, int &best) {
-    auto test_plane = [&](auto axis, const Prim &P, int i) {
-#ifndef RT_EXACT_DIV
-        rect_closest_update<decltype(axis)::value>(P.p[0], P.p[1], P.p[2], P.p[3], P.p[4], o, d, inv_d, 0.001, best_t, best, i);
-        return;
-#endif
-        double t;
-        if (rect_t<true>(decltype(axis)::value, P.p[0], P.p[1], P.p[2], P.p[3], P.p[4], o, d, inv_d, 0.001, best_t, t)) {
-            best_t = t;
-            best = i;
-        }
-    };
-    const Prim *rec = table; // ONE pointer runs through the groups (they follow each other in the table)
-    int i = 0;
-    auto group = [&](auto axis, int end) {
-        if (PAIRS) {
-            for (; i + 1 < end; i += 2, rec += 2) {
-                const Prim pa = load_prim_uniform(rec, 0), pb = load_prim_uniform(rec, 1);
-                test_plane(axis, pa, i);
-                test_plane(axis, pb, i + 1);
-            }
-            if (i < end) {
-                test_plane(axis, load_prim_uniform(rec, 0), i);
-                ++i;
-                ++rec;
-            }
-        } else {
-            for (; i < end; ++i, ++rec) test_plane(axis, load_prim_uniform(rec, 0), i);
-        }
-    };
-    // (the group bounds are re-read from the kernel arguments here: see the path loop of the other variants)
-    const RT_CONSTANT TraceArgs *KB = kernargs_here();
-    const int end_xy = KB->rect_end[0], end_xz = KB->rect_end[1], end_yz = KB->rect_end[2];
-    group(std::integral_constant<int, 2>(), end_xy); // XY
-    group(std::integral_constant<int, 1>(), end_xz); // XZ
-    group(std::integral_constant<int, 0>(), end_yz); // YZ
-}
-
-// vec3.rs:424-430 for every lane of `pending` (a wave-uniform lane mask, like the one it returns: the lanes
-// that got their sample), evaluated by the whole wave.
-// Must be called by all 64 lanes (wave-uniform control flow).  Runs at most
-// MAX_ROUNDS rounds: a lane whose request is still open afterwards is not in the
-// returned mask and keeps `base` (its first untested candidate), so the search resumes
-// at the same stream position in the next call.
-// The round count is a template constant: two rounds (the plain variants) are unrolled into straight-line code.  The
-// first round writes `result` in EVERY lane (no lane holds a sample yet), so only the later rounds write it under the
-// mask of the lanes still searching — a masked write is a copy of the old value at the join (C3 -0.8 %); both kinds of
-// round end in ONE such write (move_masked), after their branches have joined.
-// Every candidate is drawn from the scatter prefix of its request (philox_from_prefix): each lane forms its own once per
-// call, and a grouped round posts it, so a candidate costs 10 multiplies instead of 14.  A grouped round's answer comes
-// back through the request's slot, not through lane shuffles.
-template <int MAX_ROUNDS>
-__device__ __forceinline__ uint64_t coop_random_in_unit_sphere(uint64_t pending, uint32_t pixel, uint32_t sample, uint32_t seg,
-                                                           uint32_t &base, uint32_t k0, uint32_t k1, int lane,
-                                                           SphereSlot *slot, d3 &result) {
-    uint64_t have = 0;
-    const ScatterPrefix own = scatter_prefix(pixel, sample, seg, k0, k1);
-    for (int round = 0; round < MAX_ROUNDS && pending != 0; ++round) {
-        const int n = __popcll(pending);
-        // a round costs the whole wave ~70 instructions; past the first it only runs while enough requests are
-        // open to be worth that (the others resume next iteration): C2 +2.2 %, C3 +0.3 % (thresholds 2..16 and one to
-        // six rounds measured again with one-block candidates: 8 and two rounds stay)
-        if (round > 0 && n < 8) break;
-        // group size q = 2^lg, the largest power of two with n * q <= 64
-        const int lg = n > 32 ? 0 : (n > 16 ? 1 : (n > 8 ? 2 : (n > 4 ? 3 : (n > 2 ? 4 : (n > 1 ? 5 : 6)))));
-        // what `result` takes: in every lane in the first round, in the lanes of `take` in the later ones.  `result` only
-        // means something to a lane of the returned mask, so a lane that still needs a sample may take whatever its round
-        // left it, a rejected candidate included.
-        d3 cand;
-        uint64_t take;
-        if (lg == 0) { // more than 32 requests: one candidate each, so every lane tests its OWN (no LDS)
-            const d3 p = sphere_candidate(philox_from_prefix(own, base, k0, k1));
-            cand = p;
-            take = pending;
-            const uint64_t inside = ballot(len2(p) < 1.0); // (the comparison's own lane mask)
-            have |= pending & inside;
-            pending &= ~inside;
-            if (__builtin_amdgcn_inverse_ballot_w64(pending)) base += 1u;
-        } else {
-            const bool need = __builtin_amdgcn_inverse_ballot_w64(pending);
-            const int rank = lane_rank(pending);
-            if (need) post_request(slot + rank, own, base);
-            const int j = lane >> lg;              // request served by this lane
-            const int c = lane & ((1 << lg) - 1);  // candidate offset inside the group
-            const bool serving = j < n;
-            SphereSlot *const served = slot + (serving ? j : 0);
-            const ScatterPrefix r = {served->b, served->y, served->x, served->w, served->z};
-            const uint32_t i = served->base + (uint32_t)c; // candidate index = its block (rt_rng.h)
-            const d3 p = sphere_candidate(philox_from_prefix(r, i, k0, k1));
-            // (ballots of the two comparisons, ANDed as scalars: a ballot of `serving && ...` is a lane mask turned into an
-            // integer and back, v_cndmask_b32 + v_cmp_ne_u32)
-            const uint64_t accepted = ballot(serving) & ballot(len2(p) < 1.0);
-            // The first accepted candidate of every group, in stream order, answers its request in the slot it was read
-            // from (after that read: one wave's LDS accesses complete in order, and the empty asm keeps the compiler from
-            // moving the double stores above the word loads).
-            asm volatile("" ::: "memory");
-            if (__builtin_amdgcn_inverse_ballot_w64(lowest_in_groups(accepted, lg))) {
-                double *const answer = reinterpret_cast<double *>(served);
-                answer[0] = p.x;
-                answer[1] = p.y;
-                answer[2] = p.z;
-            }
-            asm volatile("" ::: "memory"); // (and the answers' loads below them)
-            // did my own request get one?  (a ballot of the comparison, ANDed with `pending` = ballot(need) as scalars)
-            const int first = need ? (rank << lg) : 0;
-            const uint64_t width_mask = lg == 6 ? ~0ull : ((1ull << (1 << lg)) - 1ull);
-            const uint64_t got = pending & ballot(((accepted >> first) & width_mask) != 0);
-            // every lane reads a slot: what it finds means nothing to a lane that got none
-            const double *const answer = reinterpret_cast<const double *>(slot + (need ? rank : 0));
-            cand = mk(answer[0], answer[1], answer[2]);
-            take = got;
-            have |= got;
-            pending &= ~got; // the lanes still searching
-            if (__builtin_amdgcn_inverse_ballot_w64(pending)) base += 1u << lg;
-        }
-        if (round == 0) {
-            result = cand;
-        } else {
-            move_masked(cand, take, result);
-        }
-    }
-    return have;
-}
-
-// util.rs:25-39 random_in_unit_disk for every lane with `need`, same scheme: one
-// Philox block per candidate (block i -> x, y), first accepted candidate in stream
-// order.  Runs until every request is settled (a fresh path needs its ray now).
-__device__ __forceinline__ void coop_random_in_unit_disk(bool need, uint32_t pixel, uint32_t sample, uint32_t k0,
-                                                         uint32_t k1, int lane, Req4 *req, double &out_x,
-                                                         double &out_y) {
-    uint32_t base = 0;
-    uint64_t pending = ballot(need);
-    while (pending != 0) {
-        const int n = __popcll(pending);
-        const int lg = n > 32 ? 0 : (n > 16 ? 1 : (n > 8 ? 2 : (n > 4 ? 3 : (n > 2 ? 4 : (n > 1 ? 5 : 6)))));
-        if (lg == 0) { // one candidate per request: every lane tests its own (the usual first round of a batch)
-            if (need) {
-                const u4 b = philox4x32(pixel, sample, RT_RNG_LENS, base, k0, k1);
-                const double x = sym53(b.a, b.b), y = sym53(b.c, b.d);
-                if (x * x + y * y < 1.0) {
-                    out_x = x;
-                    out_y = y;
-                    need = false;
-                } else {
-                    base += 1u;
-                }
-            }
-            pending = ballot(need);
-            continue;
-        }
-        const int rank = lane_rank(pending);
-        if (need) req[rank] = Req4{pixel, sample, 0u, base};
-        const int j = lane >> lg;
-        const int c = lane & ((1 << lg) - 1);
-        const bool serving = j < n;
-        const Req4 r = req[serving ? j : 0];
-        const u4 b = philox4x32(r.x, r.y, RT_RNG_LENS, r.w + (uint32_t)c, k0, k1);
-        const double x = sym53(b.a, b.b), y = sym53(b.c, b.d);
-        const uint64_t accepted = ballot(serving && x * x + y * y < 1.0);
-        const int first = need ? (rank << lg) : 0;
-        const uint64_t width_mask = lg == 6 ? ~0ull : ((1ull << (1 << lg)) - 1ull);
-        const uint64_t mine = need ? ((accepted >> first) & width_mask) : 0ull;
-        const bool got = mine != 0;
-        const int src = got ? first + __ffsll((unsigned long long)mine) - 1 : lane;
-        const double rx = shfl_d(x, src), ry = shfl_d(y, src);
-        if (got) {
-            out_x = rx;
-            out_y = ry;
-            need = false;
-        } else if (need) {
-            base += 1u << lg;
-        }
-        pending = ballot(need);
-    }
-}
-
-// SHADING SORTED BY COST: the one expensive texture.  A marble lookup (noise.rs:26-33, :98-109) is seven
-// octaves of eight gradient dots, ~900 VALU instructions, and in a wave of 64 paths it is typically wanted by
-// a handful of lanes at a time (noise_and_textures: <= 4 lanes in 60 % of the iterations that have one), so
-// evaluated where the hit is shaded it runs at ~6 % lane use.  Octaves are independent until they are
-// summed, so the wave evaluates them side by side instead: lanes note their lookup during shading
-// (texture_value_deferred), then — all 64 lanes, wave-uniform control flow — eight lookups per round take
-// eight lanes each, lane o of a group computes octave o (0.5^o * noise(2^o p), both scalings exact), and
-// the requester adds the terms in octave order like the reference's loop.  One round costs about what ONE
-// octave costs.  Every lookup goes through this code, so a value never depends on which lanes sat next to it.
-// Returns turb(p, depth) (noise.rs:98-109) to the lanes with `need`; must be called by the whole wave.
-__device__ __forceinline__ double coop_noise_turbulence(bool need, d3 p, int depth, int perlin, const TraceArgs &A,
-                                                        const Perlin *lds_perlin, int lane, NoiseSlots &S) {
-    double turb = 0.0;
-    const uint64_t pending = ballot(need);
-    const int n = __popcll(pending);
-    const int rank = lane_rank(pending);
-    const int j = lane >> 3, o8 = lane & 7; // this lane works on request j of the round, octave o8 (+ 8 per pass)
-    for (int r0 = 0; r0 < n; r0 += 8) {
-        const bool mine = need && rank >= r0 && rank < r0 + 8;
-        const int slot = rank - r0;
-        if (mine) {
-            S.p[slot][0] = p.x;
-            S.p[slot][1] = p.y;
-            S.p[slot][2] = p.z;
-            S.depth[slot] = depth;
-            S.perlin[slot] = perlin;
-        }
-        const bool serving = r0 + j < n;
-        const int dj = serving ? S.depth[j] : 0;
-        double accum = 0.0; // noise.rs:99
-        for (int ob = 0; ballot(serving && ob < dj) != 0; ob += 8) { // one pass unless a texture has more than 8 octaves
-            const int o = ob + o8;
-            double term = 0.0;
-            if (serving && o < dj) {
-                // noise.rs:103-106: temp_p doubles and weight halves per octave — powers of two, exact
-                const d3 q = mk(__builtin_ldexp(S.p[j][0], o), __builtin_ldexp(S.p[j][1], o), __builtin_ldexp(S.p[j][2], o));
-                const int pi = S.perlin[j];
-                const double nz = (lds_perlin != nullptr && pi == 0) ? perlin_noise<true>(*lds_perlin, q)
-                                                                     : perlin_noise<false>(A.perlins[pi], q);
-                term = __builtin_ldexp(nz, -o);
-            }
-            S.term[j][o8] = term;
-            if (mine) { // accum += weight * noise(temp_p), in octave order (absent octaves are +0.0)
-#pragma unroll
-                for (int k = 0; k < 8; ++k) accum += S.term[slot][k];
-            }
-        }
-        if (mine) turb = fabs(accum); // noise.rs:108
-    }
-    return turb;
-}
-
-// DELIVERY: what a delivering launch does at the end of an item (rt_device_types.h: TraceArgs.deliver_out).  Out of
-// line on purpose: inlined, its address arithmetic and loads raised the register count of the whole path loop
-// (80 -> 89 VGPRs in the plain variants, i.e. five blocks per CU instead of six).
-__device__ __noinline__ void deliver_item(const RT_CONSTANT TraceArgs *K_in, double sum0, double sum1, double sum2, bool my_valid, int chunk,
-                                          int tx, int ty, int tile_py0, bool rows_aligned, int region, uint32_t reg_tiles) {
-    const int lane = threadIdx.x & 63;
-    const RT_CONSTANT TraceArgs *K;
-    // K: the launch's own argument block in the kernarg segment, handed in by the kernel (a by-reference copy of `A` would
-    // live in scratch, and llvm.amdgcn.kernarg.segment.ptr is NULL outside a kernel).  Function arguments travel in
-    // VGPRs; readfirstlane tells the backend that this one is wave-uniform, so its fields come by scalar loads.
-    {
-        const uint64_t bits = (uint64_t)K_in;
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
-        K = (const RT_CONSTANT TraceArgs *)(((uint64_t)hi << 32) | lo);
-    }
-    chunk = __builtin_amdgcn_readfirstlane(chunk);
-    tx = __builtin_amdgcn_readfirstlane(tx);
-    ty = __builtin_amdgcn_readfirstlane(ty);
-    tile_py0 = __builtin_amdgcn_readfirstlane(tile_py0);
-    region = __builtin_amdgcn_readfirstlane(region);
-    reg_tiles = (uint32_t)__builtin_amdgcn_readfirstlane((int)reg_tiles);
-    {
-        const size_t slice = (size_t)K->slice_rows * (size_t)K->width * 3; // a slice holds the launch's owned rows only
-        // (pixel coordinates are formed again here rather than kept in registers across the path loop)
-        const int out_px = (tx * 8 + (lane & 7)) * K->step_x;
-        int out_py = tile_py0 + (lane >> 3) * K->step_y;
-        if (!rows_aligned) {
-            const int vrow = ty * 8 + (lane >> 3);
-            out_py = ((vrow / K->strip_rows) * K->strip_count + K->strip_index) * K->strip_rows + vrow % K->strip_rows;
-        }
-        const size_t in_slice = ((size_t)(ty * 8 + (lane >> 3)) * (size_t)K->width + (size_t)out_px) * 3;
-        double *dst = K->partial + (size_t)(K->chunk_base + chunk) * slice + in_slice;
-        // ---- DELIVERY: the launch finishes its own pixels (rt_device_types.h: TraceArgs.deliver_out).
-        // The slices cross waves inside ONE launch here, and an XCD's L2 is not coherent with its seven neighbours':
-        // a device-scope release fence per item (L2 write-back + invalidate) was measured first and costs C2 12 %
-        // (profiles/r03_fence_probe.txt).  Instead the slice stores and loads are device-scope relaxed atomics —
-        // plain stores / loads with the sc1 bit, which write through to / read from the level all XCDs share — and
-        // s_waitcnt orders this wave's stores before its bump of the tile's counter: no cache maintenance at all.
-        if (my_valid) {
-            __hip_atomic_store(dst + 0, sum0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(dst + 1, sum1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(dst + 2, sum2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the stores have been acknowledged at device scope
-        const int tile_id = ty * K->tiles_x + tx;
-        uint32_t chunks_before = 0;
-        if (lane == 0) chunks_before = __hip_atomic_fetch_add(K->tile_done + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        chunks_before = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunks_before);
-        if ((int)chunks_before != K->total_chunks - 1) return;
-        // Every chunk of this tile has landed: vec3.rs:119-125 scale_sqrt over the slices in chunk order —
-        // exactly k_resolve_chunks_f64's sum, so the pixels are bit-identical to the two-pass path.
-        if (my_valid) {
-            const double *src = K->partial + in_slice;
-            double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
-#pragma unroll 1
-            for (int c = 0; c < K->total_chunks; ++c) {
-                acc0 += __hip_atomic_load(src + (size_t)c * slice + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                acc1 += __hip_atomic_load(src + (size_t)c * slice + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                acc2 += __hip_atomic_load(src + (size_t)c * slice + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            const double scale = 1.0 / (double)K->samples; // what rtdev_launch_resolve_chunks passes
-            // tile-column layout of the output (one column = the plain frame): column `col` starts at pixel column
-            // col * step and is stored as [height][its width][3] behind the columns before it
-            int col = out_px / K->deliver_col_step;
-            if (col > K->deliver_cols - 1) col = K->deliver_cols - 1;
-            const int col_x = col * K->deliver_col_step;
-            const int col_w = col == K->deliver_cols - 1 ? K->width - col_x : K->deliver_col_step;
-            double *out = K->deliver_out + ((size_t)K->height * (size_t)col_x + (size_t)out_py * (size_t)col_w + (size_t)(out_px - col_x)) * 3;
-            out[0] = sqrt(scale * acc0);
-            out[1] = sqrt(scale * acc1);
-            out[2] = sqrt(scale * acc2);
-        }
-        if (lane == 0) __hip_atomic_store(K->tile_done + tile_id, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // re-armed for the next launch on this scene (written through, like the slices)
-        // The pixels may sit in HOST memory: release them at system scope before this tile is counted (once per
-        // tile, 1/19 of the items on C3), and publish the region behind an acquire of the other waves' releases.
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-        uint32_t tiles_before = 0;
-        if (lane == 0) tiles_before = __hip_atomic_fetch_add(K->region_done + region, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tiles_before = (uint32_t)__builtin_amdgcn_readfirstlane((int)tiles_before);
-        if (tiles_before == reg_tiles - 1u) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            if (lane == 0) {
-                __hip_atomic_store(K->region_done + region, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(K->deliver_flags + region, K->deliver_serial, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
-}
 
 // BVH: closest hit through the skip-link hierarchy instead of the linear loop
 // (instantiated for PRIMS_ANY only; chosen for scenes with many primitives).
@@ -1796,154 +1285,6 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
     if (lane == 0 && started) atomicAdd(A.segments + RT_STAT_SAMPLES, started);
 }
 
-// vec3.rs:119-125 scale_sqrt over the owned rows: out = sqrt(sum over chunks / samples),
-// chunks added in index order.  With step_x/step_y > 1 (preview renderer) every pixel takes
-// the value of its block's top-left pixel and pixels outside the covered area are (0,0,0)
-// (cpu_scaled.rs:50-52, :80-89).  `out` is the plain [height][width][3] frame (out_cols == 1) or the tile-column layout
-// of the tile stream — column c of out_col_step pixels (the last takes the remainder, cpu.rs:97-109) stored as
-// [height][column width][3] behind the columns before it — so that a tile of rt_render is one contiguous run.
-__global__ __launch_bounds__(256) void k_resolve_chunks_f64(const double *__restrict__ partial, double *__restrict__ out,
-                                                            int width, int height, int n_chunks, int slice_rows, int strip_rows,
-                                                            int strip_count, int strip_index, int step_x, int step_y,
-                                                            int cover_w, int cover_h, int out_col_step, int out_cols,
-                                                            double scale) {
-    // a slice holds the launch's OWNED rows only (TraceArgs.slice_rows): with strips the pass walks those rows and maps
-    // each to its image row; the preview's slice rows are grid rows, read by every pixel of a block
-    const size_t slice = (size_t)width * (size_t)slice_rows * 3;
-    const size_t n = (size_t)width * (size_t)(strip_count > 1 ? slice_rows : height) * 3;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        size_t src = i, dst = i;
-        if (strip_count > 1 || step_x > 1 || step_y > 1 || out_cols > 1) {
-            const size_t pixel = i / 3;
-            const int ch = (int)(i - pixel * 3);
-            const int r = (int)(pixel / (size_t)width), col = (int)(pixel - (size_t)r * (size_t)width);
-            int row = r;
-            if (strip_count > 1) { // r is a row of the owned-row grid
-                row = ((r / strip_rows) * strip_count + strip_index) * strip_rows + r % strip_rows;
-                if (row >= height) continue;
-            }
-            dst = ((size_t)row * (size_t)width + (size_t)col) * 3 + ch;
-            if (out_cols > 1) {
-                int c = col / out_col_step;
-                if (c > out_cols - 1) c = out_cols - 1;
-                const int col_x = c * out_col_step;
-                const int col_w = c == out_cols - 1 ? width - col_x : out_col_step;
-                dst = ((size_t)height * (size_t)col_x + (size_t)row * (size_t)col_w + (size_t)(col - col_x)) * 3 + ch;
-            }
-            if (col >= cover_w || row >= cover_h) {
-                out[dst] = 0.0;
-                continue;
-            }
-            src = ((size_t)(r / step_y) * (size_t)width + (size_t)(col - col % step_x)) * 3 + ch;
-        }
-        double acc = 0.0;
-        for (int c = 0; c < n_chunks; ++c) acc += partial[(size_t)c * slice + src];
-        out[dst] = sqrt(scale * acc);
-    }
-}
-
-// One pass of a progressive frame (rt_progressive.hip): whole-frame slices (n = width * height * 3 elements each), the
-// slices [c0, c1) added to the running sums in index order and out = sqrt(scale * running), scale = 1 / samples so far.
-// `running` starts the frame at +0.0, so the passes together are k_resolve_chunks_f64's left fold over the same slices and
-// the last pass's frame is bit-identical to the one-shot frame.
-__global__ __launch_bounds__(256) void k_fold_chunks_f64(const double *__restrict__ partial, double *__restrict__ running,
-                                                         double *__restrict__ out, size_t n, int c0, int c1, double scale) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        double acc = running[i];
-        for (int c = c0; c < c1; ++c) acc += partial[(size_t)c * n + i];
-        running[i] = acc;
-        out[i] = sqrt(scale * acc);
-    }
-}
-
-// One pass of rt_render_adaptive (rt_progressive.hip; rtdev::AdaptiveFold): one wave per 8x8 tile, one lane per pixel,
-// 16 tiles to a block.
-// A running tile folds exactly as k_fold_chunks_f64 does — same left fold from +0.0, same sqrt(scale * acc) — so its
-// pixels are the progressive frame's bits.  Its error (include/rt_abi.h) is the largest over its pixels and channels of
-// e = sigma / (sqrt(m + sigma) + sqrt(m)) with m = S / s, V = max(0, Q - S m) / (k - 1) over the k chunks as batch means,
-// sigma = sqrt(V / s); e = 0 where sigma = 0, so a black pixel needs no floor.  A stopped tile rewrites its pixels from
-// its own scale: the same bits as at its stop, so every frame slot is whole without a copy between them.
-__global__ __launch_bounds__(1024) void k_fold_adaptive_f64(const AdaptiveFold F) {
-    // the tiles that run on are appended to the next list with ONE atomic per block of 16 tiles: one per tile, all on the
-    // same counter, serialised at L2 and cost 0.38 ms a pass on a 1080p frame
-    __shared__ uint32_t keep_of[16];
-    __shared__ uint32_t list_base;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = (int)blockIdx.x * 16 + wave; // wave-uniform
-    uint32_t keep = 0; // (lane 0) this wave's tile runs on
-    if (t < F.n_tiles) {
-        const int tx = t % F.tiles_x, ty = t / F.tiles_x;
-        const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
-        const bool valid = px < F.width && py < F.height;
-        const size_t n = (size_t)F.width * (size_t)F.height * 3;
-        const size_t i = valid ? ((size_t)py * (size_t)F.width + (size_t)px) * 3 : 0;
-        double acc[3] = {0.0, 0.0, 0.0}, q[3] = {0.0, 0.0, 0.0};
-        if (valid)
-            for (int ch = 0; ch < 3; ++ch) acc[ch] = F.running[i + ch];
-        const int stop = __builtin_amdgcn_readfirstlane(F.tile_stop[t]);
-        if (stop != 0) {
-            const double scale = F.tile_scale[t];
-            if (valid)
-                for (int ch = 0; ch < 3; ++ch) F.out[i + ch] = sqrt(scale * acc[ch]);
-            if (lane == 0) F.err[t] = F.err_prev[t];
-        } else {
-            double e_max = 0.0;
-            if (valid) {
-                for (int ch = 0; ch < 3; ++ch) q[ch] = F.squares[i + ch];
-                for (int c = F.c0; c < F.c1; ++c) {
-                    const double *src = F.partial + (size_t)c * n + i;
-                    const double v0 = src[0], v1 = src[1], v2 = src[2], inv = F.inv_chunk[c];
-                    acc[0] += v0;
-                    acc[1] += v1;
-                    acc[2] += v2;
-                    q[0] += v0 * v0 * inv;
-                    q[1] += v1 * v1 * inv;
-                    q[2] += v2 * v2 * inv;
-                }
-                for (int ch = 0; ch < 3; ++ch) {
-                    F.running[i + ch] = acc[ch];
-                    F.squares[i + ch] = q[ch];
-                    F.out[i + ch] = sqrt(F.scale * acc[ch]);
-                    if (F.c1 >= 2) { // (the error is compared to a threshold, not bit for bit: reciprocals from the host)
-                        const double m = acc[ch] * F.scale;
-                        const double var = fmax(0.0, q[ch] - acc[ch] * m) * F.inv_batches;
-                        const double sigma = sqrt(var * F.scale);
-                        const double e = sigma > 0.0 ? sigma / (sqrt(m + sigma) + sqrt(m)) : 0.0;
-                        e_max = e > e_max ? e : e_max;
-                    }
-                }
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                const double o = __shfl_xor(e_max, off, 64);
-                e_max = o > e_max ? o : e_max;
-            }
-            if (lane == 0) {
-                const double err = F.c1 >= 2 ? e_max : -1.0;
-                F.err[t] = err;
-                if (F.eligible && err <= F.threshold) {
-                    F.tile_stop[t] = F.samples_done;
-                    F.tile_scale[t] = F.scale;
-                } else {
-                    keep = 1u;
-                }
-            }
-        }
-    }
-    if (lane == 0) keep_of[wave] = keep;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t total = 0;
-        for (int w = 0; w < 16; ++w) total += keep_of[w];
-        list_base = total ? atomicAdd(F.next_count, total) : 0u;
-    }
-    __syncthreads();
-    if (lane == 0 && keep) {
-        uint32_t at = list_base;
-        for (int w = 0; w < wave; ++w) at += keep_of[w];
-        F.next_list[at] = (uint32_t)t;
-    }
-}
-
 } // namespace RT_KNS
 
 #if defined(RT_BB_COUNT) && !defined(RT_EXACT_DIV)
@@ -2014,39 +1355,5 @@ extern "C" hipError_t RT_LAUNCHER(rtdev_launch_trace_pool)(const rtdev::TraceArg
     rtdev::dispatch_variant<PoolVariant>(prims_class, textured != 0, specular != 0, bvh != 0, [&](auto v) {
         decltype(v)::launch(*args, blocks, stream);
     });
-    return hipGetLastError();
-}
-
-extern "C" hipError_t RT_LAUNCHER(rtdev_launch_resolve_chunks)(const double *partial, double *out, int width, int height, int n_chunks,
-                                                               int slice_rows, int strip_rows, int strip_count, int strip_index, int step_x, int step_y,
-                                                               int cover_w, int cover_h, int out_col_step, int out_cols, int samples,
-                                                               hipStream_t stream) {
-    if (out_cols <= 1 || out_col_step <= 0) {
-        out_cols = 1;
-        out_col_step = width;
-    }
-    size_t n = (size_t)width * (size_t)(strip_count > 1 ? slice_rows : height) * 3;
-    unsigned blocks = (unsigned)((n + 255) / 256);
-    if (blocks > 4096u) blocks = 4096u;
-    if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(RT_KNS::k_resolve_chunks_f64, dim3(blocks), dim3(256), 0, stream, partial, out, width, height,
-                       n_chunks, slice_rows, strip_rows, strip_count, strip_index, step_x, step_y, cover_w, cover_h, out_col_step, out_cols,
-                       1.0 / (double)samples);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t RT_LAUNCHER(rtdev_launch_fold_chunks)(const double *partial, double *running, double *out, size_t n, int c0,
-                                                            int c1, int samples_done, hipStream_t stream) {
-    unsigned blocks = (unsigned)((n + 255) / 256);
-    if (blocks > 4096u) blocks = 4096u;
-    if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(RT_KNS::k_fold_chunks_f64, dim3(blocks), dim3(256), 0, stream, partial, running, out, n, c0, c1,
-                       1.0 / (double)samples_done);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t RT_LAUNCHER(rtdev_launch_fold_adaptive)(const rtdev::AdaptiveFold *f, hipStream_t stream) {
-    if (f->n_tiles <= 0) return hipSuccess;
-    hipLaunchKernelGGL(RT_KNS::k_fold_adaptive_f64, dim3((unsigned)(f->n_tiles + 15) / 16), dim3(1024), 0, stream, *f);
     return hipGetLastError();
 }

@@ -56,3 +56,19 @@ def test_plan_rules_are_clean_under_asan_and_ubsan(host, tmp_path):
     assert run.stderr == "", run.stderr[-3000:]
     assert "runtime error" not in run.stdout and "Sanitizer" not in run.stdout
     assert len(run.stdout.splitlines()) == sum(P.LINES[c.split()[0]] for c in commands)
+
+
+def test_tile_error_is_clean_under_asan_and_ubsan(tmp_path):
+    """The error function of the adaptive decision step (racer-tracer_amd/csrc/rt_tile_decide.h) as a stand-alone program
+    — tests/tile_error_driver.cpp — over every case tests/test_tile_decide_cpu.py gives it, with the same answers."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    import test_tile_decide_cpu as T
+    exe = str(tmp_path / "tile_error_sanitize")
+    build = T.build_driver(exe, ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"])
+    if build.returncode != 0 and ("asan" in build.stderr or "ubsan" in build.stderr):
+        pytest.skip("sanitizer runtimes not installed: " + build.stderr[-200:])
+    assert build.returncode == 0, build.stderr[-2000:]
+    rows, edges = T.cases()
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    T.check(T.run_driver(exe, rows, env=env), rows, edges)

@@ -1,6 +1,6 @@
 """Developer probe: the delivering launch under stress.  Every frame that rt_render_frame / rt_render hand to the host must
 be the two-pass frame bit for bit — the slices cross waves on eight XCDs through sc1 stores / loads and a relaxed counter
-(rt_trace_pool_kernel.hip: deliver_item), so a visibility bug would show as a rare stale pixel — with cancels raised at
+(rt_pool_deliver.h: deliver_item), so a visibility bug would show as a rare stale pixel — with cancels raised at
 random moments in between (the per-tile counters of a launch that was cut short must be cleared)."""
 import ctypes as C, importlib, os, sys, hashlib, random, threading, time
 import numpy as np
