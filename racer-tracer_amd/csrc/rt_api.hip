@@ -173,30 +173,18 @@ int enqueue_v1(RtScene *s, rtdev::TraceArgs &a, const RtRenderParams *p, double 
 
 } // namespace
 
-// A delivering launch (rt_deliver.hip): its items queued region by region, its counters cleared where they must be.
+// A delivering launch (rt_deliver.hip): its items queued region by region (rt_plan.h: queue_order), its counters cleared
+// where they must be.
 int rtapi::setup_delivery(RtScene *s, rtdev::TraceArgs &a, const Delivery &delivery, int total_chunks, hipStream_t stream) {
-    if (delivery.regions.empty() || (int)delivery.regions.size() > rtdev::RT_MAX_REGIONS)
-        return fail(RT_ERR_INVALID_ARGUMENT, "bad region list");
-    rtapi::RenderBuffers &b = s->buf;
-    const int rc = reserve_delivery_counters(s, (size_t)a.n_tiles);
+    int rc = rtapi::queue_order(delivery.regions, a.tiles_x, a.n_tiles, total_chunks, a.regions, a.n_regions);
     if (rc != RT_OK) return rc;
+    rtapi::RenderBuffers &b = s->buf;
+    if ((rc = reserve_delivery_counters(s, (size_t)a.n_tiles)) != RT_OK) return rc;
     if (b.deliver_dirty) { // fresh buffers, or a launch that was cut short (cancel, error): counters back to zero
         RT_HIP(hipMemsetAsync(b.tile_done.ptr, 0, b.tile_done.count * sizeof(unsigned int), stream));
         RT_HIP(hipMemsetAsync(b.region_done.ptr, 0, b.region_done.count * sizeof(unsigned int), stream));
     }
     b.deliver_dirty = true; // until every region has been published (rt_deliver.hip clears it)
-    a.n_regions = (int)delivery.regions.size();
-    uint64_t at = 0;
-    for (int r = 0; r < a.n_regions; ++r) {
-        rtdev::Region reg = delivery.regions[(size_t)r];
-        if (reg.ntx <= 0 || reg.nty <= 0 || reg.tx0 < 0 || reg.ty0 < 0 || reg.tx0 + reg.ntx > a.tiles_x ||
-            (reg.ty0 + reg.nty) * a.tiles_x > a.n_tiles)
-            return fail(RT_ERR_INVALID_ARGUMENT, "region outside the tile grid");
-        reg.item_begin = (uint32_t)at;
-        at += (uint64_t)reg.ntx * (uint64_t)reg.nty * (uint64_t)total_chunks;
-        a.regions[r] = reg;
-    }
-    if (at != (uint64_t)a.n_tiles * (uint64_t)total_chunks) return fail(RT_ERR_INVALID_ARGUMENT, "the regions do not tile the grid");
     a.deliver_out = delivery.out;
     a.tile_done = b.tile_done.ptr;
     a.region_done = b.region_done.ptr;

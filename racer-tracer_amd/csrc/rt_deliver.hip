@@ -17,9 +17,11 @@
 // persistent grid, which is what the round-2 form (ten windowed launches on two streams + a strided copy per column)
 // paid 15 % of the frame for.  Pixels are bit-identical to the two-pass path (same slices, same sum order).
 //
-// Host code only.
+// Host code only.  What a call launches, waits for and copies is planned without a device (rt_plan.h: TileGrid,
+// frame_bands, stream_windows, copy_runs); this file holds what needs the runtime.
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <string>
@@ -46,8 +48,6 @@ int rtapi::ensure_host_frame(RtScene *s, size_t doubles) {
 }
 
 namespace {
-
-inline int up8(int x) { return (x + 7) & ~7; }
 
 // One device's part of a delivering call.
 struct Share {
@@ -148,8 +148,8 @@ int launch_shares(std::vector<Share> &shares, const RtCamera *camera, bool cance
 }
 
 // ------------------------------------------------------------------------------------------------ whole frames
-// Regions = bands of tile rows; the calling thread copies a band's rows from the pinned frame into the caller's
-// (pageable) frame while the GPU renders the next band, so only the last band's copy is exposed.
+// Regions = bands of tile rows (rt_plan.h: frame_bands); the calling thread copies a band's rows from the pinned frame
+// into the caller's (pageable) frame while the GPU renders the next band, so only the last band's copy is exposed.
 int deliver_frame(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p, int strip_rows,
                   double *out_rgb) {
     std::vector<Share> shares;
@@ -158,56 +158,24 @@ int deliver_frame(RtScene *const *scenes, int n, const RtCamera *camera, const R
     const size_t row_doubles = (size_t)p->width * 3;
     rc = ensure_host_frame(scenes[0], row_doubles * (size_t)p->height);
     if (rc != RT_OK) return rc;
-    const int tiles_x = (p->width + 7) / 8;
-    int most_bands = 0;
+    size_t most_bands = 0;
     for (Share &sh : shares) {
-        const int tile_rows = (rtapi::owned_rows_of(&sh.params) + 7) / 8;
-        // How many bands?  The launch ends on the LAST band's last chunks — (tiles of the band) x (a few chunks) items for
-        // thousands of resident waves — so a small last band costs an unbalanced tail of about one item's duration,
-        // while a large one costs the copy of its rows after the GPU is done.  Items are short when a frame has many
-        // chunks (C3: 19 chunks, 0.2 ms items: 32 bands, +0.8 ms in all) and long when it has few (64 spp of a
-        // 485-sphere scene: 4 chunks, 1.6 ms items: 32 bands cost +3.5 ms, 8 bands +0.7): two bands per chunk.
-        int bands = tile_rows / 2; // at least two tile rows each
-        const int by_chunks = 2 * rtapi::chunk_count(sh.params.samples);
-        if (bands > by_chunks) bands = by_chunks < 4 ? 4 : by_chunks;
-        if (bands > rtdev::RT_MAX_REGIONS) bands = rtdev::RT_MAX_REGIONS;
-        if (bands > tile_rows) bands = tile_rows;
-        if (bands < 1) bands = 1;
-        for (int b = 0; b < bands; ++b) {
-            rtdev::Region reg;
-            reg.item_begin = 0;
-            reg.tx0 = 0;
-            reg.ntx = tiles_x;
-            reg.ty0 = (int)((long long)tile_rows * b / bands);
-            reg.nty = (int)((long long)tile_rows * (b + 1) / bands) - reg.ty0;
-            if (reg.nty > 0) sh.delivery.regions.push_back(reg);
-        }
+        sh.delivery.regions = rtapi::frame_bands(rtapi::tiles_across(rtapi::owned_rows_of(&sh.params)), rtapi::tiles_across(p->width),
+                                                 rtapi::chunk_count(sh.params.samples));
         sh.delivery.out = scenes[0]->buf.host_frame;
         sh.delivery.col_step = p->width;
         sh.delivery.cols = 1;
-        most_bands = (int)sh.delivery.regions.size() > most_bands ? (int)sh.delivery.regions.size() : most_bands;
+        most_bands = std::max(most_bands, sh.delivery.regions.size());
     }
     rc = launch_shares(shares, camera);
-    for (int b = 0; b < most_bands && rc == RT_OK; ++b)
+    for (size_t b = 0; b < most_bands && rc == RT_OK; ++b)
         for (Share &sh : shares) {
-            if (b >= (int)sh.delivery.regions.size()) continue;
-            rc = wait_region(sh, b, Cancel());
+            if (b >= sh.delivery.regions.size()) continue;
+            rc = wait_region(sh, (int)b, Cancel());
             if (rc != RT_OK) break;
-            const rtdev::Region &reg = sh.delivery.regions[(size_t)b];
-            const int owned = rtapi::owned_rows_of(&sh.params);
-            int vr = reg.ty0 * 8, vr_end = (reg.ty0 + reg.nty) * 8;
-            if (vr_end > owned) vr_end = owned;
-            while (vr < vr_end) { // runs of consecutive image rows (a strip, or the whole band without strips)
-                const int row = rtapi::owned_row_to_image_row(&sh.params, vr);
-                int run = 1;
-                while (vr + run < vr_end && rtapi::owned_row_to_image_row(&sh.params, vr + run) == row + run) ++run;
-                if (row < p->height) {
-                    const int rows = row + run <= p->height ? run : p->height - row;
-                    memcpy(out_rgb + (size_t)row * row_doubles, scenes[0]->buf.host_frame + (size_t)row * row_doubles,
-                           (size_t)rows * row_doubles * sizeof(double));
-                }
-                vr += run;
-            }
+            for (const rtapi::RowRun &run : rtapi::copy_runs(&sh.params, sh.delivery.regions[b], p->height))
+                memcpy(out_rgb + (size_t)run.image_row * row_doubles, scenes[0]->buf.host_frame + (size_t)run.image_row * row_doubles,
+                       (size_t)run.rows * row_doubles * sizeof(double));
         }
     if (rc != RT_OK) {
         abort_shares(shares);
@@ -217,86 +185,53 @@ int deliver_frame(RtScene *const *scenes, int n, const RtCamera *camera, const R
 }
 
 // ------------------------------------------------------------------------------------------------- tile stream
+// One callback per tile of tile column `ws` of the grid, top to bottom; `col` is that column as [height][w][3], so a
+// tile is a contiguous run of it.  The hook is polled before every tile; true: it cut the column short.  An empty tile —
+// more tile rows than image rows, more tile columns than pixels — is still ONE BufferUpdate, as in the reference, whose
+// raytrace sends the buffer of every SubImage, empty or not (cpu.rs:64-70).
+bool emit_column(const rtapi::TileGrid &grid, int ws, const double *col, RtTileCallback callback, void *user, const Cancel &cancel) {
+    const rtapi::TileGrid::Span x = grid.column(ws);
+    for (int hs = 0; hs < grid.tiles_h; ++hs) {
+        if (cancel.raised()) return true;
+        const rtapi::TileGrid::Span y = grid.row(hs);
+        callback(user, col + (size_t)y.at * (size_t)x.size * 3, y.at, x.at, x.size, y.size);
+    }
+    return false;
+}
+
+// Regions = windows of tile columns (rt_plan.h: stream_windows).  The pinned frame holds tile column ws as
+// [height][w][3] behind the columns before it, and a column goes out as soon as every share has published its window.
 // nee: NULL, or rt_render_nee's light sampling — the same stream from k_nee_stream_f64's launch (one scene)
 int deliver_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p, int strip_rows,
                   RtTileCallback callback, void *user, const Cancel &cancel, const RtLightSamplingParams *nee = nullptr) {
     std::vector<Share> shares;
     int rc = make_shares(scenes, n, p, strip_rows, shares);
     if (rc != RT_OK) return rc;
-    // cpu.rs:73-115 tile grid, column-major, remainders in the last row/column
-    const int width_step = p->width / p->tiles_w, height_step = p->height / p->tiles_h;
-    auto column_x = [&](int ws) { return width_step * ws; };
-    auto column_w = [&](int ws) { return ws == p->tiles_w - 1 ? p->width - width_step * ws : width_step; };
+    const rtapi::TileGrid grid(p->width, p->height, p->tiles_w, p->tiles_h);
     rc = ensure_host_frame(scenes[0], (size_t)p->width * (size_t)p->height * 3);
     if (rc != RT_OK) return rc;
     const double *frame = scenes[0]->buf.host_frame;
-    // One callback per tile of tile column `ws`, top to bottom.  The pinned frame holds column ws as
-    // [height][w][3] behind the columns before it, so a tile is a contiguous run of it.
-    auto emit_column = [&](int ws) {
-        const int x = column_x(ws), w = column_w(ws);
-        const double *col = frame + (size_t)p->height * (size_t)x * 3;
-        for (int hs = 0; hs < p->tiles_h; ++hs) {
-            if (cancel.raised()) return false;
-            const int y = height_step * hs;
-            const int h = hs == p->tiles_h - 1 ? p->height - y : height_step;
-            // (an empty tile — more tile rows than image rows — is still ONE BufferUpdate, as in the reference, whose
-            // raytrace sends the buffer of every SubImage, empty or not: cpu.rs:64-70)
-            callback(user, col + (size_t)y * (size_t)(w > 0 ? w : 0) * 3, y, x, w > 0 ? w : 0, h > 0 ? h : 0);
-        }
-        return true;
-    };
-    // A pixel's sum depends on the order its samples meet in LDS, i.e. on which 8x8 item tile it sits in, so the
-    // regions are cut on the whole-frame item grid: the window of tile columns [a, b) is the pixel range
-    // [up8(x_a), up8(x_b)) (first from 0, last to the image edge) and holds exactly the item tiles of the
-    // whole-frame render; tile column k is complete once the windows up to its own are (up8(x_k+1) >= x_k+1).
-    // More than RT_MAX_REGIONS tile columns share regions.  A window may be empty.
-    auto window_begin = [&](int ws) {
-        if (ws <= 0) return 0;
-        if (ws >= p->tiles_w) return p->width;
-        const int x = up8(column_x(ws));
-        return x < p->width ? x : p->width;
-    };
-    const int per_region = (p->tiles_w + rtdev::RT_MAX_REGIONS - 1) / rtdev::RT_MAX_REGIONS;
-    std::vector<int> columns_after; // columns_after[r] = tile columns [.., this) are complete once region r is
-    std::vector<rtdev::Region> regions;
-    for (int a = 0; a < p->tiles_w; a += per_region) {
-        const int b = a + per_region < p->tiles_w ? a + per_region : p->tiles_w;
-        const int x0 = window_begin(a), x1 = window_begin(b);
-        if (x1 > x0) {
-            rtdev::Region reg;
-            reg.item_begin = 0;
-            reg.tx0 = x0 / 8;
-            reg.ntx = (x1 + 7) / 8 - reg.tx0;
-            reg.ty0 = 0;
-            reg.nty = 0; // per share below
-            regions.push_back(reg);
-            columns_after.push_back(b);
-        } else if (!columns_after.empty()) {
-            columns_after.back() = b; // nothing of its own to wait for
-        }
-    }
-    if (regions.empty()) return fail(RT_ERR_INVALID_ARGUMENT, "empty frame");
-    columns_after.back() = p->tiles_w;
+    const std::vector<int> columns_after = rtapi::stream_windows(p->width, p->tiles_w, rtapi::tiles_across(p->height)).columns_after;
+    if (columns_after.empty()) return fail(RT_ERR_INVALID_ARGUMENT, "empty frame");
     for (Share &sh : shares) {
-        const int tile_rows = (rtapi::owned_rows_of(&sh.params) + 7) / 8;
-        if (tile_rows > 0) sh.delivery.regions = regions; // (none: the share owns no rows and is not launched)
-        for (rtdev::Region &reg : sh.delivery.regions) reg.nty = tile_rows;
+        sh.delivery.regions = rtapi::stream_windows(p->width, p->tiles_w, rtapi::tiles_across(rtapi::owned_rows_of(&sh.params))).regions;
         sh.delivery.out = scenes[0]->buf.host_frame;
-        sh.delivery.col_step = width_step;
+        sh.delivery.col_step = grid.width_step;
         sh.delivery.cols = p->tiles_w;
         sh.delivery.nee = nee;
     }
     rc = launch_shares(shares, camera, cancel.armed());
     bool cancelled = false;
     int emitted = 0;
-    for (size_t r = 0; r < regions.size() && rc == RT_OK && !cancelled; ++r) {
+    for (size_t r = 0; r < columns_after.size() && rc == RT_OK && !cancelled; ++r) {
         for (Share &sh : shares) {
             if (!sh.launched) continue; // owns no rows
             rc = wait_region(sh, (int)r, cancel);
             if (rc != RT_OK) break;
         }
         if (rc != RT_OK) break;
-        for (; emitted < columns_after[r] && !cancelled; ++emitted) cancelled = !emit_column(emitted);
+        for (; emitted < columns_after[r] && !cancelled; ++emitted)
+            cancelled = emit_column(grid, emitted, frame + (size_t)p->height * (size_t)grid.column(emitted).at * 3, callback, user, cancel);
     }
     if (rc == RT_ERR_CANCEL_EVENT) {
         cancelled = true;
@@ -329,9 +264,9 @@ int tiles_from_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p
         if (batch < 16) batch = 16;
         if (batch > p->samples) batch = p->samples;
     }
-    const int width_step = p->width / p->tiles_w, height_step = p->height / p->tiles_h;
-    const bool column_layout = !s->use_v1 && width_step > 0 && p->tiles_w > 1; // written by the resolve pass itself
-    rc = rtapi::enqueue_render(s, camera, p, s->buf.frame.ptr, s->buf.stream, batch, cancel, nullptr, column_layout ? width_step : 0,
+    const rtapi::TileGrid grid(p->width, p->height, p->tiles_w, p->tiles_h);
+    const bool column_layout = !s->use_v1 && grid.width_step > 0 && p->tiles_w > 1; // written by the resolve pass itself
+    rc = rtapi::enqueue_render(s, camera, p, s->buf.frame.ptr, s->buf.stream, batch, cancel, nullptr, column_layout ? grid.width_step : 0,
                                column_layout ? p->tiles_w : 1);
     hipEvent_t copied = s->buf.ev_resolved; // re-recorded behind the copy: rt_scene_last_stats reads ev_traced -> ev_resolved (+ the copy)
     if (rc == RT_OK) {
@@ -355,11 +290,11 @@ int tiles_from_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p
     RT_HIP(hipStreamSynchronize(s->buf.stream));
     std::vector<double> column; // v1 / single-column grids: one column of the plain frame, repacked
     for (int ws = 0; ws < p->tiles_w; ++ws) {
-        const int x = width_step * ws, w = ws == p->tiles_w - 1 ? p->width - x : width_step;
+        const int x = grid.column(ws).at, w = grid.column(ws).size;
         const double *col;
         if (column_layout) {
             col = s->buf.host_frame + (size_t)p->height * (size_t)x * 3;
-        } else if (w == p->width || w <= 0) {
+        } else if (w == p->width || w == 0) {
             col = s->buf.host_frame; // (w == 0: an empty tile column — more tile columns than pixels — reads nothing)
         } else {
             column.resize((size_t)w * (size_t)p->height * 3);
@@ -367,12 +302,7 @@ int tiles_from_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p
                 memcpy(&column[(size_t)r * w * 3], s->buf.host_frame + ((size_t)r * p->width + x) * 3, (size_t)w * 3 * sizeof(double));
             col = column.data();
         }
-        for (int hs = 0; hs < p->tiles_h; ++hs) {
-            if (cancel.raised()) return RT_OK;
-            const int y = height_step * hs;
-            const int h = hs == p->tiles_h - 1 ? p->height - y : height_step;
-            callback(user, col + (size_t)y * (size_t)(w > 0 ? w : 0) * 3, y, x, w > 0 ? w : 0, h > 0 ? h : 0); // empty tiles are sent too (cpu.rs:64-70)
-        }
+        if (emit_column(grid, ws, col, callback, user, cancel)) return RT_OK;
     }
     return RT_OK;
 }
@@ -410,23 +340,15 @@ int render_tiles_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p
     if (p->tiles_w <= 0 || p->tiles_h <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "tile grid must be positive");
     if (cancel.raised()) return RT_ERR_CANCEL_EVENT; // cpu.rs:82-85
     RT_HIP(hipSetDevice(s->device));
-    const int width_step = p->width / p->tiles_w, height_step = p->height / p->tiles_h;
-    if (width_step > 0) {
+    if (p->width / p->tiles_w > 0) {
         RtScene *scenes[1] = {s};
         return deliver_tiles(scenes, 1, camera, p, 0, callback, user, cancel, ls);
     }
     std::vector<double> frame((size_t)p->width * (size_t)p->height * 3);
     if ((rc = rtapi::nee_frame_to_host(s, camera, p, ls, frame.data())) != RT_OK) return rc;
-    std::vector<double> column;
-    for (int ws = 0; ws < p->tiles_w; ++ws) { // width_step == 0: empty columns, the last one is the whole frame
-        const int x = width_step * ws, w = ws == p->tiles_w - 1 ? p->width - x : width_step;
-        for (int hs = 0; hs < p->tiles_h; ++hs) {
-            if (cancel.raised()) return RT_OK; // cpu.rs:55-62
-            const int y = height_step * hs;
-            const int h = hs == p->tiles_h - 1 ? p->height - y : height_step;
-            callback(user, frame.data() + (size_t)y * (size_t)(w > 0 ? w : 0) * 3, y, x, w > 0 ? w : 0, h > 0 ? h : 0);
-        }
-    }
+    const rtapi::TileGrid grid(p->width, p->height, p->tiles_w, p->tiles_h);
+    for (int ws = 0; ws < p->tiles_w; ++ws) // width_step == 0: empty columns, the last one is the whole frame
+        if (emit_column(grid, ws, frame.data(), callback, user, cancel)) return RT_OK; // cpu.rs:55-62
     return RT_OK;
 }
 

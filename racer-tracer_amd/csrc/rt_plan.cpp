@@ -1,6 +1,7 @@
 // rt_plan.cpp — the device-free rules of rt_plan.h: validation, kernel selection, the radiance bound and the error budget
 // of the fixed-point sums, the device records and their permutations, the light list, the chunk plan (which fixes the
-// order of every pixel's sum), launches, passes, the pixel grid and strips.  Host code for any C++17 compiler.
+// order of every pixel's sum), launches, passes, the pixel grid and strips, the plans of a delivering call.  Host code for
+// any C++17 compiler.
 #include "rt_plan.h"
 #include <stdlib.h>
 #include <string.h>
@@ -540,6 +541,90 @@ int deal_strips(const RtRenderParams *p, int n, int &strip_rows, std::vector<RtR
             params[(size_t)i].strip_index = i;
         }
     return RT_OK;
+}
+
+// ----------------------------------------------------------------------------------------------------------- a delivery
+std::vector<rtdev::Region> frame_bands(int tile_rows, int tiles_x, int chunk_count) {
+    // How many bands?  The launch ends on the LAST band's last chunks — (tiles of the band) x (a few chunks) items for
+    // thousands of resident waves — so a small last band costs an unbalanced tail of about one item's duration,
+    // while a large one costs the copy of its rows after the GPU is done.  Items are short when a frame has many
+    // chunks (C3: 19 chunks, 0.2 ms items: 32 bands, +0.8 ms in all) and long when it has few (64 spp of a
+    // 485-sphere scene: 4 chunks, 1.6 ms items: 32 bands cost +3.5 ms, 8 bands +0.7): two bands per chunk.
+    int bands = tile_rows / 2; // at least two tile rows each
+    const int by_chunks = 2 * chunk_count;
+    if (bands > by_chunks) bands = by_chunks < 4 ? 4 : by_chunks;
+    if (bands > rtdev::RT_MAX_REGIONS) bands = rtdev::RT_MAX_REGIONS;
+    if (bands > tile_rows) bands = tile_rows;
+    if (bands < 1) bands = 1;
+    std::vector<rtdev::Region> regions;
+    for (int b = 0; b < bands; ++b) {
+        const int ty0 = (int)((long long)tile_rows * b / bands), ty1 = (int)((long long)tile_rows * (b + 1) / bands);
+        if (ty1 > ty0) regions.push_back(rtdev::Region{0, 0, tiles_x, ty0, ty1 - ty0});
+    }
+    return regions;
+}
+
+// A pixel's sum depends on the order its samples meet in LDS, i.e. on which 8x8 item tile it sits in, so the
+// regions are cut on the whole-frame item grid: the window of tile columns [a, b) is the pixel range
+// [up8(x_a), up8(x_b)) (first from 0, last to the image edge) and holds exactly the item tiles of the
+// whole-frame render; tile column k is complete once the windows up to its own are (up8(x_k+1) >= x_k+1).
+// More than RT_MAX_REGIONS tile columns share regions.  A window may be empty.
+StreamWindows stream_windows(int width, int tiles_w, int tile_rows) {
+    const int width_step = width / tiles_w;
+    auto window_begin = [&](int ws) {
+        if (ws <= 0) return 0;
+        if (ws >= tiles_w) return width;
+        const int x = (width_step * ws + 7) & ~7;
+        return x < width ? x : width;
+    };
+    const int per_region = (tiles_w + rtdev::RT_MAX_REGIONS - 1) / rtdev::RT_MAX_REGIONS;
+    StreamWindows win;
+    for (int a = 0; a < tiles_w; a += per_region) {
+        const int b = a + per_region < tiles_w ? a + per_region : tiles_w;
+        const int x0 = window_begin(a), x1 = window_begin(b);
+        if (x1 > x0) {
+            win.regions.push_back(rtdev::Region{0, x0 / 8, tiles_across(x1) - x0 / 8, 0, tile_rows});
+            win.columns_after.push_back(b);
+        } else if (!win.columns_after.empty()) {
+            win.columns_after.back() = b; // nothing of its own to wait for
+        }
+    }
+    if (!win.columns_after.empty()) win.columns_after.back() = tiles_w;
+    if (tile_rows <= 0) win.regions.clear(); // (the share owns no rows and is not launched)
+    return win;
+}
+
+int queue_order(const std::vector<rtdev::Region> &regions, int tiles_x, int n_tiles, int chunks_per_tile,
+                rtdev::Region out[rtdev::RT_MAX_REGIONS], int &n_out) {
+    if (regions.empty() || (int)regions.size() > rtdev::RT_MAX_REGIONS) return fail(RT_ERR_INVALID_ARGUMENT, "bad region list");
+    n_out = (int)regions.size();
+    uint64_t at = 0;
+    for (int r = 0; r < n_out; ++r) {
+        rtdev::Region reg = regions[(size_t)r];
+        if (reg.ntx <= 0 || reg.nty <= 0 || reg.tx0 < 0 || reg.ty0 < 0 || reg.tx0 + reg.ntx > tiles_x ||
+            (reg.ty0 + reg.nty) * tiles_x > n_tiles)
+            return fail(RT_ERR_INVALID_ARGUMENT, "region outside the tile grid");
+        reg.item_begin = (uint32_t)at;
+        at += (uint64_t)reg.ntx * (uint64_t)reg.nty * (uint64_t)chunks_per_tile;
+        out[r] = reg;
+    }
+    if (at != (uint64_t)n_tiles * (uint64_t)chunks_per_tile) return fail(RT_ERR_INVALID_ARGUMENT, "the regions do not tile the grid");
+    return RT_OK;
+}
+
+std::vector<RowRun> copy_runs(const RtRenderParams *p, const rtdev::Region &band, int height) {
+    const int owned = owned_rows_of(p);
+    int vr = band.ty0 * 8, vr_end = (band.ty0 + band.nty) * 8;
+    if (vr_end > owned) vr_end = owned;
+    std::vector<RowRun> runs;
+    while (vr < vr_end) {
+        const int row = owned_row_to_image_row(p, vr);
+        int run = 1;
+        while (vr + run < vr_end && owned_row_to_image_row(p, vr + run) == row + run) ++run;
+        if (row < height) runs.push_back(RowRun{row, row + run <= height ? run : height - row});
+        vr += run;
+    }
+    return runs;
 }
 
 } // namespace rtapi

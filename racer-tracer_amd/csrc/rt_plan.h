@@ -1,8 +1,9 @@
 // rt_plan.h — the rules that turn a scene description and render parameters into plain numbers and tables: what a
 // description may hold, which kernel it selects, its radiance bound, the device records and their order, the light list,
-// the sample chunks and launches of a render, its pixel grid and strips.  Nothing here needs a device or the runtime, and
-// nothing takes an RtScene: rt_scene_create.hip and rt_api.hip upload and enqueue what these functions return, and
-// tests/plan_driver.cpp runs them as they are.  Private to the library.
+// the sample chunks and launches of a render, its pixel grid and strips, the regions, tiles and copies of a delivering
+// call.  Nothing here needs a device or the runtime, and nothing takes an RtScene: rt_scene_create.hip, rt_api.hip and
+// rt_deliver.hip upload, enqueue and wait for what these functions return, and tests/plan_driver.cpp runs them as they
+// are.  Private to the library.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -119,5 +120,51 @@ inline void set_tile_grid(rtdev::TraceArgs &a, int cols, int rows) {
     a.tiles_x = tiles_across(cols);
     a.n_tiles = a.tiles_x * tiles_across(rows);
 }
+
+// ---------------------------------------------------------------------------------------------------------- a delivery
+// What rt_deliver.hip launches, waits for and copies; rt_api.hip queues it.
+
+// The reference's tile grid (cpu.rs:73-115): tiles_w x tiles_h tiles of width_step x height_step pixels, sent column by
+// column, the remainders in the last column and row.  Sizes come out as the callbacks get them: never below 0.
+struct TileGrid {
+    int width, height, tiles_w, tiles_h, width_step, height_step;
+    struct Span {
+        int at, size;
+    };
+    TileGrid(int w, int h, int tw, int th) : width(w), height(h), tiles_w(tw), tiles_h(th), width_step(w / tw), height_step(h / th) {}
+    Span column(int ws) const { return span(ws, tiles_w, width_step, width); } // (x, w)
+    Span row(int hs) const { return span(hs, tiles_h, height_step, height); }  // (y, h)
+
+  private:
+    static Span span(int i, int n, int step, int extent) {
+        const int size = i == n - 1 ? extent - step * i : step;
+        return Span{step * i, size > 0 ? size : 0};
+    }
+};
+
+// The regions of a whole-frame call: bands of tile rows over all `tiles_x` tile columns, top to bottom (rt_plan.cpp).
+std::vector<rtdev::Region> frame_bands(int tile_rows, int tiles_x, int chunk_count);
+
+// The regions of the tile stream, `tile_rows` tile rows each (none for a share that owns no rows): windows of tile
+// columns of the grid's `tiles_w` columns, cut on the whole-frame item grid.  Tile columns [.., columns_after[r]) are
+// complete once regions [0, r] are.  No window at all: an empty frame.
+struct StreamWindows {
+    std::vector<rtdev::Region> regions;
+    std::vector<int> columns_after;
+};
+StreamWindows stream_windows(int width, int tiles_w, int tile_rows);
+
+// The queue order of a launch: `regions`, each inside the tiles_x-wide grid of n_tiles tiles, with item_begin set for
+// `chunks_per_tile` items per tile.  Refused: no region or more than RT_MAX_REGIONS, a region outside the grid, item
+// counts that do not add up to the grid's.
+int queue_order(const std::vector<rtdev::Region> &regions, int tiles_x, int n_tiles, int chunks_per_tile,
+                rtdev::Region out[rtdev::RT_MAX_REGIONS], int &n_out);
+
+// The rows of a finished band that exist in an image of `height` rows, as runs of consecutive image rows in increasing
+// order (a strip, or the whole band without strips).
+struct RowRun {
+    int image_row, rows;
+};
+std::vector<RowRun> copy_runs(const RtRenderParams *p, const rtdev::Region &band, int height);
 
 } // namespace rtapi

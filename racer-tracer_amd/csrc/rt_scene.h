@@ -114,7 +114,7 @@ struct Cancel {
 struct Delivery {
     double *out = nullptr;              // device-visible address of the output (pinned host memory or HBM)
     int col_step = 0, cols = 1;         // tile-column layout; cols == 1: plain [H][W][3] with col_step == width
-    std::vector<rtdev::Region> regions; // non-empty rectangles of item tiles in queue order (item_begin is filled in)
+    std::vector<rtdev::Region> regions; // rt_plan.h: frame_bands / stream_windows, in queue order (queue_order fills item_begin in)
     uint32_t serial = 0;                // value published in the scene's host_flags[region]
     bool cancellable = false;           // the caller polls a cancel hook while this launch runs: the waves read the scene's cancel word
     // rt_render_nee: the launch is k_nee_stream_f64's with this light sampling (rt_nee.hip: enqueue_nee_stream), not the pooled kernel's
@@ -387,8 +387,9 @@ int enqueue_nee_pass(RtScene *s, NeePasses &np, int c0, int c1, hipStream_t stre
 int enqueue_nee_stream(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
                        const Delivery &delivery);
 int nee_frame_to_host(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, double *out);
-// A delivering launch's regions and counters in its argument block (rt_api.hip): item_begin of every region for
-// `chunks_per_tile` items per tile, the counters cleared where a launch was cut short, TraceArgs.deliver_*.
+// A delivering launch's regions and counters in its argument block (rt_api.hip): the regions in queue order for
+// `chunks_per_tile` items per tile (rt_plan.h: queue_order, which refuses a list that does not fit the tile grid), the
+// counters cleared where a launch was cut short, TraceArgs.deliver_*.
 int setup_delivery(RtScene *s, rtdev::TraceArgs &a, const Delivery &delivery, int chunks_per_tile, hipStream_t stream);
 // The pinned host frame of the host-output entry points, at least `doubles` long (rt_deliver.hip).
 int ensure_host_frame(RtScene *s, size_t doubles);

@@ -10,6 +10,15 @@
 //   grid W H STRIP_ROWS STRIP_COUNT STRIP_INDEX SCALE TILES_W TILES_H
 //                                  -> fill_grid: "owned_rows owned_rows_of step_x step_y cover_w cover_h strip_rows
 //                                     strip_count strip_index", then owned_row_to_image_row of every owned row
+//   tiles W H TILES_W TILES_H      -> TileGrid: "x y w h" of every tile, column by column, each column top to bottom
+//   bands TILE_ROWS TILES_X CHUNKS -> frame_bands: "tx0 ntx ty0 nty" of every band
+//   windows W TILES_W TILE_ROWS    -> stream_windows, two lines: "tx0 ntx ty0 nty" of every region / columns_after
+//   queue TILES_X N_TILES CHUNKS [TX0 NTX TY0 NTY]...
+//                                  -> queue_order, two lines: rc, then "item_begin tx0 ntx ty0 nty" of every queued region /
+//                                     the refusal's text (nothing when rc is 0)
+//   runs H STRIP_ROWS STRIP_COUNT STRIP_INDEX TILES_X CHUNKS
+//                                  -> the bands of a frame of H rows with these strips ("tx0 ntx ty0 nty" each), then
+//                                     copy_runs of every band: "band image_row rows" of every run
 // FILE holds a description as the library gets it: the bytes of an RtSceneDesc, then its primitive, material, texture,
 // image and Perlin tables (n_* records each); the pointers are set here.  Host code only: rt_plan.cpp, rt_error.cpp and
 // rt_bvh.cpp need no HIP (tests/test_plan_cpu.py compiles them with g++, tests/test_host_sanitizers.py under sanitizers).
@@ -54,6 +63,12 @@ void print(const char *label, const std::vector<int32_t> &v) {
     printf("%s", label);
     for (int32_t x : v) printf(" %d", x);
     printf("\n");
+}
+
+void print(const char *label, const std::vector<rtdev::Region> &regions) {
+    std::vector<int32_t> v;
+    for (const rtdev::Region &r : regions) v.insert(v.end(), {r.tx0, r.ntx, r.ty0, r.nty});
+    print(label, v);
 }
 
 } // namespace
@@ -136,6 +151,50 @@ int main() {
             std::vector<int32_t> rows;
             for (int vr = 0; vr < args.owned_rows; ++vr) rows.push_back(rtapi::owned_row_to_image_row(&p, vr));
             print("rows", rows);
+        } else if (!strcmp(cmd, "tiles")) {
+            int w = 0, h = 0;
+            if (sscanf(rest, "%d %d %d %d", &w, &h, &a, &b) != 4 || a <= 0 || b <= 0) return 2;
+            const rtapi::TileGrid grid(w, h, a, b);
+            std::vector<int32_t> tiles;
+            for (int ws = 0; ws < a; ++ws)
+                for (int hs = 0; hs < b; ++hs) tiles.insert(tiles.end(), {grid.column(ws).at, grid.row(hs).at, grid.column(ws).size, grid.row(hs).size});
+            print("tiles", tiles);
+        } else if (!strcmp(cmd, "bands")) {
+            int chunks = 0;
+            if (sscanf(rest, "%d %d %d", &a, &b, &chunks) != 3) return 2;
+            print("bands", rtapi::frame_bands(a, b, chunks));
+        } else if (!strcmp(cmd, "windows")) {
+            int tile_rows = 0;
+            if (sscanf(rest, "%d %d %d", &a, &b, &tile_rows) != 3 || b <= 0) return 2;
+            const rtapi::StreamWindows win = rtapi::stream_windows(a, b, tile_rows);
+            print("regions", win.regions);
+            print("after", win.columns_after);
+        } else if (!strcmp(cmd, "queue")) {
+            int chunks = 0, used = 0;
+            if (sscanf(rest, "%d %d %d%n", &a, &b, &chunks, &used) != 3) return 2;
+            std::vector<rtdev::Region> regions;
+            rtdev::Region reg{};
+            for (const char *at = rest + used; sscanf(at, "%d %d %d %d%n", &reg.tx0, &reg.ntx, &reg.ty0, &reg.nty, &used) == 4; at += used)
+                regions.push_back(reg);
+            rtdev::Region queued[rtdev::RT_MAX_REGIONS];
+            int n = 0;
+            const int rc = rtapi::queue_order(regions, a, b, chunks, queued, n);
+            std::vector<int32_t> out(1, rc);
+            for (int r = 0; rc == RT_OK && r < n; ++r)
+                out.insert(out.end(), {(int32_t)queued[r].item_begin, queued[r].tx0, queued[r].ntx, queued[r].ty0, queued[r].nty});
+            print("queue", out);
+            printf("refusal %s\n", rc == RT_OK ? "" : rt_last_error_message());
+        } else if (!strcmp(cmd, "runs")) {
+            RtRenderParams p;
+            memset(&p, 0, sizeof p);
+            int tiles_x = 0, chunks = 0;
+            if (sscanf(rest, "%d %d %d %d %d %d", &p.height, &p.strip_rows, &p.strip_count, &p.strip_index, &tiles_x, &chunks) != 6) return 2;
+            const std::vector<rtdev::Region> bands = rtapi::frame_bands(rtapi::tiles_across(rtapi::owned_rows_of(&p)), tiles_x, chunks);
+            print("bands", bands);
+            std::vector<int32_t> runs;
+            for (size_t k = 0; k < bands.size(); ++k)
+                for (const rtapi::RowRun &run : rtapi::copy_runs(&p, bands[k], p.height)) runs.insert(runs.end(), {(int32_t)k, run.image_row, run.rows});
+            print("runs", runs);
         } else {
             return 2; // an unknown or malformed command
         }

@@ -405,3 +405,69 @@ def test_delivery_with_strips_that_cut_item_tiles(rt, gpu, rows, count):
             assert np.abs(got[own] - whole[own]).max() < 1e-12
     finally:
         scene.close()
+
+
+# ---- every route of the tile stream on the oracle's grid ----------------------------------------------------------------------
+
+GRIDS = [(5, 4),      # a remainder column and a remainder row
+         (3, 30),     # more tile rows than pixel rows: empty tiles inside the delivering launch
+         (40, 3)]     # more tile columns than pixels: the routes that do not deliver
+STREAM_W, STREAM_H, STREAM_SPP = 37, 21, 6
+
+
+class _StreamRoutes:
+    """route -> (the frame call the route is paired with, its tile stream) on scenes that stay open for the module; a
+    frame that does not depend on the tile grid is rendered once."""
+
+    def __init__(self, rt):
+        balls, self.balls_cam, _ = S.three_balls()
+        box, self.box_cam, _ = S.cornell_box()
+        self.pool, self.v1, self.lit = rt.Scene(balls), rt.Scene(balls, kernel=S.abi.RT_KERNEL_V1), rt.Scene(box)
+        self.frames = {}
+
+    def close(self):
+        for scene in (self.pool, self.v1, self.lit):
+            scene.close()
+
+    def render(self, route, grid):
+        """-> (frame, [(r, c, w, h)], the tiles stitched onto zeros)"""
+        scale = 2 if route == "pool_scale2" else 0
+        params = S.abi.render_params(STREAM_W, STREAM_H, STREAM_SPP, tiles_w=grid[0], tiles_h=grid[1], scale=scale)
+        camera = S.camera_for(self.box_cam if route == "nee" else self.balls_cam, STREAM_W, STREAM_H)
+        scene = {"pool_hook": self.pool, "v1": self.v1, "pool_scale2": self.pool, "nee": self.lit}[route]
+        key = (route, grid) if scale else route            # (the preview's blocks follow the tile grid: rt_abi.h)
+        if key not in self.frames:
+            self.frames[key] = scene.render_frame_nee(camera, params) if route == "nee" else scene.render_frame(camera, params)
+        if route == "nee":
+            stitched, order = scene.render_tiles_nee(camera, params)
+            return self.frames[key], order, stitched
+        tiles = scene.render_tiles(camera, params, cancel=(lambda: False) if route == "pool_hook" else None)
+        stitched = np.zeros_like(self.frames[key])
+        for r, c, w, h, arr in tiles:
+            assert arr.shape == (h, w, 3)
+            stitched[r:r + h, c:c + w] = arr
+        return self.frames[key], [t[:4] for t in tiles], stitched
+
+
+@pytest.fixture(scope="module")
+def stream_routes(rt, gpu):
+    routes = _StreamRoutes(rt)
+    yield routes
+    routes.close()
+
+
+@pytest.mark.parametrize("route", ["pool_hook", "v1", "pool_scale2", "nee"])
+@pytest.mark.parametrize("grid", GRIDS, ids=["%dx%d" % g for g in GRIDS])
+def test_every_route_streams_the_oracles_grid(orc, stream_routes, grid, route):
+    """rt_render_ex with a hook that never fires (the delivering launch; two-pass where the grid is wider than the image),
+    the v1 kernel (tiles_from_frame, plain frame), the preview scale (tiles_from_frame, column layout) and rt_render_nee
+    (k_nee_stream_f64's launch and its fallback): the callbacks come in the order and with the (r, c, w, h) of the
+    oracle's tile grid (cpu.rs:73-115), empty tiles included, and the tiles are the pixels of the route's frame call."""
+    tw, th = grid
+    buf = (C.c_int32 * (4 * tw * th))()
+    assert orc.lib().orc_tile_grid(STREAM_W, STREAM_H, tw, th, buf, tw * th) == tw * th
+    want_order = [(buf[4 * k + 1], buf[4 * k], max(buf[4 * k + 2], 0), max(buf[4 * k + 3], 0)) for k in range(tw * th)]
+    frame, order, stitched = stream_routes.render(route, grid)
+    assert order == want_order
+    assert np.array_equal(stitched, frame)
+    assert (frame > 0).any()

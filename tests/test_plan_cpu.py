@@ -10,9 +10,13 @@ and answers commands on standard input.
 3. Permutations, on a hand-made table of a dozen primitives of all six groups: group_linear_table is a stable grouping, the
    light tables follow it, leaf_geometry tags what the fast leaf test cannot take.
 4. fill_grid: plain frames, strips and the preview scale.
+5. The plans of a delivering call: the stream's tile grid is the oracle's, the stream's windows and a whole
+   frame's bands are Python replicas written here and keep the properties the delivering launch rests on, the queue order
+   covers every item tile exactly once, and a band's copy runs are exactly the owned image rows.  Every check is exact.
 tests/test_host_sanitizers.py runs the same commands through the driver under ASan and UBSan."""
 import ctypes as C
 import glob
+import itertools
 import os
 import shutil
 import subprocess
@@ -26,7 +30,8 @@ from test_fixed_point_sums import BOUNDS, MAX_CHUNKS, SAMPLES, chunk_plan
 abi = S.abi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "racer-tracer_amd", "csrc")
-LINES = {"chunks": 1, "passes": 1, "sumexp": 1, "select": 1, "tables": 7, "leaves": 2, "grid": 2}   # answer lines per command
+LINES = {"chunks": 1, "passes": 1, "sumexp": 1, "select": 1, "tables": 7, "leaves": 2, "grid": 2,      # answer lines per command
+         "tiles": 1, "bands": 1, "windows": 2, "queue": 2, "runs": 2}
 
 COUNTS = list(range(1, 4097)) + [8192, 65536, 1000000]
 PASSES = [(1, 1), (64, 1), (1000, 1), (37, 37), (1024, 64), (1024, 100), (1024, 1024), (1024, 5000), (4096, 24), (100000, 7)]
@@ -157,6 +162,94 @@ STRIPS = [(64, 37, 4, 3), (1920, 1080, 8, 7), (128, 100, 8, 13)]       # (w, h, 
 PREVIEW = [(1920, 1080, 8, 8, 3), (1920, 1080, 8, 8, 7), (1920, 1080, 8, 7, 7), (100, 60, 3, 4, 5)]   # (w, h, tiles_w, tiles_h, scale)
 
 
+# ---- the plans of a delivering call -----------------------------------------------------------------------------------------
+
+MAX_REGIONS = 32        # rt_device_types.h: RT_MAX_REGIONS
+
+
+def across(cells):
+    return (cells + 7) // 8
+
+
+# (w, h, tiles_w, tiles_h).  Widths and heights 1..40, grids 1..45 (more tiles than pixels included): every (width, tiles_w)
+# pair and every (height, tiles_h) pair occurs, twice — once beside its own mirror image (h, tiles_h) = (41 - w, 46 - tiles_w)
+# and once in a square frame with a square grid.  A tile's x and w are functions of (width, tiles_w, column) and its y and h
+# of (height, tiles_h, row) in the oracle (oracle/render.c: orc_tile_grid), so the pairs are what there is to sweep; the
+# full four-way product is 3.2 million grids of 530 tiles on average, which no suite can run.
+TILE_CASES = [(1920, 1080, 10, 10), (400, 225, 10, 10)]
+TILE_CASES += [(w, 41 - w, tw, 46 - tw) for w in range(1, 41) for tw in range(1, 46)]
+TILE_CASES += [(w, w, tw, tw) for w in range(1, 41) for tw in range(1, 46)]
+
+WINDOW_TILES_W = list(range(1, 80)) + [100, 200, 399, 400, 500]
+WINDOW_CASES = [(w, tw, 1 + w % 5) for w in range(1, 400) for tw in WINDOW_TILES_W if w // tw > 0]    # (width, tiles_w, tile_rows)
+WINDOWS_WITHOUT_ROWS = [(100, 40, 0), (37, 5, 0)]
+BAND_CASES = [(rows, 1 + rows % 7, chunks) for rows in range(1, 300) for chunks in range(1, 65)]      # (tile_rows, tiles_x, chunks)
+BAND_CASES += [(0, 5, 1), (0, 5, 19)]
+
+# (w, h, tiles_w, chunk count of the bands)
+QUEUE_SHAPES = [(37, 21, 5, 1), (37, 21, 3, 2), (100, 45, 40, 1), (333, 64, 64, 3), (64, 36, 33, 1), (1920, 1080, 10, 19),
+                (1920, 1080, 10, 4), (400, 225, 10, 2), (8, 8, 1, 1), (9, 250, 2, 64), (399, 17, 79, 5), (203, 117, 7, 2)]
+QUEUE_CHUNKS = (1, 3, 19)
+# (tiles_x, n_tiles, chunks, regions as (tx0, ntx, ty0, nty), the refusal)
+BAD_QUEUES = [
+    (5, 15, 3, [], "bad region list"),
+    (33, 33, 1, [(k, 1, 0, 1) for k in range(33)], "bad region list"),
+    (5, 15, 3, [(0, 3, 0, 3), (3, 3, 0, 3)], "region outside the tile grid"),          # over the right edge
+    (5, 15, 3, [(0, 5, 0, 2), (0, 5, 2, 2)], "region outside the tile grid"),          # over the lower edge
+    (5, 15, 3, [(0, 5, 0, 0), (0, 5, 0, 3)], "region outside the tile grid"),          # an empty rectangle
+    (5, 15, 3, [(0, 2, 0, 3), (3, 2, 0, 3)], "the regions do not tile the grid"),      # tile column 2 is missing
+]
+
+RUN_STRIPS = [(0, 0, 0)] + [(rows, count, i) for rows, count in ((5, 3), (12, 2), (3, 4), (8, 2), (8, 3), (8, 5)) for i in range(count)]
+RUN_CASES = [(h, rows, count, i, across(150), 2) for h in (83, 16) for rows, count, i in RUN_STRIPS]   # + (tiles_x, chunk count)
+
+
+def queue_command(tiles_x, n_tiles, chunks, regions):
+    return "queue %d %d %d" % (tiles_x, n_tiles, chunks) + "".join(" %d %d %d %d" % tuple(r) for r in regions)
+
+
+def windows_replica(width, tiles_w, tile_rows):
+    """The tile stream's regions as (tx0, ntx, ty0, nty) and columns_after, from the rule as DESIGN.md 4.4 states it: window
+    [a, b) of tile columns is the pixel range [up8(x_a), up8(x_b)), first from 0, last to the image edge; at most 32 windows;
+    an empty window has nothing of its own to wait for and joins the one before it."""
+    step = width // tiles_w
+
+    def begin(ws):
+        if ws <= 0:
+            return 0
+        return width if ws >= tiles_w else min(-(-step * ws // 8) * 8, width)
+
+    per_region = -(-tiles_w // MAX_REGIONS)
+    regions, after = [], []
+    for a in range(0, tiles_w, per_region):
+        b = min(a + per_region, tiles_w)
+        x0, x1 = begin(a), begin(b)
+        if x1 > x0:
+            regions.append((x0 // 8, across(x1) - x0 // 8, 0, tile_rows))
+            after.append(b)
+        elif after:
+            after[-1] = b
+    if after:
+        after[-1] = tiles_w
+    return (regions if tile_rows > 0 else []), after
+
+
+def bands_replica(tile_rows, tiles_x, chunks):
+    """A whole frame's bands: two per chunk (at least 4) where that caps tile_rows / 2, at most 32, at most tile_rows, at least 1."""
+    bands = tile_rows // 2
+    if bands > 2 * chunks:
+        bands = max(2 * chunks, 4)
+    bands = max(min(bands, MAX_REGIONS, tile_rows), 1)
+    cuts = [tile_rows * b // bands for b in range(bands + 1)]
+    return [(0, tiles_x, lo, hi - lo) for lo, hi in zip(cuts, cuts[1:]) if hi > lo]
+
+
+def quads(words, n=4):
+    v = [int(x) for x in words]
+    assert len(v) % n == 0
+    return [tuple(v[k:k + n]) for k in range(0, len(v), n)]
+
+
 def all_commands(directory, host):
     """Every command the tests of this module send (tests/test_host_sanitizers.py feeds them to the sanitizer build)."""
     cmds = ["chunks %d" % n for n in COUNTS] + ["passes %d %d" % sp for sp in PASSES]
@@ -170,6 +263,12 @@ def all_commands(directory, host):
     cmds += [grid_command(w, h) for w, h in PLAIN]
     cmds += [grid_command(w, h, rows, count, i) for w, h, rows, count in STRIPS for i in range(count)]
     cmds += [grid_command(w, h, scale=scale, tiles_w=tw, tiles_h=th) for w, h, tw, th, scale in PREVIEW]
+    cmds += ["tiles %d %d %d %d" % c for c in TILE_CASES] + ["windows %d %d %d" % c for c in WINDOW_CASES + WINDOWS_WITHOUT_ROWS]
+    cmds += ["bands %d %d %d" % c for c in BAND_CASES]
+    for w, h, tiles_w, samples_chunks in QUEUE_SHAPES:
+        for plan in (bands_replica(across(h), across(w), samples_chunks), windows_replica(w, tiles_w, across(h))[0]):
+            cmds += [queue_command(across(w), across(w) * across(h), chunks, plan) for chunks in QUEUE_CHUNKS]
+    cmds += [queue_command(*bad[:4]) for bad in BAD_QUEUES] + ["runs %d %d %d %d %d %d" % c for c in RUN_CASES]
     return cmds
 
 
@@ -322,3 +421,111 @@ def test_preview_grids(driver):
         assert g["owned"] == h // g["step_y"] and g["owned_of"] == h        # grid rows; the buffers are sized for the frame
         assert g["rows"] == list(range(g["owned"])) and g["rows"][-1] < h
     assert _grid(answers_[0])["step_x"] == 3 and _grid(answers_[1])["step_x"] == 6      # 1920 / 8 = 240: 3 | 240, 7 does not
+
+
+# ---- 5. the plans of a delivering call --------------------------------------------------------------------------------------
+
+def test_the_streams_tile_grid_is_the_oracles(orc, driver):
+    """x, y, w, h of every tile in emission order, negative sizes of the oracle's clamped to 0 as the callbacks get them."""
+    assert any(tw > w for w, _, tw, _ in TILE_CASES) and any(th > h for _, h, _, th in TILE_CASES)
+    assert {(w, tw) for w, _, tw, _ in TILE_CASES} >= {(w, tw) for w in range(1, 41) for tw in range(1, 46)}
+    assert {(h, th) for _, h, _, th in TILE_CASES} >= {(h, th) for h in range(1, 41) for th in range(1, 46)}
+    buf = (C.c_int32 * (4 * 45 * 45))()
+    for (w, h, tw, th), (tiles,) in zip(TILE_CASES, driver(["tiles %d %d %d %d" % c for c in TILE_CASES])):
+        assert orc.lib().orc_tile_grid(w, h, tw, th, buf, tw * th) == tw * th
+        want = [(x, y, max(tile_w, 0), max(tile_h, 0)) for x, y, tile_w, tile_h in quads(buf[:4 * tw * th])]
+        assert quads(tiles) == want, (w, h, tw, th)
+
+
+def test_stream_windows_are_cut_on_the_item_grid_and_release_only_complete_columns(driver):
+    assert any(tw > MAX_REGIONS for _, tw, _ in WINDOW_CASES) and len(WINDOW_CASES) > 15000
+    merged = 0
+    for (width, tiles_w, tile_rows), (regions, after) in zip(WINDOW_CASES, driver(["windows %d %d %d" % c for c in WINDOW_CASES])):
+        regions, after = quads(regions), [int(x) for x in after]
+        case = (width, tiles_w)
+        assert (regions, after) == windows_replica(width, tiles_w, tile_rows), case
+        assert 1 <= len(regions) <= MAX_REGIONS and len(after) == len(regions), case
+        assert all(ntx > 0 and (ty0, nty) == (0, tile_rows) for _, ntx, ty0, nty in regions), case
+        # contiguous in tile columns of the whole-frame item grid, from 0 to its last column: every boundary is a multiple of
+        # 8 pixels except the image's edge
+        assert regions[0][0] == 0 and regions[-1][0] + regions[-1][1] == across(width), case
+        assert all(a[0] + a[1] == b[0] for a, b in zip(regions, regions[1:])), case
+        assert after == sorted(after) and after[-1] == tiles_w, case
+        # every stream column that has gone out once region r is complete, k < after[r], lies inside regions [0, r]
+        step = width // tiles_w
+        rights = [width if k == tiles_w - 1 else step * k + step for k in range(tiles_w)]       # x_k + w_k
+        reach = list(itertools.accumulate(rights, max))                                          # max over columns [0, k]
+        for (tx0, ntx, _, _), n in zip(regions, after):
+            assert n >= 1 and reach[n - 1] <= min(8 * (tx0 + ntx), width), (case, n)
+        merged += len(regions) < -(-tiles_w // -(-tiles_w // MAX_REGIONS))
+    assert merged > 0                                           # empty windows were among the cases
+    for (width, tiles_w, tile_rows), (regions, after) in zip(WINDOWS_WITHOUT_ROWS, driver(["windows %d %d %d" % c for c in WINDOWS_WITHOUT_ROWS])):
+        assert regions == [] and [int(x) for x in after] == windows_replica(width, tiles_w, tile_rows)[1]
+
+
+def test_frame_bands_partition_the_tile_rows(driver):
+    counts = set()
+    for (tile_rows, tiles_x, chunks), (bands,) in zip(BAND_CASES, driver(["bands %d %d %d" % c for c in BAND_CASES])):
+        bands = quads(bands)
+        assert bands == bands_replica(tile_rows, tiles_x, chunks), (tile_rows, chunks)
+        if tile_rows == 0:
+            assert bands == []
+            continue
+        assert 1 <= len(bands) <= MAX_REGIONS, (tile_rows, chunks)
+        assert all((tx0, ntx) == (0, tiles_x) and nty > 0 for tx0, ntx, _, nty in bands), (tile_rows, chunks)
+        assert bands[0][2] == 0 and bands[-1][2] + bands[-1][3] == tile_rows, (tile_rows, chunks)
+        assert all(a[2] + a[3] == b[2] for a, b in zip(bands, bands[1:])), (tile_rows, chunks)
+        counts.add(len(bands))
+    assert counts == set(range(1, MAX_REGIONS + 1))
+    assert any(rows == 0 for rows, _, _ in BAND_CASES)
+
+
+def test_queue_order_covers_every_item_tile_once(driver):
+    assert len(QUEUE_SHAPES) >= 12
+    plans = driver([c for w, h, tiles_w, chunks in QUEUE_SHAPES
+                    for c in ("bands %d %d %d" % (across(h), across(w), chunks), "windows %d %d %d" % (w, tiles_w, across(h)))])
+    cases = []
+    for k, (w, h, _, _) in enumerate(QUEUE_SHAPES):
+        for plan in (quads(plans[2 * k][0]), quads(plans[2 * k + 1][0])):
+            cases += [(across(w), across(w) * across(h), chunks, plan) for chunks in QUEUE_CHUNKS]
+    assert any(len(plan) == MAX_REGIONS for _, _, _, plan in cases)
+    for (tiles_x, n_tiles, chunks, plan), (queued, refusal) in zip(cases, driver([queue_command(*c) for c in cases])):
+        case = (tiles_x, n_tiles, chunks, plan)
+        assert queued[0] == "0" and refusal == [], case
+        queued = quads(queued[1:], 5)
+        assert [q[1:] for q in queued] == plan, case
+        at, marks = 0, [0] * n_tiles
+        for item_begin, tx0, ntx, ty0, nty in queued:
+            assert item_begin == at, case
+            at += ntx * nty * chunks
+            for ty in range(ty0, ty0 + nty):
+                for tx in range(tx0, tx0 + ntx):
+                    assert 0 <= tx < tiles_x
+                    marks[ty * tiles_x + tx] += 1
+        assert at == n_tiles * chunks and marks == [1] * n_tiles, case
+    for bad, (queued, refusal) in zip(BAD_QUEUES, driver([queue_command(*bad[:4]) for bad in BAD_QUEUES])):
+        assert [int(x) for x in queued] == [abi.RT_ERR_INVALID_ARGUMENT] and " ".join(refusal) == bad[4], bad
+    assert {bad[4] for bad in BAD_QUEUES} == {"bad region list", "region outside the tile grid", "the regions do not tile the grid"}
+
+
+def test_copy_runs_are_the_owned_image_rows(driver):
+    nothing_owned = most_bands = 0
+    for (h, rows, count, index, tiles_x, chunks), (bands, runs) in zip(RUN_CASES, driver(["runs %d %d %d %d %d %d" % c for c in RUN_CASES])):
+        case = (h, rows, count, index)
+        bands, runs = quads(bands), quads(runs, 3)
+        owned = [r for r in range(h) if count <= 1 or (r // rows) % count == index]
+        n_owned_rows = len(owned) if count <= 1 else -(-len(owned) // rows) * rows      # (the last strip may hang over the edge)
+        assert bands == bands_replica(across(n_owned_rows), tiles_x, chunks), case
+        assert all(0 <= band < len(bands) and n > 0 for band, _, n in runs), case
+        assert [band for band, _, _ in runs] == sorted(band for band, _, _ in runs), case
+        # every owned row below the image's edge, once, in increasing order
+        assert [r for _, row, n in runs for r in range(row, row + n)] == owned, case
+        # maximal: two runs of one band do not touch
+        assert all(a[1] + a[2] < b[1] for a, b in zip(runs, runs[1:]) if a[0] == b[0]), case
+        if count <= 1:
+            assert [(ty0 * 8, min(ty0 * 8 + nty * 8, h) - ty0 * 8) for _, _, ty0, nty in bands] == [(row, n) for _, row, n in runs], case
+        nothing_owned += not owned
+        most_bands = max(most_bands, len(bands))
+        if not owned:
+            assert bands == [] and runs == []
+    assert nothing_owned > 0 and most_bands > 1
