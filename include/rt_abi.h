@@ -679,7 +679,7 @@ int rt_render_adaptive_nee(RtScene *scene, const RtCamera *camera, const RtRende
                            RtFrameCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
 
 /* rt_render_ex's contract with rt_render_frame_nee's estimator: the tile stream of ONE next-event-estimation frame, delivered
- * while it renders, with a cancel hook that stops it quickly.  One device; no `volatile int` form.
+ * while it renders, with a cancel hook that stops it quickly.  One device (several: rt_render_nee_multi below); no `volatile int` form.
  *  - Tiles: the tiles_w x tiles_h grid, column-major, the last row / column absorbing the remainders, ONE callback per tile
  *    (an empty tile included), on the calling thread, while the launch is still running.  For the same `params` the sequence
  *    of (r, c, width, height) is exactly rt_render_ex's.
@@ -704,6 +704,52 @@ int rt_render_adaptive_nee(RtScene *scene, const RtCamera *camera, const RtRende
 int rt_render_nee(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
                   const RtLightSamplingParams *light_sampling,
                   RtTileCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
+
+/* ---------------------------------------------------------------- next-event estimation on several devices
+ * rt_render_frame_multi, rt_render_frame_multi_device and rt_render_multi with rt_render_frame_nee's estimator, and the
+ * strip-owning form of rt_render_frame_nee_device that a multi-process gather would call.
+ *  - Shares as in rt_render_frame_multi: scenes[i] are distinct RtScene objects of the SAME description, one per share (a
+ *    device may carry several); the frame is cut into strips of strip_rows rows (0 = 8) and strip j belongs to
+ *    scenes[j % n_scenes].  Every share traces its strips on its own stream at the same time.
+ *  - Pixels: every pixel delivered or written equals rt_render_frame_nee's pixel for the same scene, camera, params and
+ *    light_sampling, BIT FOR BIT, for every n_scenes >= 1 and every strip_rows >= 1, strips that cut 8x8 tiles included:
+ *    a pixel's samples are added in sample order to an f64 sum of its own and every draw is addressed by the pixel's index
+ *    in the whole image, so nothing depends on which share traces it or on how the rows are cut.  (The plain several-
+ *    device calls promise this for strip heights that are multiples of 8 only.)  The value is sqrt((1 / samples) * sum).
+ *  - rt_render_frame_nee_strips_device: rt_render_frame_nee_device honouring params->strip_*: the rows the share owns are
+ *    rendered and written, every other row of rgb_device is left alone.  With strip_count <= 1 it IS
+ *    rt_render_frame_nee_device; with strip_count > 1 the strip values are held to what rt_render_frame_device asks
+ *    (strip_rows > 0, 0 <= strip_index < strip_count).  Enqueued on `hip_stream`, not synchronised.
+ *  - rt_render_frame_nee_multi: out_rgb is HOST memory; every share writes its finished pixels into one pinned frame, which
+ *    the call copies to out_rgb band by band.  rt_render_frame_nee_multi_device: out_rgb_device is memory of scenes[0]'s
+ *    device, the strips are gathered as rt_render_frame_multi_device gathers them; synchronises before returning.
+ *  - rt_render_nee_multi: rt_render_nee's contract over the shares.  The sequence of (r, c, width, height) is rt_render_nee's
+ *    (and so rt_render_ex's); a tile column goes out once EVERY share has published it.  Cancel as in rt_render_multi and
+ *    rt_render_nee: raised on entry, RT_ERR_CANCEL_EVENT and no callback; raised later, RT_OK, nothing further is delivered,
+ *    every share's launch is ended, and a later render on any of the scenes sees nothing stale.  Where the delivering
+ *    launch does not apply (a tile grid wider than the image) n_scenes == 1 falls back as rt_render_nee does and
+ *    n_scenes > 1 returns RT_ERR_UNSUPPORTED, as rt_render_multi does for its non-delivering routes.
+ *  - A share that owns no rows (more shares than strips; a strip_index whose first strip lies below the image) launches
+ *    nothing and the call succeeds; rt_render_frame_nee_strips_device then writes nothing.
+ *  - Refused with RT_ERR_INVALID_ARGUMENT before any device is touched: everything rt_render_frame_nee refuses about camera,
+ *    params and light_sampling (NULLs, an unknown heuristic, max_lights outside 0..64, a non-zero _reserved,
+ *    params->scale > 1); for the three several-scene forms a NULL or repeated scene, n_scenes <= 0, params->strip_count > 1
+ *    (the call deals the strips) and a negative strip_rows; a NULL output or callback.  A scene created with RT_KERNEL_V1
+ *    is NOT refused (the NEE kernels are their own).
+ *  - rt_scene_last_stats(scenes[i]) afterwards gives share i's own counts: the samples add up to W*H*N, the segments to
+ *    EXACTLY rt_render_frame_nee's count (a pixel's paths do not depend on its share), kernel_launches is 1 for a share
+ *    that launched and 0 for one that owned nothing.
+ * Nothing here has run on more than one physical device yet.  A binding detects these entry points by
+ * symbol lookup (RT_ABI_VERSION is unchanged by them). */
+int rt_render_frame_nee_strips_device(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                                      const RtLightSamplingParams *light_sampling, double *rgb_device, void *hip_stream);
+int rt_render_frame_nee_multi(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *params,
+                              const RtLightSamplingParams *light_sampling, int strip_rows, double *out_rgb /* HOST */);
+int rt_render_frame_nee_multi_device(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *params,
+                                     const RtLightSamplingParams *light_sampling, int strip_rows, double *out_rgb_device);
+int rt_render_nee_multi(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *params,
+                        const RtLightSamplingParams *light_sampling, int strip_rows,
+                        RtTileCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
 
 /* What the reference does to a finished tile downstream of the renderer, on
  * the device: ScreenBuffer::update's tone map (image_buffer.rs:147-153) and

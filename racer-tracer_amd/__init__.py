@@ -212,6 +212,53 @@ def render_tiles_multi(scenes, camera, params, strip_rows=0, cancel=None):
     return tiles
 
 
+def _light_sampling(heuristic, max_lights):
+    return light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
+
+
+def render_frame_nee_multi(scenes, camera, params, strip_rows=0, heuristic=None, max_lights=None):
+    """rt_render_frame_nee_multi: one next-event-estimation frame over several Scene objects (one per device share)
+    -> float64 [H, W, 3] on the host, bit-identical to Scene.render_frame_nee's.  heuristic and max_lights as there."""
+    ls = _light_sampling(heuristic, max_lights)
+    out = np.zeros((params.height, params.width, 3), dtype=np.float64)
+    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
+    check(scenes[0]._lib.rt_render_frame_nee_multi(handles, len(scenes), C.byref(camera), C.byref(params), C.byref(ls), strip_rows,
+                                                   out.ctypes.data_as(C.POINTER(C.c_double))), "rt_render_frame_nee_multi",
+          scenes[0]._lib)
+    return out
+
+
+def render_frame_nee_multi_device(scenes, camera, params, out_ptr, strip_rows=0, heuristic=None, max_lights=None):
+    """rt_render_frame_nee_multi_device: out_ptr = device address (int) on scenes[0]'s device."""
+    ls = _light_sampling(heuristic, max_lights)
+    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
+    check(scenes[0]._lib.rt_render_frame_nee_multi_device(handles, len(scenes), C.byref(camera), C.byref(params), C.byref(ls),
+                                                          strip_rows, C.c_void_p(out_ptr)),
+          "rt_render_frame_nee_multi_device", scenes[0]._lib)
+
+
+def render_tiles_nee_multi(scenes, camera, params, strip_rows=0, heuristic=None, max_lights=None, cancel=None, on_tile=None):
+    """rt_render_nee_multi: Scene.render_tiles_nee over several Scene objects (one per device share) -> (frame float64
+    [H, W, 3] assembled from the tiles that arrived (zero elsewhere), list of (r, c, width, height) in arrival order)."""
+    ls = _light_sampling(heuristic, max_lights)
+    frame = np.zeros((params.height, params.width, 3), dtype=np.float64)
+    order = []
+
+    def on_update(_user, rgb, r, c, w, h):
+        if w > 0 and h > 0:  # `rgb` is only valid during the callback
+            frame[r:r + h, c:c + w] = np.ctypeslib.as_array(rgb, shape=(h, w, 3))
+        order.append((r, c, w, h))
+        if on_tile is not None:
+            on_tile(r, c, w, h)
+
+    cb = abi.RtTileCallback(on_update)
+    hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
+    check(scenes[0]._lib.rt_render_nee_multi(handles, len(scenes), C.byref(camera), C.byref(params), C.byref(ls), strip_rows, cb,
+                                             None, hook, None), "rt_render_nee_multi", scenes[0]._lib)
+    return frame, order
+
+
 class Scene:
     """RtScene handle: a scene uploaded to one GPU (rt_scene_create)."""
 
@@ -261,6 +308,14 @@ class Scene:
         ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
         check(self._lib.rt_render_frame_nee_device(self._h, C.byref(camera), C.byref(params), C.byref(ls), C.c_void_p(out_ptr),
                                                    C.c_void_p(stream or 0)), "rt_render_frame_nee_device", self._lib)
+
+    def render_frame_nee_strips_device(self, camera, params, out_ptr, stream=None, heuristic=None, max_lights=None):
+        """rt_render_frame_nee_strips_device: render_frame_nee_device honouring params.strip_*: only the rows this share
+        owns are written.  out_ptr = device address (int) of a full frame, stream = hipStream_t (int)."""
+        ls = _light_sampling(heuristic, max_lights)
+        check(self._lib.rt_render_frame_nee_strips_device(self._h, C.byref(camera), C.byref(params), C.byref(ls),
+                                                          C.c_void_p(out_ptr), C.c_void_p(stream or 0)),
+              "rt_render_frame_nee_strips_device", self._lib)
 
     def lights(self):
         """rt_scene_lights -> the listed lights (indices into the description's primitives, table order, uncapped)."""

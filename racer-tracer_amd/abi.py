@@ -218,6 +218,16 @@ PROTOTYPES = {
                                          RtCancelCallback, C.c_void_p]),
     "rt_render_nee": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.POINTER(RtLightSamplingParams),
                                 RtTileCallback, C.c_void_p, RtCancelCallback, C.c_void_p]),
+    "rt_render_frame_nee_strips_device": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
+                                                    C.POINTER(RtLightSamplingParams), C.c_void_p, C.c_void_p]),
+    "rt_render_frame_nee_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
+                                            C.POINTER(RtLightSamplingParams), C.c_int, C.POINTER(C.c_double)]),
+    "rt_render_frame_nee_multi_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(RtCamera),
+                                                   C.POINTER(RtRenderParams), C.POINTER(RtLightSamplingParams), C.c_int,
+                                                   C.c_void_p]),
+    "rt_render_nee_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
+                                      C.POINTER(RtLightSamplingParams), C.c_int, RtTileCallback, C.c_void_p,
+                                      RtCancelCallback, C.c_void_p]),
     "rt_post_rgba8_device": (C.c_int, [C.c_void_p, C.POINTER(RtToneMap), C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rt_render_frame_rgba8": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),

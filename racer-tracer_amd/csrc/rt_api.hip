@@ -110,10 +110,8 @@ int rtapi::fill_trace_args(const RtScene *s, const RtCamera *camera, const RtRen
     return fill_args(s, camera, p, a);
 }
 
-namespace {
-
 // The counters of a delivering launch over `n_tiles` item tiles (zero between launches: fresh ones must be cleared).
-int reserve_delivery_counters(RtScene *s, size_t n_tiles) {
+int rtapi::reserve_delivery_counters(RtScene *s, size_t n_tiles) {
     rtapi::RenderBuffers &b = s->buf;
     if (b.tile_done.count < n_tiles) {
         RT_HIP(b.tile_done.alloc(n_tiles));
@@ -125,8 +123,7 @@ int reserve_delivery_counters(RtScene *s, size_t n_tiles) {
     }
     return RT_OK;
 }
-
-} // namespace
+using rtapi::reserve_delivery_counters;
 
 // What a pooled-kernel launch of these parameters needs in device memory, allocated now.  enqueue_render does the same
 // when it finds a buffer too small; a call over SEVERAL shares reserves for all of them before it launches the first

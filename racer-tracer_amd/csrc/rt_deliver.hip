@@ -1,6 +1,7 @@
 // rt_deliver.hip — the entry points that hand finished pixels to the HOST: rt_render_frame, rt_render /
 // rt_render_ex (the reference's tile stream), their several-device forms rt_render_frame_multi / rt_render_multi, and
-// rt_render_nee (the tile stream of the next-event estimator).
+// rt_render_nee (the tile stream of the next-event estimator) with its several-device forms
+// rt_render_frame_nee_multi / rt_render_nee_multi.
 //
 // What the reference does here: CpuRenderer::render shards the frame into tiles, every tile is traced on a rayon
 // worker and sent to the writer the moment it is finished (racer-tracer/src/renderer/cpu.rs:64-70,118-131), with
@@ -127,16 +128,23 @@ int make_shares(RtScene *const *scenes, int n, const RtRenderParams *p, int stri
 
 int launch_shares(std::vector<Share> &shares, const RtCamera *camera, bool cancellable = false) {
     for (Share &sh : shares) { // every allocation of the call before its first launch (rt_api.hip: reserve_render_buffers)
-        if (sh.delivery.regions.empty() || sh.delivery.nee) continue; // (rt_render_nee: one share; enqueue_nee_stream allocates what it needs ahead of its launch)
-        const int rc = rtapi::reserve_render_buffers(sh.scene, &sh.params, true);
+        if (sh.delivery.regions.empty()) continue;
+        const int rc = sh.delivery.nee ? rtapi::reserve_nee_buffers(sh.scene, &sh.params, true) : rtapi::reserve_render_buffers(sh.scene, &sh.params, true);
         if (rc != RT_OK) return rc;
     }
     for (Share &sh : shares) {
         sh.delivery.cancellable = cancellable;
         // A share that owns no rows (more shares than strips: height 16 over three scenes; a strip_index whose first
         // strip lies below the image) has nothing to launch and nothing to wait for: it counts as published, and the
-        // rows of the frame stay as they are — what the two-pass path does with n_items == 0.
-        if (sh.delivery.regions.empty()) continue;
+        // rows of the frame stay as they are — what the two-pass path does with n_items == 0.  (The NEE calls promise such a
+        // share's statistics: those of an empty call.)
+        if (sh.delivery.regions.empty()) {
+            if (sh.delivery.nee) {
+                const int rc = rtapi::note_idle_share(sh.scene, sh.scene->buf.stream);
+                if (rc != RT_OK) return rc;
+            }
+            continue;
+        }
         sh.delivery.serial = ++sh.scene->buf.deliver_serial;
         if (sh.delivery.serial == 0) sh.delivery.serial = ++sh.scene->buf.deliver_serial; // 0 is the flags' idle value
         const int rc = sh.delivery.nee ? rtapi::enqueue_nee_stream(sh.scene, camera, &sh.params, sh.delivery.nee, sh.delivery)
@@ -150,8 +158,10 @@ int launch_shares(std::vector<Share> &shares, const RtCamera *camera, bool cance
 // ------------------------------------------------------------------------------------------------ whole frames
 // Regions = bands of tile rows (rt_plan.h: frame_bands); the calling thread copies a band's rows from the pinned frame
 // into the caller's (pageable) frame while the GPU renders the next band, so only the last band's copy is exposed.
+// nee: NULL, or rt_render_frame_nee_multi's light sampling — the same bands from k_nee_stream_f64's launch, whose item is a
+// whole tile: the bands change nothing in its queue (tile rows top to bottom either way), so it gets as many as fit.
 int deliver_frame(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p, int strip_rows,
-                  double *out_rgb) {
+                  double *out_rgb, const RtLightSamplingParams *nee = nullptr) {
     std::vector<Share> shares;
     int rc = make_shares(scenes, n, p, strip_rows, shares);
     if (rc != RT_OK) return rc;
@@ -161,10 +171,11 @@ int deliver_frame(RtScene *const *scenes, int n, const RtCamera *camera, const R
     size_t most_bands = 0;
     for (Share &sh : shares) {
         sh.delivery.regions = rtapi::frame_bands(rtapi::tiles_across(rtapi::owned_rows_of(&sh.params)), rtapi::tiles_across(p->width),
-                                                 rtapi::chunk_count(sh.params.samples));
+                                                 nee ? rtdev::RT_MAX_REGIONS : rtapi::chunk_count(sh.params.samples));
         sh.delivery.out = scenes[0]->buf.host_frame;
         sh.delivery.col_step = p->width;
         sh.delivery.cols = 1;
+        sh.delivery.nee = nee;
         most_bands = std::max(most_bands, sh.delivery.regions.size());
     }
     rc = launch_shares(shares, camera);
@@ -201,7 +212,7 @@ bool emit_column(const rtapi::TileGrid &grid, int ws, const double *col, RtTileC
 
 // Regions = windows of tile columns (rt_plan.h: stream_windows).  The pinned frame holds tile column ws as
 // [height][w][3] behind the columns before it, and a column goes out as soon as every share has published its window.
-// nee: NULL, or rt_render_nee's light sampling — the same stream from k_nee_stream_f64's launch (one scene)
+// nee: NULL, or rt_render_nee's / rt_render_nee_multi's light sampling — the same stream from k_nee_stream_f64's launches
 int deliver_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p, int strip_rows,
                   RtTileCallback callback, void *user, const Cancel &cancel, const RtLightSamplingParams *nee = nullptr) {
     std::vector<Share> shares;
@@ -328,22 +339,22 @@ int frame_two_pass(RtScene *s, const RtCamera *camera, const RtRenderParams *p, 
     return RT_OK;
 }
 
-// rt_render_nee: render_tiles with rt_render_frame_nee's estimator, on one scene.  The delivering launch is
-// k_nee_stream_f64's (the NEE kernels are their own: a scene made with RT_KERNEL_V1 streams too); where it does not apply —
-// a tile grid wider than the image — the frame is rt_render_frame_nee's launch and the tiles are cut from it on the host,
-// the hook being looked at before the launch and before every tile.
-int render_tiles_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
-                     RtTileCallback callback, void *user, const Cancel &cancel) {
+// rt_render_nee / rt_render_nee_multi: render_tiles with rt_render_frame_nee's estimator, over the shares of `n` scenes.  The
+// delivering launch is k_nee_stream_f64's, one per share (the NEE kernels are their own: a scene made with RT_KERNEL_V1
+// streams too); where it does not apply — a tile grid wider than the image — ONE scene's frame is rt_render_frame_nee's
+// launch and the tiles are cut from it on the host, the hook being looked at before the launch and before every tile;
+// several scenes have no such route (as rt_render_multi has none for its non-delivering ones).
+int render_tiles_nee(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                     int strip_rows, RtTileCallback callback, void *user, const Cancel &cancel, const char *what) {
     if (!callback) return fail(RT_ERR_INVALID_ARGUMENT, "callback is NULL");
-    int rc = rtapi::check_nee(s, camera, p, ls, "rt_render_nee");
+    int rc = rtapi::check_nee_shares(scenes, n, camera, p, ls, strip_rows, what);
     if (rc != RT_OK) return rc;
     if (p->tiles_w <= 0 || p->tiles_h <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "tile grid must be positive");
     if (cancel.raised()) return RT_ERR_CANCEL_EVENT; // cpu.rs:82-85
+    if (p->width / p->tiles_w > 0) return deliver_tiles(scenes, n, camera, p, strip_rows, callback, user, cancel, ls);
+    if (n > 1) return fail(RT_ERR_UNSUPPORTED, std::string(what) + ": a tile grid wider than the image renders on one device");
+    RtScene *s = scenes[0];
     RT_HIP(hipSetDevice(s->device));
-    if (p->width / p->tiles_w > 0) {
-        RtScene *scenes[1] = {s};
-        return deliver_tiles(scenes, 1, camera, p, 0, callback, user, cancel, ls);
-    }
     std::vector<double> frame((size_t)p->width * (size_t)p->height * 3);
     if ((rc = rtapi::nee_frame_to_host(s, camera, p, ls, frame.data())) != RT_OK) return rc;
     const rtapi::TileGrid grid(p->width, p->height, p->tiles_w, p->tiles_h);
@@ -381,6 +392,17 @@ int rtapi::check_scenes(RtScene *const *scenes, int n) {
         for (int j = 0; j < i; ++j)
             if (scenes[i] == scenes[j]) return fail(RT_ERR_INVALID_ARGUMENT, "the same RtScene is listed twice (create one per share)");
     return RT_OK;
+}
+
+// What the several-scene NEE calls refuse before a device is touched: what check_nee refuses about camera, params and light
+// sampling (strips of the caller's own and the preview scale included), then the scene list and a negative strip height
+int rtapi::check_nee_shares(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p,
+                            const RtLightSamplingParams *ls, int strip_rows, const char *what) {
+    int rc = rtapi::check_nee_args(camera, p, ls, what);
+    if (rc != RT_OK) return rc;
+    if ((rc = rtapi::check_scenes(scenes, n)) != RT_OK) return rc;
+    if (strip_rows < 0) return fail(RT_ERR_INVALID_ARGUMENT, "strip_rows must not be negative");
+    return rtapi::check_params(camera, p);
 }
 
 extern "C" {
@@ -428,8 +450,31 @@ int rt_render_ex(RtScene *s, const RtCamera *camera, const RtRenderParams *p, Rt
 
 int rt_render_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *light_sampling,
                   RtTileCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user) {
+    RtScene *scenes[1] = {s};
     return rtapi::guarded("rt_render_nee", [&] {
-        return render_tiles_nee(s, camera, p, light_sampling, callback, user, Cancel{nullptr, cancelled, cancel_user});
+        if (!callback) return fail(RT_ERR_INVALID_ARGUMENT, "callback is NULL");
+        const int rc = rtapi::check_nee(s, camera, p, light_sampling, "rt_render_nee"); // (one scene: the refusal names it, not a list)
+        if (rc != RT_OK) return rc;
+        return render_tiles_nee(scenes, 1, camera, p, light_sampling, 0, callback, user, Cancel{nullptr, cancelled, cancel_user}, "rt_render_nee");
+    });
+}
+
+int rt_render_nee_multi(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *p,
+                        const RtLightSamplingParams *light_sampling, int strip_rows, RtTileCallback callback, void *user,
+                        RtCancelCallback cancelled, void *cancel_user) {
+    const Cancel c{nullptr, cancelled, cancel_user};
+    return rtapi::guarded("rt_render_nee_multi", [&] {
+        return render_tiles_nee(scenes, n_scenes, camera, p, light_sampling, strip_rows, callback, user, c, "rt_render_nee_multi");
+    });
+}
+
+int rt_render_frame_nee_multi(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *p,
+                              const RtLightSamplingParams *light_sampling, int strip_rows, double *out_rgb) {
+    return rtapi::guarded("rt_render_frame_nee_multi", [&] {
+        const int rc = rtapi::check_nee_shares(scenes, n_scenes, camera, p, light_sampling, strip_rows, "rt_render_frame_nee_multi");
+        if (rc != RT_OK) return rc;
+        if (!out_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgb is NULL");
+        return deliver_frame(scenes, n_scenes, camera, p, strip_rows, out_rgb, light_sampling);
     });
 }
 

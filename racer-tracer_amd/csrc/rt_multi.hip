@@ -1,5 +1,6 @@
 // rt_multi.hip — one frame on several GPUs of ONE process, collected in device 0's HBM (include/rt_abi.h:
-// rt_render_frame_multi_device; the host-output forms rt_render_frame_multi / rt_render_multi live in rt_deliver.hip).
+// rt_render_frame_multi_device and, with the next-event estimator, rt_render_frame_nee_multi_device; the host-output forms
+// rt_render_frame_multi / rt_render_multi and their NEE counterparts live in rt_deliver.hip).
 //
 // The reference shards a frame over its rayon pool by tile inside one
 // `CpuRenderer::render` call (racer-tracer/src/renderer/cpu.rs:118-131).  Here
@@ -15,6 +16,7 @@
 //
 // Host code only.
 #include <hip/hip_runtime.h>
+#include <functional>
 #include <string>
 #include <vector>
 #include "rt_scene.h"
@@ -30,15 +32,17 @@ struct Share {
     bool in_place;  // target IS the output buffer: no copy
 };
 
-int render_multi(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p, int strip_rows,
-                 double *out) {
-    int rc = rtapi::check_scenes(scenes, n);
-    if (rc != RT_OK) return rc;
-    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
-    rc = rtapi::check_params(camera, p);
-    if (rc != RT_OK) return rc;
+// What a share of the gather renders with: `reserve` allocates what its launches need (before the call's first launch),
+// `enqueue` puts its trace and resolve launches on the scene's stream, the resolve writing the share's rows of `target`.
+struct ShareRender {
+    std::function<int(RtScene *, const RtRenderParams *)> reserve;
+    std::function<int(RtScene *, const RtRenderParams *, double *target)> enqueue;
+};
+
+// The arguments are checked by the caller.
+int render_multi(RtScene *const *scenes, int n, const RtRenderParams *p, int strip_rows, double *out, const ShareRender &render) {
     std::vector<RtRenderParams> params;
-    rc = rtapi::deal_strips(p, n, strip_rows, params);
+    int rc = rtapi::deal_strips(p, n, strip_rows, params);
     if (rc != RT_OK) return rc;
 
     const size_t row_elems = (size_t)p->width * 3;
@@ -63,7 +67,7 @@ int render_multi(RtScene *const *scenes, int n, const RtCamera *camera, const Rt
         RT_HIP(hipSetDevice(sh.scene->device));
         sh.in_place = sh.scene->device == dst_device && !sh.scene->gather_staged;
         if (!sh.in_place && sh.scene->buf.frame.count < n_elems) RT_HIP(sh.scene->buf.frame.alloc(n_elems));
-        rc = rtapi::reserve_render_buffers(sh.scene, &sh.params, false);
+        rc = render.reserve(sh.scene, &sh.params);
         if (rc != RT_OK) return rc;
     }
     // 1. every device starts tracing before any copy is enqueued (a copy to pageable host memory
@@ -74,7 +78,7 @@ int render_multi(RtScene *const *scenes, int n, const RtCamera *camera, const Rt
         // RT_GATHER_STAGED (RtSceneOptions.gather, a test switch): the share renders into its own staging frame and is
         // copied even when it sits on the output's device, so that ONE card runs what several run
         sh.target = sh.in_place ? out : sh.scene->buf.frame.ptr;
-        rc = rtapi::enqueue_render(sh.scene, camera, &sh.params, sh.target, sh.scene->buf.stream, 0, rtapi::Cancel());
+        rc = render.enqueue(sh.scene, &sh.params, sh.target);
         drain.launched.push_back(sh.scene);
         if (rc != RT_OK) return rc;
     }
@@ -151,8 +155,34 @@ extern "C" {
 
 int rt_render_frame_multi_device(RtScene *const *scenes, int n_scenes, const RtCamera *camera,
                                  const RtRenderParams *params, int strip_rows, double *out_rgb_device) {
-    return rtapi::guarded("rt_render_frame_multi_device",
-                          [&] { return render_multi(scenes, n_scenes, camera, params, strip_rows, out_rgb_device); });
+    return rtapi::guarded("rt_render_frame_multi_device", [&] {
+        int rc = rtapi::check_scenes(scenes, n_scenes);
+        if (rc != RT_OK) return rc;
+        if (!out_rgb_device) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+        if ((rc = rtapi::check_params(camera, params)) != RT_OK) return rc;
+        const ShareRender pooled{
+            [](RtScene *s, const RtRenderParams *sp) { return rtapi::reserve_render_buffers(s, sp, false); },
+            [&](RtScene *s, const RtRenderParams *sp, double *target) {
+                return rtapi::enqueue_render(s, camera, sp, target, s->buf.stream, 0, rtapi::Cancel());
+            }};
+        return render_multi(scenes, n_scenes, params, strip_rows, out_rgb_device, pooled);
+    });
+}
+
+// The same gather behind rt_render_frame_nee_device's launches (rt_nee.hip: enqueue_nee honours a share's strips)
+int rt_render_frame_nee_multi_device(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *params,
+                                     const RtLightSamplingParams *light_sampling, int strip_rows, double *out_rgb_device) {
+    return rtapi::guarded("rt_render_frame_nee_multi_device", [&] {
+        const int rc = rtapi::check_nee_shares(scenes, n_scenes, camera, params, light_sampling, strip_rows, "rt_render_frame_nee_multi_device");
+        if (rc != RT_OK) return rc;
+        if (!out_rgb_device) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgb_device is NULL");
+        const ShareRender nee{
+            [](RtScene *s, const RtRenderParams *sp) { return rtapi::reserve_nee_buffers(s, sp, false); },
+            [&](RtScene *s, const RtRenderParams *sp, double *target) {
+                return rtapi::enqueue_nee(s, camera, sp, light_sampling, target, s->buf.stream);
+            }};
+        return render_multi(scenes, n_scenes, params, strip_rows, out_rgb_device, nee);
+    });
 }
 
 } // extern "C"

@@ -1,6 +1,6 @@
 // rt_nee.hip — next-event estimation: the upload of the scene's light list (rt_plan.cpp: light_tables) and
-// the entry points rt_render_frame_nee, rt_render_frame_nee_device, rt_scene_lights and rt_light_sampling_params_default
-// (include/rt_abi.h).  The kernel is rt_nee_kernel.hip's k_nee_f64, compiled in both arithmetic flavours; a scene uses its
+// the entry points rt_render_frame_nee, rt_render_frame_nee_device, rt_render_frame_nee_strips_device, rt_scene_lights and
+// rt_light_sampling_params_default (include/rt_abi.h); the several-device forms live in rt_deliver.hip and rt_multi.hip.  The kernel is rt_nee_kernel.hip's k_nee_f64, compiled in both arithmetic flavours; a scene uses its
 // own (RtScene.kernels).
 #include "rt_scene.h"
 
@@ -11,9 +11,8 @@
 using rtapi::fail;
 using rtapi::kMaxLights;
 
-// Everything that is refused before a device is touched; the scene last, so that each refusal names its own cause
-int rtapi::check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
-                     const char *what) {
+// What every NEE entry point refuses about camera, params and light sampling, short of check_params
+int rtapi::check_nee_args(const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, const char *what, bool strips) {
     if (!camera || !p || !ls) return fail(RT_ERR_INVALID_ARGUMENT, "camera/params/light_sampling is NULL");
     if (ls->heuristic != RT_MIS_POWER && ls->heuristic != RT_MIS_BALANCE)
         return fail(RT_ERR_INVALID_ARGUMENT, "light_sampling->heuristic is not an RtMisHeuristic");
@@ -21,8 +20,16 @@ int rtapi::check_nee(const RtScene *s, const RtCamera *camera, const RtRenderPar
         return fail(RT_ERR_INVALID_ARGUMENT, "light_sampling->max_lights must be in 0..64");
     for (int32_t r : ls->_reserved)
         if (r != 0) return fail(RT_ERR_INVALID_ARGUMENT, "light_sampling->_reserved must be 0");
-    if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, std::string(what) + " renders whole frames: params->strip_* is not supported");
+    if (p->strip_count > 1 && !strips) return fail(RT_ERR_INVALID_ARGUMENT, std::string(what) + " renders whole frames: params->strip_* is not supported");
     if (p->scale > 1) return fail(RT_ERR_INVALID_ARGUMENT, std::string(what) + " renders full-resolution frames: params->scale must be 0 or 1");
+    return RT_OK;
+}
+
+// Everything that is refused before a device is touched; the scene last, so that each refusal names its own cause
+int rtapi::check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                     const char *what, bool strips) {
+    const int rc = check_nee_args(camera, p, ls, what, strips);
+    if (rc != RT_OK) return rc;
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     return rtapi::check_params(camera, p);
 }
@@ -30,7 +37,8 @@ int rtapi::check_nee(const RtScene *s, const RtCamera *camera, const RtRenderPar
 namespace {
 using rtapi::check_nee;
 
-// The argument blocks of a k_nee_f64 / k_nee_pass_f64 launch over the whole frame's samples
+// The argument blocks of a k_nee_f64 / k_nee_pass_f64 / k_nee_stream_f64 launch over all samples of the rows `p` owns (the
+// whole frame without strips; rt_plan.cpp: fill_grid sets strip_* and owned_rows)
 int fill_nee_args(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, rtdev::TraceArgs &a,
                   rtdev::NeeArgs &nee) {
     // the render's own argument block (tables, tree, camera, grid); its fixed-point sums are the pooled kernel's, and this
@@ -61,26 +69,58 @@ int open_launches(RtScene *s, hipStream_t stream, bool clear_queue = false) {
     return RT_OK;
 }
 
-// One launch of k_nee_f64 over the whole frame into the scene's accumulator, then the resolve pass into out_device
-int enqueue_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, double *out_device,
-                hipStream_t stream) {
+} // namespace
+
+// A share that owns no rows launches nothing: its statistics are those of an empty call (no sample, no segment, no launch)
+int rtapi::note_idle_share(RtScene *s, hipStream_t stream) {
+    RT_HIP(hipSetDevice(s->device));
+    const int rc = open_launches(s, stream);
+    if (rc != RT_OK) return rc;
+    RT_HIP(hipEventRecord(s->buf.ev_traced, stream));
+    RT_HIP(hipEventRecord(s->buf.ev_resolved, stream));
+    rtapi::note_launches(s, 0);
+    return RT_OK;
+}
+
+// What the NEE launches of these parameters need in device memory, allocated now (a call over several shares: before its
+// first launch, rt_api.hip: reserve_render_buffers says why): the full-frame accumulator of k_nee_f64, or the item counter
+// and the delivery counters of k_nee_stream_f64
+int rtapi::reserve_nee_buffers(RtScene *s, const RtRenderParams *p, bool delivering) {
+    RT_HIP(hipSetDevice(s->device));
+    rtapi::RenderBuffers &b = s->buf;
+    if (!delivering) {
+        const size_t n = (size_t)p->width * (size_t)p->height * 3;
+        if (b.accum.count < n) RT_HIP(b.accum.alloc(n));
+        return RT_OK;
+    }
+    if (b.queue.count < 1) RT_HIP(b.queue.alloc(1));
+    return rtapi::reserve_delivery_counters(s, rtapi::tile_count(p->width, rtapi::owned_rows_of(p)));
+}
+
+// One launch of k_nee_f64 over the rows `p` owns into the scene's accumulator (a full-frame [height][width][3] buffer, owned
+// rows written), then the resolve pass of those rows into out_device
+int rtapi::enqueue_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, double *out_device,
+                       hipStream_t stream) {
     RT_HIP(hipSetDevice(s->device));
     rtdev::TraceArgs a;
     rtdev::NeeArgs nee;
     int rc = fill_nee_args(s, camera, p, ls, a, nee);
     if (rc != RT_OK) return rc;
+    if (a.owned_rows <= 0) return note_idle_share(s, stream); // a strip_index whose first strip lies below the image
+    if ((rc = reserve_nee_buffers(s, p, false)) != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
-    const size_t n = (size_t)p->width * (size_t)p->height * 3;
-    if (b.accum.count < n) RT_HIP(b.accum.alloc(n));
     a.accum = b.accum.ptr;
     if ((rc = open_launches(s, stream)) != RT_OK) return rc;
     RT_HIP(s->kernels->nee(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh, stream));
     RT_HIP(hipEventRecord(b.ev_traced, stream));
-    RT_HIP(s->kernels->resolve(b.accum.ptr, out_device, p->width, p->height, p->height, 1, 0, p->samples, stream));
+    RT_HIP(s->kernels->resolve(b.accum.ptr, out_device, p->width, p->height, a.strip_rows, a.strip_count, a.strip_index, p->samples, stream));
     RT_HIP(hipEventRecord(b.ev_resolved, stream));
     rtapi::note_launches(s, 1);
     return RT_OK;
 }
+
+namespace {
+using rtapi::enqueue_nee;
 
 int render_frame_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, double *out) {
     int rc = check_nee(s, camera, p, ls);
@@ -97,6 +137,15 @@ int render_frame_nee_device(RtScene *s, const RtCamera *camera, const RtRenderPa
     return enqueue_nee(s, camera, p, ls, out, (hipStream_t)stream);
 }
 
+// ... honouring params->strip_* (the strip values checked as rt_render_frame_device checks them: rt_plan.cpp: check_params)
+int render_frame_nee_strips_device(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                                   double *out, void *stream) {
+    int rc = check_nee(s, camera, p, ls, "rt_render_frame_nee_strips_device", /*strips=*/true);
+    if (rc != RT_OK) return rc;
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device is NULL");
+    return enqueue_nee(s, camera, p, ls, out, (hipStream_t)stream);
+}
+
 int scene_lights(const RtScene *s, int32_t *out, int32_t capacity, int32_t *count) {
     if (!s || !count) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out_count is NULL");
     if (capacity < 0 || (capacity > 0 && !out)) return fail(RT_ERR_INVALID_ARGUMENT, "out_prims is NULL or capacity is negative");
@@ -108,6 +157,7 @@ int scene_lights(const RtScene *s, int32_t *out, int32_t capacity, int32_t *coun
 } // namespace
 
 // rt_render_nee's delivering launch: k_nee_stream_f64 as one persistent grid over the delivery's regions, ONE item per tile
+// of the width x owned_rows grid (a share's strips; the whole frame without)
 int rtapi::enqueue_nee_stream(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
                               const Delivery &delivery) {
     RT_HIP(hipSetDevice(s->device));
@@ -117,11 +167,12 @@ int rtapi::enqueue_nee_stream(RtScene *s, const RtCamera *camera, const RtRender
     if (rc != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     hipStream_t stream = b.stream;
-    rtapi::set_tile_grid(a, p->width, p->height); // the tiles k_nee_stream_f64 draws its work from
+    rtapi::set_tile_grid(a, p->width, a.owned_rows); // the tiles k_nee_stream_f64 draws its work from: region rows are owned rows
     a.n_items = (uint32_t)a.n_tiles;
     a.total_chunks = a.n_chunks = 1;
-    if (b.queue.count < 1) RT_HIP(b.queue.alloc(1)); // (allocations, here and in fill_nee_args / setup_delivery, may follow earlier work of the
-                                                     // stream; nothing of THIS call is in flight before the launch below)
+    // (allocations, here and in setup_delivery, may follow earlier work of the stream; nothing of THIS share is in flight
+    // before the launch below, and a call over several shares has reserved all of it before its first launch)
+    if ((rc = reserve_nee_buffers(s, p, true)) != RT_OK) return rc;
     if ((rc = rtapi::setup_delivery(s, a, delivery, 1, stream)) != RT_OK) return rc;
     a.queue = b.queue.ptr;
     if (delivery.cancellable) rtapi::arm_cancel_word(s, a); // the waves read it at every hand-out and chunk boundary
@@ -219,6 +270,12 @@ int rt_render_frame_nee_device(RtScene *s, const RtCamera *camera, const RtRende
                                double *rgb_device, void *hip_stream) {
     return rtapi::guarded("rt_render_frame_nee_device",
                           [&] { return render_frame_nee_device(s, camera, p, ls, rgb_device, hip_stream); });
+}
+
+int rt_render_frame_nee_strips_device(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
+                                      double *rgb_device, void *hip_stream) {
+    return rtapi::guarded("rt_render_frame_nee_strips_device",
+                          [&] { return render_frame_nee_strips_device(s, camera, p, ls, rgb_device, hip_stream); });
 }
 
 } // extern "C"

@@ -24,7 +24,15 @@ __global__ __launch_bounds__(256) void k_nee_f64(const TraceArgs A, const NeeArg
     const int bx = blockIdx.x % tiles_x;
     const int by = blockIdx.x / tiles_x;
     const int px = bx * 16 + (wave & 1) * 8 + (lane & 7);
-    const int py = by * 16 + (wave >> 1) * 8 + (lane >> 3);
+    const int vrow = by * 16 + (wave >> 1) * 8 + (lane >> 3); // a row of the launch's owned-row grid
+    int py = vrow;
+    { // owned row -> image row, once: the draws and the sums below are the IMAGE pixel's.  The strip fields are read through
+      // kernargs_here(), next to their one use, so that a launch without strips keeps no register for them.
+        const RT_CONSTANT TraceArgs *K = kernargs_here();
+        if (K->strip_count > 1)
+            py = ((vrow / K->strip_rows) * K->strip_count + K->strip_index) * K->strip_rows + vrow % K->strip_rows;
+    }
+    // (an owned row at or beyond owned_rows lies in a strip that starts below the image: its image row is >= height)
     const bool in_image = px < A.width && py < A.height;
 
     PathRng rng;
@@ -69,12 +77,13 @@ template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH> struct NeeVariant {
 };
 } // namespace
 
-// The whole frame's samples [sample_begin, sample_end) into args->accum (written, not added to).  prims_class:
-// rtdev::PRIMS_*; bvh: closest hits through args' tree (then PRIMS_ANY).
+// The samples [sample_begin, sample_end) of the launch's owned rows (args->strip_*; the whole frame without strips) into
+// args->accum, a full-frame buffer (written, not added to; rows not owned are left alone).  prims_class: rtdev::PRIMS_*;
+// bvh: closest hits through args' tree (then PRIMS_ANY).
 extern "C" hipError_t RT_LAUNCHER(rtdev_launch_nee)(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, int prims_class,
                                                     int textured, int specular, int bvh, hipStream_t stream) {
     const int tiles_x = (args->width + 15) / 16;
-    const int tiles_y = (args->height + 15) / 16;
+    const int tiles_y = (args->owned_rows + 15) / 16; // the grid covers width x owned_rows
     if (tiles_x <= 0 || tiles_y <= 0) return hipSuccess;
     const unsigned blocks = (unsigned)(tiles_x * tiles_y);
     rtdev::dispatch_variant<NeeVariant>(prims_class, textured != 0, specular != 0, bvh != 0, [&](auto v) {

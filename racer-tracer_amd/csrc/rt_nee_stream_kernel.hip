@@ -3,7 +3,9 @@
 // tile with rt_nee_common.h's nee_samples — the loop k_nee_f64 runs, a pixel's samples added in sample order to an f64 sum
 // that starts at +0.0 — and write the tile's finished pixels, sqrt((1 / samples) * sum), straight into the caller's pinned
 // tile-column frame.  The wave that finishes a region's last tile publishes the region to the host.  A pixel is therefore
-// rt_render_frame_nee's pixel, bit for bit, whatever the tile grid, the grid size or the order the waves run in.
+// rt_render_frame_nee's pixel, bit for bit, whatever the tile grid, the grid size or the order the waves run in — and whatever
+// share of the frame's rows the launch owns (TraceArgs.strip_*: rt_render_frame_nee_multi / rt_render_nee_multi):
+// the tiles are those of the launch's owned-row grid, and a lane's row is mapped to its image row before anything is drawn.
 #include "rt_nee_common.h"
 #include "rt_variant_dispatch.h"
 
@@ -44,7 +46,7 @@ constexpr int kStreamWaves = TEXTURED ? 1
 // own copy.  Three variants are compiled the other way round: in the default shape their kernels carry a 32- or 64-byte
 // stack frame that no instruction touches (slots of scalar spills that ended up in VGPR lanes), and a private segment has
 // to be set up for every wave of such a launch; in this shape they have none and stay in k_nee_f64's occupancy step
-// (tests/test_nee_stream_isa.py holds both).  Same arithmetic either way.  The price: fast (0,1,1,0) takes 252 VGPRs in
+// (tests/test_nee_stream_isa.py holds both).  Same arithmetic either way.  The price: fast (0,1,1,0) takes 250 VGPRs in
 // this shape (k_nee_f64: 235) — the same step, 1 wave, but with little room left under 256.
 enum : unsigned { STREAM_PROLOGUE_FROM_COPY = 1u, STREAM_LOOP_FROM_KERNARGS = 2u };
 template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH>
@@ -67,6 +69,35 @@ __device__ __forceinline__ void stream_tile_of(const RT_CONSTANT TraceArgs *K, u
     reg_tiles = ntx * (uint32_t)K->regions[region].nty;
 }
 
+// Tile row -> image row of the lane's pixel.  A region's tile rows are rows of the launch's OWNED-row grid (rt_device_types.h:
+// Region), so with strips (strip_count > 1: a share of rt_render_frame_nee_multi / rt_render_nee_multi) the lane's owned row
+// ty * 8 + lane / 8 maps to the image row every other kernel forms.  Strips of whole tile rows (strip_rows % 8 == 0) keep
+// every strip quantity wave-uniform: the tile's first image row is scalar and the lane adds its offset; only a strip that
+// cuts a tile takes the per-lane division, as k_trace_pool_f64 does around rows_aligned.  An owned row at or beyond
+// owned_rows (a last tile row that hangs over) lies in a strip that starts below the image: its image row is >= height.
+__device__ __forceinline__ int stream_image_row(const RT_CONSTANT TraceArgs *K, int ty, int lane) {
+    const int sub = lane >> 3;
+    const int strip_count = K->strip_count;
+    if (strip_count <= 1) return ty * 8 + sub;
+    const int strip_rows = K->strip_rows, strip_index = K->strip_index;
+    if ((strip_rows & 7) == 0) {
+        const int q = (ty * 8) / strip_rows; // wave-uniform
+        return (q * strip_count + strip_index) * strip_rows + (ty * 8 - q * strip_rows) + sub;
+    }
+    const int vrow = ty * 8 + sub;
+    return ((vrow / strip_rows) * strip_count + strip_index) * strip_rows + vrow % strip_rows;
+}
+
+// ... as a call, for the tile prologue of the kernel: the strip road's registers are the callee's, live for the length of
+// the call and not beside the path loop's (the kernel has almost none to spare: DESIGN.md 4.10).  Only called with strips.
+__device__ __noinline__ int stream_image_row_strips(const RT_CONSTANT TraceArgs *K_in, int ty) {
+    const uint64_t bits = (uint64_t)K_in; // (arguments travel in VGPRs: readfirstlane makes them scalar again)
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
+    const RT_CONSTANT TraceArgs *K = (const RT_CONSTANT TraceArgs *)(((uint64_t)hi << 32) | lo);
+    return stream_image_row(K, __builtin_amdgcn_readfirstlane(ty), (int)(threadIdx.x & 63));
+}
+
 // The end of a tile: its pixels into TraceArgs.deliver_out (tile-column layout, rt_device_types.h), then the region's
 // counter and — by the wave that finishes the region — its flag: k_trace_pool_f64's deliver_item from the release fence
 // on, the hand-off that has been soaked on hardware.  Out of line, and fed the item number alone: the tile's coordinates
@@ -85,7 +116,7 @@ __device__ __noinline__ void stream_deliver_tile(const RT_CONSTANT TraceArgs *K_
     int region, tx, ty;
     uint32_t reg_tiles;
     stream_tile_of(K, item, region, tx, ty, reg_tiles);
-    const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
+    const int px = tx * 8 + (lane & 7), py = stream_image_row(K, ty, lane); // the IMAGE row: deliver_out is the whole frame's
     if (px < K->width && py < K->height) {
         // column `col` starts at pixel column col * step and is stored as [height][its width][3] behind the columns before it
         int col = px / K->deliver_col_step;
@@ -141,10 +172,13 @@ __global__ __launch_bounds__(256, (kStreamWaves<PRIMS, TEXTURED, SPECULAR, BVH>)
         uint32_t reg_tiles;
         stream_tile_of(kernargs_here(), item, region, tx, ty, reg_tiles);
         const int px = tx * 8 + (lane & 7);
-        const int py = ty * 8 + (lane >> 3);
+        int py = ty * 8 + (lane >> 3);
+        if (kernargs_here()->strip_count > 1) py = stream_image_row_strips(kernargs_here(), ty); // owned row -> image row, once per tile
         const RT_CONSTANT TraceArgs *K = kernargs_here();
         const bool from_copy = (SHAPE & STREAM_PROLOGUE_FROM_COPY) != 0u;
-        const int width = from_copy ? A.width : K->width;
+        // (the width through kernargs_here() in both shapes: with the row map above, a copy-shaped prologue that also takes the
+        // width from the copy brings the unused stack frame back to fast (0,1,1,0); height and seeds stay the shape's)
+        const int width = K->width;
         const bool in_image = px < width && py < (from_copy ? A.height : K->height);
 
         PathRng rng;

@@ -364,8 +364,25 @@ int enqueue_denoise(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *
 int build_light_list(RtScene *s, const LightTables &t);
 // What every NEE entry point refuses before a device is touched (rt_nee.hip), the scene last so that each refusal names
 // its own cause; `what` is the entry point's name in the messages about whole frames.
+// `strips`: params->strip_count > 1 is not refused (rt_render_frame_nee_strips_device; check_params holds the strip values).
 int check_nee(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
-              const char *what = "rt_render_frame_nee");
+              const char *what = "rt_render_frame_nee", bool strips = false);
+// ... the part about camera, params and light sampling alone, short of check_params (the several-scene calls, rt_deliver.hip
+// and rt_multi.hip, check their scene list next).
+int check_nee_args(const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, const char *what,
+                   bool strips = false);
+// rt_render_frame_nee_device's launches for the rows `p` owns (rt_nee.hip): k_nee_f64 into the scene's full-frame
+// accumulator, then the resolve pass of the owned rows into out_device (a full frame; rows not owned are not written), on
+// `stream`, not synchronised.  A share that owns no rows launches nothing (note_idle_share).  reserve_nee_buffers
+// allocates now what enqueue_nee (`delivering` false) or enqueue_nee_stream (true) would allocate for these parameters: a
+// call over several shares reserves for all of them before its first launch.  note_idle_share gives a share that launched
+// nothing the statistics of an empty call (no sample, no segment, kernel_launches 0).
+int enqueue_nee(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, double *out_device,
+                hipStream_t stream);
+int reserve_nee_buffers(RtScene *s, const RtRenderParams *p, bool delivering);
+int note_idle_share(RtScene *s, hipStream_t stream);
+// The counters of a delivering launch over `n_tiles` item tiles (rt_api.hip; zero between launches).
+int reserve_delivery_counters(RtScene *s, size_t n_tiles);
 // A whole NEE frame enqueued pass by pass (rt_progressive.hip), the NEE form of begin_passes / enqueue_chunks:
 // begin_nee_passes fills the argument blocks and enqueues what precedes the first launch — statistics cleared, the cancel
 // word armed when `cancellable`, ev_begin — and enqueue_nee_pass launches, chunk by chunk of [c0, c1), k_nee_pass_f64 for
@@ -395,4 +412,7 @@ int setup_delivery(RtScene *s, rtdev::TraceArgs &a, const Delivery &delivery, in
 int ensure_host_frame(RtScene *s, size_t doubles);
 // The several-device calls (rt_deliver.hip, rt_multi.hip): a non-empty list of distinct, non-NULL scenes.
 int check_scenes(RtScene *const *scenes, int n);
+// ... of the NEE forms (rt_deliver.hip): check_nee_args, check_scenes, strip_rows >= 0, check_params — no device touched.
+int check_nee_shares(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p,
+                     const RtLightSamplingParams *ls, int strip_rows, const char *what);
 } // namespace rtapi

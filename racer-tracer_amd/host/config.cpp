@@ -222,6 +222,14 @@ Args Args::parse(int argc, const char *const *argv) {
                 throw TracerError::ArgumentParsingError("--temporal needs a positive number of frames, not '" + v + "'");
             a.temporal = (int)k;
         }
+        else if (s == "--nee-devices") {
+            const std::string v = val();
+            char *end = nullptr;
+            const long k = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || end == nullptr || *end != '\0' || k < 1 || k > 1024)
+                throw TracerError::ArgumentParsingError("--nee-devices needs a positive number of devices, not '" + v + "'");
+            a.nee_devices = (int)k;
+        }
         else if (s == "-h" || s == "--help") a.help = true;
         else throw TracerError::ArgumentParsingError("unknown argument " + s);
     }
@@ -243,6 +251,10 @@ Args Args::parse(int argc, const char *const *argv) {
         throw TracerError::ArgumentParsingError("--temporal renders on one device: it does not combine with --devices > 1");
     if (a.nee && a.devices > 1)
         throw TracerError::ArgumentParsingError("--nee renders on one device: it does not combine with --devices > 1");
+    if (a.nee_devices > 0 && (a.nee || a.nee_stream || a.adaptive > 0.0 || a.nee_adaptive > 0.0 || a.temporal > 0))
+        throw TracerError::ArgumentParsingError("--nee-devices is a render mode of its own: it does not combine with --nee, --nee-stream, --adaptive, --nee-adaptive or --temporal");
+    if (a.nee_devices > 0 && a.devices > 1)
+        throw TracerError::ArgumentParsingError("--nee-devices N names its own devices: it does not combine with --devices > 1");
     return a;
 }
 

@@ -9,7 +9,8 @@
 // frame through rt_render_adaptive, a tile stopping once its error is at most T; --denoise filters that frame) and --nee (one
 // device renders the frame through rt_render_frame_nee, next-event estimation; --denoise filters that frame) and
 // --nee-adaptive T (--adaptive's stop rule with the next-event estimator: rt_render_adaptive_nee) and --nee-stream (--nee's
-// frame through rt_render_nee, tile by tile into the screen buffer; the PNG has --nee's bytes) and --temporal K (one device
+// frame through rt_render_nee, tile by tile into the screen buffer; the PNG has --nee's bytes) and --nee-devices N (the same
+// stream through rt_render_nee_multi, the frame's strips dealt to devices device .. device+N-1) and --temporal K (one device
 // renders K frames of the configured sample count at seeds seed .. seed + K - 1 from the configured camera through
 // rt_render_temporal and writes the last; --denoise gives the filter its levels, without it the history alone is shown).
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
@@ -56,7 +57,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee] [--nee-stream] [--nee-adaptive T] [--temporal K]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--temporal K]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -78,7 +79,8 @@ int main(int argc, char **argv) {
     auto destroy_scenes = [&] {
         for (RtScene *s : scenes) rt_scene_destroy(s);
     };
-    for (int k = 0; k < args.devices; ++k) { // one upload of the (tiny) scene per device
+    const int n_devices = args.nee_devices > 0 ? args.nee_devices : args.devices;
+    for (int k = 0; k < n_devices; ++k) { // one upload of the (tiny) scene per device
         RtScene *scene = nullptr;
         rc = rt_scene_create(rth_session_scene(session), args.device + k, &scene);
         if (rc != RT_OK) {
@@ -146,6 +148,11 @@ int main(int argc, char **argv) {
         RtLightSamplingParams ls;
         rt_light_sampling_params_default(&ls);
         rc = rt_render_nee(scenes[0], rth_session_camera(session), &params, &ls, on_tile, &sb, nullptr, nullptr);
+    } else if (args.nee_devices > 0) { // --nee-stream's tiles from every device's strips: a tile column arrives once all have it
+        RtLightSamplingParams ls;
+        rt_light_sampling_params_default(&ls);
+        rc = rt_render_nee_multi(scenes.data(), (int)scenes.size(), rth_session_camera(session), &params, &ls, 0, on_tile, &sb, nullptr,
+                                 nullptr);
     } else if (scenes.size() == 1) {
         // the reference's tile stream (cpu.rs:64-70): every finished tile goes through ScreenBuffer::update's tone map;
         // with several devices a tile column arrives once every device has finished its strips of it
