@@ -273,7 +273,13 @@ int launch_pool(RtScene *s, rtdev::TraceArgs &a, const std::vector<int> &starts,
         return fail(RT_ERR_UNSUPPORTED, "more than 2^30 work items in one launch");
     a.queue = s->buf.queue.ptr + index;
     const unsigned blocks = std::min(max_blocks, (a.n_items + 3) / 4);
-    RT_HIP(s->kernels->trace_pool(&a, s->prims_class, s->textured, s->specular, s->use_bvh, blocks, stream));
+    // the pixel rectangle of every rect record (rt_primary_bounds.h), from this call's camera like the scene's own, which
+    // fill_args has put into `a`: the kernel's second argument (tests/test_background_flag_cpu.py holds TraceArgs to
+    // ending at bg_black).  A few dozen 3x3 determinants per launch; nothing is kept between calls.
+    const rtdev::PrimaryRects rects = rtdev::primary_rects(a.cam.origin, a.cam.ulc, a.cam.horizontal, a.cam.vertical, a.width, a.height,
+                                                           rtdev::PixelRect{a.cull_px0, a.cull_px1, a.cull_py0, a.cull_py1},
+                                                           s->primary_rect_geo.data(), (int)s->primary_rect_geo.size());
+    RT_HIP(s->kernels->trace_pool(&a, &rects, s->prims_class, s->textured, s->specular, s->use_bvh, blocks, stream));
     return RT_OK;
 }
 

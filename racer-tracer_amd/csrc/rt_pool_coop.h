@@ -3,6 +3,7 @@
 // (unit sphere, lens disk, Perlin turbulence) over the request slots of rt_pool_lds.h.
 #pragma once
 #include "rt_pool_lds.h"
+#include "rt_primary_bounds.h"
 
 namespace RT_KNS {
 
@@ -41,6 +42,12 @@ __device__ __forceinline__ void move_masked(const d3 &p, uint64_t mask, d3 &v) {
 __device__ __forceinline__ void increment_masked(uint32_t &v, uint64_t mask) {
     asm("v_addc_co_u32 %[v], vcc, 0, %[v], %[mask]" : [v] "+v"(v) : [mask] "s"(mask) : "vcc");
 }
+// The pooled kernel's second argument (rt_primary_bounds.h: PrimaryRects), re-read where it is used like the first
+// (kernargs_here): it follows TraceArgs in the kernel argument segment.
+static_assert(sizeof(TraceArgs) % alignof(rtdev::PrimaryRects) == 0, "no padding between the kernel's two arguments");
+__device__ __forceinline__ const RT_CONSTANT rtdev::PrimaryRects *primary_rects_here() {
+    return (const RT_CONSTANT rtdev::PrimaryRects *)((const RT_CONSTANT unsigned char *)kernargs_here() + sizeof(TraceArgs));
+}
 // The lowest set bit of every group of 2^lg bits of x (1 <= lg <= 6), in the scalar unit: x & -x within each group, the
 // negation done per group as (~x without the groups' top bits) + 1 in every group, whose carry stops at the group's top
 // bit, XOR the top bits of ~x
@@ -57,8 +64,13 @@ __device__ __forceinline__ uint64_t lowest_in_groups(uint64_t x, int lg) {
 // strict `t < best_t`), one straight-line test per group with the plane a compile-time constant.  PAIRS: two records per
 // scalar-load wait (what the path loop runs); without, one test site per plane (the camera batches: every site is a copy
 // of the rect test in the kernel's text).
+// `rect_mask` (the batches only): record i is stepped over, in front of its scalar load, when bit i is clear — no ray of
+// the call can hit it (rt_trace_pool_kernel.hip: start_item).  Bits exist for the table's first RT_PRIMARY_RECTS records;
+// a longer table comes with every bit set, so the bit of record i & 31 answers for record i.
+static_assert(rtdev::RT_PRIMARY_RECTS <= 32, "a rect mask is one 32-bit word");
 template <bool PAIRS>
-__device__ __forceinline__ void closest_hit_rects(const Prim *table, const d3 &o, const d3 &d, const d3 &inv_d, double &best_t, int &best) {
+__device__ __forceinline__ void closest_hit_rects(const Prim *table, const d3 &o, const d3 &d, const d3 &inv_d, double &best_t, int &best,
+                                                  uint32_t rect_mask = ~0u) {
     auto test_plane = [&](auto axis, const Prim &P, int i) {
 #ifndef RT_EXACT_DIV
         rect_closest_update<decltype(axis)::value>(P.p[0], P.p[1], P.p[2], P.p[3], P.p[4], o, d, inv_d, 0.001, best_t, best, i);
@@ -85,7 +97,16 @@ __device__ __forceinline__ void closest_hit_rects(const Prim *table, const d3 &o
                 ++rec;
             }
         } else {
-            for (; i < end; ++i, ++rec) test_plane(axis, load_prim_uniform(rec, 0), i);
+            // a plane none of whose records is left: stepped over whole, in front of the ray's reciprocal on that axis
+            // (which the compiler forms where the group's first test needs it)
+            const int n = end - i;
+            if (n > 0 && n < 32 && ((rect_mask >> (i & 31)) & ((1u << n) - 1u)) == 0u) {
+                i = end;
+                // (the byte offset as a 32-bit product, in the scalar unit)
+                rec = reinterpret_cast<const Prim *>(reinterpret_cast<const unsigned char *>(rec) + (uint32_t)n * (uint32_t)sizeof(Prim));
+            }
+            for (; i < end; ++i, ++rec)
+                if ((rect_mask >> (i & 31)) & 1u) test_plane(axis, load_prim_uniform(rec, 0), i);
         }
     };
     // (the group bounds are re-read from the kernel arguments here: see the path loop of the other variants)

@@ -97,6 +97,11 @@ struct PretraceLds {
     uint32_t ring_w[RING_SLOTS];   // (its index in the item's pool)
     uint16_t ring_best[RING_SLOTS]; // ... and primitive (the table is staged in LDS, 192 bytes a record: under 1 000 records)
     uint32_t n_started;            // paths this wave has started (RtRenderStats.samples): every entry of every batch
+    // the current item's rect mask (start_item): bit i clear = no pixel of the item can see record i of the table, and the
+    // item's batches step over it.  Here, not in a scalar register: the path loop has none to spare.  (32 bits for the
+    // RT_PRIMARY_RECTS = 16 records that have a rectangle: the word fills the padding in front of `info`, so the block's
+    // static LDS stays at 20 096 bytes.)
+    uint32_t rect_mask;
     ItemInfo info[1]; // (one item at a time)
     double ulc[3];
 };

@@ -36,8 +36,8 @@
       (int prims_class, int textured, int specular, int bvh, size_t dyn_lds))                                              \
     X(pool_static_lds, rtdev_pool_static_lds, int, (int prims_class, int textured, int specular, int bvh))                 \
     X(trace_pool, rtdev_launch_trace_pool, hipError_t,                                                                     \
-      (const rtdev::TraceArgs *args, int prims_class, int textured, int specular, int bvh, unsigned blocks,               \
-       hipStream_t stream))                                                                                                \
+      (const rtdev::TraceArgs *args, const rtdev::PrimaryRects *rects, int prims_class, int textured, int specular,       \
+       int bvh, unsigned blocks, hipStream_t stream))                                                                      \
     X(resolve_chunks, rtdev_launch_resolve_chunks, hipError_t,                                                             \
       (const double *partial, double *out, int width, int height, int n_chunks, int slice_rows, int strip_rows,           \
        int strip_count, int strip_index, int step_x, int step_y, int cover_w, int cover_h, int out_col_step, int out_cols, \
@@ -234,6 +234,9 @@ struct RtScene {
     // union of the primitives' bounds (rt_bvh.h: primitive_bounds), for the pixel rectangle camera rays can hit anything
     // in (rt_primary_bounds.h); empty (mn > mx) for a scene without primitives
     double box_mn[3] = {1.0, 1.0, 1.0}, box_mx[3] = {-1.0, -1.0, -1.0};
+    // the records of a linear table of plain rects only, in device table order, for their own pixel rectangles
+    // (rt_primary_bounds.h: primary_rects); empty for every other table and for one of more than RT_PRIMARY_RECTS records
+    std::vector<rtdev::RectGeo> primary_rect_geo;
 
     // closest hit: linear loop for small scenes, skip-link BVH (rt_bvh.h) above kBvhThreshold primitives
     int use_bvh = 0;

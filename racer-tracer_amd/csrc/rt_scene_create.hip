@@ -250,6 +250,13 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
         for (int g = 0; g < 3; ++g) s->rect_end[g] = groups.rect_end[g];
         s->sphere_end = groups.sphere_end;
         s->box_end = groups.box_end;
+        // a table of plain rects only: what their own pixel rectangles are formed from on every render (rt_primary_bounds.h)
+        const int n_rects = groups.rect_end[2];
+        if (n_rects == d->n_primitives && n_rects <= rtdev::RT_PRIMARY_RECTS)
+            for (int j = 0; j < n_rects; ++j) {
+                const rtdev::Prim &q = prims[(size_t)j];
+                s->primary_rect_geo.push_back(rtdev::RectGeo{j < groups.rect_end[0] ? 2 : (j < groups.rect_end[1] ? 1 : 0), q.p[0], q.p[1], q.p[2], q.p[3], q.p[4]});
+            }
     }
     const rtapi::LightTables lights = rtapi::light_tables(d, order, rtapi::kMaxLights);
 

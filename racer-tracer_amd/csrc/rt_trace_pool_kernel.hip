@@ -67,6 +67,8 @@
 //    lane that takes an entry traces the path's SECOND segment in the same iteration.  Every sample keeps its bits; the
 //    order in which an item's samples reach its sums changes (spp 1 and 2 frames are bit-identical to the old loop's).
 //    C3 59.6 -> 56.4 ms (LABNOTES R10.1).  The other variants keep the loop of ideas 1 - 9.
+//    An item none of whose pixels can see the scene takes no batch at all, and a batch tests only the rects — and forms
+//    the ray's reciprocal only on the planes — that some pixel of its item can see (rt_primary_bounds.h; start_item).
 //
 // The launch is VALU-throughput bound with the CU's one scalar ALU close behind (scalar_busy 0.60 on C3: count scalar
 // instructions before vector ones; DESIGN.md 4.2 / 6 and LABNOTES.md have the counters, the per-region cycle profile of the
@@ -75,6 +77,7 @@
 #include <cstddef>
 #include <type_traits>
 #include "rt_trace_common.h"
+#include "rt_primary_bounds.h"
 #include "rt_variant_dispatch.h"
 #include "rt_pool_profile.h"
 #include "rt_pool_lds.h"
@@ -106,7 +109,9 @@ namespace RT_KNS {
 // BVH: closest hit through the skip-link hierarchy instead of the linear loop
 // (instantiated for PRIMS_ANY only; chosen for scenes with many primitives).
 template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH>
-__global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC_TEX_BVH : RT_OCC_TEX_ANY) : RT_OCC_TEX) : (BVH ? 4 : (PRIMS == PRIMS_ANY ? RT_OCC_ANY : (SPECULAR ? RT_OCC_SPEC : RT_OCC_PLAIN)))) void k_trace_pool_f64(const TraceArgs A) {
+__global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC_TEX_BVH : RT_OCC_TEX_ANY) : RT_OCC_TEX) : (BVH ? 4 : (PRIMS == PRIMS_ANY ? RT_OCC_ANY : (SPECULAR ? RT_OCC_SPEC : RT_OCC_PLAIN)))) void k_trace_pool_f64(const TraceArgs A, const rtdev::PrimaryRects) {
+    // (the second argument, the rect records' pixel rectangles, is read by the PRETRACE variant alone, through the kernel
+    // argument segment where it is used: primary_rects_here)
     // Two batches of camera samples stay ahead of the hand-out, so that it may straddle a batch
     // boundary; the BVH variants keep one (their node array wants the LDS: three resident blocks
     // instead of two on the `random` scene) and a hand-out stops at the end of its batch.
@@ -353,6 +358,24 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             const int x0 = K->cull_px0, x1 = K->cull_px1, y0 = K->cull_py0, y1 = K->cull_py1;
             const uint64_t seen = valid_mask & ballot(my_px >= x0) & ballot(my_px <= x1) & ballot(my_py >= y0) & ballot(my_py <= y1);
             culled = seen == 0ull && K->bg.kind != RT_BG_SKY && K->max_depth >= 1;
+            // RECTS NO CAMERA RAY OF THE ITEM CAN HIT.  The host also bounds the pixels that can see each of the table's first
+            // records (PrimaryRects, the kernel's second argument): bit i of the item's mask says that some valid pixel of the
+            // item lies inside record i's rectangle, and the item's batches step over the records whose bit is clear
+            // (closest_hit_rects<false>) — such a record's test would change neither `best` nor `best_t` of any of their rays.
+            // Per PIXEL, as above, not per tile box: strips that cut the tiles scatter an item's rows over the image.  The
+            // bits of the records without a rectangle stay set.  The mask waits in LDS: a scalar register kept across the path
+            // loop is one the loop has not got.
+            uint32_t rect_mask = ~0u;
+            if (!culled) {
+                const RT_CONSTANT rtdev::PrimaryRects *R = primary_rects_here();
+                const int n_rects = R->n;
+                for (int i = 0; i < n_rects; ++i) {
+                    const int rx0 = R->r[i].px0, rx1 = R->r[i].px1, ry0 = R->r[i].py0, ry1 = R->r[i].py1;
+                    const uint64_t sees = valid_mask & ballot(my_px >= rx0) & ballot(my_px <= rx1) & ballot(my_py >= ry0) & ballot(my_py <= ry1);
+                    if (sees == 0ull) rect_mask &= ~(1u << i);
+                }
+            }
+            if (lane == 0) L.rect_mask = rect_mask;
         }
         {
             if (!culled) { // (a culled item forms no ray)
@@ -573,7 +596,9 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         double best_t = __builtin_inf();
         int best = -1;
         increment_masked(n_segments, in_pool);
-        closest_hit_rects<false>(A.prims, bo, bd, rcp3(bd), best_t, best);
+        // (the records no pixel of this item can see are stepped over: start_item)
+        const uint32_t rect_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.rect_mask);
+        closest_hit_rects<false>(A.prims, bo, bd, rcp3(bd), best_t, best, rect_mask);
         // what the path adds to its pixel if it ends here (its throughput is 1): the background
         // (background_color.rs:27-33 / :45-48), or what it hit
         d3 C = ld3(L.bg_top);
@@ -595,9 +620,12 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         const uint64_t ends = kernargs_here()->max_depth <= 1 ? in_pool : (in_pool & ~hit) | light;
         const uint64_t lives = in_pool & ~ends;
         if (__builtin_amdgcn_inverse_ballot_w64(ends)) { // vec3.rs:38-42 Color::add into the pixel's sum
-            atomicAdd(&L.sum[pix_b][0], C.x);
-            atomicAdd(&L.sum[pix_b][1], C.y);
-            atomicAdd(&L.sum[pix_b][2], C.z);
+            // (the pixel's sum by a 32-bit product, one v_mad_u32_u24: written &L.sum[pix_b][k] the address is a 64-bit
+            // v_mad_u64_u32 wherever the compiler has not kept L.u's address of the same pixel to add to)
+            double *const sum = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(&L.sum[0][0]) + (uint32_t)pix_b * (uint32_t)sizeof(L.sum[0]));
+            atomicAdd(sum + 0, C.x);
+            atomicAdd(sum + 1, C.y);
+            atomicAdd(sum + 2, C.z);
         }
         if (lane == 0) L.n_started += (uint32_t)__popcll(in_pool);
         // ---- the others queue up behind the ring's entries, in pool order: an entry's place is at or below where its
@@ -1310,10 +1338,10 @@ namespace {
 // One table entry per compiled variant: PRIMS x TEXTURED x SPECULAR with the
 // linear closest-hit loop, plus PRIMS_ANY x TEXTURED x SPECULAR with the BVH.
 template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH> struct PoolVariant {
-    static void launch(const rtdev::TraceArgs &a, unsigned blocks, hipStream_t stream) {
+    static void launch(const rtdev::TraceArgs &a, const rtdev::PrimaryRects &r, unsigned blocks, hipStream_t stream) {
         const size_t dyn = rtdev::pool_lds_layout(BVH, TEXTURED, a.n_prims, a.n_textures, a.bvh_lds_nodes, a.perlin_in_lds, a.lens_lds,
                                                   a.time_lds).bytes;
-        hipLaunchKernelGGL((RT_KNS::k_trace_pool_f64<PRIMS, TEXTURED, SPECULAR, BVH>), dim3(blocks), dim3(256), dyn, stream, a);
+        hipLaunchKernelGGL((RT_KNS::k_trace_pool_f64<PRIMS, TEXTURED, SPECULAR, BVH>), dim3(blocks), dim3(256), dyn, stream, a, r);
     }
     static int blocks_per_cu(size_t dyn_lds) {
         int n = 0;
@@ -1349,11 +1377,11 @@ extern "C" int RT_LAUNCHER(rtdev_pool_static_lds)(int prims_class, int textured,
                                                 [](auto v) { return decltype(v)::static_lds(); });
 }
 
-extern "C" hipError_t RT_LAUNCHER(rtdev_launch_trace_pool)(const rtdev::TraceArgs *args, int prims_class, int textured, int specular,
-                                              int bvh, unsigned blocks, hipStream_t stream) {
+extern "C" hipError_t RT_LAUNCHER(rtdev_launch_trace_pool)(const rtdev::TraceArgs *args, const rtdev::PrimaryRects *rects, int prims_class,
+                                              int textured, int specular, int bvh, unsigned blocks, hipStream_t stream) {
     if (blocks == 0 || args->n_items == 0) return hipSuccess;
     rtdev::dispatch_variant<PoolVariant>(prims_class, textured != 0, specular != 0, bvh != 0, [&](auto v) {
-        decltype(v)::launch(*args, blocks, stream);
+        decltype(v)::launch(*args, *rects, blocks, stream);
     });
     return hipGetLastError();
 }
