@@ -74,16 +74,20 @@ template <bool TEXTURED, int NBUF, bool OVERLAP> struct WaveLds {
     double ulc[3];
 };
 
-// Survivors a camera batch of the PRETRACE variant may park (see PRIMARY SEGMENTS IN THE BATCHES in the kernel): a batch
-// adds up to 64 and runs when at most RING_SLOTS - 64 are waiting.
-enum : uint32_t { RING_SLOTS = 92u };
+// Survivors of the PRETRACE variant's camera batches that may wait for a lane (see PRIMARY SEGMENTS IN THE BATCHES in the
+// kernel): a batch adds up to 64 and runs when at most RING_SLOTS - 64 are waiting.  67 is what 2 024 bytes per wave hold
+// of 30-byte entries; nothing but a batch needs free slots.
+enum : uint32_t { RING_SLOTS = 67u };
+// A ring entry's `best` word: the primitive in the low bits (the table is staged in LDS, 192 bytes a record: under 1 000
+// records), and above it the sign bits of the camera ray's direction, which is all the normal of the hit needs of it
+enum : uint32_t { RING_BEST_BITS = 13u, RING_BEST_MASK = (1u << RING_BEST_BITS) - 1u };
 // Per-wave scratch of the PRETRACE variant (rects only, no textures, no specular materials): the members of WaveLds that
 // variant reads, under the same names, and the ring of pool entries whose primary segment a batch has traced and that
-// live on.  An entry keeps what its ray is formed from (v; the pixel's u stays in `u`) and its first hit: 22 bytes, where
-// the ray itself would take 48.  WaveLds' `base` and `v` have no counterpart (the ray is formed from u and the ring's v);
-// with them gone the block has 20 096 bytes of static LDS, 64 fewer than before, and seven blocks still fit a CU beside
-// C3's primitive table (the seven-block edge is 23 040 bytes).  The lens samples of the ring's entries sit in the dynamic
-// LDS that holds the two batches' in the other variants (128 slots per wave).
+// live on.  An entry is the POINT of its primary hit, its pool index, and the `best` word above: 30 bytes, as a structure
+// of arrays.  The lane that takes it loads the point into its ray origin and computes nothing: the camera ray, its
+// parameter and the lens sample were consumed by the batch.  WaveLds' `base` and `v` have no counterpart.  The block has
+// at most 20 096 bytes of static LDS, and seven blocks fit a CU beside C3's primitive table (the seven-block edge is
+// 23 040 bytes) — in the RT_PROFILE_REGIONS build too, which 64 bytes more would cost a block per CU.
 struct PretraceLds {
     // camera.origin and background.top, for the same reason as `ulc` below: a rect test and an LDS add take their
     // operands from vector registers, and an LDS read puts them there without a vector instruction
@@ -92,10 +96,9 @@ struct PretraceLds {
     double sum[64][3]; // per-pixel radiance sums (doubles)
     SamplerScratch<false> scratch;
     uint8_t pix_of[64];
-    double ring_v[RING_SLOTS];     // (py + jv) / (H - 1) of the entry
-    double ring_t[RING_SLOTS];     // its primary hit: ray parameter ...
-    uint32_t ring_w[RING_SLOTS];   // (its index in the item's pool)
-    uint16_t ring_best[RING_SLOTS]; // ... and primitive (the table is staged in LDS, 192 bytes a record: under 1 000 records)
+    double ring_p[3][RING_SLOTS];   // the entry's primary hit: its point (ray_at of the batch's ray) ...
+    uint32_t ring_w[RING_SLOTS];    // (its index in the item's pool)
+    uint16_t ring_best[RING_SLOTS]; // ... its primitive, and the ray direction's signs: bit RING_BEST_BITS + k set = d[k] < 0
     uint32_t n_started;            // paths this wave has started (RtRenderStats.samples): every entry of every batch
     // the current item's rect mask (start_item): bit i clear = no pixel of the item can see record i of the table, and the
     // item's batches step over it.  Here, not in a scalar register: the path loop has none to spare.  (32 bits for the

@@ -696,6 +696,11 @@ __device__ __forceinline__ UV sphere_uv_f32(d3 outward) {
               (double)theta * (1.0 / 3.14159265358979323846)};
 }
 
+// ray.rs:30-32 Ray::at.  ONE expression for every place that forms a hit's point (prim_hit_record below; the rects-only
+// pooled kernel behind its closest-hit loops): the fast flavour contracts it to three fma wherever it stands, the
+// RT_ARITH_REFERENCE flavour keeps the product and the sum, so a point's bits never depend on where it was formed.
+__device__ __forceinline__ d3 ray_at(d3 o, double t, d3 d) { return o + t * d; }
+
 // Rebuild the HitRecord of the winning primitive (geometry.rs:17-57).
 // FAST_UV: a plain sphere's (u, v) may come from sphere_uv_f32 (Hit.uv_approx says so); the pooled kernel's texture code
 // certifies it, the v1 kernel keeps the f64 form.
@@ -709,7 +714,7 @@ __device__ __forceinline__ Hit prim_hit_record(const Prim &P, d3 o, d3 d, double
         dd = rot_fwd(dd, P.rot_sin, P.rot_cos);
     }
     Hit h;
-    h.point = oo + t * dd; // ray.rs:30-32
+    h.point = ray_at(oo, t, dd);
     h.u = 0.0;
     h.v = 0.0;
     h.uv_approx = false;

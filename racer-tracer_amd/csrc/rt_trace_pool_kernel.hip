@@ -62,9 +62,10 @@
 // 10. PRIMARY SEGMENTS ARE TRACED IN THE CAMERA BATCHES (the rects-only plain variant, C3's, in both arithmetic flavours).
 //    The batch of idea 4 forms the rays of its 64 entries and runs the closest-hit loop on them, all lanes busy and the
 //    rays coherent; an entry whose path ends on that segment (a miss, a light, max_depth <= 1) adds its contribution there
-//    and never takes a lane, the others wait in a ring of 92 slots in LDS with their hit (22 bytes each).  The path loop of
-//    that variant is ROTATED: hand-out from the ring, shade the pending hits, sampler, new direction, trace, ends — so a
-//    lane that takes an entry traces the path's SECOND segment in the same iteration.  Every sample keeps its bits; the
+//    and never takes a lane, the others wait in a ring of 67 slots in LDS with the POINT of their hit, their primitive and
+//    the signs of their ray (30 bytes each).  The path loop of that variant is ROTATED: hand-out from the ring, shade the
+//    pending hits, sampler, new direction, trace, ends — so a lane that takes an entry loads a point and traces the path's
+//    SECOND segment in the same iteration; it forms no camera ray (LABNOTES R19.1).  Every sample keeps its bits; the
 //    order in which an item's samples reach its sums changes (spp 1 and 2 frames are bit-identical to the old loop's).
 //    C3 59.6 -> 56.4 ms (LABNOTES R10.1).  The other variants keep the loop of ideas 1 - 9.
 //    An item none of whose pixels can see the scene takes no batch at all, and a batch tests only the rects — and forms
@@ -524,11 +525,10 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
     // the closest-hit loop on them, with the expressions and the order of the path loop (a value never depends on where
     // it was computed).  An entry whose path ENDS on that segment (a miss, a light, or a depth limit of 0 or 1) adds its
     // contribution to the tile's sums right here and never takes a lane: on C3, whose camera looks at the box from
-    // outside, that is half the paths.  The others go to a ring in LDS (PretraceLds) with their hit, and the hand-out gives
-    // lanes ring entries instead of pool entries.
-    // The camera ray of pixel `pix` of the tile (camera.rs:326-337), for the batch and for the hand-out: ONE expression,
-    // so both get the same bits (upper_left_corner + u * horizontal, the vector the other variants keep per pixel, is
-    // formed here as the two-item variants do).
+    // outside, that is half the paths.  The others go to a ring in LDS (PretraceLds) with the POINT of their hit, and the
+    // hand-out gives lanes ring entries instead of pool entries: the camera ray is formed here and nowhere else.
+    // The camera ray of pixel `pix` of the tile (camera.rs:326-337) (upper_left_corner + u * horizontal, the vector the
+    // other variants keep per pixel, is formed here as the two-item variants do).
     // (TraceArgs.lens_lds is set exactly when the camera has an aperture: an integer the scalar unit can test)
     auto camera_ray = [&](int pix, double v, double lens_x, double lens_y, d3 &ro, d3 &rd) {
         if constexpr (PRETRACE) {
@@ -542,8 +542,6 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         }
         }
     };
-    double (*const lens_ring)[2] = reinterpret_cast<double (*)[2]>(lens); // lens samples of the ring's entries, by slot
-    static_assert(RING_SLOTS <= 2 * 64, "the ring's lens samples take the LDS of two batches'");
     auto pretrace_batch = [&](uint32_t b) {
         if constexpr (PRETRACE) {
         int lane = lane_of_wave; // (opaque, like start_item's)
@@ -568,12 +566,9 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             return;
         }
         const u4 bc = philox4x32(pixel_b, sample_b, RT_RNG_CAMERA, 0u, A.seed_lo, A.seed_hi);
-        // The 64 slots behind the ring's entries are free (the path loop sees to that: at most RING_SLOTS - 64 entries wait
-        // when a batch runs).  Lane l parks its camera sample in the l-th of them while the segment is traced — the registers
-        // are wanted there — and an entry that lives on moves it down to its place in the queue afterwards.
+        // (the 64 slots behind the ring's entries are free — the path loop sees to that: at most RING_SLOTS - 64 entries
+        // wait when a batch runs)
         const uint32_t in_ring = min(b << 6, total) - next;
-        uint32_t park = ring_head + in_ring + (uint32_t)lane; // (head < RING_SLOTS, in_ring + lane < RING_SLOTS)
-        if (park >= RING_SLOTS) park -= RING_SLOTS;
         d3 bo, bd;
         {
             const double v = div_by((double)py_b + u53(bc.a, bc.b), (double)(A.height - 1), K->inv_height_m1); // cpu.rs:39-40
@@ -586,11 +581,8 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 coop_random_in_unit_disk(w_here < total, pixel_b, sample_b, A.seed_lo, A.seed_hi, lane, L.scratch.req, lx, ly);
                 lx = lx * K->cam.lens_radius;
                 ly = ly * K->cam.lens_radius;
-                lens_ring[park][0] = lx;
-                lens_ring[park][1] = ly;
             }
-            L.ring_v[park] = v;
-            camera_ray(pix_b, v, lx, ly, bo, bd);
+            camera_ray(pix_b, v, lx, ly, bo, bd); // (the camera sample is consumed here: a ring entry carries none of it)
         }
         // ---- the primary segment (renderer.rs:56-58)
         double best_t = __builtin_inf();
@@ -628,27 +620,22 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             atomicAdd(sum + 2, C.z);
         }
         if (lane == 0) L.n_started += (uint32_t)__popcll(in_pool);
-        // ---- the others queue up behind the ring's entries, in pool order: an entry's place is at or below where its
-        // lane parked (rank <= lane), and one wave's LDS accesses complete in order — every read below before any write
+        // ---- the others queue up behind the ring's entries, in pool order (head < RING_SLOTS, in_ring + rank < RING_SLOTS),
+        // with the point of their hit — the expression and the operands the path loop's trace block gives ray_at — and the
+        // signs of the ray's direction, of which the normal takes the one on the rect's axis
         uint32_t slot = ring_head + in_ring + (uint32_t)lane_rank(lives);
         if (slot >= RING_SLOTS) slot -= RING_SLOTS;
         if (__builtin_amdgcn_inverse_ballot_w64(lives)) {
-            const double v = L.ring_v[park];
-            double lx, ly;
-            asm volatile("" : "=v"(lx), "=v"(ly));
-            if (kernargs_here()->lens_lds != 0) {
-                lx = lens_ring[park][0];
-                ly = lens_ring[park][1];
-            }
-            asm volatile("" ::: "memory"); // (the compiler keeps the reads above the writes)
-            L.ring_v[slot] = v;
-            L.ring_t[slot] = best_t;
+            asm volatile("; hit_point_begin" : "+v"(best_t));
+            d3 p = ray_at(bo, best_t, bd);
+            asm volatile("; hit_point_end" : "+v"(p.x), "+v"(p.y), "+v"(p.z));
+            auto sign_of = [](double dk) { return (uint32_t)((unsigned long long)__double_as_longlong(dk) >> 63); };
+            L.ring_p[0][slot] = p.x;
+            L.ring_p[1][slot] = p.y;
+            L.ring_p[2][slot] = p.z;
             L.ring_w[slot] = w;
-            L.ring_best[slot] = (uint16_t)best;
-            if (kernargs_here()->lens_lds != 0) {
-                lens_ring[slot][0] = lx;
-                lens_ring[slot][1] = ly;
-            }
+            L.ring_best[slot] = (uint16_t)((uint32_t)best | sign_of(bd.x) << RING_BEST_BITS | sign_of(bd.y) << (RING_BEST_BITS + 1u) |
+                                           sign_of(bd.z) << (RING_BEST_BITS + 2u));
         }
         next += (uint32_t)__popcll(ends); // `next` counts the entries that have left the pool: ended here, or handed out
         }
@@ -705,17 +692,19 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             ray_time = fuzz = 0.0;
         }
         // ---- the path loop of the PRETRACE variant, ROTATED: hand-out, shade the pending hits, sampler, new direction,
-        // trace, ends.  A lane leaves the trace block with its hit (`best`, `best_t`) or ended; the back edge sits between
-        // the trace block and the shading.  A lane that takes a ring entry gets the entry's primary hit in the same two
-        // registers, so it is shaded with the others, gets its sample and traces its SECOND segment in the iteration that
-        // hands it out: the loop traces no primary segment at all.  Across the sampler a lane holds what it holds in the
-        // other variants (`waiting`: o = the hit's point, d = its normal).
+        // trace, ends.  A lane leaves the trace block with its hit — `best`, and the hit's POINT in `o`, formed right behind
+        // the closest-hit loop (ray_at); `d` still holds the incoming direction, whose sign on the rect's axis makes the
+        // normal — or ended; the back edge sits between the trace block and the shading.  A lane that takes a ring entry
+        // LOADS the same: the point its batch formed with the same expression, `best`, and a direction of +-1.0s with the
+        // camera ray's signs.  So it is shaded with the others, gets its sample and traces its SECOND segment in the
+        // iteration that hands it out: the loop traces no primary segment and forms no camera ray.  Across the sampler a
+        // lane holds what it holds in the other variants (`waiting`: o = the hit's point, d = its normal).
         if constexpr (PRETRACE) {
-            double best_t = __builtin_inf(); // the pending hit of a lane with a path that is not `waiting`
-            int best = -1;
+            int best = -1; // the pending hit of a lane with a path that is not `waiting`
             for (;;) {
                 // ---- camera batches: keep more than RING_SLOTS - 64 entries in the ring while the pool has any (a batch
-                // needs 64 free slots; the hand-out goes short only where more lanes are idle than that, at an item's start)
+                // needs 64 free slots, and nothing else does; the hand-out goes short only where more lanes are idle than
+                // entries wait — at an item's start, and in the iteration that follows a batch most of whose entries ended)
                 while (batches_done < n_batches && min(batches_done << 6, total) - next <= RING_SLOTS - 64u) pretrace_batch(batches_done++);
                 RT_REGION(1); // batches
                 // ---- hand ring entries to the lanes without a path (ballot + prefix count)
@@ -740,21 +729,34 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                     next += n_take;
                     ring_head += n_take;
                     if (ring_head >= RING_SLOTS) ring_head -= RING_SLOTS;
-                    if (__builtin_amdgcn_inverse_ballot_w64(taking)) { // cpu.rs:39-40 + camera.rs:326-337, and the hit the batch found
+                    if (__builtin_amdgcn_inverse_ballot_w64(taking)) { // the hit the batch found: loads, and no arithmetic on doubles
+                        asm volatile("; hand_out_begin");
                         spix = pix_new;
                         rng.pixel = pixel_new;
                         rng.sample = (uint32_t)(smp0 + s_off);
-                        double lens_x, lens_y;
-                        asm volatile("" : "=v"(lens_x), "=v"(lens_y));
-                        if (kernargs_here()->lens_lds != 0) {
-                            lens_x = lens_ring[slot][0];
-                            lens_y = lens_ring[slot][1];
-                        }
-                        camera_ray(pix_new, L.ring_v[slot], lens_x, lens_y, o, d);
-                        best_t = L.ring_t[slot];
-                        best = (int)L.ring_best[slot];
+                        o = mk(L.ring_p[0][slot], L.ring_p[1][slot], L.ring_p[2][slot]);
+                        uint32_t word = L.ring_best[slot];
+                        asm volatile("" : "+v"(word)); // (a 32-bit value to shift: as a 16-bit one every shift count takes a register)
+                        best = (int)(word & RING_BEST_MASK);
+                        // What the shading below reads of the incoming direction is its sign on the rect's axis, so the lane
+                        // gets a direction with the camera ray's three signs.  The fast flavour's against() reads the sign bit
+                        // of the high word and nothing else: a shift that brings the entry's bit there is the whole
+                        // component (what it leaves below the sign bit is never read as a number).  The reference flavour's
+                        // set_face_normal takes a dot product with the axis: +-1.0.  The low words are whatever their
+                        // registers hold (the empty asm "defines" them without a move): mantissa bits of a finite number.
+                        auto signed_like = [word](uint32_t k) {
+                            uint32_t lo;
+                            asm volatile("" : "=v"(lo));
+                            uint32_t hi = word << (31u - RING_BEST_BITS - k);
+#ifdef RT_EXACT_DIV
+                            hi = 0x3FF00000u | (hi & 0x80000000u);
+#endif
+                            return __longlong_as_double((long long)((unsigned long long)hi << 32 | lo));
+                        };
+                        d = mk(signed_like(0u), signed_like(1u), signed_like(2u));
                         T = mk(1.0, 1.0, 1.0);
                         seg = 0;
+                        asm volatile("; hand_out_end");
                     }
                     alive_m |= taking;
                 }
@@ -770,14 +772,14 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 if (__builtin_amdgcn_inverse_ballot_w64(hit_m)) {
                     const Prim &P = lds_prims[best];
                     const Material &M = P.mat;
-                    const Hit h = prim_hit_record<PRIMS, TEXTURED, true>(P, o, d, ray_time, best_t, 0, false);
+                    // (the hit record: its point is in `o` since the segment was traced — or the entry handed out — and the
+                    // normal is formed below, from the sign of `d` on the rect's axis)
                     kind = M.kind;
                     RT_REGION(8); // hit record
                     T = T * ld3(M.color); // emission (the path ends) or attenuation: solid_color.rs:24-28
                     RT_REGION(9); // texture, step 1
                     // a light (diffuse_light.rs:25-37) ends the path, anything else is a Lambertian (lambertian.rs:26-38,
                     // direction below); what a Lambertian hit sets is dead in a path that has ended
-                    o = h.point;
                     cand_base = 0;
                     // the incoming direction is dead: lambertian.rs:27 starts from the normal
 #ifndef RT_EXACT_DIV
@@ -799,7 +801,11 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                                against(d.z, __builtin_amdgcn_inverse_ballot_w64(xy_m)));
                     }
 #else
-                    d = h.normal;
+                    {
+                        Hit h; // (prim_hit_record's normal of a plain rect: xy_rect.rs:43-45 and its siblings)
+                        set_face_normal_axis(h, d, P.kind == RT_PRIM_XY_RECT ? 2 : (P.kind == RT_PRIM_XZ_RECT ? 1 : 0));
+                        d = h.normal;
+                    }
 #endif
                 }
                 asm volatile("" : "+v"(kind));
@@ -846,13 +852,19 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 RT_LANES(__popcll(shooting), next >= total);
                 // (the pending hit is dead here — a lane that does not shoot is `waiting`, ended or idle, and none of those reads
                 // it before it is set again — and saying so costs no instruction: set to "no hit" out here, for every lane,
-                // the three moves were issued twice, here and again in front of the closest-hit loop)
-                asm volatile("" : "=v"(best_t), "=v"(best));
+                // the move was issued twice, here and again in front of the closest-hit loop)
+                asm volatile("" : "=v"(best));
                 if (__builtin_amdgcn_inverse_ballot_w64(shooting)) {
-                    best_t = __builtin_inf(); // closest hit, t in [0.001, inf) (renderer.rs:58)
+                    double best_t = __builtin_inf(); // closest hit, t in [0.001, inf) (renderer.rs:58): dead behind this block
                     best = -1;
                     ++n_segments;
                     closest_hit_rects<true>(A.prims, o, d, rcp3(d), best_t, best);
+                    // the hit's point takes the ray origin's place where the segment is traced: the shading block of the next
+                    // iteration forms none, and a ring entry can hand one out.  (A lane that missed gets o + inf * d, which
+                    // nothing reads: it ends below.)
+                    asm volatile("; hit_point_begin" : "+v"(best_t));
+                    o = ray_at(o, best_t, d);
+                    asm volatile("; hit_point_end" : "+v"(o.x), "+v"(o.y), "+v"(o.z));
                     RT_REGION(3); // closest hit
                 }
                 const uint64_t miss_m = shooting & ballot(best < 0);
