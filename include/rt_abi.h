@@ -636,6 +636,53 @@ int rt_render_frame_nee(RtScene *scene, const RtCamera *camera, const RtRenderPa
 int rt_render_frame_nee_device(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
                                const RtLightSamplingParams *light_sampling, double *rgb_device, void *hip_stream);
 
+/* ---------------------------------------------------------------- the light list of a scene
+ * rt_scene_create lists what the paragraph above says and picks among the listed lights uniformly: moving spheres, boxes
+ * and wrapped primitives are never listed.  rt_scene_set_lights widens that per scene ("the
+ * extended list"); until it is called a scene behaves as described above, and calling it with the defaults restores that
+ * list exactly.
+ *  - Listing.  Primitives are listed in table order, at most 64.  A primitive is listed when its material is
+ *    DiffuseLight and it is a Sphere with r > 0 or a rect of non-zero area (inside Translate / RotateY only with
+ *    RT_LIGHTS_WRAPPED), a Box of positive surface area with RT_LIGHTS_BOXES (a wrapped one needs RT_LIGHTS_WRAPPED too),
+ *    or a MovingSphere with r > 0 with RT_LIGHTS_MOVING.  rt_scene_lights reports the new list.
+ *  - Pick.  RT_PICK_UNIFORM: light k = min(floor(e0 n), n - 1) with probability 1 / n, n = min(max_lights, count).
+ *    RT_PICK_POWER: w_k = A_k L_k, A the object-frame surface area (rect |da db|, sphere 4 pi r^2, box 2 (ab + bc + ca)),
+ *    L the largest colour component of a SolidColor emitter (a negative or non-finite one counts as 0), else 1;
+ *    p_k = w_k / sum_{j<n} w_j, the running sums formed in f64 in table order with the last one set to 1, k the first
+ *    index with e0 < cdf_k.  A sum that is not positive and finite gives the uniform pick.  A light with p_k = 0 is never
+ *    sampled, and a bounce that hits it keeps weight 1.
+ *  - Kernels.  A scene whose list holds a wrapped, box or moving light, or whose pick is RT_PICK_POWER, is rendered by
+ *    the extended-light forms of the NEE kernels, which exist for the "anything" primitive class only: a rects-only or
+ *    spheres-only scene that asks for RT_PICK_POWER goes through that class's linear loop, whose primitive kinds are a
+ *    superset (same hits, same frame up to the arithmetic of another closest-hit loop).
+ *  - rt_scene_set_lights waits for the scene's own stream, replaces the device tables and may be called any number of
+ *    times; the caller serialises it with renders on that scene, as every call on one RtScene.  Every NEE entry point uses
+ *    the new list from then on.  The several-scene NEE calls refuse scenes that do not all carry the same list params.
+ *  - rt_scene_light_weights: the pick probabilities p_k of the whole (uncapped) list, the first min(capacity, count) into
+ *    out_p (may be NULL when capacity is 0), their number into *out_count.
+ *  - Refused with RT_ERR_INVALID_ARGUMENT before a device is touched: NULLs, kinds outside 0..7, an unknown pick, a
+ *    non-zero _reserved. */
+enum RtLightKinds {
+    RT_LIGHTS_PLAIN = 0,   /* what rt_scene_create lists */
+    RT_LIGHTS_WRAPPED = 1, /* ... inside Translate and / or RotateY too */
+    RT_LIGHTS_BOXES = 2,   /* Box emitters */
+    RT_LIGHTS_MOVING = 4,  /* MovingSphere emitters */
+    RT_LIGHTS_ALL = 7
+};
+enum RtLightPick {
+    RT_PICK_UNIFORM = 0,
+    RT_PICK_POWER = 1
+};
+typedef struct RtLightListParams {
+    int32_t kinds;        /* RtLightKinds, or-ed */
+    int32_t pick;         /* RtLightPick */
+    int32_t _reserved[6]; /* must be 0 */
+} RtLightListParams;
+/* The defaults: RT_LIGHTS_PLAIN, RT_PICK_UNIFORM — what rt_scene_create lists.  A NULL is ignored. */
+void rt_light_list_params_default(RtLightListParams *out);
+int rt_scene_set_lights(RtScene *scene, const RtLightListParams *p);
+int rt_scene_light_weights(RtScene *scene, double *out_p, int32_t capacity, int32_t *out_count);
+
 /* ---------------------------------------------------------------- next-event estimation in passes
  * rt_render_progressive and rt_render_adaptive with the next-event estimator: whole frames while
  * they converge, a cancel hook and the adaptive stop rule for rt_render_frame_nee's frames.

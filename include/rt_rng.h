@@ -69,6 +69,8 @@
 #define RT_RNG_LIGHT 8      /* rt_render_frame_nee: the light sample of the Lambertian vertex   */
                             /* of segment `seg`.  block 0: three 42-bit draws */
                             /* packed as RT_RNG_SCATTER's; e0 picks the light, e1, e2 its point */
+                            /* block 1 (a Box light of rt_scene_set_lights' list only): d0, a   */
+                            /* 53-bit draw, picks the box's side in proportion to its area      */
 
 /* Philox4x32 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3",
  * SC'11) with SEVEN rounds: the paper's Crush-resistant member of the family (Philox4x32-7

@@ -148,6 +148,16 @@ def light_sampling_params(**overrides):
     return ls
 
 
+def light_list_params(**overrides):
+    """rt_light_list_params_default, with fields overridden by keyword (kinds, pick) -> abi.RtLightListParams.  No device
+    needed."""
+    lp = abi.RtLightListParams()
+    lib().rt_light_list_params_default(C.byref(lp))
+    for k, v in overrides.items():
+        setattr(lp, k, v)
+    return lp
+
+
 def temporal_params(**overrides):
     """rt_temporal_params_default, with fields overridden by keyword (alpha, alpha_moments, max_history, normal_tolerance,
     plane_tolerance, sigma_luminance) -> abi.RtTemporalParams.  No device needed."""
@@ -322,6 +332,19 @@ class Scene:
         n = C.c_int32(0)
         out = (C.c_int32 * 64)()
         check(self._lib.rt_scene_lights(self._h, out, len(out), C.byref(n)), "rt_scene_lights", self._lib)
+        return list(out[:n.value])
+
+    def set_lights(self, kinds=abi.RT_LIGHTS_PLAIN, pick=abi.RT_PICK_UNIFORM):
+        """rt_scene_set_lights: list the scene's lights again (kinds: abi.RT_LIGHTS_*, or-ed; pick: abi.RT_PICK_*).  The
+        defaults restore rt_scene_create's list."""
+        lp = light_list_params(kinds=kinds, pick=pick)
+        check(self._lib.rt_scene_set_lights(self._h, C.byref(lp)), "rt_scene_set_lights", self._lib)
+
+    def light_weights(self):
+        """rt_scene_light_weights -> the pick probabilities of the listed lights (uncapped list)."""
+        n = C.c_int32(0)
+        out = (C.c_double * 64)()
+        check(self._lib.rt_scene_light_weights(self._h, out, len(out), C.byref(n)), "rt_scene_light_weights", self._lib)
         return list(out[:n.value])
 
     def render_frame_device(self, camera, params, out_ptr, stream=None):

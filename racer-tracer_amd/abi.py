@@ -143,6 +143,14 @@ class RtLightSamplingParams(C.Structure):
     _fields_ = [("heuristic", C.c_int32), ("max_lights", C.c_int32), ("_reserved", C.c_int32 * 6)]
 
 
+RT_LIGHTS_PLAIN, RT_LIGHTS_WRAPPED, RT_LIGHTS_BOXES, RT_LIGHTS_MOVING, RT_LIGHTS_ALL = 0, 1, 2, 4, 7
+RT_PICK_UNIFORM, RT_PICK_POWER = 0, 1
+
+
+class RtLightListParams(C.Structure):
+    _fields_ = [("kinds", C.c_int32), ("pick", C.c_int32), ("_reserved", C.c_int32 * 6)]
+
+
 class RtGuides(C.Structure):
     _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("albedo", C.c_void_p), ("footprint", C.c_void_p),
                 ("obj_id", C.c_void_p)]
@@ -205,6 +213,9 @@ PROTOTYPES = {
                                      C.c_void_p, RtCancelCallback, C.c_void_p]),
     "rt_light_sampling_params_default": (None, [C.POINTER(RtLightSamplingParams)]),
     "rt_scene_lights": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
+    "rt_light_list_params_default": (None, [C.POINTER(RtLightListParams)]),
+    "rt_scene_set_lights": (C.c_int, [C.c_void_p, C.POINTER(RtLightListParams)]),
+    "rt_scene_light_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32)]),
     "rt_render_frame_nee": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
                                       C.POINTER(RtLightSamplingParams), C.POINTER(C.c_double)]),
     "rt_render_frame_nee_device": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),

@@ -350,6 +350,7 @@ int render_tiles_nee(RtScene *const *scenes, int n, const RtCamera *camera, cons
     int rc = rtapi::check_nee_shares(scenes, n, camera, p, ls, strip_rows, what);
     if (rc != RT_OK) return rc;
     if (p->tiles_w <= 0 || p->tiles_h <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "tile grid must be positive");
+    if ((rc = rtapi::check_same_light_lists(scenes, n, what)) != RT_OK) return rc;
     if (cancel.raised()) return RT_ERR_CANCEL_EVENT; // cpu.rs:82-85
     if (p->width / p->tiles_w > 0) return deliver_tiles(scenes, n, camera, p, strip_rows, callback, user, cancel, ls);
     if (n > 1) return fail(RT_ERR_UNSUPPORTED, std::string(what) + ": a tile grid wider than the image renders on one device");
@@ -403,6 +404,15 @@ int rtapi::check_nee_shares(RtScene *const *scenes, int n, const RtCamera *camer
     if ((rc = rtapi::check_scenes(scenes, n)) != RT_OK) return rc;
     if (strip_rows < 0) return fail(RT_ERR_INVALID_ARGUMENT, "strip_rows must not be negative");
     return rtapi::check_params(camera, p);
+}
+
+// The shares of one NEE frame sample one light list (rt_scene_set_lights).  The only refusal that READS a scene: an entry
+// point asks it last, behind every refusal about its other arguments, and still before a device is touched.
+int rtapi::check_same_light_lists(RtScene *const *scenes, int n, const char *what) {
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->light_params.kinds != scenes[0]->light_params.kinds || scenes[i]->light_params.pick != scenes[0]->light_params.pick)
+            return fail(RT_ERR_INVALID_ARGUMENT, std::string(what) + ": the scenes do not carry the same light list params");
+    return RT_OK;
 }
 
 extern "C" {
@@ -471,9 +481,10 @@ int rt_render_nee_multi(RtScene *const *scenes, int n_scenes, const RtCamera *ca
 int rt_render_frame_nee_multi(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *p,
                               const RtLightSamplingParams *light_sampling, int strip_rows, double *out_rgb) {
     return rtapi::guarded("rt_render_frame_nee_multi", [&] {
-        const int rc = rtapi::check_nee_shares(scenes, n_scenes, camera, p, light_sampling, strip_rows, "rt_render_frame_nee_multi");
+        int rc = rtapi::check_nee_shares(scenes, n_scenes, camera, p, light_sampling, strip_rows, "rt_render_frame_nee_multi");
         if (rc != RT_OK) return rc;
         if (!out_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgb is NULL");
+        if ((rc = rtapi::check_same_light_lists(scenes, n_scenes, "rt_render_frame_nee_multi")) != RT_OK) return rc;
         return deliver_frame(scenes, n_scenes, camera, p, strip_rows, out_rgb, light_sampling);
     });
 }

@@ -284,6 +284,17 @@ struct NeeArgs {
     double inv_samples;
 };
 
+// What the extended-light NEE kernels read on top of NeeArgs (rt_nee_lights.h; rt_scene_set_lights): the pick among the
+// NeeArgs.n_lights lights in play.  pick 0: uniform, k = min(floor(e0 n), n - 1) with 1 / n, the arrays are not read.
+// pick 1: p[k] is light k's probability and cdf[k] the running sum in table order (cdf[n - 1] = 1), both formed by the
+// host in f64 (rt_plan.cpp: light_pick); k is the first index with e0 < cdf[k].
+struct NeeLightArgs {
+    const double *p;
+    const double *cdf;
+    int32_t pick;
+    int32_t _pad;
+};
+
 // The decision step of an adaptive pass (rt_tile_decide.h), one wave per 8x8 tile of the whole frame: what both estimators
 // tell it.  A running tile (tile_stop 0) writes its pixels and its error and either stops or appends itself to next_list;
 // a stopped tile rewrites its pixels from its own scale and carries its error over.

@@ -173,9 +173,10 @@ int rt_render_frame_multi_device(RtScene *const *scenes, int n_scenes, const RtC
 int rt_render_frame_nee_multi_device(RtScene *const *scenes, int n_scenes, const RtCamera *camera, const RtRenderParams *params,
                                      const RtLightSamplingParams *light_sampling, int strip_rows, double *out_rgb_device) {
     return rtapi::guarded("rt_render_frame_nee_multi_device", [&] {
-        const int rc = rtapi::check_nee_shares(scenes, n_scenes, camera, params, light_sampling, strip_rows, "rt_render_frame_nee_multi_device");
+        int rc = rtapi::check_nee_shares(scenes, n_scenes, camera, params, light_sampling, strip_rows, "rt_render_frame_nee_multi_device");
         if (rc != RT_OK) return rc;
         if (!out_rgb_device) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgb_device is NULL");
+        if ((rc = rtapi::check_same_light_lists(scenes, n_scenes, "rt_render_frame_nee_multi_device")) != RT_OK) return rc;
         const ShareRender nee{
             [](RtScene *s, const RtRenderParams *sp) { return rtapi::reserve_nee_buffers(s, sp, false); },
             [&](RtScene *s, const RtRenderParams *sp, double *target) {

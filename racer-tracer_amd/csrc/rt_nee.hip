@@ -1,7 +1,9 @@
 // rt_nee.hip — next-event estimation: the upload of the scene's light list (rt_plan.cpp: light_tables) and
 // the entry points rt_render_frame_nee, rt_render_frame_nee_device, rt_render_frame_nee_strips_device, rt_scene_lights and
 // rt_light_sampling_params_default (include/rt_abi.h); the several-device forms live in rt_deliver.hip and rt_multi.hip.  The kernel is rt_nee_kernel.hip's k_nee_f64, compiled in both arithmetic flavours; a scene uses its
-// own (RtScene.kernels).
+// own (RtScene.kernels).  rt_scene_set_lights, rt_scene_light_weights and rt_light_list_params_default list a scene's lights
+// again (rt_plan.cpp: list_lights, light_pick); a scene whose list holds a wrapped, box or moving light, or picks by power,
+// launches the k_nee_lights_* kernels (rt_nee_lights_kernel.hip and its two siblings) in place of the three above.
 #include "rt_scene.h"
 
 #include <algorithm>
@@ -40,7 +42,7 @@ using rtapi::check_nee;
 // The argument blocks of a k_nee_f64 / k_nee_pass_f64 / k_nee_stream_f64 launch over all samples of the rows `p` owns (the
 // whole frame without strips; rt_plan.cpp: fill_grid sets strip_* and owned_rows)
 int fill_nee_args(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls, rtdev::TraceArgs &a,
-                  rtdev::NeeArgs &nee) {
+                  rtdev::NeeArgs &nee, rtdev::NeeLightArgs &lx) {
     // the render's own argument block (tables, tree, camera, grid); its fixed-point sums are the pooled kernel's, and this
     // kernel sums in f64, so they are sized for one sample (which no bound refuses) and not read
     RtRenderParams one = *p;
@@ -56,6 +58,16 @@ int fill_nee_args(RtScene *s, const RtCamera *camera, const RtRenderParams *p, c
     nee.n_lights = std::min(ls->max_lights, (int32_t)s->lights.size());
     nee.heuristic = ls->heuristic;
     nee.inv_samples = 1.0 / (double)p->samples; // what rtdev_launch_resolve forms
+    // the pick of this cap (read by the extended-light kernels only): row n_lights - 1 of the scene's table
+    lx.p = lx.cdf = nullptr;
+    lx.pick = RT_PICK_UNIFORM;
+    lx._pad = 0;
+    if (s->lights_extended && nee.n_lights > 0 && !s->pick_uniform[(size_t)nee.n_lights - 1]) {
+        const size_t count = s->lights.size();
+        lx.p = s->nee_pick.ptr + (size_t)(nee.n_lights - 1) * 2 * count;
+        lx.cdf = lx.p + count;
+        lx.pick = RT_PICK_POWER;
+    }
     return RT_OK;
 }
 
@@ -104,14 +116,16 @@ int rtapi::enqueue_nee(RtScene *s, const RtCamera *camera, const RtRenderParams 
     RT_HIP(hipSetDevice(s->device));
     rtdev::TraceArgs a;
     rtdev::NeeArgs nee;
-    int rc = fill_nee_args(s, camera, p, ls, a, nee);
+    rtdev::NeeLightArgs lx;
+    int rc = fill_nee_args(s, camera, p, ls, a, nee, lx);
     if (rc != RT_OK) return rc;
     if (a.owned_rows <= 0) return note_idle_share(s, stream); // a strip_index whose first strip lies below the image
     if ((rc = reserve_nee_buffers(s, p, false)) != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     a.accum = b.accum.ptr;
     if ((rc = open_launches(s, stream)) != RT_OK) return rc;
-    RT_HIP(s->kernels->nee(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh, stream));
+    if (s->lights_extended) RT_HIP(s->kernels->nee_lights(&a, &nee, &lx, s->textured, s->specular, s->use_bvh, stream));
+    else RT_HIP(s->kernels->nee(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh, stream));
     RT_HIP(hipEventRecord(b.ev_traced, stream));
     RT_HIP(s->kernels->resolve(b.accum.ptr, out_device, p->width, p->height, a.strip_rows, a.strip_count, a.strip_index, p->samples, stream));
     RT_HIP(hipEventRecord(b.ev_resolved, stream));
@@ -163,7 +177,8 @@ int rtapi::enqueue_nee_stream(RtScene *s, const RtCamera *camera, const RtRender
     RT_HIP(hipSetDevice(s->device));
     rtdev::TraceArgs a;
     rtdev::NeeArgs nee;
-    int rc = fill_nee_args(s, camera, p, ls, a, nee);
+    rtdev::NeeLightArgs lx;
+    int rc = fill_nee_args(s, camera, p, ls, a, nee, lx);
     if (rc != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     hipStream_t stream = b.stream;
@@ -176,11 +191,13 @@ int rtapi::enqueue_nee_stream(RtScene *s, const RtCamera *camera, const RtRender
     if ((rc = rtapi::setup_delivery(s, a, delivery, 1, stream)) != RT_OK) return rc;
     a.queue = b.queue.ptr;
     if (delivery.cancellable) rtapi::arm_cancel_word(s, a); // the waves read it at every hand-out and chunk boundary
-    const int per_cu = s->kernels->nee_stream_blocks_per_cu(s->prims_class, s->textured, s->specular, s->use_bvh);
+    const int per_cu = s->lights_extended ? s->kernels->nee_lights_stream_blocks_per_cu(s->textured, s->specular, s->use_bvh)
+                                          : s->kernels->nee_stream_blocks_per_cu(s->prims_class, s->textured, s->specular, s->use_bvh);
     const unsigned resident = (unsigned)(s->num_cus > 0 ? s->num_cus : 1) * (unsigned)per_cu;
     const unsigned blocks = std::min(resident, (a.n_items + 3u) / 4u);
     if ((rc = open_launches(s, stream, /*clear_queue=*/true)) != RT_OK) return rc;
-    RT_HIP(s->kernels->nee_stream(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh, blocks, stream));
+    if (s->lights_extended) RT_HIP(s->kernels->nee_lights_stream(&a, &nee, &lx, s->textured, s->specular, s->use_bvh, blocks, stream));
+    else RT_HIP(s->kernels->nee_stream(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh, blocks, stream));
     RT_HIP(hipEventRecord(b.ev_traced, stream));
     RT_HIP(hipEventRecord(b.ev_resolved, stream)); // no resolve launch: the waves finish their own pixels
     rtapi::note_launches(s, 1);
@@ -203,7 +220,7 @@ int rtapi::begin_nee_passes(RtScene *s, const RtCamera *camera, const RtRenderPa
                             hipStream_t stream, bool cancellable, NeePasses &np) {
     RT_HIP(hipSetDevice(s->device));
     rtdev::TraceArgs &a = np.args;
-    int rc = fill_nee_args(s, camera, p, ls, a, np.nee);
+    int rc = fill_nee_args(s, camera, p, ls, a, np.nee, np.lights);
     if (rc != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     const size_t n = (size_t)p->width * (size_t)p->height * 3;
@@ -232,7 +249,8 @@ int rtapi::enqueue_nee_pass(RtScene *s, NeePasses &np, int c0, int c1, hipStream
         a.chunk_base = c;
         a.sample_begin = np.starts[(size_t)c];
         a.sample_end = np.starts[(size_t)c + 1];
-        RT_HIP(s->kernels->nee_pass(&a, &np.nee, s->prims_class, s->textured, s->specular, s->use_bvh, stream));
+        if (s->lights_extended) RT_HIP(s->kernels->nee_lights_pass(&a, &np.nee, &np.lights, s->textured, s->specular, s->use_bvh, stream));
+        else RT_HIP(s->kernels->nee_pass(&a, &np.nee, s->prims_class, s->textured, s->specular, s->use_bvh, stream));
         RT_HIP(s->kernels->nee_chunk(b.accum.ptr, b.partial.ptr, b.squares.ptr, n, a.sample_end - a.sample_begin, stream));
     }
     ++s->last_launches;
@@ -248,7 +266,92 @@ int rtapi::build_light_list(RtScene *s, const LightTables &t) {
     return RT_OK;
 }
 
+// rt_scene_set_lights: the list of these params from the scene's own facts (rt_plan.cpp: list_lights), its device tables,
+// and the pick of every cap n = 1 .. count (RtScene.nee_pick).  The scene's stream is idle first: no launch of an earlier
+// call on it still reads the tables that are replaced.  ALL OR NOTHING: the three device tables are made and filled beside
+// the scene's own, and the scene takes them — with the list, the params and the kernel choice that go with them — only
+// once every allocation and copy has succeeded; a failure leaves the scene exactly as it was.
+int rtapi::set_light_list(RtScene *s, const RtLightListParams &lp) {
+    RT_HIP(hipSetDevice(s->device));
+    RT_HIP(hipStreamSynchronize(s->buf.stream));
+    const std::vector<int32_t> lights = rtapi::list_lights(s->light_facts, lp.kinds, kMaxLights);
+    const LightTables t = rtapi::light_tables_of(lights, s->table_order);
+    bool extended = lp.pick == RT_PICK_POWER;
+    for (int32_t i : lights) extended = extended || !rtapi::light_is_plain(s->light_facts[(size_t)i]);
+    const size_t count = lights.size();
+    std::vector<char> uniform(count, 1);
+    std::vector<double> rows(count * count * 2, 0.0);
+    for (size_t n = 1; n <= count; ++n) {
+        const rtapi::LightPick pick = rtapi::light_pick(s->light_facts, lights, (int)n, lp.pick);
+        uniform[n - 1] = pick.uniform ? 1 : 0;
+        std::copy(pick.p.begin(), pick.p.end(), rows.begin() + (n - 1) * 2 * count);
+        std::copy(pick.cdf.begin(), pick.cdf.end(), rows.begin() + (n - 1) * 2 * count + count);
+    }
+    std::vector<double> weights = rtapi::light_pick(s->light_facts, lights, (int)count, lp.pick).p;
+
+    struct Tables { // freed on every way out: after the exchange below they hold the scene's OLD tables
+        rtapi::DevBuf<int32_t> slot, prim;
+        rtapi::DevBuf<double> pick;
+        ~Tables() {
+            slot.release();
+            prim.release();
+            pick.release();
+        }
+    } fresh;
+    auto fill = [](auto &buf, const auto &host) -> hipError_t {
+        hipError_t e = buf.alloc(host.size());
+        if (e == hipSuccess && !host.empty())
+            e = hipMemcpy(buf.ptr, host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice);
+        return e;
+    };
+    RT_HIP(fill(fresh.slot, t.slot));
+    RT_HIP(fill(fresh.prim, t.prim));
+    RT_HIP(fill(fresh.pick, rows));
+    // nothing below can fail
+    std::swap(s->nee_slot, fresh.slot);
+    std::swap(s->nee_prim, fresh.prim);
+    std::swap(s->nee_pick, fresh.pick);
+    s->lights = t.lights;
+    s->light_params = lp;
+    s->lights_extended = extended;
+    s->pick_uniform.swap(uniform);
+    s->pick_weights.swap(weights);
+    return RT_OK;
+}
+
+namespace {
+int scene_set_lights(RtScene *s, const RtLightListParams *p) {
+    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    const int rc = rtapi::check_light_list_params(p);
+    if (rc != RT_OK) return rc;
+    return rtapi::set_light_list(s, *p);
+}
+
+int scene_light_weights(const RtScene *s, double *out, int32_t capacity, int32_t *count) {
+    if (!s || !count) return fail(RT_ERR_INVALID_ARGUMENT, "scene/out_count is NULL");
+    if (capacity < 0 || (capacity > 0 && !out)) return fail(RT_ERR_INVALID_ARGUMENT, "out_p is NULL or capacity is negative");
+    *count = (int32_t)s->pick_weights.size();
+    for (int32_t k = 0; k < capacity && k < *count; ++k) out[k] = s->pick_weights[(size_t)k];
+    return RT_OK;
+}
+} // namespace
+
 extern "C" {
+
+void rt_light_list_params_default(RtLightListParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof *out);
+    out->kinds = RT_LIGHTS_PLAIN;
+    out->pick = RT_PICK_UNIFORM;
+}
+
+int rt_scene_set_lights(RtScene *s, const RtLightListParams *p) {
+    return rtapi::guarded("rt_scene_set_lights", [&] { return scene_set_lights(s, p); });
+}
+
+int rt_scene_light_weights(RtScene *s, double *out_p, int32_t capacity, int32_t *out_count) {
+    return rtapi::guarded("rt_scene_light_weights", [&] { return scene_light_weights(s, out_p, capacity, out_count); });
+}
 
 void rt_light_sampling_params_default(RtLightSamplingParams *out) {
     if (!out) return;

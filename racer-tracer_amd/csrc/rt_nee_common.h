@@ -2,7 +2,9 @@
 // per-pixel sample loop that k_nee_f64 (rt_nee_kernel.hip: a whole frame in one launch) and k_nee_pass_f64
 // (rt_nee_pass_kernel.hip: listed tiles, a range of samples on top of a carried-in sum) both inline.  The loop adds a
 // pixel's samples to `sum` in sample order and every draw is addressed by (pixel, sample, ...), so what a sample adds does
-// not depend on the launch it is traced in: the passes' sums are the one-shot launch's, bit for bit.
+// not depend on the launch it is traced in: the passes' sums are the one-shot launch's, bit for bit.  The loop's light
+// code — the pick, the sample, the pdf of a bounce direction — is a policy: PlainLights below, the list rt_scene_create
+// makes, and ExtendedLights (rt_nee_lights.h), the list of rt_scene_set_lights.
 #pragma once
 #include "rt_trace_common.h"
 
@@ -20,61 +22,93 @@ __device__ __forceinline__ double mis_weight(double p, double q, int heuristic) 
 // Solid-angle pdf of light L (a plain Sphere or an untransformed rect) from x toward the point y it was hit at, along
 // the unit direction w: rect: p_pick |y - x|^2 / (|n_L . w| A) (inf when grazing); sphere: p_pick / (2 pi (1 - cos_max)),
 // 0 from inside.
-__device__ __forceinline__ double light_pdf(const Prim &L, d3 x, d3 y, d3 w, double p_pick) {
+// (the sphere's part on its own: the extended lights of rt_nee_lights.h evaluate it around other centres)
+__device__ __forceinline__ double sphere_light_pdf(d3 center, double radius2, d3 x, double p_pick) {
     const double PI = 3.14159265358979323846;
-    if (L.kind == RT_PRIM_SPHERE) {
-        const double dc2 = len2(ld3(L.p) - x);
-        if (dc2 <= L.radius2) return 0.0;
-        const double cos_max = sqrt(fmax(0.0, 1.0 - L.radius2 / dc2));
-        return p_pick / (2.0 * PI * (1.0 - cos_max));
-    }
+    const double dc2 = len2(center - x);
+    if (dc2 <= radius2) return 0.0;
+    const double cos_max = sqrt(fmax(0.0, 1.0 - radius2 / dc2));
+    return p_pick / (2.0 * PI * (1.0 - cos_max));
+}
+__device__ __forceinline__ double light_pdf(const Prim &L, d3 x, d3 y, d3 w, double p_pick) {
+    if (L.kind == RT_PRIM_SPHERE) return sphere_light_pdf(ld3(L.p), L.radius2, x, p_pick);
     const int axis = L.kind == RT_PRIM_XY_RECT ? 2 : (L.kind == RT_PRIM_XZ_RECT ? 1 : 0);
     const double area = fabs((L.p[1] - L.p[0]) * (L.p[3] - L.p[2]));
     return p_pick * len2(y - x) / (fabs(comp(w, axis)) * area);
 }
 
-// A light sample from x: the unit direction toward the sampled point and its solid-angle pdf (0: no sample).
-__device__ __forceinline__ double sample_light(const Prim &L, d3 x, double e1, double e2, double p_pick, d3 &w) {
+// A light sample from x: the unit direction toward the sampled point and its solid-angle pdf (0: no sample).  The sphere's
+// and the rect's parts stand on their own: the extended lights of rt_nee_lights.h take them in a light's object frame.
+__device__ __forceinline__ double sample_sphere_light(d3 center, double radius2, d3 x, double e1, double e2, double p_pick, d3 &w) {
     const double PI = 3.14159265358979323846;
-    if (L.kind == RT_PRIM_SPHERE) { // uniform in the cone the sphere subtends
-        const d3 cx = ld3(L.p) - x;
-        const double dc2 = len2(cx);
-        if (dc2 <= L.radius2) return 0.0; // from inside: no sample
-        const double cos_max = sqrt(fmax(0.0, 1.0 - L.radius2 / dc2));
-        const double one_m = 1.0 - cos_max;
-        if (!(one_m > 0.0)) return 0.0;
-        const double cos_t = 1.0 - e1 * one_m;
-        const double sin_t = sqrt(fmax(0.0, 1.0 - cos_t * cos_t));
-        const double phi = 2.0 * PI * e2;
-        const d3 z = cx * (1.0 / sqrt(dc2));
-        // Duff et al. 2017, "Building an orthonormal basis, revisited"
-        const double sign = copysign(1.0, z.z);
-        const double a = -1.0 / (sign + z.z);
-        const double b = z.x * z.y * a;
-        const d3 b1 = mk(1.0 + sign * z.x * z.x * a, sign * b, -sign * z.x);
-        const d3 b2 = mk(b, sign + z.y * z.y * a, -z.y);
-        // (sin_lean: the library's sin / cos carry a Payne-Hanek path that costs scratch memory; phi is in [0, 2 pi))
-        w = (sin_t * sin_lean(phi + 0.5 * PI)) * b1 + (sin_t * sin_lean(phi)) * b2 + cos_t * z;
-        return p_pick / (2.0 * PI * one_m);
-    }
-    const int axis = L.kind == RT_PRIM_XY_RECT ? 2 : (L.kind == RT_PRIM_XZ_RECT ? 1 : 0);
-    const double ca = L.p[0] + (L.p[1] - L.p[0]) * e1, cb = L.p[2] + (L.p[3] - L.p[2]) * e2;
-    const d3 y = axis == 2 ? mk(ca, cb, L.p[4]) : (axis == 1 ? mk(ca, L.p[4], cb) : mk(L.p[4], ca, cb));
+    // uniform in the cone the sphere subtends
+    const d3 cx = center - x;
+    const double dc2 = len2(cx);
+    if (dc2 <= radius2) return 0.0; // from inside: no sample
+    const double cos_max = sqrt(fmax(0.0, 1.0 - radius2 / dc2));
+    const double one_m = 1.0 - cos_max;
+    if (!(one_m > 0.0)) return 0.0;
+    const double cos_t = 1.0 - e1 * one_m;
+    const double sin_t = sqrt(fmax(0.0, 1.0 - cos_t * cos_t));
+    const double phi = 2.0 * PI * e2;
+    const d3 z = cx * (1.0 / sqrt(dc2));
+    // Duff et al. 2017, "Building an orthonormal basis, revisited"
+    const double sign = copysign(1.0, z.z);
+    const double a = -1.0 / (sign + z.z);
+    const double b = z.x * z.y * a;
+    const d3 b1 = mk(1.0 + sign * z.x * z.x * a, sign * b, -sign * z.x);
+    const d3 b2 = mk(b, sign + z.y * z.y * a, -z.y);
+    // (sin_lean: the library's sin / cos carry a Payne-Hanek path that costs scratch memory; phi is in [0, 2 pi))
+    w = (sin_t * sin_lean(phi + 0.5 * PI)) * b1 + (sin_t * sin_lean(phi)) * b2 + cos_t * z;
+    return p_pick / (2.0 * PI * one_m);
+}
+// (axis: the rect's constant axis, at k; [a0, a1] x [b0, b1] on the two others in order)
+__device__ __forceinline__ double sample_rect_light(int axis, double a0, double a1, double b0, double b1, double k, d3 x, double e1,
+                                                    double e2, double p_pick, d3 &w) {
+    const double ca = a0 + (a1 - a0) * e1, cb = b0 + (b1 - b0) * e2;
+    const d3 y = axis == 2 ? mk(ca, cb, k) : (axis == 1 ? mk(ca, k, cb) : mk(k, ca, cb));
     const d3 v = y - x;
     const double dist2 = len2(v);
     w = v * (1.0 / sqrt(dist2));
-    const double area = fabs((L.p[1] - L.p[0]) * (L.p[3] - L.p[2]));
+    const double area = fabs((a1 - a0) * (b1 - b0));
     const double g = fabs(comp(w, axis)) * area;
     if (!(g > 0.0) || !(dist2 > 0.0)) return 0.0; // grazing: nothing
     return p_pick * dist2 / g;
 }
+__device__ __forceinline__ double sample_light(const Prim &L, d3 x, double e1, double e2, double p_pick, d3 &w) {
+    if (L.kind == RT_PRIM_SPHERE) return sample_sphere_light(ld3(L.p), L.radius2, x, e1, e2, p_pick, w);
+    const int axis = L.kind == RT_PRIM_XY_RECT ? 2 : (L.kind == RT_PRIM_XZ_RECT ? 1 : 0);
+    return sample_rect_light(axis, L.p[0], L.p[1], L.p[2], L.p[3], L.p[4], x, e1, e2, p_pick, w);
+}
+
+// THE LIGHT CODE of nee_samples, a policy: how light k is picked from the draw e0, sampled from a vertex, and what density
+// the light sampler has for a bounce direction that found a listed light.  PlainLights is the code of rt_render_frame_nee
+// since its first day — unwrapped spheres and rects, a uniform pick — and the default; ExtendedLights (rt_nee_lights.h)
+// is rt_scene_set_lights' list.  X: the policy's own argument block, p_uniform: 1 / n_lights.
+struct NoLightArgs {};
+struct PlainLights {
+    typedef NoLightArgs Args;
+    static __device__ __forceinline__ void pick(const NeeArgs &N, const Args &, double e0, double p_uniform, int &k, double &p_k) {
+        k = (int)floor(e0 * (double)N.n_lights);
+        if (k > N.n_lights - 1) k = N.n_lights - 1;
+        p_k = p_uniform;
+    }
+    static __device__ __forceinline__ double sample(const Prim &L, d3 x, double e1, double e2, double p_k, const PathRng &, uint32_t,
+                                                    double, d3 &w) {
+        return sample_light(L, x, e1, e2, p_k, w);
+    }
+    static __device__ __forceinline__ double pdf(const Args &, const Prim &L, int, d3 x, d3 y, d3 w, double, double p_uniform) {
+        return light_pdf(L, x, y, w, p_uniform);
+    }
+};
 
 // Samples [s_begin, s_end) of pixel (px, py) added to `sum` in sample order (s_begin == s_end: none, the lane idles through
 // the wave's loop).  u: the pixel's horizontal coordinate (cpu.rs:35-36).  n_segments / n_started: path segments (shadow
 // rays excluded) and primary rays, added to.
-template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH>
+template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH, class LIGHTS = PlainLights>
 __device__ __forceinline__ void nee_samples(const TraceArgs &A, const NeeArgs &N, PathRng &rng, int px, int py, double u, int s_begin,
-                                            int s_end, d3 &sum, unsigned int &n_segments, unsigned int &n_started) {
+                                            int s_end, d3 &sum, unsigned int &n_segments, unsigned int &n_started,
+                                            const typename LIGHTS::Args &X = typename LIGHTS::Args()) {
     const double INV_PI = 0.31830988618379067154;
     const double p_pick = N.n_lights > 0 ? 1.0 / (double)N.n_lights : 0.0;
 
@@ -178,7 +212,7 @@ __device__ __forceinline__ void nee_samples(const TraceArgs &A, const NeeArgs &N
                     const int k = N.slot[best];
                     if (eligible && k >= 0 && k < N.n_lights) { // a listed light found by the bounce of an NEE vertex
                         const double inv_len = rsqrt_f64(len2(d));
-                        const double p_l = light_pdf(P, x_prev, h.point, d * inv_len, p_pick);
+                        const double p_l = LIGHTS::pdf(X, P, k, x_prev, h.point, d * inv_len, ray_time, p_pick);
                         contrib = contrib * mis_weight(cos_b * INV_PI, p_l, N.heuristic);
                     }
                     ended = true;
@@ -197,11 +231,12 @@ __device__ __forceinline__ void nee_samples(const TraceArgs &A, const NeeArgs &N
                         const double e0 = (sym42_bits(__builtin_amdgcn_alignbit(bl.a, bl.d << 22, 12), bl.a) + 1.0) * 0.5;
                         const double e1 = (sym42(bl.b, bl.d & 0x000FFC00u) + 1.0) * 0.5;
                         const double e2 = (sym42(bl.c, (bl.d >> 10) & 0x000FFC00u) + 1.0) * 0.5;
-                        int k = (int)floor(e0 * (double)N.n_lights);
-                        if (k > N.n_lights - 1) k = N.n_lights - 1;
+                        int k;
+                        double p_k;
+                        LIGHTS::pick(N, X, e0, p_pick, k, p_k);
                         const int li = N.prim[k];
                         d3 w;
-                        const double p_l = sample_light(A.prims[li], h.point, e1, e2, p_pick, w);
+                        const double p_l = LIGHTS::sample(A.prims[li], h.point, e1, e2, p_k, rng, seg, ray_time, w);
                         const double cos_x = dot(h.normal, w);
                         if (p_l > 0.0 && cos_x > 0.0) { // trace the shadow ray next: 2 cos_x w, the bounce ray toward w
                             const double p_b = cos_x * INV_PI;

@@ -4,7 +4,7 @@
 // the next pass.  The estimator itself is rt_nee_common.h's nee_samples, the loop k_nee_f64 runs: a pixel's samples are
 // added in sample order to a sum that travels from launch to launch in TraceArgs.accum, so after any pass the sums are
 // the ones k_nee_f64 forms with that many samples, bit for bit.
-#include "rt_nee_common.h"
+#include "rt_nee_pass.h"
 #include "rt_tile_decide.h"
 #include "rt_variant_dispatch.h"
 
@@ -27,55 +27,7 @@ namespace RT_KNS {
 // accum / squares is not read again: the host delivers nothing of it and the next call starts its sums afresh.
 template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH>
 __global__ __launch_bounds__(256) void k_nee_pass_f64(const TraceArgs A, const NeeArgs N) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const uint32_t item = 4u * blockIdx.x + (uint32_t)wave; // wave-uniform
-    // (a wave without work — beyond the list, or cancelled — runs through with no pixel in the image rather than return
-    // early: with the early exits the compiler gave the twelve linear-loop variants a 68- or 132-byte stack frame that
-    // no instruction touches, and a private segment has to be set up for every wave of a launch)
-    unsigned int up = item >= A.n_items;
-    if (A.cancel_flag != nullptr && lane == 0) up |= __hip_atomic_load(A.cancel_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    up = __builtin_amdgcn_readfirstlane(up);
-    uint32_t tile = item;
-    if (A.tile_list != nullptr) tile = __builtin_amdgcn_readfirstlane(A.tile_list[up ? 0u : item]);
-    const bool idle = up != 0u || tile >= (uint32_t)A.n_tiles; // (a list holds tiles of the grid only)
-    const int px = (int)(tile % (uint32_t)A.tiles_x) * 8 + (lane & 7);
-    const int py = (int)(tile / (uint32_t)A.tiles_x) * 8 + (lane >> 3);
-    const bool in_image = !idle && px < A.width && py < A.height;
-
-    PathRng rng;
-    rng.pixel = (uint32_t)py * (uint32_t)A.width + (uint32_t)px;
-    rng.k0 = A.seed_lo;
-    rng.k1 = A.seed_hi;
-
-    // cpu.rs:35-36: one horizontal jitter per pixel
-    rng.sample = RT_RNG_SAMPLE_PIXEL;
-    const u4 bj = rng.block(0, RT_RNG_PIXEL, 0);
-    const double u = ((double)px + u53(bj.a, bj.b)) / (double)(A.width - 1);
-
-    d3 sum = mk(0.0, 0.0, 0.0); // the pixel's running sum (+0.0 before the first chunk: the host cleared accum)
-    if (in_image) {
-        const double *px_sum = A.accum + 3 * (size_t)rng.pixel;
-        sum = mk(px_sum[0], px_sum[1], px_sum[2]);
-    }
-    unsigned int n_segments = 0, n_started = 0;
-    nee_samples<PRIMS, TEXTURED, SPECULAR, BVH>(A, N, rng, px, py, u, in_image ? A.sample_begin : A.sample_end, A.sample_end, sum,
-                                                n_segments, n_started);
-    if (in_image) {
-        double *px_sum = A.accum + 3 * (size_t)rng.pixel;
-        px_sum[0] = sum.x;
-        px_sum[1] = sum.y;
-        px_sum[2] = sum.z;
-    }
-    // one atomic per wave for each statistic: path segments (shadow rays excluded) and primary rays
-    unsigned long long total = n_segments;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
-    if (lane == 0 && total) atomicAdd(A.segments + RT_STAT_SEGMENTS, total);
-    unsigned long long started = n_started;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) started += __shfl_down(started, off, 64);
-    if (lane == 0 && started) atomicAdd(A.segments + RT_STAT_SAMPLES, started);
+    nee_pass<PRIMS, TEXTURED, SPECULAR, BVH, PlainLights>(A, N, NoLightArgs());
 }
 
 // Behind every chunk: per pixel and channel S_j = running - boundary, squares += S_j^2 / n_j, boundary = running.  A

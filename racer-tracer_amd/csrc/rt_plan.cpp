@@ -336,22 +336,64 @@ LeafTable leaf_geometry(const std::vector<rtdev::Prim> &prims) {
     return leaves;
 }
 
+std::vector<LightFact> light_facts(const RtSceneDesc *d) {
+    std::vector<LightFact> facts((size_t)d->n_primitives);
+    for (int i = 0; i < d->n_primitives; ++i) {
+        const RtPrimitive &p = d->primitives[i];
+        LightFact &f = facts[(size_t)i];
+        memset(&f, 0, sizeof f);
+        f.kind = p.kind;
+        f.flags = p.flags;
+        for (int k = 0; k < 6; ++k) f.p[k] = p.p[k];
+        f.tex_kind = -1;
+        if (p.material < 0 || p.material >= d->n_materials) continue;
+        const RtMaterial &m = d->materials[p.material];
+        f.emitter = m.kind == RT_MAT_DIFFUSE_LIGHT ? 1 : 0;
+        if (m.kind == RT_MAT_DIELECTRIC || m.texture < 0 || m.texture >= d->n_textures) continue;
+        f.tex_kind = d->textures[m.texture].kind;
+        for (int k = 0; k < 3; ++k) f.color[k] = d->textures[m.texture].color[k];
+    }
+    return facts;
+}
+
+int check_light_list_params(const RtLightListParams *p) {
+    if (!p) return fail(RT_ERR_INVALID_ARGUMENT, "light list params is NULL");
+    if (p->kinds < 0 || p->kinds > RT_LIGHTS_ALL) return fail(RT_ERR_INVALID_ARGUMENT, "light list kinds must be in 0..7");
+    if (p->pick != RT_PICK_UNIFORM && p->pick != RT_PICK_POWER) return fail(RT_ERR_INVALID_ARGUMENT, "light list pick is not an RtLightPick");
+    for (int32_t r : p->_reserved)
+        if (r != 0) return fail(RT_ERR_INVALID_ARGUMENT, "light list _reserved must be 0");
+    return RT_OK;
+}
+
 namespace {
-// Listed: an unwrapped Sphere of positive radius or an unwrapped rect of non-zero area, made of DiffuseLight
-bool listed(const RtSceneDesc *d, const RtPrimitive &p) {
-    if (p.flags != 0 || p.material < 0 || p.material >= d->n_materials) return false;
-    if (d->materials[p.material].kind != RT_MAT_DIFFUSE_LIGHT) return false;
-    if (p.kind == RT_PRIM_SPHERE) return p.p[3] > 0.0;
-    if (p.kind == RT_PRIM_XY_RECT || p.kind == RT_PRIM_XZ_RECT || p.kind == RT_PRIM_YZ_RECT)
-        return (p.p[1] - p.p[0]) * (p.p[3] - p.p[2]) != 0.0;
+bool is_rect(int kind) { return kind == RT_PRIM_XY_RECT || kind == RT_PRIM_XZ_RECT || kind == RT_PRIM_YZ_RECT; }
+double box_area(const double *p) {
+    const double a = std::fabs(p[3] - p[0]), b = std::fabs(p[4] - p[1]), c = std::fabs(p[5] - p[2]);
+    return 2.0 * (a * b + b * c + c * a);
+}
+// Listed by today's rule (mask 0): an unwrapped Sphere of positive radius or an unwrapped rect of non-zero area, made of
+// DiffuseLight; the mask adds wrapped ones, boxes and moving spheres (include/rt_abi.h: RtLightKinds)
+bool listed(const LightFact &f, int kinds) {
+    if (!f.emitter) return false;
+    if (f.flags != 0 && !(kinds & RT_LIGHTS_WRAPPED)) return false;
+    if (f.kind == RT_PRIM_SPHERE) return f.p[3] > 0.0;
+    if (is_rect(f.kind)) return (f.p[1] - f.p[0]) * (f.p[3] - f.p[2]) != 0.0;
+    if (f.kind == RT_PRIM_BOX) return (kinds & RT_LIGHTS_BOXES) != 0 && box_area(f.p) > 0.0;
+    if (f.kind == RT_PRIM_MOVING_SPHERE) return (kinds & RT_LIGHTS_MOVING) != 0 && f.p[3] > 0.0;
     return false;
 }
 } // namespace
 
-LightTables light_tables(const RtSceneDesc *d, const std::vector<int32_t> &order, int max_lights) {
+std::vector<int32_t> list_lights(const std::vector<LightFact> &facts, int kinds, int max_lights) {
+    std::vector<int32_t> lights;
+    for (size_t i = 0; i < facts.size() && (int)lights.size() < max_lights; ++i)
+        if (listed(facts[i], kinds)) lights.push_back((int32_t)i);
+    return lights;
+}
+
+LightTables light_tables_of(const std::vector<int32_t> &lights, const std::vector<int32_t> &order) {
     LightTables t;
-    for (int32_t i = 0; i < d->n_primitives && (int)t.lights.size() < max_lights; ++i)
-        if (listed(d, d->primitives[i])) t.lights.push_back(i);
+    t.lights = lights;
     std::vector<int32_t> device_of(order.size(), -1);
     for (size_t j = 0; j < order.size(); ++j) device_of[(size_t)order[j]] = (int32_t)j;
     t.slot.assign(order.size(), -1);
@@ -361,6 +403,53 @@ LightTables light_tables(const RtSceneDesc *d, const std::vector<int32_t> &order
         t.slot[(size_t)t.prim[k]] = (int32_t)k;
     }
     return t;
+}
+
+LightTables light_tables(const RtSceneDesc *d, const std::vector<int32_t> &order, int max_lights) {
+    return light_tables_of(list_lights(light_facts(d), RT_LIGHTS_PLAIN, max_lights), order);
+}
+
+bool light_is_plain(const LightFact &f) { return f.flags == 0 && (f.kind == RT_PRIM_SPHERE || is_rect(f.kind)); }
+
+double light_weight(const LightFact &f) {
+    const double PI = 3.14159265358979323846;
+    double area;
+    if (f.kind == RT_PRIM_SPHERE || f.kind == RT_PRIM_MOVING_SPHERE) area = 4.0 * PI * (f.p[3] * f.p[3]);
+    else if (f.kind == RT_PRIM_BOX) area = box_area(f.p);
+    else area = std::fabs((f.p[1] - f.p[0]) * (f.p[3] - f.p[2]));
+    double L = 1.0;
+    if (f.tex_kind == RT_TEX_SOLID_COLOR) {
+        L = f.color[0]; // (comparisons, not std::fmax: a NaN component must not be dropped)
+        for (int k = 1; k < 3; ++k)
+            if (std::isnan(f.color[k]) || f.color[k] > L) L = std::isnan(L) ? L : f.color[k];
+        if (!std::isfinite(L) || L < 0.0) L = 0.0;
+    }
+    return area * L;
+}
+
+LightPick light_pick(const std::vector<LightFact> &facts, const std::vector<int32_t> &lights, int n, int pick) {
+    LightPick lp;
+    if (n > (int)lights.size()) n = (int)lights.size();
+    if (n <= 0) return lp;
+    std::vector<double> w((size_t)n);
+    double total = 0.0;
+    for (int k = 0; k < n; ++k) total += (w[(size_t)k] = light_weight(facts[(size_t)lights[(size_t)k]]));
+    lp.uniform = pick != RT_PICK_POWER || !(total > 0.0) || !std::isfinite(total);
+    lp.p.resize((size_t)n);
+    lp.cdf.resize((size_t)n);
+    double run = 0.0;
+    for (int k = 0; k < n; ++k) {
+        if (lp.uniform) {
+            lp.p[(size_t)k] = 1.0 / (double)n;
+            lp.cdf[(size_t)k] = (double)(k + 1) / (double)n;
+        } else {
+            run += w[(size_t)k];
+            lp.p[(size_t)k] = w[(size_t)k] / total;
+            lp.cdf[(size_t)k] = run / total;
+        }
+    }
+    lp.cdf[(size_t)n - 1] = 1.0;
+    return lp;
 }
 
 // ------------------------------------------------------------------------------------------------------------- a render

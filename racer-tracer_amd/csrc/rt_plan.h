@@ -75,6 +75,34 @@ struct LightTables {
 };
 LightTables light_tables(const RtSceneDesc *d, const std::vector<int32_t> &order, int max_lights);
 
+// The extended list (rt_scene_set_lights, include/rt_abi.h).  What a scene keeps on the host about each primitive to list
+// its lights again: kind, flags, geometry, whether its material is DiffuseLight, that material's texture kind and colour.
+struct LightFact {
+    int32_t kind, flags, emitter, tex_kind;
+    double p[6];
+    double color[3];
+};
+std::vector<LightFact> light_facts(const RtSceneDesc *d);
+// What the list params may hold: kinds in 0..7, a known pick, _reserved all zero.
+int check_light_list_params(const RtLightListParams *p);
+// The listed primitives of a `kinds` mask (RtLightKinds) in table order, at most max_lights; mask 0 is light_tables' rule.
+std::vector<int32_t> list_lights(const std::vector<LightFact> &facts, int kinds, int max_lights);
+// ... as light_tables' three arrays for a device table in `order`.
+LightTables light_tables_of(const std::vector<int32_t> &lights, const std::vector<int32_t> &order);
+// Does the NEE kernel of today sample this listed light?  (An unwrapped Sphere or rect.)
+bool light_is_plain(const LightFact &f);
+// w = A L of a listed light: the object-frame surface area times the largest colour component of a SolidColor emitter
+// (negative or not finite: 0), else 1.
+double light_weight(const LightFact &f);
+// The pick among the first n listed lights: p_k and the running sums cdf_k (cdf_{n-1} = 1), formed in f64 in table order.
+// RT_PICK_UNIFORM, or a sum of weights that is not positive and finite: p_k = 1 / n, `uniform` set, cdf_k = (k + 1) / n
+// (not read by the device, which keeps min(floor(e0 n), n - 1)).
+struct LightPick {
+    std::vector<double> p, cdf;
+    bool uniform = true;
+};
+LightPick light_pick(const std::vector<LightFact> &facts, const std::vector<int32_t> &lights, int n, int pick);
+
 // ----------------------------------------------------------------------------------------------------------- a render
 int check_params(const RtCamera *camera, const RtRenderParams *p);
 

@@ -26,6 +26,8 @@
 //   nee_stream* (rt_nee_stream_kernel.hip): the NEE estimator as ONE persistent launch of `blocks` blocks over args'
 //     region-ordered tile queue, every tile delivered into args->deliver_out; the variant's resident blocks per CU (the
 //     runtime's occupancy query); the chunk length the flavour was compiled with.
+//   nee_lights* (rt_nee_lights_kernel.hip, rt_nee_lights_pass_kernel.hip, rt_nee_lights_stream_kernel.hip): nee, nee_pass,
+//     nee_stream and its blocks per CU with the extended light code (rt_nee_lights.h), which exist for PRIMS_ANY only.
 #define RT_LAUNCHER_LIST(X)                                                                                                \
     X(trace, rtdev_launch_trace, hipError_t,                                                                               \
       (const rtdev::TraceArgs *args, int prims_class, int textured, int specular, hipStream_t stream))                     \
@@ -60,7 +62,17 @@
        unsigned blocks, hipStream_t stream))                                                                               \
     X(nee_stream_blocks_per_cu, rtdev_nee_stream_blocks_per_cu, int,                                                       \
       (int prims_class, int textured, int specular, int bvh))                                                              \
-    X(nee_stream_chunk, rtdev_nee_stream_chunk, int, (void))
+    X(nee_stream_chunk, rtdev_nee_stream_chunk, int, (void))                                                               \
+    X(nee_lights, rtdev_launch_nee_lights, hipError_t,                                                                     \
+      (const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, const rtdev::NeeLightArgs *lights, int textured,          \
+       int specular, int bvh, hipStream_t stream))                                                                         \
+    X(nee_lights_pass, rtdev_launch_nee_lights_pass, hipError_t,                                                           \
+      (const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, const rtdev::NeeLightArgs *lights, int textured,          \
+       int specular, int bvh, hipStream_t stream))                                                                         \
+    X(nee_lights_stream, rtdev_launch_nee_lights_stream, hipError_t,                                                       \
+      (const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, const rtdev::NeeLightArgs *lights, int textured,          \
+       int specular, int bvh, unsigned blocks, hipStream_t stream))                                                        \
+    X(nee_lights_stream_blocks_per_cu, rtdev_nee_lights_stream_blocks_per_cu, int, (int textured, int specular, int bvh))
 #define RT_DECLARE_LAUNCHER(member, name, ret, params) \
     extern "C" ret name params;                        \
     extern "C" ret name##_exact params;
@@ -270,6 +282,19 @@ struct RtScene {
     // the device rtdev::NeeArgs' slot per device primitive and device primitive per light
     std::vector<int32_t> lights;
     rtapi::DevBuf<int32_t> nee_slot, nee_prim;
+    // the extended list (rt_scene_set_lights): what is needed to list again — the facts of every primitive and the
+    // description index of every device record —, the params in force (all zero: rt_scene_create's list), whether the
+    // launches take the extended-light kernels (the list holds a wrapped, box or moving light, or the pick is by power),
+    // and the pick of every cap: for n = 1 .. count lights in play, row n - 1 of nee_pick holds p_0 .. p_{count-1} and
+    // cdf_0 .. cdf_{count-1} (2 * count doubles a row; entries >= n unused), pick_uniform[n - 1] whether that cap's pick
+    // is the uniform one
+    std::vector<rtapi::LightFact> light_facts;
+    std::vector<int32_t> table_order;
+    RtLightListParams light_params = {};
+    bool lights_extended = false;
+    rtapi::DevBuf<double> nee_pick;
+    std::vector<char> pick_uniform;
+    std::vector<double> pick_weights; // p_k of the uncapped list (rt_scene_light_weights)
 
     rtapi::RenderBuffers buf;
     bool has_stats = false;
@@ -365,6 +390,8 @@ int enqueue_denoise(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *
 // The scene's light list (rt_nee.hip) on the device, made by rt_scene_create once the device table's order is final
 // (rt_plan.h: light_tables).
 int build_light_list(RtScene *s, const LightTables &t);
+// ... listed again from the scene's own facts with these (checked) params, the pick tables with it (rt_scene_set_lights).
+int set_light_list(RtScene *s, const RtLightListParams &lp);
 // What every NEE entry point refuses before a device is touched (rt_nee.hip), the scene last so that each refusal names
 // its own cause; `what` is the entry point's name in the messages about whole frames.
 // `strips`: params->strip_count > 1 is not refused (rt_render_frame_nee_strips_device; check_params holds the strip values).
@@ -394,6 +421,7 @@ int reserve_delivery_counters(RtScene *s, size_t n_tiles);
 struct NeePasses {
     rtdev::TraceArgs args;
     rtdev::NeeArgs nee;
+    rtdev::NeeLightArgs lights; // read by the extended-light kernels only (RtScene.lights_extended)
     std::vector<int> starts; // chunk_plan(samples)
 };
 int begin_nee_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtLightSamplingParams *ls,
@@ -418,4 +446,6 @@ int check_scenes(RtScene *const *scenes, int n);
 // ... of the NEE forms (rt_deliver.hip): check_nee_args, check_scenes, strip_rows >= 0, check_params — no device touched.
 int check_nee_shares(RtScene *const *scenes, int n, const RtCamera *camera, const RtRenderParams *p,
                      const RtLightSamplingParams *ls, int strip_rows, const char *what);
+// ... and, behind every other refusal of the entry point: the scenes carry the same light list params (rt_scene_set_lights).
+int check_same_light_lists(RtScene *const *scenes, int n, const char *what);
 } // namespace rtapi

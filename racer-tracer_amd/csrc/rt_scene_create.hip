@@ -266,6 +266,10 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
     const std::vector<rtdev::Texture> textures = rtapi::pack_textures(d, images);
     if (s->use_bvh && (rc = upload_bvh(s, bvh, leaves)) != RT_OK) return rc;
     if ((rc = rtapi::build_light_list(s, lights)) != RT_OK) return rc;
+    // what rt_scene_set_lights lists again from; rt_scene_light_weights of the list as created: the uniform pick's
+    s->light_facts = rtapi::light_facts(d);
+    s->table_order = order;
+    s->pick_weights.assign(lights.lights.size(), lights.lights.empty() ? 0.0 : 1.0 / (double)lights.lights.size());
     if ((rc = upload(s->prims, prims)) != RT_OK) return rc;
     if ((rc = upload(s->textures, textures)) != RT_OK) return rc;
     if ((rc = upload(s->images, images)) != RT_OK) return rc;
@@ -307,6 +311,7 @@ void rt_scene_destroy(RtScene *s) {
     s->leaf_geo.release();
     s->nee_slot.release();
     s->nee_prim.release();
+    s->nee_pick.release();
     // what a render allocates — slices, frames, pinned memory, counters, streams, events — outlives the scene: the
     // reference rebuilds its scene on every object event (main.rs:174-189), and the next rt_scene_create on this
     // device takes these over instead of paying hipMalloc / hipHostMalloc again (render_cache_put); should the cache

@@ -14,6 +14,15 @@ auto dispatch_features(bool textured, bool specular, F &f) {
     return specular ? f(V<PRIMS, false, true, BVH>()) : f(V<PRIMS, false, false, BVH>());
 }
 
+// Kernels that exist for PRIMS_ANY only (the extended-light NEE kernels: a box or a wrapper forces that class, and
+// its linear loop takes every kind of a rects-only or spheres-only table too): the tree's or the linear loop's
+// <PRIMS_ANY, t, s, bvh>.
+template <template <int, bool, bool, bool> class V, class F>
+auto dispatch_any_variant(bool textured, bool specular, bool bvh, F f) {
+    if (bvh) return dispatch_features<V, PRIMS_ANY, true>(textured, specular, f);
+    return dispatch_features<V, PRIMS_ANY, false>(textured, specular, f);
+}
+
 // f(V<P, T, S, B>()) for the variant the flags select: with `bvh` the tree's <PRIMS_ANY, t, s, true>, whatever the class;
 // otherwise the linear loop of the scene's class, any value other than PRIMS_RECTS / PRIMS_SPHERES being PRIMS_ANY.
 // f is a generic callable (`[](auto v) { return decltype(v)::...; }`) with one return type for every variant.

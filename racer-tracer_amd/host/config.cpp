@@ -230,6 +230,18 @@ Args Args::parse(int argc, const char *const *argv) {
                 throw TracerError::ArgumentParsingError("--nee-devices needs a positive number of devices, not '" + v + "'");
             a.nee_devices = (int)k;
         }
+        else if (s == "--nee-lights") {
+            const std::string v = val();
+            if (v != "plain" && v != "all") throw TracerError::ArgumentParsingError("--nee-lights needs plain or all, not '" + v + "'");
+            a.nee_lights_all = v == "all";
+            a.nee_list_given = true;
+        }
+        else if (s == "--nee-pick") {
+            const std::string v = val();
+            if (v != "uniform" && v != "power") throw TracerError::ArgumentParsingError("--nee-pick needs uniform or power, not '" + v + "'");
+            a.nee_pick_power = v == "power";
+            a.nee_list_given = true;
+        }
         else if (s == "-h" || s == "--help") a.help = true;
         else throw TracerError::ArgumentParsingError("unknown argument " + s);
     }
@@ -255,6 +267,8 @@ Args Args::parse(int argc, const char *const *argv) {
         throw TracerError::ArgumentParsingError("--nee-devices is a render mode of its own: it does not combine with --nee, --nee-stream, --adaptive, --nee-adaptive or --temporal");
     if (a.nee_devices > 0 && a.devices > 1)
         throw TracerError::ArgumentParsingError("--nee-devices N names its own devices: it does not combine with --devices > 1");
+    if (a.nee_list_given && !(a.nee || a.nee_stream || a.nee_devices > 0 || a.nee_adaptive > 0.0))
+        throw TracerError::ArgumentParsingError("--nee-lights and --nee-pick set the light list of next-event estimation: they need --nee, --nee-stream, --nee-devices or --nee-adaptive");
     return a;
 }
 

@@ -67,6 +67,8 @@ struct Args { // config.rs:12-28
     bool nee_stream = false; // --nee-stream: the same frame through rt_render_nee, tile by tile into the screen buffer, one device only
     int nee_devices = 0; // --nee-devices N (N >= 1): --nee-stream's frame through rt_render_nee_multi on devices device .. device+N-1
     double adaptive = 0.0; // --adaptive T (T > 0): render through rt_render_adaptive with threshold T, one device only
+    // --nee-lights plain|all and --nee-pick uniform|power: rt_scene_set_lights on every scene the run creates (an NEE mode only)
+    bool nee_lights_all = false, nee_pick_power = false, nee_list_given = false;
     double nee_adaptive = 0.0; // --nee-adaptive T (T > 0): render through rt_render_adaptive_nee with threshold T, one device only
     int temporal = 0; // --temporal K (K >= 1): K frames at seeds seed .. seed + K - 1 through rt_render_temporal, the last one written; one device only
     bool help = false;

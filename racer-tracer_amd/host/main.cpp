@@ -13,6 +13,7 @@
 // stream through rt_render_nee_multi, the frame's strips dealt to devices device .. device+N-1) and --temporal K (one device
 // renders K frames of the configured sample count at seeds seed .. seed + K - 1 from the configured camera through
 // rt_render_temporal and writes the last; --denoise gives the filter its levels, without it the history alone is shown).
+// --nee-lights plain|all and --nee-pick uniform|power give every scene of an NEE run its light list (rt_scene_set_lights).
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -57,7 +58,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--temporal K]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -90,6 +91,19 @@ int main(int argc, char **argv) {
             return rc;
         }
         scenes.push_back(scene);
+        if (args.nee_list_given) { // --nee-lights / --nee-pick: the same list on every scene of the run
+            RtLightListParams lp;
+            rt_light_list_params_default(&lp);
+            lp.kinds = args.nee_lights_all ? RT_LIGHTS_ALL : RT_LIGHTS_PLAIN;
+            lp.pick = args.nee_pick_power ? RT_PICK_POWER : RT_PICK_UNIFORM;
+            rc = rt_scene_set_lights(scene, &lp);
+            if (rc != RT_OK) {
+                fprintf(stderr, "%s: %s\n", rt_strerror(rc), rt_last_error_message());
+                destroy_scenes();
+                rth_session_close(session);
+                return rc;
+            }
+        }
     }
     const size_t n_rgb = (size_t)params.width * (size_t)params.height * 3;
     ScreenBuffer sb{session, params.width, params.height, std::vector<double>(n_rgb, 0.0), std::vector<double>(args.denoise || args.adaptive > 0.0 || args.nee || args.nee_adaptive > 0.0 ? n_rgb : 0, 0.0)};

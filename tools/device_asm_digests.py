@@ -4,6 +4,7 @@ instructions.
 
 usage: tools/device_asm_digests.py [tree, default this one] > digests.txt
        tools/device_asm_digests.py --diff before.txt after.txt
+       tools/device_asm_digests.py --counts before_tree after_tree [unit ...]
 
 Every .hip unit of the Makefile's DEV_SRCS is compiled for the device alone with the library's flags (plus
 --cuda-device-only -S -cuid=cmp: a pinned unit id, so that two trees name their unit-local symbols alike), a second time
@@ -16,7 +17,12 @@ Labels that carry the function's index in its unit (.LBB<n>_, .Lfunc_end<n>, .Lt
 function that changes files changes its index, and the compiler's comments, which name blocks by it, are dropped.
 --diff compares two such listings by (flavour, symbol) and ignores the unit; it prints what changed, appeared, went or
 only changed files, and exits 1 if any digest or resource block differs.
+--counts says WHAT moved where a digest did: the units (default: every .hip unit both trees' Makefiles list) are compiled
+in both trees, and for every function of the first tree whose instructions or resource block differ in the second it
+prints the instruction totals, whether the resource block is the same, and the mnemonics whose counts differ (+ more in
+the second tree).  "none" means the same instructions in another order or with other operands.
 """
+import collections
 import concurrent.futures
 import hashlib
 import os
@@ -83,6 +89,60 @@ def digest_unit(job):
     return rows
 
 
+def unit_jobs(tree):
+    """(unit, flavour, compiler command without the unit) of every .hip unit of a tree's Makefile"""
+    with open(os.path.join(tree, "racer-tracer_amd", "Makefile")) as f:
+        mk = f.read()
+    hipcc = (make_var(mk, "HIPCC") or ["/opt/rocm/bin/hipcc"])[0]
+    base = [hipcc, "--offload-arch=" + (make_var(mk, "ARCH") or ["gfx950"])[0]] + make_var(mk, "CXXFLAGS")
+    exact = set(make_var(mk, "EXACT_SRCS"))
+    jobs = []
+    for unit in make_var(mk, "DEV_SRCS"):
+        if unit.endswith(".hip"):
+            jobs.append((unit, "fast", base))
+            if unit in exact:
+                jobs.append((unit, "exact", base + make_var(mk, "EXACT_FLAGS")))
+    return jobs
+
+
+def functions_of(job):
+    tree, unit, flags = job
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "unit.s")
+        subprocess.check_call(flags + ["--cuda-device-only", "-S", "-cuid=cmp", "-Wno-unused-command-line-argument", unit, "-o", out],
+                              cwd=os.path.join(tree, "racer-tracer_amd"))
+        with open(out) as f:
+            return functions(f.read())
+
+
+def counts(before, after, units):
+    after_jobs = {(u, fl): flags for u, fl, flags in unit_jobs(after)}
+    jobs = [(u, fl, flags) for u, fl, flags in unit_jobs(before) if (u, fl) in after_jobs and (not units or u in units)]
+    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+        old = list(pool.map(functions_of, [(before, u, flags) for u, fl, flags in jobs]))
+        new = list(pool.map(functions_of, [(after, u, after_jobs[(u, fl)]) for u, fl, flags in jobs]))
+    same = moved = 0
+    lines = []
+    mnemonics = lambda body: collections.Counter(l.split()[0] for l in body if not l.endswith(":"))  # noqa: E731
+    for (unit, flavour, _), (code_a, hsa_a), (code_b, hsa_b) in zip(jobs, old, new):
+        for sym in sorted(code_a):
+            if sym not in code_b:
+                lines.append("%s %s: gone (%s)" % (flavour, sym, unit))
+                continue
+            block_same = hsa_a.get(sym) == hsa_b.get(sym)
+            if code_a[sym] == code_b[sym] and block_same:
+                same += 1
+                continue
+            moved += 1
+            a, b = mnemonics(code_a[sym]), mnemonics(code_b[sym])
+            delta = ", ".join("%s %+d" % (k, b[k] - a[k]) for k in sorted(set(a) | set(b)) if a[k] != b[k])
+            lines.append("%s %s: %d -> %d instructions, resource block %s, mnemonic counts that differ: %s"
+                         % (flavour, sym, sum(a.values()), sum(b.values()), "same" if block_same else "DIFFERS", delta or "none"))
+    print("%d functions identical, %d moved" % (same, moved))
+    print("\n".join(lines))
+    return 0
+
+
 def listing_of(tree):
     with open(os.path.join(tree, "racer-tracer_amd", "Makefile")) as f:
         mk = f.read()
@@ -135,6 +195,8 @@ def diff(before, after):
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--diff":
         sys.exit(diff(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) >= 4 and sys.argv[1] == "--counts":
+        sys.exit(counts(os.path.abspath(sys.argv[2]), os.path.abspath(sys.argv[3]), sys.argv[4:]))
     tree = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for row in listing_of(tree):
         print(" ".join(row))
