@@ -2,6 +2,7 @@
 // ranks and masked register updates, the closest-hit loop of the rects-only variants, and the wave-cooperative samplers
 // (unit sphere, lens disk, Perlin turbulence) over the request slots of rt_pool_lds.h.
 #pragma once
+#include "rt_pool_groups.h"
 #include "rt_pool_lds.h"
 #include "rt_primary_bounds.h"
 
@@ -48,17 +49,16 @@ static_assert(sizeof(TraceArgs) % alignof(rtdev::PrimaryRects) == 0, "no padding
 __device__ __forceinline__ const RT_CONSTANT rtdev::PrimaryRects *primary_rects_here() {
     return (const RT_CONSTANT rtdev::PrimaryRects *)((const RT_CONSTANT unsigned char *)kernargs_here() + sizeof(TraceArgs));
 }
-// The lowest set bit of every group of 2^lg bits of x (1 <= lg <= 6), in the scalar unit: x & -x within each group, the
-// negation done per group as (~x without the groups' top bits) + 1 in every group, whose carry stops at the group's top
-// bit, XOR the top bits of ~x
-__device__ __forceinline__ uint64_t lowest_in_groups(uint64_t x, int lg) {
-    const int q = 1 << lg;
-    uint64_t low = 1; // bit 0 of every group, doubled out (a shift by 64 or more is one by 0, which adds nothing)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) low |= low << ((q << k) & 63);
-    const uint64_t top = low << (q - 1);
-    return x & (((~x & ~top) + low) ^ (~x & top));
+// The number of open requests of a sampler round, 1 .. 64, as a 32-bit scalar.  The empty asm is what keeps it one: left
+// to itself the compiler widens the count to 64 bits, for which the scalar unit has no ordered compare, and every
+// comparison with it becomes a vector compare of two scalars (v_cmp_gt_u64 and an s_and_b64 with exec behind it).
+__device__ __forceinline__ uint32_t request_count(uint64_t pending) {
+    uint32_t n = (uint32_t)__builtin_popcountll(pending);
+    asm("" : "+s"(n));
+    return n;
 }
+// (The lowest set bit of every group of 2^lg bits of a lane mask, lowest_in_groups, is in rt_pool_groups.h with the rest
+// of the group arithmetic: the formula it had here, over masks read from a table.)
 
 // The closest-hit loop of the rects-only variants over the grouped table (XY, XZ, YZ rects, in that order: record order,
 // strict `t < best_t`), one straight-line test per group with the plane a compile-time constant.  PAIRS: two records per
@@ -136,14 +136,16 @@ __device__ __forceinline__ uint64_t coop_random_in_unit_sphere(uint64_t pending,
                                                            SphereSlot *slot, d3 &result) {
     uint64_t have = 0;
     const ScatterPrefix own = scatter_prefix(pixel, sample, seg, k0, k1);
-    for (int round = 0; round < MAX_ROUNDS && pending != 0; ++round) {
-        const int n = __popcll(pending);
+    // One round; false when the rounds are over.
+    auto one_round = [&](int round) {
+        const bool FIRST = round == 0;
+        const uint32_t n = request_count(pending);
         // a round costs the whole wave ~70 instructions; past the first it only runs while enough requests are
         // open to be worth that (the others resume next iteration): C2 +2.2 %, C3 +0.3 % (thresholds 2..16 and one to
         // six rounds measured again with one-block candidates: 8 and two rounds stay)
-        if (round > 0 && n < 8) break;
+        if (!FIRST && n < 8u) return false;
         // group size q = 2^lg, the largest power of two with n * q <= 64
-        const int lg = n > 32 ? 0 : (n > 16 ? 1 : (n > 8 ? 2 : (n > 4 ? 3 : (n > 2 ? 4 : (n > 1 ? 5 : 6)))));
+        const int lg = rt_groups::group_lg(n);
         // what `result` takes: in every lane in the first round, in the lanes of `take` in the later ones.  `result` only
         // means something to a lane of the returned mask, so a lane that still needs a sample may take whatever its round
         // left it, a rejected candidate included.
@@ -158,12 +160,13 @@ __device__ __forceinline__ uint64_t coop_random_in_unit_sphere(uint64_t pending,
             pending &= ~inside;
             if (__builtin_amdgcn_inverse_ballot_w64(pending)) base += 1u;
         } else {
+            const rt_groups::GroupMasks groups = rt_groups::group_masks((uint32_t)lg); // (read here: the load waits behind the candidates' Philox)
             const bool need = __builtin_amdgcn_inverse_ballot_w64(pending);
             const int rank = lane_rank(pending);
             if (need) post_request(slot + rank, own, base);
             const int j = lane >> lg;              // request served by this lane
             const int c = lane & ((1 << lg) - 1);  // candidate offset inside the group
-            const bool serving = j < n;
+            const bool serving = (uint32_t)j < n;
             SphereSlot *const served = slot + (serving ? j : 0);
             const ScatterPrefix r = {served->b, served->y, served->x, served->w, served->z};
             const uint32_t i = served->base + (uint32_t)c; // candidate index = its block (rt_rng.h)
@@ -175,7 +178,7 @@ __device__ __forceinline__ uint64_t coop_random_in_unit_sphere(uint64_t pending,
             // from (after that read: one wave's LDS accesses complete in order, and the empty asm keeps the compiler from
             // moving the double stores above the word loads).
             asm volatile("" ::: "memory");
-            if (__builtin_amdgcn_inverse_ballot_w64(lowest_in_groups(accepted, lg))) {
+            if (__builtin_amdgcn_inverse_ballot_w64(rt_groups::lowest_in_groups(accepted, groups))) {
                 double *const answer = reinterpret_cast<double *>(served);
                 answer[0] = p.x;
                 answer[1] = p.y;
@@ -184,8 +187,7 @@ __device__ __forceinline__ uint64_t coop_random_in_unit_sphere(uint64_t pending,
             asm volatile("" ::: "memory"); // (and the answers' loads below them)
             // did my own request get one?  (a ballot of the comparison, ANDed with `pending` = ballot(need) as scalars)
             const int first = need ? (rank << lg) : 0;
-            const uint64_t width_mask = lg == 6 ? ~0ull : ((1ull << (1 << lg)) - 1ull);
-            const uint64_t got = pending & ballot(((accepted >> first) & width_mask) != 0);
+            const uint64_t got = pending & ballot(((accepted >> first) & groups.width) != 0);
             // every lane reads a slot: what it finds means nothing to a lane that got none
             const double *const answer = reinterpret_cast<const double *>(slot + (need ? rank : 0));
             cand = mk(answer[0], answer[1], answer[2]);
@@ -194,11 +196,23 @@ __device__ __forceinline__ uint64_t coop_random_in_unit_sphere(uint64_t pending,
             pending &= ~got; // the lanes still searching
             if (__builtin_amdgcn_inverse_ballot_w64(pending)) base += 1u << lg;
         }
-        if (round == 0) {
+        if (FIRST) {
             result = cand;
         } else {
             move_masked(cand, take, result);
         }
+        return true;
+    };
+    // The plain variants' two rounds are unrolled BY ORDER: round 0's unmasked write of `result` is a compile-time case of
+    // `round` only then, and with the group size read off a bit count the optimiser no longer unrolls them by itself.  The
+    // four rounds of the others stay with it (it peels round 0 and keeps ONE copy of the later rounds).
+    if constexpr (MAX_ROUNDS == 2) {
+#pragma unroll
+        for (int round = 0; round < MAX_ROUNDS && pending != 0; ++round)
+            if (!one_round(round)) break;
+    } else {
+        for (int round = 0; round < MAX_ROUNDS && pending != 0; ++round)
+            if (!one_round(round)) break;
     }
     return have;
 }
@@ -212,8 +226,8 @@ __device__ __forceinline__ void coop_random_in_unit_disk(bool need, uint32_t pix
     uint32_t base = 0;
     uint64_t pending = ballot(need);
     while (pending != 0) {
-        const int n = __popcll(pending);
-        const int lg = n > 32 ? 0 : (n > 16 ? 1 : (n > 8 ? 2 : (n > 4 ? 3 : (n > 2 ? 4 : (n > 1 ? 5 : 6)))));
+        const uint32_t n = request_count(pending);
+        const int lg = rt_groups::group_lg(n);
         if (lg == 0) { // one candidate per request: every lane tests its own (the usual first round of a batch)
             if (need) {
                 const u4 b = philox4x32(pixel, sample, RT_RNG_LENS, base, k0, k1);
@@ -233,14 +247,13 @@ __device__ __forceinline__ void coop_random_in_unit_disk(bool need, uint32_t pix
         if (need) req[rank] = Req4{pixel, sample, 0u, base};
         const int j = lane >> lg;
         const int c = lane & ((1 << lg) - 1);
-        const bool serving = j < n;
+        const bool serving = (uint32_t)j < n;
         const Req4 r = req[serving ? j : 0];
         const u4 b = philox4x32(r.x, r.y, RT_RNG_LENS, r.w + (uint32_t)c, k0, k1);
         const double x = sym53(b.a, b.b), y = sym53(b.c, b.d);
         const uint64_t accepted = ballot(serving && x * x + y * y < 1.0);
         const int first = need ? (rank << lg) : 0;
-        const uint64_t width_mask = lg == 6 ? ~0ull : ((1ull << (1 << lg)) - 1ull);
-        const uint64_t mine = need ? ((accepted >> first) & width_mask) : 0ull;
+        const uint64_t mine = need ? ((accepted >> first) & rt_groups::group_masks((uint32_t)lg).width) : 0ull;
         const bool got = mine != 0;
         const int src = got ? first + __ffsll((unsigned long long)mine) - 1 : lane;
         const double rx = shfl_d(x, src), ry = shfl_d(y, src);
