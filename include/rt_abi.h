@@ -725,6 +725,75 @@ int rt_render_adaptive_nee(RtScene *scene, const RtCamera *camera, const RtRende
                            double *out_tile_error, /* HOST, ceil(W/8)*ceil(H/8), row-major tiles; may be NULL */
                            RtFrameCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
 
+/* ---------------------------------------------------------------- variance-guided filter of an adaptive frame
+ * rt_denoise_history_device's variance-guided levels for a STILL frame, the variance taken from the batch sums the adaptive
+ * renderer keeps anyway (tests/variance_filter_model.py restates it).  After rt_render_adaptive or
+ * rt_render_adaptive_nee a pixel of a tile with s samples and k chunks done has, per channel, the running sum S and
+ * Q = sum_j S_j^2 / n_j (the adaptive paragraph above).  With a = max(albedo, 1e-3) under RT_DENOISE_DEMODULATE, else 1:
+ *    m = S / s;  sigma = sqrt(max(0, Q - S m) / (k - 1) / s);  C = m / a;  sigma' = sigma / a;
+ *    var = (0.2126 sigma'_r + 0.7152 sigma'_g + 0.0722 sigma'_b)^2          where k >= min_chunks
+ * — the squared standard error of the luminance with the channels taken as fully correlated, an upper bound.  A guide miss
+ * has var = 0.  Where k < min_chunks var is rt_denoise_history_device's 7x7 spatial estimate over C.  The filter is
+ * denoise->iterations levels of that call's a-trous level over (C, var) with filter->sigma_luminance, then
+ * sqrt(max(C albedo, 0)), which is all that iterations == 0 does; with sigma_luminance <= 0 the levels are
+ * rt_denoise_device's.
+ *  - rt_batch_variance_device: C into radiance_out_device (W*H*3 f64) and var into variance_out_device (W*H f64) from the
+ *    planes of batch_planes (samples and chunks are per PIXEL, samples >= 1) and the guides' albedo, normal, position,
+ *    footprint and obj_id.  Enqueued on `hip_stream` without synchronising.
+ *  - rt_denoise_variance_device: the levels and the re-modulation of (radiance_device, variance_device) into out_device
+ *    (gamma-encoded; out_device != radiance_device).  Neither input is written.  Scratch memory is the scene's.  Enqueued on
+ *    `hip_stream` without synchronising.
+ *  - rt_render_adaptive_filtered does, in order: rt_render_adaptive (light_sampling == NULL) or rt_render_adaptive_nee —
+ *    the same passes, callbacks (unfiltered frames), cancel and refusals —, the guides of (camera, params), the two calls
+ *    above on the scene's own sums, squares and tile state, and the download of the filtered frame into out_rgb.
+ *    outputs->raw_rgb, samples and tile_error equal the adaptive call's out_rgb, out_samples and out_tile_error bit for bit;
+ *    with adaptive->threshold <= 0 raw_rgb is rt_render_frame's frame (rt_render_frame_nee's): the still-frame case.
+ *    outputs->sums and squares are S and Q, chunks the k of every pixel's tile, variance the var fed to the levels.  On a
+ *    cancel nothing is filtered: the call returns what the adaptive call returns, out_rgb holds the last unfiltered frame as
+ *    that call leaves it, and of `outputs` only samples and tile_error are written.
+ *  - Refused with RT_ERR_INVALID_ARGUMENT before a device is touched: NULL pointers (the fields of RtBatchOutputs aside),
+ *    what rt_denoise_device refuses about params and denoise, a non-finite sigma_luminance, min_chunks < 2, a non-zero
+ *    _reserved, out_device == radiance_device; for rt_render_adaptive_filtered everything the adaptive call it runs refuses.
+ * A binding detects these entry points by symbol lookup (RT_ABI_VERSION is unchanged by them). */
+typedef struct RtVarianceFilterParams {
+    double sigma_luminance; /* luminance stop in standard errors; <= 0: rt_denoise_device's levels */
+    int32_t min_chunks;     /* the batch estimate is used from this many chunks on (>= 2) */
+    int32_t _reserved[5];   /* must be 0 */
+} RtVarianceFilterParams;
+typedef struct RtBatchPlanes { /* DEVICE memory */
+    const double *sums;     /* W*H*3: S */
+    const double *squares;  /* W*H*3: Q */
+    const int32_t *samples; /* W*H: s */
+    const int32_t *chunks;  /* W*H: k */
+} RtBatchPlanes;
+typedef struct RtBatchOutputs { /* HOST memory; each field may be NULL */
+    double *raw_rgb;     /* W*H*3 */
+    double *sums;        /* W*H*3 */
+    double *squares;     /* W*H*3 */
+    int32_t *samples;    /* W*H */
+    int32_t *chunks;     /* W*H */
+    double *tile_error;  /* ceil(W/8)*ceil(H/8), as rt_render_adaptive's */
+    double *variance;    /* W*H */
+} RtBatchOutputs;
+
+/* The defaults: sigma_luminance 4, min_chunks 4.  A NULL is ignored. */
+void rt_variance_filter_params_default(RtVarianceFilterParams *out);
+int rt_batch_variance_device(RtScene *scene, const RtRenderParams *params, const RtDenoiseParams *denoise,
+                             const RtVarianceFilterParams *filter, const RtBatchPlanes *batch_planes,
+                             const RtGuides *guides_device, double *radiance_out_device, double *variance_out_device,
+                             void *hip_stream);
+int rt_denoise_variance_device(RtScene *scene, const RtRenderParams *params, const RtDenoiseParams *denoise,
+                               const RtVarianceFilterParams *filter, const double *radiance_device,
+                               const double *variance_device, const RtGuides *guides_device, double *out_device,
+                               void *hip_stream);
+int rt_render_adaptive_filtered(RtScene *scene, const RtCamera *camera, const RtRenderParams *params,
+                                const RtLightSamplingParams *light_sampling /* NULL: the plain estimator */,
+                                const RtAdaptiveParams *adaptive, const RtDenoiseParams *denoise,
+                                const RtVarianceFilterParams *filter,
+                                double *out_rgb /* HOST, W*H*3 f64, filtered, required */,
+                                RtBatchOutputs *outputs /* may be NULL */,
+                                RtFrameCallback callback, void *user, RtCancelCallback cancelled, void *cancel_user);
+
 /* rt_render_ex's contract with rt_render_frame_nee's estimator: the tile stream of ONE next-event-estimation frame, delivered
  * while it renders, with a cancel hook that stops it quickly.  One device (several: rt_render_nee_multi below); no `volatile int` form.
  *  - Tiles: the tiles_w x tiles_h grid, column-major, the last row / column absorbing the remainders, ONE callback per tile

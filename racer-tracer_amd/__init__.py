@@ -168,6 +168,21 @@ def temporal_params(**overrides):
     return tp
 
 
+def variance_filter_params(**overrides):
+    """rt_variance_filter_params_default, with fields overridden by keyword (sigma_luminance, min_chunks)
+    -> abi.RtVarianceFilterParams.  No device needed."""
+    fp = abi.RtVarianceFilterParams()
+    lib().rt_variance_filter_params_default(C.byref(fp))
+    for k, v in overrides.items():
+        setattr(fp, k, v)
+    return fp
+
+
+def batch_planes_struct(planes):
+    """abi.RtBatchPlanes over device tensors (a dict with sums, squares [H, W, 3] f64, samples, chunks [H, W] int32)."""
+    return abi.RtBatchPlanes(*[planes[k].data_ptr() for k in ("sums", "squares", "samples", "chunks")])
+
+
 HISTORY_PLANES = ("radiance", "moments", "length", "normal", "position", "obj_id")
 
 
@@ -565,6 +580,61 @@ class Scene:
         check(self._lib.rt_denoise_history_device(self._h, C.byref(params), C.byref(dp), C.byref(tp), C.byref(history),
                                                   C.byref(guides), C.c_void_p(out_ptr), C.c_void_p(stream or 0)),
               "rt_denoise_history_device", self._lib)
+
+    def batch_variance_device(self, params, planes, guides, radiance_ptr, variance_ptr, dparams=None, fparams=None,
+                              stream=None):
+        """rt_batch_variance_device: planes an abi.RtBatchPlanes, guides an abi.RtGuides of device addresses; the radiance
+        C (W*H*3 f64) and its variance (W*H f64) go to the two device addresses.  Enqueued on `stream`, not synchronised."""
+        dp = dparams if dparams is not None else denoise_params()
+        fp = fparams if fparams is not None else variance_filter_params()
+        check(self._lib.rt_batch_variance_device(self._h, C.byref(params), C.byref(dp), C.byref(fp), C.byref(planes),
+                                                 C.byref(guides), C.c_void_p(radiance_ptr), C.c_void_p(variance_ptr),
+                                                 C.c_void_p(stream or 0)), "rt_batch_variance_device", self._lib)
+
+    def denoise_variance_device(self, params, radiance_ptr, variance_ptr, guides, out_ptr, dparams=None, fparams=None,
+                                stream=None):
+        """rt_denoise_variance_device: the variance-guided levels over (radiance, variance) and the re-modulation into
+        out_ptr (device address), gamma-encoded.  Enqueued on `stream`, not synchronised."""
+        dp = dparams if dparams is not None else denoise_params()
+        fp = fparams if fparams is not None else variance_filter_params()
+        check(self._lib.rt_denoise_variance_device(self._h, C.byref(params), C.byref(dp), C.byref(fp), C.c_void_p(radiance_ptr),
+                                                   C.c_void_p(variance_ptr), C.byref(guides), C.c_void_p(out_ptr),
+                                                   C.c_void_p(stream or 0)), "rt_denoise_variance_device", self._lib)
+
+    def render_adaptive_filtered(self, camera, params, threshold=None, pass_samples=None, min_samples=None, nee=False,
+                                 heuristic=None, max_lights=None, dparams=None, fparams=None, cancel=None, on_frame=None):
+        """rt_render_adaptive_filtered -> (filtered frame float64 [H, W, 3], outputs, frames): outputs a dict of every
+        RtBatchOutputs plane (raw_rgb, sums, squares [H, W, 3] f64; samples, chunks [H, W] int32; tile_error
+        [ceil(H/8), ceil(W/8)] f64; variance [H, W] f64), frames the callbacks' (samples_done, unfiltered copy).  nee: the
+        next-event estimator with heuristic / max_lights as render_frame_nee's.  threshold, pass_samples, min_samples as
+        render_adaptive's (threshold 0: the still frame); cancel and on_frame as render_progressive's."""
+        overrides = {k: v for k, v in (("threshold", threshold), ("pass_samples", pass_samples),
+                                       ("min_samples", min_samples)) if v is not None}
+        ap = adaptive_params(**overrides)
+        dp = dparams if dparams is not None else denoise_params()
+        fp = fparams if fparams is not None else variance_filter_params()
+        ls = _light_sampling(heuristic, max_lights) if nee else None
+        h, w = params.height, params.width
+        frame = np.zeros((h, w, 3), dtype=np.float64)
+        out = {"raw_rgb": np.zeros((h, w, 3)), "sums": np.zeros((h, w, 3)), "squares": np.zeros((h, w, 3)),
+               "samples": np.zeros((h, w), dtype=np.int32), "chunks": np.zeros((h, w), dtype=np.int32),
+               "tile_error": np.zeros(((h + 7) // 8, (w + 7) // 8)), "variance": np.zeros((h, w))}
+        bo = abi.RtBatchOutputs(*[out[k].ctypes.data_as(t) for k, t in abi.RtBatchOutputs._fields_])
+        frames = []
+
+        def on_pass(_user, rgb, samples_done, _samples_total):
+            arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()
+            frames.append((samples_done, arr))
+            if on_frame is not None:
+                on_frame(samples_done, arr)
+
+        cb = abi.RtFrameCallback(on_pass)
+        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        check(self._lib.rt_render_adaptive_filtered(self._h, C.byref(camera), C.byref(params),
+                                                    C.byref(ls) if ls is not None else None, C.byref(ap), C.byref(dp),
+                                                    C.byref(fp), frame.ctypes.data_as(C.POINTER(C.c_double)), C.byref(bo), cb,
+                                                    None, hook, None), "rt_render_adaptive_filtered", self._lib)
+        return frame, out, frames
 
     def variant(self):
         """rtdev_scene_variant: which trace kernel rt_scene_create_ex chose -> dict of abi.VARIANT_FIELDS."""

@@ -136,6 +136,20 @@ class RtAdaptiveParams(C.Structure):
                 ("_reserved", C.c_int32 * 4)]
 
 
+class RtVarianceFilterParams(C.Structure):
+    _fields_ = [("sigma_luminance", C.c_double), ("min_chunks", C.c_int32), ("_reserved", C.c_int32 * 5)]
+
+
+class RtBatchPlanes(C.Structure):
+    _fields_ = [("sums", C.c_void_p), ("squares", C.c_void_p), ("samples", C.c_void_p), ("chunks", C.c_void_p)]
+
+
+class RtBatchOutputs(C.Structure):
+    _fields_ = [("raw_rgb", C.POINTER(C.c_double)), ("sums", C.POINTER(C.c_double)), ("squares", C.POINTER(C.c_double)),
+                ("samples", C.POINTER(C.c_int32)), ("chunks", C.POINTER(C.c_int32)), ("tile_error", C.POINTER(C.c_double)),
+                ("variance", C.POINTER(C.c_double))]
+
+
 RT_MIS_POWER, RT_MIS_BALANCE = 0, 1
 
 
@@ -227,6 +241,18 @@ PROTOTYPES = {
                                          C.POINTER(RtLightSamplingParams), C.POINTER(RtAdaptiveParams), C.POINTER(C.c_double),
                                          C.POINTER(C.c_int32), C.POINTER(C.c_double), RtFrameCallback, C.c_void_p,
                                          RtCancelCallback, C.c_void_p]),
+    "rt_variance_filter_params_default": (None, [C.POINTER(RtVarianceFilterParams)]),
+    "rt_batch_variance_device": (C.c_int, [C.c_void_p, C.POINTER(RtRenderParams), C.POINTER(RtDenoiseParams),
+                                           C.POINTER(RtVarianceFilterParams), C.POINTER(RtBatchPlanes), C.POINTER(RtGuides),
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_variance_device": (C.c_int, [C.c_void_p, C.POINTER(RtRenderParams), C.POINTER(RtDenoiseParams),
+                                             C.POINTER(RtVarianceFilterParams), C.c_void_p, C.c_void_p, C.POINTER(RtGuides),
+                                             C.c_void_p, C.c_void_p]),
+    "rt_render_adaptive_filtered": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),
+                                              C.POINTER(RtLightSamplingParams), C.POINTER(RtAdaptiveParams),
+                                              C.POINTER(RtDenoiseParams), C.POINTER(RtVarianceFilterParams),
+                                              C.POINTER(C.c_double), C.POINTER(RtBatchOutputs), RtFrameCallback, C.c_void_p,
+                                              RtCancelCallback, C.c_void_p]),
     "rt_render_nee": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams), C.POINTER(RtLightSamplingParams),
                                 RtTileCallback, C.c_void_p, RtCancelCallback, C.c_void_p]),
     "rt_render_frame_nee_strips_device": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtRenderParams),

@@ -173,6 +173,8 @@ struct RenderBuffers {
     // ping-pong buffers of W*H*3 doubles each
     DevBuf<double> guide_planes, denoise_scratch;
     DevBuf<int32_t> guide_ids;
+    // rt_render_adaptive_filtered (rt_variance_filter.hip), on first use: every pixel's samples and chunks, W*H each
+    DevBuf<int32_t> batch_counts;
 
     // what rt_scene_create makes when it takes no set over: only such a set is worth caching
     bool complete() const {
@@ -196,6 +198,7 @@ struct RenderBuffers {
         guide_planes.release();
         denoise_scratch.release();
         guide_ids.release();
+        batch_counts.release();
         tile_done.release();
         region_done.release();
         if (host_frame) (void)hipHostFree(host_frame);
@@ -220,6 +223,12 @@ struct RenderBuffers {
 extern "C" hipError_t rtdev_launch_guides(const rtdev::TraceArgs *args, const RtGuides *guides, hipStream_t stream);
 extern "C" hipError_t rtdev_launch_denoise_step(const RtDenoiseParams *d, int step, int width, int height, const double *in,
                                                 const RtGuides *guides, double *out, hipStream_t stream);
+// ... of rt_temporal.hip (compiled once, RT_ARITH_FAST): level `step` of the variance-guided filter (k_temporal_atrous) —
+// rtdev_launch_denoise_step's parameters, the luminance stop sigma_l > 0 and the variance planes beside the colour ones.
+// Linked inside the library only: rt_variance_filter.hip runs the same levels.
+extern "C" __attribute__((visibility("hidden"))) hipError_t rtdev_launch_atrous_var(
+    const RtDenoiseParams *d, double sigma_l, int step, int width, int height, const double *in, const double *var,
+    const RtGuides *guides, double *out, double *var_out, hipStream_t stream);
 
 struct RtScene {
     int device = 0;

@@ -12,7 +12,8 @@
 // With sigma_luminance <= 0 the levels are rt_denoise.hip's own launches, and the re-modulation always is.
 //
 // Compiled once, with the fast arithmetic, as rt_denoise.hip.  Lane = pixel, 16x16 pixels per block, taps straight from
-// global memory.  The launchers have internal linkage: nothing outside this file starts these kernels.
+// global memory.  The launchers have internal linkage, but for rtdev_launch_atrous_var (rt_scene.h), through which
+// rt_variance_filter.hip runs the same levels over a still frame's batch variance.
 #include "rt_trace_common.h"
 #include "rt_scene.h"
 
@@ -525,6 +526,16 @@ int render_temporal(RtScene *s, RtTemporal *t, const RtCamera *camera, const RtR
 }
 
 } // namespace
+
+extern "C" hipError_t rtdev_launch_atrous_var(const RtDenoiseParams *d, double sigma_l, int step, int width, int height,
+                                              const double *in, const double *var, const RtGuides *guides, double *out,
+                                              double *var_out, hipStream_t stream) {
+    RtRenderParams p;
+    memset(&p, 0, sizeof p);
+    p.width = width;
+    p.height = height;
+    return launch_atrous_var(&p, d, sigma_l, step, in, var, guides, out, var_out, stream);
+}
 
 extern "C" {
 

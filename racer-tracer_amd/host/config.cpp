@@ -204,6 +204,7 @@ Args Args::parse(int argc, const char *const *argv) {
         else if (s == "--device") a.device = std::atoi(val().c_str());
         else if (s == "--devices") a.devices = std::atoi(val().c_str());
         else if (s == "--denoise" && !has_inline) a.denoise = true;
+        else if (s == "--denoise-variance" && !has_inline) a.denoise_variance = true;
         else if (s == "--nee" && !has_inline) a.nee = true;
         else if (s == "--nee-stream" && !has_inline) a.nee_stream = true;
         else if (s == "--adaptive" || s == "--nee-adaptive") {
@@ -267,6 +268,8 @@ Args Args::parse(int argc, const char *const *argv) {
         throw TracerError::ArgumentParsingError("--nee-devices is a render mode of its own: it does not combine with --nee, --nee-stream, --adaptive, --nee-adaptive or --temporal");
     if (a.nee_devices > 0 && a.devices > 1)
         throw TracerError::ArgumentParsingError("--nee-devices N names its own devices: it does not combine with --devices > 1");
+    if (a.denoise_variance && (a.devices > 1 || a.nee_stream || a.nee_devices > 0 || a.temporal > 0))
+        throw TracerError::ArgumentParsingError("--denoise-variance filters one device's whole frame: it does not combine with --devices > 1, --nee-stream, --nee-devices or --temporal");
     if (a.nee_list_given && !(a.nee || a.nee_stream || a.nee_devices > 0 || a.nee_adaptive > 0.0))
         throw TracerError::ArgumentParsingError("--nee-lights and --nee-pick set the light list of next-event estimation: they need --nee, --nee-stream, --nee-devices or --nee-adaptive");
     return a;

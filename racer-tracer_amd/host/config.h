@@ -71,6 +71,9 @@ struct Args { // config.rs:12-28
     bool nee_lights_all = false, nee_pick_power = false, nee_list_given = false;
     double nee_adaptive = 0.0; // --nee-adaptive T (T > 0): render through rt_render_adaptive_nee with threshold T, one device only
     int temporal = 0; // --temporal K (K >= 1): K frames at seeds seed .. seed + K - 1 through rt_render_temporal, the last one written; one device only
+    // --denoise-variance: the frame of the default, --nee, --adaptive T or --nee-adaptive T route through
+    // rt_render_adaptive_filtered (threshold 0 where no T is given), filtered by its batch variance; one device only
+    bool denoise_variance = false;
     bool help = false;
 
     static Args parse(int argc, const char *const *argv);

@@ -13,10 +13,13 @@
 // stream through rt_render_nee_multi, the frame's strips dealt to devices device .. device+N-1) and --temporal K (one device
 // renders K frames of the configured sample count at seeds seed .. seed + K - 1 from the configured camera through
 // rt_render_temporal and writes the last; --denoise gives the filter its levels, without it the history alone is shown).
+// --denoise-variance sends the frame of the default, --nee, --adaptive T or --nee-adaptive T route through
+// rt_render_adaptive_filtered instead (threshold 0 where no T is given): the variance-guided filter fed by the batch sums.
 // --nee-lights plain|all and --nee-pick uniform|power give every scene of an NEE run its light list (rt_scene_set_lights).
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -58,7 +61,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -111,7 +114,32 @@ int main(int argc, char **argv) {
     auto t0 = std::chrono::steady_clock::now();
     double traced = 1.0; // --adaptive: the fraction of the frame's samples traced
     double mean_length = 0.0; // --temporal: the mean history length behind the last frame
-    if (args.temporal > 0) { // K frames into one history; the last one, filtered inside the call, is tone-mapped here
+    double mean_sigma = 0.0;  // --denoise-variance: the mean of sqrt(var) over the frame
+    if (args.denoise_variance) { // the adaptive passes (or, with threshold 0, the still frame) and the filter in one call
+        RtAdaptiveParams ap;
+        rt_adaptive_params_default(&ap);
+        ap.threshold = args.adaptive > 0.0 ? args.adaptive : args.nee_adaptive > 0.0 ? args.nee_adaptive : 0.0;
+        RtLightSamplingParams ls;
+        rt_light_sampling_params_default(&ls);
+        RtDenoiseParams dp;
+        rt_denoise_params_default(&dp);
+        RtVarianceFilterParams fp;
+        rt_variance_filter_params_default(&fp);
+        std::vector<int32_t> counts(n_rgb / 3);
+        std::vector<double> filtered(n_rgb), var(n_rgb / 3);
+        RtBatchOutputs outputs;
+        memset(&outputs, 0, sizeof outputs);
+        outputs.samples = counts.data();
+        outputs.variance = var.data();
+        rc = rt_render_adaptive_filtered(scenes[0], rth_session_camera(session), &params, args.nee || args.nee_adaptive > 0.0 ? &ls : nullptr,
+                                         &ap, &dp, &fp, filtered.data(), &outputs, nullptr, nullptr, nullptr, nullptr);
+        double sum = 0.0;
+        for (int32_t c : counts) sum += (double)c;
+        traced = sum / ((double)counts.size() * (double)params.samples);
+        for (double v : var) mean_sigma += std::sqrt(v);
+        mean_sigma /= (double)var.size();
+        if (rc == RT_OK) rth_tone_map(session, filtered.data(), sb.buffer.data(), n_rgb / 3);
+    } else if (args.temporal > 0) { // K frames into one history; the last one, filtered inside the call, is tone-mapped here
         RtTemporalParams tp;
         rt_temporal_params_default(&tp);
         RtDenoiseParams dp;
@@ -174,7 +202,7 @@ int main(int argc, char **argv) {
     } else {
         rc = rt_render_multi(scenes.data(), (int)scenes.size(), rth_session_camera(session), &params, 0, on_tile, &sb, nullptr, nullptr);
     }
-    if (rc == RT_OK && args.denoise && args.temporal == 0) { // the whole frame, filtered, then tone-mapped like the tiles were
+    if (rc == RT_OK && args.denoise && args.temporal == 0 && !args.denoise_variance) { // the whole frame, filtered, then tone-mapped like the tiles were
         RtDenoiseParams dp;
         rt_denoise_params_default(&dp);
         std::vector<double> filtered(n_rgb);
@@ -196,6 +224,8 @@ int main(int argc, char **argv) {
         if (args.adaptive > 0.0 || args.nee_adaptive > 0.0)
             fprintf(stderr, "Adaptive sampling (threshold %g) traced %.1f %% of the %d samples per pixel.\n",
                     args.adaptive > 0.0 ? args.adaptive : args.nee_adaptive, 100.0 * traced, params.samples);
+        if (args.denoise_variance)
+            fprintf(stderr, "Variance-guided filter: mean standard error of the luminance %.6f.\n", mean_sigma);
         if (args.temporal > 0)
             fprintf(stderr, "Temporal accumulation over %d frames: mean history length %.2f.\n", args.temporal, mean_length);
         fprintf(stderr, "It took %.3f seconds to render the image. (%.1f Msamples/s, %.2f segments/sample, kernel %.1f ms)\n",
