@@ -5,8 +5,12 @@
 #include "rt_pool_groups.h"
 #include "rt_pool_lds.h"
 #include "rt_primary_bounds.h"
+#include "rt_rect_pairs.h"
 
 namespace RT_KNS {
+
+static_assert(sizeof(Prim) == rt_pairs::kRecordBytes && offsetof(Prim, p) + 4 * sizeof(double) == rt_pairs::kOffsetOfK,
+              "rt_rect_pairs.h addresses k in the table's bytes");
 
 __device__ __forceinline__ int lane_rank(uint64_t mask) { // set bits of `mask` below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -70,7 +74,7 @@ __device__ __forceinline__ uint32_t request_count(uint64_t pending) {
 static_assert(rtdev::RT_PRIMARY_RECTS <= 32, "a rect mask is one 32-bit word");
 template <bool PAIRS>
 __device__ __forceinline__ void closest_hit_rects(const Prim *table, const d3 &o, const d3 &d, const d3 &inv_d, double &best_t, int &best,
-                                                  uint32_t rect_mask = ~0u) {
+                                                  uint32_t rect_mask = ~0u, const Prim *lds_table = nullptr) {
     auto test_plane = [&](auto axis, const Prim &P, int i) {
 #ifndef RT_EXACT_DIV
         rect_closest_update<decltype(axis)::value>(P.p[0], P.p[1], P.p[2], P.p[3], P.p[4], o, d, inv_d, 0.001, best_t, best, i);
@@ -88,8 +92,54 @@ __device__ __forceinline__ void closest_hit_rects(const Prim *table, const d3 &o
         if (PAIRS) {
             for (; i + 1 < end; i += 2, rec += 2) {
                 const Prim pa = load_prim_uniform(rec, 0), pb = load_prim_uniform(rec, 1);
+#ifndef RT_EXACT_DIV
+                // A FACING PAIR (rt_rect_pairs.h; marked in the first record's p[5] by rt_scene_create): every lane selects
+                // the record its direction points at and reads that record's k, and its partner's, from the table's copy in
+                // LDS (a select between two scalars is two moves and a select per word on this target).  When the partner's
+                // plane lies behind t_min in every lane, the first test runs on the selected record and the second is
+                // stepped over; in every other case both run as they always did.
+                constexpr int AXIS = decltype(axis)::value;
+                // (the two marks as 32-bit scalars — see request_count — read as the single words they are, and in hand with
+                // the first record's bounds before the branch: left to itself the compiler loads the bounds behind the
+                // selection, one more wait in a row.  Both k stay out of this: the settled path reads neither as a scalar)
+                const RT_CONSTANT uint32_t *words = (const RT_CONSTANT uint32_t *)rec;
+                uint32_t larger = words[(rt_pairs::kOffsetOfK + 12u) / 4u], step = words[(rt_pairs::kRecordBytes + rt_pairs::kOffsetOfK + 12u) / 4u];
+                asm volatile("; pair requested" : "+s"(larger), "+s"(step) : "s"(pa.p[0]), "s"(pa.p[1]), "s"(pa.p[2]), "s"(pa.p[3]));
+                double k_first;
+                int i_first;
+                uint32_t second = 1u; // whether the second record is tested too; a 32-bit scalar (see request_count)
+                // (written as nested if / else with the plain case twice: one join behind them costs the scalar unit a flag
+                // and a branch on it)
+                auto plain = [&] {
+                    k_first = pa.p[4];
+                    i_first = i;
+                    asm volatile("; both records" : "+v"(k_first), "+v"(i_first)); // (keeps the branch a branch: see near_zero)
+                };
+                if (larger != 0u) {
+                    using lds_bytes = const __attribute__((address_space(3))) unsigned char *;
+                    const uint32_t k_of_larger = (uint32_t)(uintptr_t)(lds_bytes)reinterpret_cast<const unsigned char *>(lds_table) + larger;
+                    const uint32_t sel = rt_pairs::selected(k_of_larger, step, rt_pairs::sign_mask(comp(d, AXIS)));
+                    const double k_other = *(const __attribute__((address_space(3))) double *)(uintptr_t)rt_pairs::partner(k_of_larger, step, sel);
+                    // (the lane's own record is read with its partner's k, one wait for both: the asm holds the reads
+                    // here, in front of the branch they would otherwise sink behind)
+                    k_first = *(const __attribute__((address_space(3))) double *)(uintptr_t)sel;
+                    i_first = *(const __attribute__((address_space(3))) int *)(uintptr_t)(sel + 8u);
+                    asm volatile("; facing pair" : "+v"(k_first), "+v"(i_first));
+                    if (ballot(!rt_pairs::settled(rt_pairs::t_of_plane(k_other, comp(o, AXIS), comp(inv_d, AXIS)))) == 0) {
+                        second = 0u;
+                    } else {
+                        plain();
+                    }
+                } else {
+                    plain();
+                }
+                rect_closest_update<AXIS, true>(pa.p[0], pa.p[1], pa.p[2], pa.p[3], k_first, o, d, inv_d, 0.001, best_t, best, i_first);
+                asm("" : "+s"(second));
+                if (second != 0u) test_plane(axis, pb, i + 1);
+#else
                 test_plane(axis, pa, i);
                 test_plane(axis, pb, i + 1);
+#endif
             }
             if (i < end) {
                 test_plane(axis, load_prim_uniform(rec, 0), i);

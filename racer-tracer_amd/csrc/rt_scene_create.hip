@@ -11,6 +11,7 @@
 #include <mutex>
 #include <string>
 #include <vector>
+#include "rt_rect_pairs.h"
 #include "rt_scene.h"
 
 using rtapi::DevBuf;
@@ -250,8 +251,20 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
         for (int g = 0; g < 3; ++g) s->rect_end[g] = groups.rect_end[g];
         s->sphere_end = groups.sphere_end;
         s->box_end = groups.box_end;
-        // a table of plain rects only: what their own pixel rectangles are formed from on every render (rt_primary_bounds.h)
         const int n_rects = groups.rect_end[2];
+        // The facing pairs of the rect groups, marked in the device copy of the table, in the field behind k that no rect
+        // test reads (rt_rect_pairs.h); every other grouped rect gets "no pair" there, whatever its host record held.
+        {
+            std::vector<rtdev::RectGeo> geo;
+            for (int j = 0; j < n_rects; ++j) {
+                const rtdev::Prim &q = prims[(size_t)j];
+                geo.push_back(rtdev::RectGeo{j < groups.rect_end[0] ? 2 : (j < groups.rect_end[1] ? 1 : 0), q.p[0], q.p[1], q.p[2], q.p[3], q.p[4]});
+            }
+            std::vector<uint64_t> field((size_t)n_rects);
+            rt_pairs::mark_table(geo.data(), groups.rect_end, field.data());
+            for (int j = 0; j < n_rects; ++j) memcpy(&prims[(size_t)j].p[5], &field[(size_t)j], sizeof(uint64_t));
+        }
+        // a table of plain rects only: what their own pixel rectangles are formed from on every render (rt_primary_bounds.h)
         if (n_rects == d->n_primitives && n_rects <= rtdev::RT_PRIMARY_RECTS)
             for (int j = 0; j < n_rects; ++j) {
                 const rtdev::Prim &q = prims[(size_t)j];

@@ -45,7 +45,9 @@
 // 6. NO SCALAR SWITCH IN THE CLOSEST-HIT LOOP.  The device table is grouped by kind (plain XY / XZ / YZ
 //    rects, plain spheres, the rest); each group gets one straight-line test with the plane a compile-time
 //    constant.  With a wave-uniform index the `match` on a record's kind was scalar control flow, ~25 SALU
-//    instructions and half a dozen branches around 12 vector instructions per rect.
+//    instructions and half a dozen branches around 12 vector instructions per rect.  In the rects-only plain variant a
+//    FACING PAIR of rects (two walls on parallel planes with the same bounds: rt_rect_pairs.h) costs a lane ONE rect test,
+//    on the record its direction points at, whenever the other plane lies behind t_min in every lane of the wave.
 //
 // 7. THE ONE EXPENSIVE TEXTURE IS EVALUATED BY THE WHOLE WAVE (coop_noise_turbulence): lanes only note
 //    their Noise lookup while shading; eight lookups per round take eight lanes each, one octave per lane.
@@ -858,7 +860,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                     double best_t = __builtin_inf(); // closest hit, t in [0.001, inf) (renderer.rs:58): dead behind this block
                     best = -1;
                     ++n_segments;
-                    closest_hit_rects<true>(A.prims, o, d, rcp3(d), best_t, best);
+                    closest_hit_rects<true>(A.prims, o, d, rcp3(d), best_t, best, ~0u, lds_prims);
                     // the hit's point takes the ray origin's place where the segment is traced: the shading block of the next
                     // iteration forms none, and a ring entry can hand one out.  (A lane that missed gets o + inf * d, which
                     // nothing reads: it ends below.)
