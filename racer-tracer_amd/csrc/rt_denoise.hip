@@ -10,11 +10,14 @@
 //            the image dropped; w_pq = h(dx) h(dy) [id_p = id_q] w_n w_x w_c; misses pass through;
 //   remod    sqrt(max(I_K * albedo, 0)) (or sqrt(max(I_K, 0))).
 // Everything is f64; the tap loop adds in one fixed order (dy, then dx), so tests/denoise_model.py restates it to rounding.
+// The loop itself is rt_filter_taps.h's atrous_pixel, which rt_temporal.hip's variance-guided level instantiates too; the
+// host rules the three filter units share (guides_complete, pixel_grid, filter_stops, enqueue_levels) are defined below.
 //
 // Compiled once, with the fast arithmetic (RT_ARITH_FAST's hit functions of rt_trace_common.h).  The filter reads its taps
 // straight from global memory: the planes of a 1080p frame (~130 MB for the guides, 50 MB per colour buffer) are served by
 // L2 and the Infinity Cache, and the measured cost is in DESIGN.md.
 #include "rt_trace_common.h"
+#include "rt_filter_taps.h"
 #include "rt_scene.h"
 
 #include <cmath>
@@ -92,10 +95,8 @@ __global__ __launch_bounds__(256) void k_guides_f64(const TraceArgs A, const RtG
 // demodulation: I = g^2 (/ max(albedo, 1e-3))
 __global__ __launch_bounds__(256) void k_denoise_demod(const double *__restrict__ g, const double *__restrict__ albedo,
                                                        double *__restrict__ out, size_t n, int demodulate) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const double L = g[i] * g[i];
-        out[i] = demodulate ? L / fmax(albedo[i], 1e-3) : L;
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = demodulated(g[i], albedo[i], demodulate);
 }
 
 // remodulation: sqrt(max(I * albedo, 0)) (or sqrt(max(I, 0)))
@@ -114,65 +115,16 @@ struct AtrousArgs {
     double inv_sc2;    // 1 / (sigma_c * 2^-i)^2, or 0: the colour stop is off
 };
 
-// One a-trous level: lane = pixel, 16x16 pixels per block.  Each tap reads the neighbour's id, and where the ids agree its
-// colour, normal and position (10 doubles); the weights are exp() of the stops' squared distances, multiplied in the order
-// h(dx) h(dy) w_n w_x w_c of DESIGN.md 4.6.
+// One a-trous level: lane = pixel, 16x16 pixels per block (rt_filter_taps.h: atrous_pixel).
 __global__ __launch_bounds__(256) void k_denoise_atrous(const AtrousArgs P, const double *__restrict__ I,
                                                         const RtGuides G, double *__restrict__ out) {
-    const int px = blockIdx.x * 16 + (threadIdx.x & 15);
-    const int py = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (px >= P.width || py >= P.height) return;
-    const size_t p = (size_t)py * (size_t)P.width + (size_t)px;
-    const d3 ip = ld3(I + 3 * p);
-    const int id = G.obj_id[p];
-    if (id < 0) { // a guide miss passes through
-        out[3 * p + 0] = ip.x;
-        out[3 * p + 1] = ip.y;
-        out[3 * p + 2] = ip.z;
-        return;
-    }
-    const double kh[5] = {1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0};
-    const d3 np = ld3(G.normal + 3 * p), xp = ld3(G.position + 3 * p);
-    const d3 sp = mk(sqrt(ip.x), sqrt(ip.y), sqrt(ip.z));
-    const double inv_fx = P.inv_sx / G.footprint[p]; // 1 / (sigma_x * s * footprint_p)
-    d3 sum = mk(0.0, 0.0, 0.0);
-    double wsum = 0.0;
-    for (int dy = -2; dy <= 2; ++dy) {
-        const int qy = py + dy * P.step;
-        if (qy < 0 || qy >= P.height) continue;
-        for (int dx = -2; dx <= 2; ++dx) {
-            const int qx = px + dx * P.step;
-            if (qx < 0 || qx >= P.width) continue;
-            const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
-            if (G.obj_id[q] != id) continue;
-            const d3 iq = ld3(I + 3 * q);
-            double w = kh[dx + 2] * kh[dy + 2];
-            if (P.inv_sn2 > 0.0) {
-                const d3 dn = np - ld3(G.normal + 3 * q);
-                w *= exp(-len2(dn) * P.inv_sn2);
-            }
-            if (P.inv_sx > 0.0) {
-                const double dist = dot(np, ld3(G.position + 3 * q) - xp) * inv_fx;
-                w *= exp(-(dist * dist));
-            }
-            if (P.inv_sc2 > 0.0) {
-                const d3 dc = sp - mk(sqrt(iq.x), sqrt(iq.y), sqrt(iq.z));
-                w *= exp(-len2(dc) * P.inv_sc2);
-            }
-            sum = sum + w * iq;
-            wsum += w;
-        }
-    }
-    const double inv = 1.0 / wsum; // the centre tap alone weighs 9/64
-    out[3 * p + 0] = sum.x * inv;
-    out[3 * p + 1] = sum.y * inv;
-    out[3 * p + 2] = sum.z * inv;
+    atrous_pixel<false>(P.width, P.height, P.step, P.inv_sn2, P.inv_sx, P.inv_sc2, 0.0, I, nullptr, G, out, nullptr);
 }
 
 } // namespace RT_KNS
 
 extern "C" hipError_t rtdev_launch_guides(const rtdev::TraceArgs *args, const RtGuides *guides, hipStream_t stream) {
-    const dim3 grid((unsigned)((args->width + 15) / 16), (unsigned)((args->height + 15) / 16));
+    const dim3 grid = rtapi::pixel_grid(args->width, args->height);
     if (args->n_bvh_nodes > 0) hipLaunchKernelGGL(RT_KNS::k_guides_f64<true>, grid, dim3(256), 0, stream, *args, *guides);
     else hipLaunchKernelGGL(RT_KNS::k_guides_f64<false>, grid, dim3(256), 0, stream, *args, *guides);
     return hipGetLastError();
@@ -189,16 +141,9 @@ extern "C" hipError_t rtdev_launch_denoise_step(const RtDenoiseParams *d, int st
         else hipLaunchKernelGGL(RT_KNS::k_denoise_remod, dim3(blocks), dim3(256), 0, stream, in, guides->albedo, out, n, demodulate);
         return hipGetLastError();
     }
-    RT_KNS::AtrousArgs a;
-    a.width = width;
-    a.height = height;
-    a.step = 1 << step;
-    a.inv_sn2 = d->sigma_normal > 0.0 ? 1.0 / (d->sigma_normal * d->sigma_normal) : 0.0;
-    a.inv_sx = d->sigma_plane > 0.0 ? 1.0 / (d->sigma_plane * (double)a.step) : 0.0;
-    const double sc = d->sigma_color > 0.0 ? ldexp(d->sigma_color, -step) : 0.0;
-    a.inv_sc2 = sc > 0.0 ? 1.0 / (sc * sc) : 0.0;
-    const dim3 grid((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
-    hipLaunchKernelGGL(RT_KNS::k_denoise_atrous, grid, dim3(256), 0, stream, a, in, *guides, out);
+    const rtapi::FilterStops st = rtapi::filter_stops(d, step);
+    const RT_KNS::AtrousArgs a = {width, height, 1 << step, st.inv_sn2, st.inv_sx, st.inv_sc2};
+    hipLaunchKernelGGL(RT_KNS::k_denoise_atrous, rtapi::pixel_grid(width, height), dim3(256), 0, stream, a, in, *guides, out);
     return hipGetLastError();
 }
 
@@ -211,11 +156,22 @@ constexpr int kMaxIterations = 10;
 // calibrated on tests/denoise_model.py (cornell_box_boxes, 16 spp against 512 spp)
 constexpr double kSigmaNormal = 0.1, kSigmaPlane = 1.0;
 
-bool guides_complete(const RtGuides *g) {
+} // namespace
+
+bool rtapi::guides_complete(const RtGuides *g) {
     return g && g->normal && g->position && g->albedo && g->footprint && g->obj_id;
 }
 
-} // namespace
+dim3 rtapi::pixel_grid(int width, int height) { return dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)); }
+
+rtapi::FilterStops rtapi::filter_stops(const RtDenoiseParams *d, int level) {
+    FilterStops st;
+    st.inv_sn2 = d->sigma_normal > 0.0 ? 1.0 / (d->sigma_normal * d->sigma_normal) : 0.0;
+    st.inv_sx = d->sigma_plane > 0.0 ? 1.0 / (d->sigma_plane * (double)(1 << level)) : 0.0;
+    const double sc = d->sigma_color > 0.0 ? ldexp(d->sigma_color, -level) : 0.0;
+    st.inv_sc2 = sc > 0.0 ? 1.0 / (sc * sc) : 0.0;
+    return st;
+}
 
 int rtapi::check_denoise(const RtRenderParams *p, const RtDenoiseParams *d) {
     if (!p || !d) return fail(RT_ERR_INVALID_ARGUMENT, "params/denoise is NULL");
@@ -231,9 +187,10 @@ int rtapi::check_denoise(const RtRenderParams *p, const RtDenoiseParams *d) {
     return RT_OK;
 }
 
-int rtapi::reserve_denoise(RtScene *s, size_t pixels, bool own_guides) {
+int rtapi::reserve_denoise(RtScene *s, size_t pixels, bool own_guides, bool variance_planes) {
     RenderBuffers &b = s->buf;
-    if (b.denoise_scratch.count < 6 * pixels) RT_HIP(b.denoise_scratch.alloc(6 * pixels));
+    const size_t scratch = (variance_planes ? 8 : 6) * pixels;
+    if (b.denoise_scratch.count < scratch) RT_HIP(b.denoise_scratch.alloc(scratch));
     if (own_guides) {
         if (b.guide_planes.count < 10 * pixels) RT_HIP(b.guide_planes.alloc(10 * pixels));
         if (b.guide_ids.count < pixels) RT_HIP(b.guide_ids.alloc(pixels));
@@ -283,6 +240,29 @@ int rtapi::enqueue_denoise(RtScene *s, const RtRenderParams *p, const RtDenoiseP
     return RT_OK;
 }
 
+int rtapi::enqueue_levels(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, double sigma_l, const double *radiance,
+                          const double *variance, const RtGuides &g, double *out, hipStream_t stream) {
+    const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
+    int rc = reserve_denoise(s, pixels, false, true);
+    if (rc != RT_OK) return rc;
+    const double *in = radiance, *var = variance;
+    double *ping = s->buf.denoise_scratch.ptr, *pong = ping + n;
+    double *var_next = ping + 2 * n, *var_other = var_next + pixels;
+    for (int i = 0; i < d->iterations; ++i) {
+        if (sigma_l > 0.0) {
+            RT_HIP(rtdev_launch_atrous_var(d, sigma_l, i, p->width, p->height, in, var, &g, ping, var_next, stream));
+            var = var_next;
+            std::swap(var_next, var_other);
+        } else { // rt_denoise_device's own levels
+            RT_HIP(rtdev_launch_denoise_step(d, i, p->width, p->height, in, &g, ping, stream));
+        }
+        in = ping;
+        std::swap(ping, pong);
+    }
+    RT_HIP(rtdev_launch_denoise_step(d, d->iterations, p->width, p->height, in, &g, out, stream)); // re-modulation
+    return RT_OK;
+}
+
 namespace {
 
 int render_guides_device(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtGuides *g, void *stream) {
@@ -290,7 +270,7 @@ int render_guides_device(RtScene *s, const RtCamera *camera, const RtRenderParam
     rt_denoise_params_default(&none);
     int rc = rtapi::check_denoise(p, &none);
     if (rc != RT_OK) return rc;
-    if (!guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
+    if (!rtapi::guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     if ((rc = rtapi::check_params(camera, p)) != RT_OK) return rc;
     RT_HIP(hipSetDevice(s->device));
@@ -303,7 +283,7 @@ int denoise_device(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d
     if (rc != RT_OK) return rc;
     if (!rgb || !out) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device/out_device is NULL");
     if (rgb == out) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device and out_device must differ");
-    if (!guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
+    if (!rtapi::guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     RT_HIP(hipSetDevice(s->device));
     if ((rc = rtapi::reserve_denoise(s, (size_t)p->width * (size_t)p->height, false)) != RT_OK) return rc;

@@ -223,9 +223,10 @@ struct RenderBuffers {
 extern "C" hipError_t rtdev_launch_guides(const rtdev::TraceArgs *args, const RtGuides *guides, hipStream_t stream);
 extern "C" hipError_t rtdev_launch_denoise_step(const RtDenoiseParams *d, int step, int width, int height, const double *in,
                                                 const RtGuides *guides, double *out, hipStream_t stream);
-// ... of rt_temporal.hip (compiled once, RT_ARITH_FAST): level `step` of the variance-guided filter (k_temporal_atrous) —
-// rtdev_launch_denoise_step's parameters, the luminance stop sigma_l > 0 and the variance planes beside the colour ones.
-// Linked inside the library only: rt_variance_filter.hip runs the same levels.
+// ... of rt_temporal.hip (compiled once, RT_ARITH_FAST): the launcher of level `step` of the variance-guided filter
+// (k_temporal_atrous) — rtdev_launch_denoise_step's parameters, the luminance stop sigma_l > 0 and the variance planes
+// beside the colour ones.  Linked inside the library only: rtapi::enqueue_levels (rt_denoise.hip) runs these levels for
+// rt_temporal.hip and rt_variance_filter.hip alike.
 extern "C" __attribute__((visibility("hidden"))) hipError_t rtdev_launch_atrous_var(
     const RtDenoiseParams *d, double sigma_l, int step, int width, int height, const double *in, const double *var,
     const RtGuides *guides, double *out, double *var_out, hipStream_t stream);
@@ -385,13 +386,32 @@ int begin_passes(RtScene *s, const RtCamera *camera, const RtRenderParams *p, hi
 int enqueue_chunks(RtScene *s, PoolPasses &pp, int c0, int c1, hipStream_t stream, const uint32_t *tile_list = nullptr,
                    uint32_t n_list = 0);
 // Denoising (rt_denoise.hip).  check_denoise: the filter's parameters (NULL, iterations, sigmas, _reserved) and a whole
-// frame's size (strips and scale > 1 refused).  reserve_denoise: the filter's scratch and, with `own_guides`, the scene's
-// guide planes for a W*H frame, before the first launch.  scene_guides: those planes as an RtGuides.  enqueue_guides /
-// enqueue_denoise: the guide launch and the filter's launches on `stream` (arguments checked by the caller).
+// frame's size (strips and scale > 1 refused).  reserve_denoise: the filter's scratch (with `variance_planes`, that of
+// enqueue_levels) and, with `own_guides`, the scene's guide planes for a W*H frame, before the first launch.
+// scene_guides: those planes as an RtGuides.  enqueue_guides / enqueue_denoise: the guide launch and the filter's
+// launches on `stream` (arguments checked by the caller).
 int check_denoise(const RtRenderParams *p, const RtDenoiseParams *d);
+// What the three filter units (rt_denoise.hip, rt_temporal.hip, rt_variance_filter.hip) share on the host.
+// guides_complete: no NULL among a caller's guide planes.  pixel_grid: 16x16 pixels per block of 256 lanes.
+// filter_stops: the inverse sigmas of a-trous level `level` (step 2^level) as the kernels take them, 0 where a stop is
+// off; level 0 is also the 7x7 variance windows' (step 1; they have no colour stop).
+bool guides_complete(const RtGuides *g);
+dim3 pixel_grid(int width, int height);
+struct FilterStops {
+    double inv_sn2; // 1 / sigma_n^2
+    double inv_sx;  // 1 / (sigma_x * 2^level)
+    double inv_sc2; // 1 / (sigma_c * 2^-level)^2
+};
+FilterStops filter_stops(const RtDenoiseParams *d, int level = 0);
+// The levels of a demodulated frame and its re-modulation into `out`: plain levels (rt_denoise_device's) with
+// sigma_l <= 0, else variance-guided ones over `variance` (W*H).  The scene's scratch holds two colour buffers and, behind
+// them, two variance planes (8 W*H doubles, reserved here); `variance` may be the SECOND of those planes — level 0 reads
+// it and writes the first, level 1 swaps them — or the caller's own.
+int enqueue_levels(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, double sigma_l, const double *radiance,
+                   const double *variance, const RtGuides &g, double *out, hipStream_t stream);
 // The trace kernels' argument block of a render (rt_api.hip: fill_args), for launches of other kernels that trace rays.
 int fill_trace_args(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, rtdev::TraceArgs &a);
-int reserve_denoise(RtScene *s, size_t pixels, bool own_guides);
+int reserve_denoise(RtScene *s, size_t pixels, bool own_guides, bool variance_planes = false);
 RtGuides scene_guides(RtScene *s, size_t pixels);
 int enqueue_guides(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtGuides &g, hipStream_t stream);
 int enqueue_denoise(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, const double *rgb, const RtGuides &g,

@@ -10,16 +10,18 @@
 //   a-trous     rt_denoise.hip's level with the factor exp(-|l_p - l_q| / (sigma_l sqrt(vbar_p) + 1e-10)); the variance is
 //               filtered alongside with the squared weights
 // With sigma_luminance <= 0 the levels are rt_denoise.hip's own launches, and the re-modulation always is.
+// The demodulation, the 7x7 window and the level are rt_filter_taps.h's demodulated, spatial_variance and
+// atrous_pixel<true>: the kernels here are its callers, as rt_denoise.hip's and rt_variance_filter.hip's are.
 //
 // Compiled once, with the fast arithmetic, as rt_denoise.hip.  Lane = pixel, 16x16 pixels per block, taps straight from
 // global memory.  The launchers have internal linkage, but for rtdev_launch_atrous_var (rt_scene.h), through which
-// rt_variance_filter.hip runs the same levels over a still frame's batch variance.
+// rtapi::enqueue_levels (rt_denoise.hip) runs the levels of a history here and of a still frame's batch variance.
 #include "rt_trace_common.h"
+#include "rt_filter_taps.h"
 #include "rt_scene.h"
 
 #include <cmath>
 #include <cstring>
-#include <utility>
 
 namespace RT_KNS {
 
@@ -35,7 +37,6 @@ struct AccumulateArgs {
 __device__ __forceinline__ d3 cross3(d3 a, d3 b) {
     return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
 }
-__device__ __forceinline__ double luminance(d3 c) { return 0.2126 * c.x + 0.7152 * c.y + 0.0722 * c.z; }
 
 // One pixel of the accumulation.  Whether a history tap exists is decided on doubles: no index is formed, and nothing
 // of the previous history is loaded, before the re-projected position is known to be finite and within one pixel of the
@@ -47,13 +48,8 @@ __global__ __launch_bounds__(256) void k_temporal_accumulate(const AccumulateArg
     if (px >= P.width || py >= P.height) return;
     const size_t p = (size_t)py * (size_t)P.width + (size_t)px;
 
-    // the demodulation of rt_denoise.hip (k_denoise_demod), operation for operation
-    double c[3];
-    for (int k = 0; k < 3; ++k) {
-        const double v = g[3 * p + k];
-        const double L = v * v;
-        c[k] = P.demodulate ? L / fmax(G.albedo[3 * p + k], 1e-3) : L;
-    }
+    double c[3]; // (k_denoise_demod's values)
+    for (int k = 0; k < 3; ++k) c[k] = demodulated(g[3 * p + k], G.albedo[3 * p + k], P.demodulate);
     const d3 cp = mk(c[0], c[1], c[2]);
     const double lp = luminance(cp);
     const int id = G.obj_id[p];
@@ -153,34 +149,7 @@ __global__ __launch_bounds__(256) void k_temporal_variance(const VarianceArgs P,
         var[p] = fmax(0.0, m2 - __dmul_rn(m1, m1)) / len; // the square rounded on its own: m2 == m1^2 gives exactly 0
         return;
     }
-    const d3 np = ld3(G.normal + 3 * p), xp = ld3(G.position + 3 * p);
-    const double inv_fx = P.inv_sx / G.footprint[p];
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int dy = -3; dy <= 3; ++dy) {
-        const int qy = py + dy;
-        if (qy < 0 || qy >= P.height) continue;
-        for (int dx = -3; dx <= 3; ++dx) {
-            const int qx = px + dx;
-            if (qx < 0 || qx >= P.width) continue;
-            const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
-            if (G.obj_id[q] != id) continue;
-            double w = 1.0;
-            if (P.inv_sn2 > 0.0) {
-                const d3 dn = np - ld3(G.normal + 3 * q);
-                w *= exp(-len2(dn) * P.inv_sn2);
-            }
-            if (P.inv_sx > 0.0) {
-                const double dist = dot(np, ld3(G.position + 3 * q) - xp) * inv_fx;
-                w *= exp(-(dist * dist));
-            }
-            const double lq = luminance(ld3(radiance + 3 * q));
-            s0 += w;
-            s1 += w * lq;
-            s2 += w * __dmul_rn(lq, lq);
-        }
-    }
-    const double mean = s1 / s0; // the centre tap weighs 1
-    var[p] = fmax(0.0, s2 / s0 - __dmul_rn(mean, mean)); // ... and a pixel alone in its window likewise
+    var[p] = spatial_variance(px, py, P.width, P.height, P.inv_sn2, P.inv_sx, radiance, G, p, id);
 }
 
 struct AtrousVarArgs {
@@ -189,79 +158,11 @@ struct AtrousVarArgs {
     double sigma_l;                  // > 0
 };
 
-// One variance-guided level: k_denoise_atrous's taps, weights and order with the luminance factor, the variance filtered
-// alongside with the squared weights.
+// One variance-guided level (rt_filter_taps.h: atrous_pixel).
 __global__ __launch_bounds__(256) void k_temporal_atrous(const AtrousVarArgs P, const double *__restrict__ I,
                                                          const double *__restrict__ var, const RtGuides G,
                                                          double *__restrict__ out, double *__restrict__ var_out) {
-    const int px = blockIdx.x * 16 + (threadIdx.x & 15);
-    const int py = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (px >= P.width || py >= P.height) return;
-    const size_t p = (size_t)py * (size_t)P.width + (size_t)px;
-    const d3 ip = ld3(I + 3 * p);
-    const int id = G.obj_id[p];
-    if (id < 0) { // a guide miss passes through
-        out[3 * p + 0] = ip.x;
-        out[3 * p + 1] = ip.y;
-        out[3 * p + 2] = ip.z;
-        var_out[p] = var[p];
-        return;
-    }
-    // vbar: the 3x3 Gaussian of the variance around the centre, at step 1, over the taps inside the image
-    double vs = 0.0, vw = 0.0;
-    for (int dy = -1; dy <= 1; ++dy) {
-        const int qy = py + dy;
-        if (qy < 0 || qy >= P.height) continue;
-        for (int dx = -1; dx <= 1; ++dx) {
-            const int qx = px + dx;
-            if (qx < 0 || qx >= P.width) continue;
-            const double k = (dx == 0 ? 0.5 : 0.25) * (dy == 0 ? 0.5 : 0.25); // 1/4, 1/8, 1/16
-            vs += k * var[(size_t)qy * (size_t)P.width + (size_t)qx];
-            vw += k;
-        }
-    }
-    const double inv_sl = 1.0 / (P.sigma_l * sqrt(vs / vw) + 1e-10);
-    const double lp = luminance(ip);
-
-    const double kh[5] = {1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0};
-    const d3 np = ld3(G.normal + 3 * p), xp = ld3(G.position + 3 * p);
-    const d3 sp = mk(sqrt(ip.x), sqrt(ip.y), sqrt(ip.z));
-    const double inv_fx = P.inv_sx / G.footprint[p];
-    d3 sum = mk(0.0, 0.0, 0.0);
-    double wsum = 0.0, vsum = 0.0;
-    for (int dy = -2; dy <= 2; ++dy) {
-        const int qy = py + dy * P.step;
-        if (qy < 0 || qy >= P.height) continue;
-        for (int dx = -2; dx <= 2; ++dx) {
-            const int qx = px + dx * P.step;
-            if (qx < 0 || qx >= P.width) continue;
-            const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
-            if (G.obj_id[q] != id) continue;
-            const d3 iq = ld3(I + 3 * q);
-            double w = kh[dx + 2] * kh[dy + 2];
-            if (P.inv_sn2 > 0.0) {
-                const d3 dn = np - ld3(G.normal + 3 * q);
-                w *= exp(-len2(dn) * P.inv_sn2);
-            }
-            if (P.inv_sx > 0.0) {
-                const double dist = dot(np, ld3(G.position + 3 * q) - xp) * inv_fx;
-                w *= exp(-(dist * dist));
-            }
-            if (P.inv_sc2 > 0.0) {
-                const d3 dc = sp - mk(sqrt(iq.x), sqrt(iq.y), sqrt(iq.z));
-                w *= exp(-len2(dc) * P.inv_sc2);
-            }
-            w *= exp(-fabs(lp - luminance(iq)) * inv_sl);
-            sum = sum + w * iq;
-            wsum += w;
-            vsum += (w * w) * var[q];
-        }
-    }
-    const double inv = 1.0 / wsum; // the centre tap alone weighs 9/64
-    out[3 * p + 0] = sum.x * inv;
-    out[3 * p + 1] = sum.y * inv;
-    out[3 * p + 2] = sum.z * inv;
-    var_out[p] = vsum * (inv * inv);
+    atrous_pixel<true>(P.width, P.height, P.step, P.inv_sn2, P.inv_sx, P.inv_sc2, P.sigma_l, I, var, G, out, var_out);
 }
 
 } // namespace RT_KNS
@@ -282,7 +183,8 @@ struct RtTemporal {
 
 namespace {
 
-dim3 pixel_grid(int width, int height) { return dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)); }
+using rtapi::guides_complete;
+using rtapi::pixel_grid;
 
 hipError_t launch_accumulate(const RtRenderParams *p, const RtTemporalParams *t, int demodulate, const double *rgb,
                              const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out,
@@ -311,30 +213,10 @@ hipError_t launch_accumulate(const RtRenderParams *p, const RtTemporalParams *t,
 
 hipError_t launch_variance(const RtRenderParams *p, const RtDenoiseParams *d, const RtHistory *h, const RtGuides *g, double *var,
                            hipStream_t stream) {
-    RT_KNS::VarianceArgs a;
-    a.width = p->width;
-    a.height = p->height;
-    a.inv_sn2 = d->sigma_normal > 0.0 ? 1.0 / (d->sigma_normal * d->sigma_normal) : 0.0;
-    a.inv_sx = d->sigma_plane > 0.0 ? 1.0 / d->sigma_plane : 0.0;
+    const rtapi::FilterStops st = rtapi::filter_stops(d);
+    const RT_KNS::VarianceArgs a = {p->width, p->height, st.inv_sn2, st.inv_sx};
     hipLaunchKernelGGL(RT_KNS::k_temporal_variance, pixel_grid(p->width, p->height), dim3(256), 0, stream, a, h->radiance,
                        h->moments, h->length, *g, var);
-    return hipGetLastError();
-}
-
-// level `step` of the variance-guided filter: the parameters of rtdev_launch_denoise_step (rt_denoise.hip) and sigma_l
-hipError_t launch_atrous_var(const RtRenderParams *p, const RtDenoiseParams *d, double sigma_l, int step, const double *in,
-                             const double *var, const RtGuides *g, double *out, double *var_out, hipStream_t stream) {
-    RT_KNS::AtrousVarArgs a;
-    a.width = p->width;
-    a.height = p->height;
-    a.step = 1 << step;
-    a.inv_sn2 = d->sigma_normal > 0.0 ? 1.0 / (d->sigma_normal * d->sigma_normal) : 0.0;
-    a.inv_sx = d->sigma_plane > 0.0 ? 1.0 / (d->sigma_plane * (double)a.step) : 0.0;
-    const double sc = d->sigma_color > 0.0 ? ldexp(d->sigma_color, -step) : 0.0;
-    a.inv_sc2 = sc > 0.0 ? 1.0 / (sc * sc) : 0.0;
-    a.sigma_l = sigma_l;
-    hipLaunchKernelGGL(RT_KNS::k_temporal_atrous, pixel_grid(p->width, p->height), dim3(256), 0, stream, a, in, var, *g, out,
-                       var_out);
     return hipGetLastError();
 }
 
@@ -342,7 +224,6 @@ hipError_t launch_atrous_var(const RtRenderParams *p, const RtDenoiseParams *d, 
 constexpr double kAlpha = 0.2, kMaxHistory = 32.0;
 constexpr double kNormalTolerance = 0.25, kPlaneTolerance = 2.0, kSigmaLuminance = 4.0;
 
-bool guides_complete(const RtGuides *g) { return g && g->normal && g->position && g->albedo && g->footprint && g->obj_id; }
 bool history_complete(const RtHistory *h) {
     return h && h->radiance && h->moments && h->length && h->normal && h->position && h->obj_id;
 }
@@ -366,32 +247,19 @@ int enqueue_accumulate(const RtRenderParams *p, const RtTemporalParams *t, const
     return RT_OK;
 }
 
-// the filter of a history into `out`; the scene's scratch holds two colour buffers and, behind them, two variance planes
+// the filter of a history into `out`: its variance, where levels will use one, into the second variance plane of the
+// scene's scratch (rt_scene.h: enqueue_levels)
 int enqueue_denoise_history(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, const RtTemporalParams *t,
                             const RtHistory *h, const RtGuides *g, double *out, hipStream_t stream) {
-    const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
-    rtapi::RenderBuffers &b = s->buf;
-    if (b.denoise_scratch.count < 8 * pixels) RT_HIP(b.denoise_scratch.alloc(8 * pixels));
-    const double *in = h->radiance;
-    double *ping = b.denoise_scratch.ptr, *pong = ping + n;
+    const size_t pixels = (size_t)p->width * (size_t)p->height;
+    double *var = nullptr;
     if (t->sigma_luminance > 0.0 && d->iterations > 0) {
-        double *var = ping + 2 * n, *var_next = var + pixels;
+        int rc = rtapi::reserve_denoise(s, pixels, false, true);
+        if (rc != RT_OK) return rc;
+        var = s->buf.denoise_scratch.ptr + 7 * pixels;
         RT_HIP(launch_variance(p, d, h, g, var, stream));
-        for (int i = 0; i < d->iterations; ++i) {
-            RT_HIP(launch_atrous_var(p, d, t->sigma_luminance, i, in, var, g, ping, var_next, stream));
-            in = ping;
-            std::swap(ping, pong);
-            std::swap(var, var_next);
-        }
-    } else {
-        for (int i = 0; i < d->iterations; ++i) { // rt_denoise_device's own levels
-            RT_HIP(rtdev_launch_denoise_step(d, i, p->width, p->height, in, g, ping, stream));
-            in = ping;
-            std::swap(ping, pong);
-        }
     }
-    RT_HIP(rtdev_launch_denoise_step(d, d->iterations, p->width, p->height, in, g, out, stream)); // re-modulation
-    return RT_OK;
+    return rtapi::enqueue_levels(s, p, d, var ? t->sigma_luminance : 0.0, h->radiance, var, *g, out, stream);
 }
 
 int accumulate_device(RtScene *s, const RtRenderParams *p, const RtTemporalParams *t, const RtDenoiseParams *d, const double *rgb,
@@ -530,11 +398,11 @@ int render_temporal(RtScene *s, RtTemporal *t, const RtCamera *camera, const RtR
 extern "C" hipError_t rtdev_launch_atrous_var(const RtDenoiseParams *d, double sigma_l, int step, int width, int height,
                                               const double *in, const double *var, const RtGuides *guides, double *out,
                                               double *var_out, hipStream_t stream) {
-    RtRenderParams p;
-    memset(&p, 0, sizeof p);
-    p.width = width;
-    p.height = height;
-    return launch_atrous_var(&p, d, sigma_l, step, in, var, guides, out, var_out, stream);
+    const rtapi::FilterStops st = rtapi::filter_stops(d, step);
+    const RT_KNS::AtrousVarArgs a = {width, height, 1 << step, st.inv_sn2, st.inv_sx, st.inv_sc2, sigma_l};
+    hipLaunchKernelGGL(RT_KNS::k_temporal_atrous, rtapi::pixel_grid(width, height), dim3(256), 0, stream, a, in, var, *guides, out,
+                       var_out);
+    return hipGetLastError();
 }
 
 extern "C" {

@@ -8,19 +8,20 @@
 //   batch variance  m = S / s; sigma = sqrt(max(0, Q - S m) / (k - 1) / s); C = m / a, sigma' = sigma / a with
 //                   a = max(albedo, 1e-3) (or 1); var = (0.2126 sigma'_r + 0.7152 sigma'_g + 0.0722 sigma'_b)^2 where
 //                   k >= min_chunks, 0 on a guide miss, else WAITING
-//   spatial         a waiting pixel takes k_temporal_variance's neighbourhood estimate over C: the 7x7 window (dy, then dx)
-//   levels          rtdev_launch_atrous_var (rt_temporal.hip: k_temporal_atrous) and the re-modulation of
-//                   rtdev_launch_denoise_step (rt_denoise.hip), both unchanged
+//   spatial         a waiting pixel takes k_temporal_variance's neighbourhood estimate over C: the 7x7 window (dy, then dx),
+//                   rt_filter_taps.h's spatial_variance for both
+//   levels          rtapi::enqueue_levels (rt_denoise.hip), as rt_denoise_history_device: k_temporal_atrous's levels and
+//                   the re-modulation of rtdev_launch_denoise_step
 //
 // Compiled once, with the fast arithmetic, as rt_denoise.hip and rt_temporal.hip.  Lane = pixel, 16x16 pixels per block,
 // taps straight from global memory.
 #include "rt_trace_common.h"
+#include "rt_filter_taps.h"
 #include "rt_scene.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <utility>
 #include <vector>
 
 namespace RT_KNS {
@@ -49,7 +50,6 @@ __global__ __launch_bounds__(256) void k_batch_variance(const BatchVarianceArgs 
     const int k = chunks[p];
     const bool batch = k >= P.min_chunks;
     const double batches = (double)(k - 1);
-    const double luma[3] = {0.2126, 0.7152, 0.0722};
     double sl = 0.0;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_batch_variance(const BatchVarianceArgs 
         C[3 * p + c] = m / a;
         if (batch) {
             const double sigma = sqrt(fmax(0.0, Q[3 * p + c] - __dmul_rn(Sc, m)) / batches / s);
-            sl += luma[c] * (sigma / a);
+            sl += luminance_weight(c) * (sigma / a);
         }
     }
     var[p] = G.obj_id[p] < 0 ? 0.0 : batch ? __dmul_rn(sl, sl) : kWaiting;
@@ -71,8 +71,8 @@ struct SpatialArgs {
     double inv_sx;  // 1 / sigma_x (step 1), or 0: the plane stop is off
 };
 
-// The waiting pixels: the second branch of k_temporal_variance (rt_temporal.hip) over C, operation for operation.  A
-// pixel reads var at its own place only, so the pass needs no second plane.
+// The waiting pixels: the 7x7 estimate of k_temporal_variance's short histories (rt_filter_taps.h: spatial_variance) over
+// C.  A pixel reads var at its own place only, so the pass needs no second plane.
 __global__ __launch_bounds__(256) void k_batch_variance_spatial(const SpatialArgs P, const double *__restrict__ C,
                                                                 const RtGuides G, double *var) {
     const int px = blockIdx.x * 16 + (threadIdx.x & 15);
@@ -81,35 +81,7 @@ __global__ __launch_bounds__(256) void k_batch_variance_spatial(const SpatialArg
     const size_t p = (size_t)py * (size_t)P.width + (size_t)px;
     if (!(var[p] < 0.0)) return;
     const int id = G.obj_id[p]; // (>= 0: a miss never waits)
-    const d3 np = ld3(G.normal + 3 * p), xp = ld3(G.position + 3 * p);
-    const double inv_fx = P.inv_sx / G.footprint[p];
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int dy = -3; dy <= 3; ++dy) {
-        const int qy = py + dy;
-        if (qy < 0 || qy >= P.height) continue;
-        for (int dx = -3; dx <= 3; ++dx) {
-            const int qx = px + dx;
-            if (qx < 0 || qx >= P.width) continue;
-            const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
-            if (G.obj_id[q] != id) continue;
-            double w = 1.0;
-            if (P.inv_sn2 > 0.0) {
-                const d3 dn = np - ld3(G.normal + 3 * q);
-                w *= exp(-len2(dn) * P.inv_sn2);
-            }
-            if (P.inv_sx > 0.0) {
-                const double dist = dot(np, ld3(G.position + 3 * q) - xp) * inv_fx;
-                w *= exp(-(dist * dist));
-            }
-            const d3 cq = ld3(C + 3 * q);
-            const double lq = 0.2126 * cq.x + 0.7152 * cq.y + 0.0722 * cq.z;
-            s0 += w;
-            s1 += w * lq;
-            s2 += w * __dmul_rn(lq, lq);
-        }
-    }
-    const double mean = s1 / s0; // the centre tap weighs 1
-    var[p] = fmax(0.0, s2 / s0 - __dmul_rn(mean, mean));
+    var[p] = spatial_variance(px, py, P.width, P.height, P.inv_sn2, P.inv_sx, C, G, p, id);
 }
 
 } // namespace RT_KNS
@@ -123,9 +95,8 @@ namespace {
 constexpr double kSigmaLuminance = 4.0;
 constexpr int kMinChunks = 4;
 
-dim3 pixel_grid(int width, int height) { return dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)); }
-
-bool guides_complete(const RtGuides *g) { return g && g->normal && g->position && g->albedo && g->footprint && g->obj_id; }
+using rtapi::guides_complete;
+using rtapi::pixel_grid;
 
 int check_filter(const RtVarianceFilterParams *f) {
     if (!f) return fail(RT_ERR_INVALID_ARGUMENT, "filter is NULL");
@@ -146,45 +117,11 @@ int enqueue_batch_variance(const RtRenderParams *p, const RtDenoiseParams *d, co
     hipLaunchKernelGGL(RT_KNS::k_batch_variance, pixel_grid(p->width, p->height), dim3(256), 0, stream, a, b->sums, b->squares,
                        b->samples, b->chunks, *g, radiance, var);
     RT_HIP(hipGetLastError());
-    RT_KNS::SpatialArgs sa;
-    sa.width = p->width;
-    sa.height = p->height;
-    sa.inv_sn2 = d->sigma_normal > 0.0 ? 1.0 / (d->sigma_normal * d->sigma_normal) : 0.0;
-    sa.inv_sx = d->sigma_plane > 0.0 ? 1.0 / d->sigma_plane : 0.0;
+    const rtapi::FilterStops st = rtapi::filter_stops(d);
+    const RT_KNS::SpatialArgs sa = {p->width, p->height, st.inv_sn2, st.inv_sx};
     hipLaunchKernelGGL(RT_KNS::k_batch_variance_spatial, pixel_grid(p->width, p->height), dim3(256), 0, stream, sa,
                        (const double *)radiance, *g, var);
     RT_HIP(hipGetLastError());
-    return RT_OK;
-}
-
-// the levels over (radiance, var) into `out`; the scene's scratch holds two colour buffers and, behind them, two variance
-// planes, as for rt_denoise_history_device
-int enqueue_denoise_variance(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d, const RtVarianceFilterParams *f,
-                             const double *radiance, const double *variance, const RtGuides *g, double *out,
-                             hipStream_t stream) {
-    const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
-    rtapi::RenderBuffers &b = s->buf;
-    if (b.denoise_scratch.count < 8 * pixels) RT_HIP(b.denoise_scratch.alloc(8 * pixels));
-    const double *in = radiance;
-    double *ping = b.denoise_scratch.ptr, *pong = ping + n;
-    if (f->sigma_luminance > 0.0) {
-        const double *var = variance;
-        double *var_next = ping + 2 * n, *var_other = var_next + pixels;
-        for (int i = 0; i < d->iterations; ++i) {
-            RT_HIP(rtdev_launch_atrous_var(d, f->sigma_luminance, i, p->width, p->height, in, var, g, ping, var_next, stream));
-            in = ping;
-            var = var_next;
-            std::swap(ping, pong);
-            std::swap(var_next, var_other);
-        }
-    } else {
-        for (int i = 0; i < d->iterations; ++i) { // rt_denoise_device's own levels
-            RT_HIP(rtdev_launch_denoise_step(d, i, p->width, p->height, in, g, ping, stream));
-            in = ping;
-            std::swap(ping, pong);
-        }
-    }
-    RT_HIP(rtdev_launch_denoise_step(d, d->iterations, p->width, p->height, in, g, out, stream)); // re-modulation
     return RT_OK;
 }
 
@@ -213,7 +150,7 @@ int denoise_variance_device(RtScene *s, const RtRenderParams *p, const RtDenoise
     if (out == radiance) return fail(RT_ERR_INVALID_ARGUMENT, "out_device and radiance_device must differ");
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     RT_HIP(hipSetDevice(s->device));
-    return enqueue_denoise_variance(s, p, d, f, radiance, var, g, out, (hipStream_t)stream);
+    return rtapi::enqueue_levels(s, p, d, f->sigma_luminance, radiance, var, *g, out, (hipStream_t)stream);
 }
 
 // the caller's cancel hook, remembering whether it was ever raised: a cancelled adaptive call returns RT_OK
@@ -275,7 +212,7 @@ int render_adaptive_filtered(RtScene *s, const RtCamera *camera, const RtRenderP
     if ((rc = rtapi::enqueue_guides(s, camera, p, g, stream)) != RT_OK) return rc;
     const RtBatchPlanes planes = {b.accum.ptr, b.squares.ptr, b.batch_counts.ptr, b.batch_counts.ptr + pixels};
     if ((rc = enqueue_batch_variance(p, d, f, &planes, &g, radiance, var, stream)) != RT_OK) return rc;
-    if ((rc = enqueue_denoise_variance(s, p, d, f, radiance, var, &g, filtered, stream)) != RT_OK) return rc;
+    if ((rc = rtapi::enqueue_levels(s, p, d, f->sigma_luminance, radiance, var, g, filtered, stream)) != RT_OK) return rc;
     if (outputs && outputs->raw_rgb) memcpy(outputs->raw_rgb, out_rgb, n * sizeof(double));
     RT_HIP(hipMemcpyAsync(out_rgb, filtered, n * sizeof(double), hipMemcpyDeviceToHost, stream));
     if (outputs && outputs->sums) RT_HIP(hipMemcpyAsync(outputs->sums, b.accum.ptr, n * sizeof(double), hipMemcpyDeviceToHost, stream));
