@@ -16,7 +16,7 @@
 // Compiled once, with the fast arithmetic (RT_ARITH_FAST's hit functions of rt_trace_common.h).  The filter reads its taps
 // straight from global memory: the planes of a 1080p frame (~130 MB for the guides, 50 MB per colour buffer) are served by
 // L2 and the Infinity Cache, and the measured cost is in DESIGN.md.
-#include "rt_trace_common.h"
+#include "rt_path_steps.h"
 #include "rt_filter_taps.h"
 #include "rt_scene.h"
 
@@ -36,31 +36,18 @@ __global__ __launch_bounds__(256) void k_guides_f64(const TraceArgs A, const RtG
     if (px >= A.width || py >= A.height) return;
     const size_t pix = (size_t)py * (size_t)A.width + (size_t)px;
 
-    // camera.rs:326-337 with the lens offset at zero, through the pixel's centre, at the middle of the shutter interval
+    // primary_ray's camera (rt_path_steps.h) with the lens offset at zero, through the pixel's centre, at the middle of the
+    // shutter interval: a ray of its own, without a draw
     const double u = ((double)px + 0.5) / (double)(A.width - 1);
     const double v = ((double)py + 0.5) / (double)(A.height - 1);
     const d3 o = ld3(A.cam.origin);
     const d3 d = ld3(A.cam.ulc) + u * ld3(A.cam.horizontal) - v * ld3(A.cam.vertical) - o;
     const double time = (A.cam.time_a + A.cam.time_b) * 0.5;
 
-    // closest hit over [0.001, inf) (renderer.rs:58), the render's own rule
-    double best_t = __builtin_inf();
-    int best = -1, best_aux = 0;
-    const d3 inv_d = rcp3(d);
-    const double inv_a = rcp_f64(len2(d));
-    if (BVH) {
-        closest_hit_bvh<PRIMS_ANY>(A, bvh_nodes_for(A, d), o, d, inv_d, inv_a, time, 0.001, best_t, best, best_aux);
-    } else {
-        for (int i = 0; i < A.n_prims; ++i) {
-            double t;
-            int aux;
-            if (prim_t<PRIMS_ANY>(load_prim_uniform(A.prims, i), o, d, inv_d, inv_a, time, 0.001, best_t, t, aux)) {
-                best_t = t;
-                best = i;
-                best_aux = aux;
-            }
-        }
-    }
+    // the render's own closest-hit rule
+    double best_t;
+    int best, best_aux;
+    closest_hit<PRIMS_ANY, BVH>(A, o, d, time, best_t, best, best_aux);
 
     d3 n = mk(0.0, 0.0, 0.0), x = n, albedo = mk(1.0, 1.0, 1.0);
     double footprint = __builtin_inf();

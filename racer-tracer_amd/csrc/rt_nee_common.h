@@ -6,7 +6,7 @@
 // code — the pick, the sample, the pdf of a bounce direction — is a policy: PlainLights below, the list rt_scene_create
 // makes, and ExtendedLights (rt_nee_lights.h), the list of rt_scene_set_lights.
 #pragma once
-#include "rt_trace_common.h"
+#include "rt_path_steps.h"
 
 namespace RT_KNS {
 
@@ -133,28 +133,10 @@ __device__ __forceinline__ void nee_samples(const TraceArgs &A, const NeeArgs &N
     while (s < s_end) {
         if (!alive) {
             ++n_started;
-            // cpu.rs:39-40 + camera.rs:326-337
-            rng.sample = (uint32_t)s;
-            const u4 bc = rng.block(0, RT_RNG_CAMERA, 0);
-            const double v = ((double)py + u53(bc.a, bc.b)) / (double)(A.height - 1);
-            d3 offset = mk(0.0, 0.0, 0.0);
-            if (A.cam.lens_radius != 0.0) {
-                double rx, ry;
-                for (uint32_t i = 0;; ++i) { // util.rs:25-39
-                    const u4 b = rng.block(0, RT_RNG_LENS, i);
-                    rx = sym53(b.a, b.b);
-                    ry = sym53(b.c, b.d);
-                    if (rx * rx + ry * ry >= 1.0) continue;
-                    break;
-                }
-                rx *= A.cam.lens_radius;
-                ry *= A.cam.lens_radius;
-                offset = ld3(A.cam.right) * rx + ld3(A.cam.up) * ry;
-            }
-            const d3 co = ld3(A.cam.origin);
-            o = co + offset;
-            d = ld3(A.cam.ulc) + u * ld3(A.cam.horizontal) - v * ld3(A.cam.vertical) - co - offset;
-            ray_time = A.cam.time_a + (A.cam.time_b - A.cam.time_a) * u53(bc.c, bc.d); // camera.rs:335
+            const PrimaryRay r = primary_ray(A, rng, s, py, u);
+            o = r.o;
+            d = r.d;
+            ray_time = r.time;
             T = mk(1.0, 1.0, 1.0);
             acc = mk(0.0, 0.0, 0.0);
             seg = 0;
@@ -169,7 +151,9 @@ __device__ __forceinline__ void nee_samples(const TraceArgs &A, const NeeArgs &N
             ended = true;
         } else {
             if (!shadow) ++n_segments;
-            // THE closest-hit site, t in [0.001, inf) (renderer.rs:58): a path segment or a shadow ray
+            // THE closest-hit site, t in [0.001, inf) (renderer.rs:58): a path segment or a shadow ray.  rt_path_steps.h's
+            // closest_hit, written out: as a call the linear loop is optimised on its own first and the register counts move
+            // by two, which takes exact <PRIMS_RECTS, plain, SPECULAR> out of the pair tests/test_nee_stream_isa.py pins.
             double best_t = __builtin_inf();
             int best = -1, best_aux = 0;
             const d3 inv_d = rcp3(d);
@@ -195,13 +179,8 @@ __device__ __forceinline__ void nee_samples(const TraceArgs &A, const NeeArgs &N
                 }
                 shadow = false;
                 d = bounce; // the path goes on from the same vertex
-            } else if (best < 0) { // background_color.rs:27-33 / :45-48
-                d3 bgc = ld3(A.bg.top);
-                if (A.bg.kind == RT_BG_SKY) {
-                    const double t = 0.5 * (unit_fast(d).y + 1.0);
-                    bgc = (1.0 - t) * ld3(A.bg.top) + t * ld3(A.bg.bottom);
-                }
-                contrib = T * bgc;
+            } else if (best < 0) {
+                contrib = T * background_colour(A, d);
                 ended = true;
             } else {
                 const Prim &P = A.prims[best];
@@ -247,55 +226,20 @@ __device__ __forceinline__ void nee_samples(const TraceArgs &A, const NeeArgs &N
                             shadow = true;
                         }
                     }
-                } else if (SPECULAR && M.kind == RT_MAT_METAL) { // metal.rs:26-43
+                } else if (SPECULAR && M.kind == RT_MAT_METAL) {
                     eligible = false;
-                    const d3 ud = unit_fast(d);
-                    d3 dir = ud - (2.0 * dot(ud, h.normal)) * h.normal;
-                    if (M.fuzz != 0.0) dir = dir + M.fuzz * random_in_unit_sphere(rng, seg);
-                    if (dot(dir, h.normal) < 0.0) {
+                    const d3 dir = metal_scatter(M, h, d, rng, seg);
+                    if (dot(dir, h.normal) < 0.0) { // absorbed
                         ended = true;
                     } else {
                         T = T * texture_value<TEXTURED>(A, nullptr, A.textures, M, h.u, h.v, h.point);
                         o = h.point;
                         d = dir;
                     }
-                } else if (SPECULAR) { // dialectric.rs:25-55
+                } else if (SPECULAR) {
                     eligible = false;
-                    const double ratio = h.front ? 1.0 / M.ior : M.ior;
-                    const d3 ud = unit_fast(d);
-                    const double cos_theta = fmin(dot(-ud, h.normal), 1.0);
-                    const double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
-                    bool reflect_it = ratio * sin_theta > 1.0;
-#ifdef RT_EXACT_DIV
-                    // RT_ARITH_REFERENCE forms the Fresnel term on every lane, not under `if (!reflect_it)` (the draw is
-                    // addressed, so an unused one changes nothing).  With the nested branch the compiler's code for the
-                    // <PRIMS_RECTS, plain, SPECULAR> kernels lost `o = h.point` on the lanes that reflect by the draw:
-                    // LABNOTES 10 has the instructions; tests/test_gpu_nee.py holds every variant to the oracle.
-                    const bool total_reflection = reflect_it;
-                    {
-#else
-                    if (!reflect_it) { // the draw happens only when refraction is possible
-#endif
-                        double r0 = (1.0 - ratio) / (1.0 + ratio);
-                        r0 = r0 * r0;
-                        const double m = 1.0 - cos_theta;
-                        const double m2 = m * m;
-                        const double refl = r0 + (1.0 - r0) * (m2 * m2 * m);
-                        const u4 b = rng.block(seg, RT_RNG_DIELECTRIC, 0);
-                        reflect_it = refl > u53(b.a, b.b);
-                    }
-#ifdef RT_EXACT_DIV
-                    reflect_it = reflect_it || total_reflection;
-#endif
-                    d3 dir;
-                    if (reflect_it) {
-                        dir = ud - (2.0 * dot(ud, h.normal)) * h.normal;
-                    } else { // vec3.rs:416-422
-                        const d3 perp = ratio * (ud + cos_theta * h.normal);
-                        dir = perp + (-sqrt(fabs(1.0 - len2(perp)))) * h.normal;
-                    }
+                    d = dielectric_scatter(M, h, d, rng, seg);
                     o = h.point;
-                    d = dir;
                 } else { // unreachable: the host picks SPECULAR whenever such a material exists
                     ended = true;
                 }

@@ -15,13 +15,9 @@ __device__ __forceinline__ void nee_frame(const TraceArgs &A, const NeeArgs &N, 
     const int by = blockIdx.x / tiles_x;
     const int px = bx * 16 + (wave & 1) * 8 + (lane & 7);
     const int vrow = by * 16 + (wave >> 1) * 8 + (lane >> 3); // a row of the launch's owned-row grid
-    int py = vrow;
-    { // owned row -> image row, once: the draws and the sums below are the IMAGE pixel's.  The strip fields are read through
-      // kernargs_here(), next to their one use, so that a launch without strips keeps no register for them.
-        const RT_CONSTANT TraceArgs *K = kernargs_here();
-        if (K->strip_count > 1)
-            py = ((vrow / K->strip_rows) * K->strip_count + K->strip_index) * K->strip_rows + vrow % K->strip_rows;
-    }
+    // owned row -> image row, once: the draws and the sums below are the IMAGE pixel's.  The strip fields are read through
+    // kernargs_here(), next to their one use, so that a launch without strips keeps no register for them.
+    const int py = image_row(kernargs_here(), vrow);
     // (an owned row at or beyond owned_rows lies in a strip that starts below the image: its image row is >= height)
     const bool in_image = px < A.width && py < A.height;
 
@@ -30,10 +26,7 @@ __device__ __forceinline__ void nee_frame(const TraceArgs &A, const NeeArgs &N, 
     rng.k0 = A.seed_lo;
     rng.k1 = A.seed_hi;
 
-    // cpu.rs:35-36: one horizontal jitter per pixel
-    rng.sample = RT_RNG_SAMPLE_PIXEL;
-    const u4 bj = rng.block(0, RT_RNG_PIXEL, 0);
-    const double u = ((double)px + u53(bj.a, bj.b)) / (double)(A.width - 1);
+    const double u = pixel_jitter(rng, px, A.width);
 
     d3 sum = mk(0.0, 0.0, 0.0); // the pixel's sum
     unsigned int n_segments = 0, n_started = 0;
@@ -46,15 +39,8 @@ __device__ __forceinline__ void nee_frame(const TraceArgs &A, const NeeArgs &N, 
         px_out[1] = sum.y;
         px_out[2] = sum.z;
     }
-    // one atomic per wave for each statistic: path segments (shadow rays excluded) and primary rays
-    unsigned long long total = n_segments;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
-    if (lane == 0 && total) atomicAdd(A.segments + RT_STAT_SEGMENTS, total);
-    unsigned long long started = n_started;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) started += __shfl_down(started, off, 64);
-    if (lane == 0 && started) atomicAdd(A.segments + RT_STAT_SAMPLES, started);
+    wave_stat_add(A, lane, RT_STAT_SEGMENTS, n_segments); // path segments (shadow rays excluded)
+    wave_stat_add(A, lane, RT_STAT_SAMPLES, n_started);   // primary rays
 }
 
 } // namespace RT_KNS

@@ -29,10 +29,8 @@ template <int PRIMS, bool TEXTURED, bool SPECULAR, bool BVH> struct NeeLightsVar
 extern "C" hipError_t RT_LAUNCHER(rtdev_launch_nee_lights)(const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee,
                                                            const rtdev::NeeLightArgs *lights, int textured, int specular, int bvh,
                                                            hipStream_t stream) {
-    const int tiles_x = (args->width + 15) / 16;
-    const int tiles_y = (args->owned_rows + 15) / 16; // the grid covers width x owned_rows
-    if (tiles_x <= 0 || tiles_y <= 0) return hipSuccess;
-    const unsigned blocks = (unsigned)(tiles_x * tiles_y);
+    const unsigned blocks = rtdev::frame_blocks(*args);
+    if (blocks == 0) return hipSuccess;
     rtdev::dispatch_any_variant<NeeLightsVariant>(textured != 0, specular != 0, bvh != 0, [&](auto v) {
         decltype(v)::launch(*args, *nee, *lights, blocks, stream);
     });

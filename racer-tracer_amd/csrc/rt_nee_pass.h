@@ -29,7 +29,9 @@ __device__ __forceinline__ void nee_pass(const TraceArgs &A, const NeeArgs &N, c
     rng.k0 = A.seed_lo;
     rng.k1 = A.seed_hi;
 
-    // cpu.rs:35-36: one horizontal jitter per pixel
+    // cpu.rs:35-36: one horizontal jitter per pixel.  rt_path_steps.h's pixel_jitter, written out: as a call it changes nothing
+    // but the numbering of scalar registers, and rt_render_progressive_nee's kernel time rose by 0.4 to 0.5 % on the Cornell
+    // scenes with it, in every run (LABNOTES 16)
     rng.sample = RT_RNG_SAMPLE_PIXEL;
     const u4 bj = rng.block(0, RT_RNG_PIXEL, 0);
     const double u = ((double)px + u53(bj.a, bj.b)) / (double)(A.width - 1);
@@ -48,15 +50,8 @@ __device__ __forceinline__ void nee_pass(const TraceArgs &A, const NeeArgs &N, c
         px_sum[1] = sum.y;
         px_sum[2] = sum.z;
     }
-    // one atomic per wave for each statistic: path segments (shadow rays excluded) and primary rays
-    unsigned long long total = n_segments;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
-    if (lane == 0 && total) atomicAdd(A.segments + RT_STAT_SEGMENTS, total);
-    unsigned long long started = n_started;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) started += __shfl_down(started, off, 64);
-    if (lane == 0 && started) atomicAdd(A.segments + RT_STAT_SAMPLES, started);
+    wave_stat_add(A, lane, RT_STAT_SEGMENTS, n_segments); // path segments (shadow rays excluded)
+    wave_stat_add(A, lane, RT_STAT_SAMPLES, n_started);   // primary rays
 }
 
 } // namespace RT_KNS

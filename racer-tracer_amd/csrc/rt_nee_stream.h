@@ -171,10 +171,7 @@ __device__ __forceinline__ void nee_stream(const TraceArgs &A, const NeeArgs &N,
         rng.k0 = from_copy ? A.seed_lo : K->seed_lo;
         rng.k1 = from_copy ? A.seed_hi : K->seed_hi;
 
-        // cpu.rs:35-36: one horizontal jitter per pixel
-        rng.sample = RT_RNG_SAMPLE_PIXEL;
-        const u4 bj = rng.block(0, RT_RNG_PIXEL, 0);
-        const double u = ((double)px + u53(bj.a, bj.b)) / (double)(width - 1);
+        const double u = pixel_jitter(rng, px, width);
 
         d3 sum = mk(0.0, 0.0, 0.0); // the pixel's sum, carried from chunk to chunk
         unsigned int up = 0u;
@@ -189,15 +186,8 @@ __device__ __forceinline__ void nee_stream(const TraceArgs &A, const NeeArgs &N,
         }
         if (up == 0u) stream_deliver_tile(kernargs_here(), item, sum.x, sum.y, sum.z, N.inv_samples);
     }
-    // one atomic per wave for each statistic: path segments (shadow rays excluded) and primary rays
-    unsigned long long total = n_segments;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
-    if (lane == 0 && total) atomicAdd(A.segments + RT_STAT_SEGMENTS, total);
-    unsigned long long started = n_started;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) started += __shfl_down(started, off, 64);
-    if (lane == 0 && started) atomicAdd(A.segments + RT_STAT_SAMPLES, started);
+    wave_stat_add(A, lane, RT_STAT_SEGMENTS, n_segments); // path segments (shadow rays excluded)
+    wave_stat_add(A, lane, RT_STAT_SAMPLES, n_started);   // primary rays
 }
 
 } // namespace RT_KNS

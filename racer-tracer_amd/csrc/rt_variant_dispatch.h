@@ -34,4 +34,12 @@ auto dispatch_variant(int prims_class, bool textured, bool specular, bool bvh, F
     return dispatch_features<V, PRIMS_ANY, false>(textured, specular, f);
 }
 
+// Blocks of a launch that gives every 16x16 pixels of width x owned_rows (args.strip_*: the whole frame without strips) one
+// block of 256 threads, as k_trace_f64 and the whole-frame NEE kernels index them; 0: nothing to launch.
+inline unsigned frame_blocks(const TraceArgs &args) {
+    const int tiles_x = (args.width + 15) / 16;
+    const int tiles_y = (args.owned_rows + 15) / 16;
+    return tiles_x <= 0 || tiles_y <= 0 ? 0u : (unsigned)(tiles_x * tiles_y);
+}
+
 } // namespace rtdev
