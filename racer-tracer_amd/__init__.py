@@ -28,6 +28,15 @@ class RtError(RuntimeError):
 _lib = None
 
 
+def _open(path):
+    """The library at `path` with every prototype of abi.py attached, refused unless it is of the binding's ABI version."""
+    library = abi.bind(abi.bind(C.CDLL(path), abi.PROTOTYPES), abi.DEV_PROTOTYPES)
+    if library.rt_abi_version() != abi.ABI_VERSION:
+        raise ImportError("ABI version mismatch in %s: library %d, binding %d"
+                          % (path, library.rt_abi_version(), abi.ABI_VERSION))
+    return library
+
+
 def lib():
     """The loaded C-ABI library (raises if it has not been built)."""
     global _lib
@@ -44,10 +53,7 @@ def lib():
             import torch  # noqa: F401
         except ImportError:
             pass
-        _lib = abi.bind(abi.bind(C.CDLL(LIB_PATH), abi.PROTOTYPES), abi.DEV_PROTOTYPES)
-        if _lib.rt_abi_version() != abi.ABI_VERSION:
-            raise ImportError("ABI version mismatch: library %d, binding %d"
-                              % (_lib.rt_abi_version(), abi.ABI_VERSION))
+        _lib = _open(LIB_PATH)
     return _lib
 
 
@@ -55,10 +61,7 @@ def load_library(path):
     """Another build of the same ABI (e.g. build/libracer_tracer_amd_exact.so, the tests' exact-arithmetic
     build) next to the default one: pass the result as Scene(..., library=...)."""
     lib()  # the default library (and torch's HIP runtime) first
-    other = abi.bind(abi.bind(C.CDLL(path), abi.PROTOTYPES), abi.DEV_PROTOTYPES)
-    if other.rt_abi_version() != abi.ABI_VERSION:
-        raise ImportError("ABI version mismatch in %s" % path)
-    return other
+    return _open(path)
 
 
 def _strerror(code):
@@ -118,64 +121,117 @@ def nee_stream_chunk(arithmetic=abi.RT_ARITH_FAST):
     return lib().rtdev_nee_stream_chunk_exact() if arithmetic == abi.RT_ARITH_REFERENCE else lib().rtdev_nee_stream_chunk()
 
 
+def _params(struct, default, overrides):
+    """A parameter block: `struct` as the default library's function named `default` fills it, then the overrides."""
+    p = struct()
+    getattr(lib(), default)(C.byref(p))
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
 def denoise_params(**overrides):
     """rt_denoise_params_default, with fields overridden by keyword (iterations, flags, sigma_color, sigma_normal,
     sigma_plane) -> abi.RtDenoiseParams.  No device needed."""
-    dp = abi.RtDenoiseParams()
-    lib().rt_denoise_params_default(C.byref(dp))
-    for k, v in overrides.items():
-        setattr(dp, k, v)
-    return dp
+    return _params(abi.RtDenoiseParams, "rt_denoise_params_default", overrides)
 
 
 def adaptive_params(**overrides):
     """rt_adaptive_params_default, with fields overridden by keyword (threshold, pass_samples, min_samples)
     -> abi.RtAdaptiveParams.  No device needed."""
-    ap = abi.RtAdaptiveParams()
-    lib().rt_adaptive_params_default(C.byref(ap))
-    for k, v in overrides.items():
-        setattr(ap, k, v)
-    return ap
+    return _params(abi.RtAdaptiveParams, "rt_adaptive_params_default", overrides)
 
 
 def light_sampling_params(**overrides):
     """rt_light_sampling_params_default, with fields overridden by keyword (heuristic, max_lights)
     -> abi.RtLightSamplingParams.  No device needed."""
-    ls = abi.RtLightSamplingParams()
-    lib().rt_light_sampling_params_default(C.byref(ls))
-    for k, v in overrides.items():
-        setattr(ls, k, v)
-    return ls
+    return _params(abi.RtLightSamplingParams, "rt_light_sampling_params_default", overrides)
 
 
 def light_list_params(**overrides):
     """rt_light_list_params_default, with fields overridden by keyword (kinds, pick) -> abi.RtLightListParams.  No device
     needed."""
-    lp = abi.RtLightListParams()
-    lib().rt_light_list_params_default(C.byref(lp))
-    for k, v in overrides.items():
-        setattr(lp, k, v)
-    return lp
+    return _params(abi.RtLightListParams, "rt_light_list_params_default", overrides)
 
 
 def temporal_params(**overrides):
     """rt_temporal_params_default, with fields overridden by keyword (alpha, alpha_moments, max_history, normal_tolerance,
     plane_tolerance, sigma_luminance) -> abi.RtTemporalParams.  No device needed."""
-    tp = abi.RtTemporalParams()
-    lib().rt_temporal_params_default(C.byref(tp))
-    for k, v in overrides.items():
-        setattr(tp, k, v)
-    return tp
+    return _params(abi.RtTemporalParams, "rt_temporal_params_default", overrides)
 
 
 def variance_filter_params(**overrides):
     """rt_variance_filter_params_default, with fields overridden by keyword (sigma_luminance, min_chunks)
     -> abi.RtVarianceFilterParams.  No device needed."""
-    fp = abi.RtVarianceFilterParams()
-    lib().rt_variance_filter_params_default(C.byref(fp))
-    for k, v in overrides.items():
-        setattr(fp, k, v)
-    return fp
+    return _params(abi.RtVarianceFilterParams, "rt_variance_filter_params_default", overrides)
+
+
+def _or_default(block, default):
+    """A caller's parameter block, or (None) what `default`, one of the *_params functions above, returns."""
+    return block if block is not None else default()
+
+
+def _light_sampling(heuristic, max_lights):
+    return light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
+
+
+def _adaptive(threshold, pass_samples, min_samples):
+    return adaptive_params(**{k: v for k, v in (("threshold", threshold), ("pass_samples", pass_samples),
+                                                ("min_samples", min_samples)) if v is not None})
+
+
+def _adaptive_outputs(params):
+    """The host arrays an adaptive render fills: (frame [H, W, 3] f64, samples [H, W] int32, tile_error f64, one value
+    per 8x8 tile)."""
+    h, w = params.height, params.width
+    return (np.zeros((h, w, 3), dtype=np.float64), np.zeros((h, w), dtype=np.int32),
+            np.zeros(((h + 7) // 8, (w + 7) // 8), dtype=np.float64))
+
+
+# The three functions below return ctypes callback objects.  The C side keeps only the address, so the caller holds
+# what it got in a local until the C call has returned.
+
+def _cancel_hook(cancel):
+    """The RtCancelCallback of `cancel` (a callable returning True once the render should stop), or NULL for None."""
+    return abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+
+
+def _frame_collector(h, w, on_frame):
+    """(RtFrameCallback, frames): every pass appends (samples_done, a copy of its h x w frame) to `frames` and hands the
+    same two to `on_frame` (None: nobody)."""
+    frames = []
+
+    def on_pass(_user, rgb, samples_done, _samples_total):
+        arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()  # `rgb` is only valid during the callback
+        frames.append((samples_done, arr))
+        if on_frame is not None:
+            on_frame(samples_done, arr)
+
+    return abi.RtFrameCallback(on_pass), frames
+
+
+def _nee_tile_assembler(params, on_tile):
+    """(RtTileCallback, frame, order): every tile is copied into `frame` (float64 [H, W, 3], zero where none arrived),
+    appended to `order` as (r, c, width, height) and handed as those four to `on_tile` (None: nobody)."""
+    frame = np.zeros((params.height, params.width, 3), dtype=np.float64)
+    order = []
+
+    def on_update(_user, rgb, r, c, w, h):
+        if w > 0 and h > 0:  # `rgb` is only valid during the callback
+            frame[r:r + h, c:c + w] = np.ctypeslib.as_array(rgb, shape=(h, w, 3))
+        order.append((r, c, w, h))
+        if on_tile is not None:
+            on_tile(r, c, w, h)
+
+    return abi.RtTileCallback(on_update), frame, order
+
+
+def _tile_collector(tiles):
+    def on_tile(_user, rgb, r, c, w, h):
+        # `rgb` is only valid during the callback; an empty tile (more tile rows / columns than pixels) carries no pixels
+        arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy() if w > 0 and h > 0 else np.zeros((h, w, 3))
+        tiles.append((r, c, w, h, arr))
+    return on_tile
 
 
 def batch_planes_struct(planes):
@@ -200,87 +256,71 @@ def device_count():
     return lib().rt_device_count()
 
 
+def _handles(scenes):
+    """(library, RtScene handle array) of a multi-scene call.  The library is the one that made scenes[0]: a handle
+    means nothing to another loaded copy, and that copy's last-error text is not this call's.  (No scenes: the default
+    library refuses the call.)"""
+    return scenes[0]._lib if scenes else lib(), (C.c_void_p * len(scenes))(*[s._h for s in scenes])
+
+
 def render_frame_multi(scenes, camera, params, strip_rows=0):
     """rt_render_frame_multi: one frame over several Scene objects (one per device share)
     -> float64 [H, W, 3] on the host."""
+    library, handles = _handles(scenes)
     out = np.zeros((params.height, params.width, 3), dtype=np.float64)
-    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
-    check(lib().rt_render_frame_multi(handles, len(scenes), C.byref(camera), C.byref(params), strip_rows,
-                                      out.ctypes.data_as(C.POINTER(C.c_double))), "rt_render_frame_multi")
+    check(library.rt_render_frame_multi(handles, len(scenes), C.byref(camera), C.byref(params), strip_rows,
+                                        out.ctypes.data_as(C.POINTER(C.c_double))), "rt_render_frame_multi", library)
     return out
 
 
 def render_frame_multi_device(scenes, camera, params, out_ptr, strip_rows=0):
     """rt_render_frame_multi_device: out_ptr = device address (int) on scenes[0]'s device."""
-    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
-    check(lib().rt_render_frame_multi_device(handles, len(scenes), C.byref(camera), C.byref(params), strip_rows,
-                                             C.c_void_p(out_ptr)), "rt_render_frame_multi_device")
-
-
-def _tile_collector(tiles):
-    def on_tile(_user, rgb, r, c, w, h):
-        # `rgb` is only valid during the callback; an empty tile (more tile rows / columns than pixels) carries no pixels
-        arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy() if w > 0 and h > 0 else np.zeros((h, w, 3))
-        tiles.append((r, c, w, h, arr))
-    return on_tile
+    library, handles = _handles(scenes)
+    check(library.rt_render_frame_multi_device(handles, len(scenes), C.byref(camera), C.byref(params), strip_rows,
+                                               C.c_void_p(out_ptr)), "rt_render_frame_multi_device", library)
 
 
 def render_tiles_multi(scenes, camera, params, strip_rows=0, cancel=None):
     """rt_render_multi: the tile stream of one frame rendered by several Scene objects (one per device share)
     -> list of (r, c, width, height, float64 [height, width, 3]); cancel: None or a callable."""
+    library, handles = _handles(scenes)
     tiles = []
     cb = abi.RtTileCallback(_tile_collector(tiles))
-    hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
-    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
-    check(lib().rt_render_multi(handles, len(scenes), C.byref(camera), C.byref(params), strip_rows, cb, None, hook, None),
-          "rt_render_multi")
+    hook = _cancel_hook(cancel)
+    check(library.rt_render_multi(handles, len(scenes), C.byref(camera), C.byref(params), strip_rows, cb, None, hook, None),
+          "rt_render_multi", library)
     return tiles
-
-
-def _light_sampling(heuristic, max_lights):
-    return light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
 
 
 def render_frame_nee_multi(scenes, camera, params, strip_rows=0, heuristic=None, max_lights=None):
     """rt_render_frame_nee_multi: one next-event-estimation frame over several Scene objects (one per device share)
     -> float64 [H, W, 3] on the host, bit-identical to Scene.render_frame_nee's.  heuristic and max_lights as there."""
+    library, handles = _handles(scenes)
     ls = _light_sampling(heuristic, max_lights)
     out = np.zeros((params.height, params.width, 3), dtype=np.float64)
-    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
-    check(scenes[0]._lib.rt_render_frame_nee_multi(handles, len(scenes), C.byref(camera), C.byref(params), C.byref(ls), strip_rows,
-                                                   out.ctypes.data_as(C.POINTER(C.c_double))), "rt_render_frame_nee_multi",
-          scenes[0]._lib)
+    check(library.rt_render_frame_nee_multi(handles, len(scenes), C.byref(camera), C.byref(params), C.byref(ls), strip_rows,
+                                            out.ctypes.data_as(C.POINTER(C.c_double))), "rt_render_frame_nee_multi", library)
     return out
 
 
 def render_frame_nee_multi_device(scenes, camera, params, out_ptr, strip_rows=0, heuristic=None, max_lights=None):
     """rt_render_frame_nee_multi_device: out_ptr = device address (int) on scenes[0]'s device."""
+    library, handles = _handles(scenes)
     ls = _light_sampling(heuristic, max_lights)
-    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
-    check(scenes[0]._lib.rt_render_frame_nee_multi_device(handles, len(scenes), C.byref(camera), C.byref(params), C.byref(ls),
-                                                          strip_rows, C.c_void_p(out_ptr)),
-          "rt_render_frame_nee_multi_device", scenes[0]._lib)
+    check(library.rt_render_frame_nee_multi_device(handles, len(scenes), C.byref(camera), C.byref(params), C.byref(ls),
+                                                   strip_rows, C.c_void_p(out_ptr)),
+          "rt_render_frame_nee_multi_device", library)
 
 
 def render_tiles_nee_multi(scenes, camera, params, strip_rows=0, heuristic=None, max_lights=None, cancel=None, on_tile=None):
     """rt_render_nee_multi: Scene.render_tiles_nee over several Scene objects (one per device share) -> (frame float64
     [H, W, 3] assembled from the tiles that arrived (zero elsewhere), list of (r, c, width, height) in arrival order)."""
+    library, handles = _handles(scenes)
     ls = _light_sampling(heuristic, max_lights)
-    frame = np.zeros((params.height, params.width, 3), dtype=np.float64)
-    order = []
-
-    def on_update(_user, rgb, r, c, w, h):
-        if w > 0 and h > 0:  # `rgb` is only valid during the callback
-            frame[r:r + h, c:c + w] = np.ctypeslib.as_array(rgb, shape=(h, w, 3))
-        order.append((r, c, w, h))
-        if on_tile is not None:
-            on_tile(r, c, w, h)
-
-    cb = abi.RtTileCallback(on_update)
-    hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
-    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
-    check(scenes[0]._lib.rt_render_nee_multi(handles, len(scenes), C.byref(camera), C.byref(params), C.byref(ls), strip_rows, cb,
-                                             None, hook, None), "rt_render_nee_multi", scenes[0]._lib)
+    cb, frame, order = _nee_tile_assembler(params, on_tile)
+    hook = _cancel_hook(cancel)
+    check(library.rt_render_nee_multi(handles, len(scenes), C.byref(camera), C.byref(params), C.byref(ls), strip_rows, cb,
+                                      None, hook, None), "rt_render_nee_multi", library)
     return frame, order
 
 
@@ -322,7 +362,7 @@ class Scene:
     def render_frame_nee(self, camera, params, heuristic=None, max_lights=None):
         """rt_render_frame_nee -> float64 [H, W, 3], gamma-encoded, not tone-mapped.  heuristic (abi.RT_MIS_*) and
         max_lights: None keeps rt_light_sampling_params_default's value."""
-        ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
+        ls = _light_sampling(heuristic, max_lights)
         out = np.zeros((params.height, params.width, 3), dtype=np.float64)
         check(self._lib.rt_render_frame_nee(self._h, C.byref(camera), C.byref(params), C.byref(ls),
                                             out.ctypes.data_as(C.POINTER(C.c_double))), "rt_render_frame_nee", self._lib)
@@ -330,7 +370,7 @@ class Scene:
 
     def render_frame_nee_device(self, camera, params, out_ptr, stream=None, heuristic=None, max_lights=None):
         """rt_render_frame_nee_device: out_ptr = device address (int), stream = hipStream_t (int)."""
-        ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
+        ls = _light_sampling(heuristic, max_lights)
         check(self._lib.rt_render_frame_nee_device(self._h, C.byref(camera), C.byref(params), C.byref(ls), C.c_void_p(out_ptr),
                                                    C.c_void_p(stream or 0)), "rt_render_frame_nee_device", self._lib)
 
@@ -388,7 +428,7 @@ class Scene:
         tiles = []
         cb = abi.RtTileCallback(_tile_collector(tiles))
         if callable(cancel):
-            hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0)
+            hook = _cancel_hook(cancel)
             check(self._lib.rt_render_ex(self._h, C.byref(camera), C.byref(params), cb, None, hook, None), "rt_render_ex", self._lib)
         else:
             cancel_ptr = C.cast(cancel, C.POINTER(C.c_int)) if cancel is not None else None
@@ -401,17 +441,8 @@ class Scene:
         on_frame: None or a callable(samples_done, frame) run inside each callback, with the copy that is kept.
         denoise: None, True (the defaults) or an abi.RtDenoiseParams: rt_render_progressive_denoised, every frame
         filtered, the last one equal to denoise(camera, params, render_frame(...))."""
-        frames = []
-        h, w = params.height, params.width
-
-        def on_pass(_user, rgb, samples_done, _samples_total):
-            arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()
-            frames.append((samples_done, arr))
-            if on_frame is not None:
-                on_frame(samples_done, arr)
-
-        cb = abi.RtFrameCallback(on_pass)
-        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        cb, frames = _frame_collector(params.height, params.width, on_frame)
+        hook = _cancel_hook(cancel)
         if denoise is None or denoise is False:
             check(self._lib.rt_render_progressive(self._h, C.byref(camera), C.byref(params), int(pass_samples), cb, None, hook,
                                                   None), "rt_render_progressive", self._lib)
@@ -427,23 +458,10 @@ class Scene:
         """rt_render_adaptive -> (frame float64 [H, W, 3], samples int32 [H, W], tile_error float64 [ceil(H/8), ceil(W/8)],
         frames), frames being the list of (samples_done, float64 [H, W, 3] copy) of the callbacks.  threshold, pass_samples,
         min_samples: None keeps rt_adaptive_params_default's value.  cancel and on_frame as render_progressive's."""
-        overrides = {k: v for k, v in (("threshold", threshold), ("pass_samples", pass_samples),
-                                       ("min_samples", min_samples)) if v is not None}
-        ap = adaptive_params(**overrides)
-        h, w = params.height, params.width
-        frame = np.zeros((h, w, 3), dtype=np.float64)
-        samples = np.zeros((h, w), dtype=np.int32)
-        tile_error = np.zeros(((h + 7) // 8, (w + 7) // 8), dtype=np.float64)
-        frames = []
-
-        def on_pass(_user, rgb, samples_done, _samples_total):
-            arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()
-            frames.append((samples_done, arr))
-            if on_frame is not None:
-                on_frame(samples_done, arr)
-
-        cb = abi.RtFrameCallback(on_pass)
-        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        ap = _adaptive(threshold, pass_samples, min_samples)
+        frame, samples, tile_error = _adaptive_outputs(params)
+        cb, frames = _frame_collector(params.height, params.width, on_frame)
+        hook = _cancel_hook(cancel)
         check(self._lib.rt_render_adaptive(self._h, C.byref(camera), C.byref(params), C.byref(ap),
                                            frame.ctypes.data_as(C.POINTER(C.c_double)),
                                            samples.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -455,18 +473,9 @@ class Scene:
         """rt_render_progressive_nee -> list of (samples_done, float64 [H, W, 3] copy), one per pass, EACH equal to
         render_frame_nee's frame at samples = samples_done.  heuristic and max_lights as render_frame_nee's; cancel and
         on_frame as render_progressive's."""
-        ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
-        frames = []
-        h, w = params.height, params.width
-
-        def on_pass(_user, rgb, samples_done, _samples_total):
-            arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()
-            frames.append((samples_done, arr))
-            if on_frame is not None:
-                on_frame(samples_done, arr)
-
-        cb = abi.RtFrameCallback(on_pass)
-        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        ls = _light_sampling(heuristic, max_lights)
+        cb, frames = _frame_collector(params.height, params.width, on_frame)
+        hook = _cancel_hook(cancel)
         check(self._lib.rt_render_progressive_nee(self._h, C.byref(camera), C.byref(params), C.byref(ls), int(pass_samples), cb,
                                                   None, hook, None), "rt_render_progressive_nee", self._lib)
         return frames
@@ -475,24 +484,11 @@ class Scene:
                             max_lights=None, cancel=None, on_frame=None):
         """rt_render_adaptive_nee -> (frame, samples, tile_error, frames) as render_adaptive's, every pixel being
         render_frame_nee's at its own sample count.  heuristic and max_lights as render_frame_nee's."""
-        ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
-        overrides = {k: v for k, v in (("threshold", threshold), ("pass_samples", pass_samples),
-                                       ("min_samples", min_samples)) if v is not None}
-        ap = adaptive_params(**overrides)
-        h, w = params.height, params.width
-        frame = np.zeros((h, w, 3), dtype=np.float64)
-        samples = np.zeros((h, w), dtype=np.int32)
-        tile_error = np.zeros(((h + 7) // 8, (w + 7) // 8), dtype=np.float64)
-        frames = []
-
-        def on_pass(_user, rgb, samples_done, _samples_total):
-            arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()
-            frames.append((samples_done, arr))
-            if on_frame is not None:
-                on_frame(samples_done, arr)
-
-        cb = abi.RtFrameCallback(on_pass)
-        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        ls = _light_sampling(heuristic, max_lights)
+        ap = _adaptive(threshold, pass_samples, min_samples)
+        frame, samples, tile_error = _adaptive_outputs(params)
+        cb, frames = _frame_collector(params.height, params.width, on_frame)
+        hook = _cancel_hook(cancel)
         check(self._lib.rt_render_adaptive_nee(self._h, C.byref(camera), C.byref(params), C.byref(ls), C.byref(ap),
                                                frame.ctypes.data_as(C.POINTER(C.c_double)),
                                                samples.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -505,19 +501,9 @@ class Scene:
         (r, c, width, height) in arrival order).  Every tile equals render_frame_nee's pixels.  heuristic and max_lights as
         render_frame_nee's; cancel: None or a callable returning True once the render should stop; on_tile: None or a
         callable(r, c, width, height) run inside each callback."""
-        ls = light_sampling_params(**{k: v for k, v in (("heuristic", heuristic), ("max_lights", max_lights)) if v is not None})
-        frame = np.zeros((params.height, params.width, 3), dtype=np.float64)
-        order = []
-
-        def on_update(_user, rgb, r, c, w, h):
-            if w > 0 and h > 0:  # `rgb` is only valid during the callback
-                frame[r:r + h, c:c + w] = np.ctypeslib.as_array(rgb, shape=(h, w, 3))
-            order.append((r, c, w, h))
-            if on_tile is not None:
-                on_tile(r, c, w, h)
-
-        cb = abi.RtTileCallback(on_update)
-        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        ls = _light_sampling(heuristic, max_lights)
+        cb, frame, order = _nee_tile_assembler(params, on_tile)
+        hook = _cancel_hook(cancel)
         check(self._lib.rt_render_nee(self._h, C.byref(camera), C.byref(params), C.byref(ls), cb, None, hook, None),
               "rt_render_nee", self._lib)
         return frame, order
@@ -543,13 +529,13 @@ class Scene:
 
     def denoise_device(self, params, rgb_ptr, guides, out_ptr, dparams=None, stream=None):
         """rt_denoise_device on device addresses (ints); guides: an abi.RtGuides of device addresses."""
-        dp = dparams if dparams is not None else denoise_params()
+        dp = _or_default(dparams, denoise_params)
         check(self._lib.rt_denoise_device(self._h, C.byref(params), C.byref(dp), C.c_void_p(rgb_ptr), C.byref(guides),
                                           C.c_void_p(out_ptr), C.c_void_p(stream or 0)), "rt_denoise_device", self._lib)
 
     def denoise(self, camera, params, rgb, dparams=None):
         """rt_denoise_frame: the guides of (camera, params) and the filter over a host frame -> float64 [H, W, 3]."""
-        dp = dparams if dparams is not None else denoise_params()
+        dp = _or_default(dparams, denoise_params)
         src = np.ascontiguousarray(rgb, dtype=np.float64)
         if src.shape != (params.height, params.width, 3):
             raise ValueError("rgb must be float64 [H, W, 3] of the params' size")
@@ -564,8 +550,8 @@ class Scene:
         """rt_temporal_accumulate_device: rgb_ptr = device address (int) of a gamma-encoded frame; guides an abi.RtGuides,
         out_history / prev_history abi.RtHistory of device addresses; prev_camera and prev_history both None: a first frame.
         dparams decides the demodulation (None: the defaults).  Enqueued on `stream`, not synchronised."""
-        tp = tparams if tparams is not None else temporal_params()
-        dp = dparams if dparams is not None else denoise_params()
+        tp = _or_default(tparams, temporal_params)
+        dp = _or_default(dparams, denoise_params)
         check(self._lib.rt_temporal_accumulate_device(
             self._h, C.byref(params), C.byref(tp), C.byref(dp), C.c_void_p(rgb_ptr), C.byref(guides),
             C.byref(prev_camera) if prev_camera is not None else None,
@@ -575,8 +561,8 @@ class Scene:
     def denoise_history_device(self, params, history, guides, out_ptr, dparams=None, tparams=None, stream=None):
         """rt_denoise_history_device: the variance-guided filter of a history's radiance into out_ptr (device address),
         gamma-encoded.  Enqueued on `stream`, not synchronised."""
-        tp = tparams if tparams is not None else temporal_params()
-        dp = dparams if dparams is not None else denoise_params()
+        tp = _or_default(tparams, temporal_params)
+        dp = _or_default(dparams, denoise_params)
         check(self._lib.rt_denoise_history_device(self._h, C.byref(params), C.byref(dp), C.byref(tp), C.byref(history),
                                                   C.byref(guides), C.c_void_p(out_ptr), C.c_void_p(stream or 0)),
               "rt_denoise_history_device", self._lib)
@@ -585,8 +571,8 @@ class Scene:
                               stream=None):
         """rt_batch_variance_device: planes an abi.RtBatchPlanes, guides an abi.RtGuides of device addresses; the radiance
         C (W*H*3 f64) and its variance (W*H f64) go to the two device addresses.  Enqueued on `stream`, not synchronised."""
-        dp = dparams if dparams is not None else denoise_params()
-        fp = fparams if fparams is not None else variance_filter_params()
+        dp = _or_default(dparams, denoise_params)
+        fp = _or_default(fparams, variance_filter_params)
         check(self._lib.rt_batch_variance_device(self._h, C.byref(params), C.byref(dp), C.byref(fp), C.byref(planes),
                                                  C.byref(guides), C.c_void_p(radiance_ptr), C.c_void_p(variance_ptr),
                                                  C.c_void_p(stream or 0)), "rt_batch_variance_device", self._lib)
@@ -595,8 +581,8 @@ class Scene:
                                 stream=None):
         """rt_denoise_variance_device: the variance-guided levels over (radiance, variance) and the re-modulation into
         out_ptr (device address), gamma-encoded.  Enqueued on `stream`, not synchronised."""
-        dp = dparams if dparams is not None else denoise_params()
-        fp = fparams if fparams is not None else variance_filter_params()
+        dp = _or_default(dparams, denoise_params)
+        fp = _or_default(fparams, variance_filter_params)
         check(self._lib.rt_denoise_variance_device(self._h, C.byref(params), C.byref(dp), C.byref(fp), C.c_void_p(radiance_ptr),
                                                    C.c_void_p(variance_ptr), C.byref(guides), C.c_void_p(out_ptr),
                                                    C.c_void_p(stream or 0)), "rt_denoise_variance_device", self._lib)
@@ -608,28 +594,18 @@ class Scene:
         [ceil(H/8), ceil(W/8)] f64; variance [H, W] f64), frames the callbacks' (samples_done, unfiltered copy).  nee: the
         next-event estimator with heuristic / max_lights as render_frame_nee's.  threshold, pass_samples, min_samples as
         render_adaptive's (threshold 0: the still frame); cancel and on_frame as render_progressive's."""
-        overrides = {k: v for k, v in (("threshold", threshold), ("pass_samples", pass_samples),
-                                       ("min_samples", min_samples)) if v is not None}
-        ap = adaptive_params(**overrides)
-        dp = dparams if dparams is not None else denoise_params()
-        fp = fparams if fparams is not None else variance_filter_params()
+        ap = _adaptive(threshold, pass_samples, min_samples)
+        dp = _or_default(dparams, denoise_params)
+        fp = _or_default(fparams, variance_filter_params)
         ls = _light_sampling(heuristic, max_lights) if nee else None
         h, w = params.height, params.width
-        frame = np.zeros((h, w, 3), dtype=np.float64)
+        frame, samples, tile_error = _adaptive_outputs(params)
         out = {"raw_rgb": np.zeros((h, w, 3)), "sums": np.zeros((h, w, 3)), "squares": np.zeros((h, w, 3)),
-               "samples": np.zeros((h, w), dtype=np.int32), "chunks": np.zeros((h, w), dtype=np.int32),
-               "tile_error": np.zeros(((h + 7) // 8, (w + 7) // 8)), "variance": np.zeros((h, w))}
+               "samples": samples, "chunks": np.zeros((h, w), dtype=np.int32), "tile_error": tile_error,
+               "variance": np.zeros((h, w))}
         bo = abi.RtBatchOutputs(*[out[k].ctypes.data_as(t) for k, t in abi.RtBatchOutputs._fields_])
-        frames = []
-
-        def on_pass(_user, rgb, samples_done, _samples_total):
-            arr = np.ctypeslib.as_array(rgb, shape=(h, w, 3)).copy()
-            frames.append((samples_done, arr))
-            if on_frame is not None:
-                on_frame(samples_done, arr)
-
-        cb = abi.RtFrameCallback(on_pass)
-        hook = abi.RtCancelCallback(lambda _user: 1 if cancel() else 0) if cancel is not None else C.cast(None, abi.RtCancelCallback)
+        cb, frames = _frame_collector(h, w, on_frame)
+        hook = _cancel_hook(cancel)
         check(self._lib.rt_render_adaptive_filtered(self._h, C.byref(camera), C.byref(params),
                                                     C.byref(ls) if ls is not None else None, C.byref(ap), C.byref(dp),
                                                     C.byref(fp), frame.ctypes.data_as(C.POINTER(C.c_double)), C.byref(bo), cb,
@@ -663,8 +639,8 @@ class Temporal:
         """rt_render_temporal: the frame of (camera, params) accumulated into the history and filtered -> float64 [H, W, 3],
         or (frame, history length float64 [H, W]) with with_length.  The caller advances params.seed from frame to frame:
         equal seeds trace equal samples."""
-        tp = tparams if tparams is not None else temporal_params()
-        dp = dparams if dparams is not None else denoise_params()
+        tp = _or_default(tparams, temporal_params)
+        dp = _or_default(dparams, denoise_params)
         out = np.zeros((params.height, params.width, 3), dtype=np.float64)
         length = np.zeros((params.height, params.width), dtype=np.float64) if with_length else None
         check(self._lib.rt_render_temporal(scene._h, self._h, C.byref(camera), C.byref(params), C.byref(tp), C.byref(dp),

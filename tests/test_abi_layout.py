@@ -34,6 +34,23 @@ def test_python_prototypes_cover_the_headers(rt):
     assert sorted(host._PROTOS) == declared_functions("rt_host.h")
 
 
+def declared_parameter_counts(header):
+    """name -> number of parameters of every declaration declared_functions() finds; (void) is none."""
+    text = open(os.path.join(INC, header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    found = re.findall(r"\b(rth?_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
+    return {name: 0 if params.strip() == "void" else len(params.split(",")) for name, params in found}
+
+
+def test_python_prototypes_take_as_many_arguments_as_the_header_declares(rt):
+    """tests/test_binding_calls_cpu.py holds the binding's calls to abi.PROTOTYPES; this holds PROTOTYPES to rt_abi.h."""
+    declared = declared_parameter_counts("rt_abi.h")
+    assert sorted(declared) == declared_functions("rt_abi.h")
+    wrong = {name: (len(argtypes), declared[name]) for name, (_res, argtypes) in rt.abi.PROTOTYPES.items()
+             if len(argtypes) != declared[name]}
+    assert not wrong, wrong
+
+
 def test_abi_version_and_strerror(rt):
     assert rt.lib().rt_abi_version() == rt.abi.ABI_VERSION == 5
     # error.rs:71-97 numbering
