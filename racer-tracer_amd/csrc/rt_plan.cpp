@@ -571,6 +571,22 @@ std::vector<int> pass_ends(const std::vector<int> &starts, int pass_samples) {
     return ends;
 }
 
+PreviewGrid preview_grid(const RtRenderParams *p) {
+    PreviewGrid g{1, 1, p->width, p->height};
+    if (p->scale > 1) { // CpuRendererScaled::new (cpu_scaled.rs:33-41) + raytrace's scaled grid (:50-52)
+        auto highest_divisible = [](int value, int div) { // cpu_scaled.rs:18-24
+            while (value % div != 0) --div;
+            return div;
+        };
+        const int tw = p->tiles_w > 0 ? p->tiles_w : 1, th = p->tiles_h > 0 ? p->tiles_h : 1;
+        g.step_x = highest_divisible(p->width / tw, p->scale);
+        g.step_y = highest_divisible(p->height / th, p->scale);
+        g.cover_w = (p->width / g.step_x) * g.step_x;
+        g.cover_h = (p->height / g.step_y) * g.step_y;
+    }
+    return g;
+}
+
 void fill_grid(const RtRenderParams *p, rtdev::TraceArgs &a) {
     a.width = p->width;
     a.height = p->height;
@@ -589,21 +605,12 @@ void fill_grid(const RtRenderParams *p, rtdev::TraceArgs &a) {
         a.strip_index = 0;
         a.owned_rows = p->height;
     }
-    a.step_x = a.step_y = 1;
-    a.cover_w = p->width;
-    a.cover_h = p->height;
-    if (p->scale > 1) { // CpuRendererScaled::new (cpu_scaled.rs:33-41) + raytrace's scaled grid (:50-52)
-        auto highest_divisible = [](int value, int div) { // cpu_scaled.rs:18-24
-            while (value % div != 0) --div;
-            return div;
-        };
-        const int tw = p->tiles_w > 0 ? p->tiles_w : 1, th = p->tiles_h > 0 ? p->tiles_h : 1;
-        a.step_x = highest_divisible(p->width / tw, p->scale);
-        a.step_y = highest_divisible(p->height / th, p->scale);
-        a.cover_w = (p->width / a.step_x) * a.step_x;
-        a.cover_h = (p->height / a.step_y) * a.step_y;
-        a.owned_rows = p->height / a.step_y; // grid rows
-    }
+    const PreviewGrid g = preview_grid(p);
+    a.step_x = g.step_x;
+    a.step_y = g.step_y;
+    a.cover_w = g.cover_w;
+    a.cover_h = g.cover_h;
+    if (p->scale > 1) a.owned_rows = p->height / a.step_y; // grid rows
     a.seed_lo = (uint32_t)(p->seed & 0xffffffffull);
     a.seed_hi = (uint32_t)(p->seed >> 32);
     a.inv_width_m1 = 1.0 / (double)(p->width - 1);

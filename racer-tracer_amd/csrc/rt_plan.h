@@ -127,7 +127,13 @@ std::vector<Launch> plan_launches(const std::vector<int> &starts, int batch);
 // one it starts at, or the end of the frame.
 std::vector<int> pass_ends(const std::vector<int> &starts, int pass_samples);
 
-// The render's pixel grid: sizes, samples, strips, the preview's coarser grid, the seed.
+// The preview's coarser grid (cpu_scaled.rs:18-41): step = the largest divisor <= scale of width / max(tiles_w, 1), rows
+// likewise; cover = (size / step) * step.  scale <= 1: steps of 1 and the whole image.
+struct PreviewGrid {
+    int step_x, step_y, cover_w, cover_h;
+};
+PreviewGrid preview_grid(const RtRenderParams *p);
+// The render's pixel grid: sizes, samples, strips, the preview's coarser grid (preview_grid), the seed.
 void fill_grid(const RtRenderParams *p, rtdev::TraceArgs &a);
 // Rows of the owned-row grid of a render with these parameters (a multiple of strip_rows with strips).
 int owned_rows_of(const RtRenderParams *p);

@@ -205,6 +205,7 @@ Args Args::parse(int argc, const char *const *argv) {
         else if (s == "--devices") a.devices = std::atoi(val().c_str());
         else if (s == "--denoise" && !has_inline) a.denoise = true;
         else if (s == "--denoise-variance" && !has_inline) a.denoise_variance = true;
+        else if (s == "--preview-upsample" && !has_inline) a.preview_upsample = true;
         else if (s == "--nee" && !has_inline) a.nee = true;
         else if (s == "--nee-stream" && !has_inline) a.nee_stream = true;
         else if (s == "--adaptive" || s == "--nee-adaptive") {
@@ -270,6 +271,9 @@ Args Args::parse(int argc, const char *const *argv) {
         throw TracerError::ArgumentParsingError("--nee-devices N names its own devices: it does not combine with --devices > 1");
     if (a.denoise_variance && (a.devices > 1 || a.nee_stream || a.nee_devices > 0 || a.temporal > 0))
         throw TracerError::ArgumentParsingError("--denoise-variance filters one device's whole frame: it does not combine with --devices > 1, --nee-stream, --nee-devices or --temporal");
+    if (a.preview_upsample && (a.devices > 1 || a.nee || a.nee_stream || a.nee_devices > 0 || a.adaptive > 0.0 || a.nee_adaptive > 0.0 ||
+                               a.temporal > 0 || a.denoise_variance))
+        throw TracerError::ArgumentParsingError("--preview-upsample is a render mode of its own on one device: it combines with --denoise only");
     if (a.nee_list_given && !(a.nee || a.nee_stream || a.nee_devices > 0 || a.nee_adaptive > 0.0))
         throw TracerError::ArgumentParsingError("--nee-lights and --nee-pick set the light list of next-event estimation: they need --nee, --nee-stream, --nee-devices or --nee-adaptive");
     return a;

@@ -74,6 +74,9 @@ struct Args { // config.rs:12-28
     // --denoise-variance: the frame of the default, --nee, --adaptive T or --nee-adaptive T route through
     // rt_render_adaptive_filtered (threshold 0 where no T is given), filtered by its batch variance; one device only
     bool denoise_variance = false;
+    // --preview-upsample: the config's `preview:` block through rt_render_preview_upsampled (include/rt_preview.h): the scaled
+    // preview frame upsampled with full-resolution guides; --denoise adds the default a-trous levels; one device only
+    bool preview_upsample = false;
     bool help = false;
 
     static Args parse(int argc, const char *const *argv);

@@ -16,6 +16,8 @@
 // --denoise-variance sends the frame of the default, --nee, --adaptive T or --nee-adaptive T route through
 // rt_render_adaptive_filtered instead (threshold 0 where no T is given): the variance-guided filter fed by the batch sums.
 // --nee-lights plain|all and --nee-pick uniform|power give every scene of an NEE run its light list (rt_scene_set_lights).
+// --preview-upsample renders the config's `preview:` block (scale > 1) through rt_render_preview_upsampled: the scaled preview
+// frame upsampled to full resolution with full-resolution guides; --denoise passes the default number of a-trous levels.
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -25,6 +27,7 @@
 #include <string>
 #include <vector>
 #include "../../include/rt_host.h"
+#include "../../include/rt_preview.h"
 #include "config.h"
 #include "error.h"
 
@@ -61,7 +64,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -73,7 +76,7 @@ int main(int argc, char **argv) {
         return rc;
     }
     RtRenderParams params;
-    rth_session_params(session, 0, &params);
+    rth_session_params(session, args.preview_upsample ? 1 : 0, &params); // --preview-upsample: the `preview:` block
     if (args.devices < 1) {
         fprintf(stderr, "--devices must be at least 1\n");
         rth_session_close(session);
@@ -115,7 +118,14 @@ int main(int argc, char **argv) {
     double traced = 1.0; // --adaptive: the fraction of the frame's samples traced
     double mean_length = 0.0; // --temporal: the mean history length behind the last frame
     double mean_sigma = 0.0;  // --denoise-variance: the mean of sqrt(var) over the frame
-    if (args.denoise_variance) { // the adaptive passes (or, with threshold 0, the still frame) and the filter in one call
+    if (args.preview_upsample) { // the preview frame, its guides, the upsample and (--denoise) the levels in one call
+        RtDenoiseParams dp;
+        rt_denoise_params_default(&dp);
+        if (!args.denoise) dp.iterations = 0;
+        std::vector<double> frame(n_rgb);
+        rc = rt_render_preview_upsampled(scenes[0], rth_session_camera(session), &params, &dp, frame.data(), nullptr);
+        if (rc == RT_OK) rth_tone_map(session, frame.data(), sb.buffer.data(), n_rgb / 3);
+    } else if (args.denoise_variance) { // the adaptive passes (or, with threshold 0, the still frame) and the filter in one call
         RtAdaptiveParams ap;
         rt_adaptive_params_default(&ap);
         ap.threshold = args.adaptive > 0.0 ? args.adaptive : args.nee_adaptive > 0.0 ? args.nee_adaptive : 0.0;
@@ -202,7 +212,7 @@ int main(int argc, char **argv) {
     } else {
         rc = rt_render_multi(scenes.data(), (int)scenes.size(), rth_session_camera(session), &params, 0, on_tile, &sb, nullptr, nullptr);
     }
-    if (rc == RT_OK && args.denoise && args.temporal == 0 && !args.denoise_variance) { // the whole frame, filtered, then tone-mapped like the tiles were
+    if (rc == RT_OK && args.denoise && args.temporal == 0 && !args.denoise_variance && !args.preview_upsample) { // the whole frame, filtered, then tone-mapped like the tiles were
         RtDenoiseParams dp;
         rt_denoise_params_default(&dp);
         std::vector<double> filtered(n_rgb);
