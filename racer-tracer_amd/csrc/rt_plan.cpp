@@ -587,6 +587,30 @@ PreviewGrid preview_grid(const RtRenderParams *p) {
     return g;
 }
 
+PreviewPhase preview_phase(const PreviewGrid &g, int64_t frame_index) {
+    const int64_t n = (int64_t)g.step_x * (int64_t)g.step_y;
+    auto gcd = [](int64_t a, int64_t b) {
+        while (b != 0) {
+            const int64_t r = a % b;
+            a = b;
+            b = r;
+        }
+        return a;
+    };
+    int64_t stride = std::max<int64_t>(1, (5 * n + 4) / 8);
+    while (gcd(stride, n) != 1) ++stride; // (n + 1 is coprime to n: the loop ends)
+    const int64_t i = ((frame_index % n) * (stride % n)) % n;
+    return PreviewPhase{(int)(i % g.step_x), (int)(i / g.step_x)};
+}
+
+RtCamera preview_phase_camera(const RtCamera &camera, int width, int height, int jx, int jy) {
+    RtCamera out = camera;
+    if (jx == 0 && jy == 0) return out; // (-0.0 + 0.0 would not be the same bits)
+    const double fx = (double)jx / (double)(width - 1), fy = (double)jy / (double)(height - 1);
+    for (int c = 0; c < 3; ++c) out.upper_left_corner[c] += fx * camera.horizontal[c] - fy * camera.vertical[c];
+    return out;
+}
+
 void fill_grid(const RtRenderParams *p, rtdev::TraceArgs &a) {
     a.width = p->width;
     a.height = p->height;

@@ -133,6 +133,16 @@ struct PreviewGrid {
     int step_x, step_y, cover_w, cover_h;
 };
 PreviewGrid preview_grid(const RtRenderParams *p);
+// The pixel of its block that frame `frame_index` (>= 0) of a jittered preview traces: with
+// n = step_x step_y and g the smallest integer >= max(1, (5 n + 4) / 8) coprime to n, i = (frame_index mod n) g mod n,
+// jx = i mod step_x, jy = i / step_x.  A permutation of the block per n frames that starts at (0, 0).
+struct PreviewPhase {
+    int jx, jy;
+};
+PreviewPhase preview_phase(const PreviewGrid &g, int64_t frame_index);
+// `camera` with upper_left_corner += (jx / (W - 1)) horizontal - (jy / (H - 1)) vertical, per component as written: the
+// anchor of block (i, j) then traces the rays of pixel (i step_x + jx, j step_y + jy).  (0, 0): the camera bit for bit.
+RtCamera preview_phase_camera(const RtCamera &camera, int width, int height, int jx, int jy);
 // The render's pixel grid: sizes, samples, strips, the preview's coarser grid (preview_grid), the seed.
 void fill_grid(const RtRenderParams *p, rtdev::TraceArgs &a);
 // Rows of the owned-row grid of a render with these parameters (a multiple of strip_rows with strips).

@@ -391,6 +391,9 @@ int enqueue_chunks(RtScene *s, PoolPasses &pp, int c0, int c1, hipStream_t strea
 // scene_guides: those planes as an RtGuides.  enqueue_guides / enqueue_denoise: the guide launch and the filter's
 // launches on `stream` (arguments checked by the caller).
 int check_denoise(const RtRenderParams *p, const RtDenoiseParams *d);
+// What the entry points that take a preview frame (rt_upsample.hip, rt_preview_temporal.hip) refuse about params and
+// denoise; `full` becomes params at full resolution (scale 0), what the guides and the filter's levels take.
+int check_upsample(const RtRenderParams *p, const RtDenoiseParams *d, RtRenderParams &full);
 // What the three filter units (rt_denoise.hip, rt_temporal.hip, rt_variance_filter.hip) share on the host.
 // guides_complete: no NULL among a caller's guide planes.  pixel_grid: 16x16 pixels per block of 256 lanes.
 // filter_stops: the inverse sigmas of a-trous level `level` (step 2^level) as the kernels take them, 0 where a stop is

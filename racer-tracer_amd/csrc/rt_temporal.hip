@@ -19,6 +19,7 @@
 #include "rt_trace_common.h"
 #include "rt_filter_taps.h"
 #include "rt_scene.h"
+#include "rt_temporal_state.h"
 
 #include <cmath>
 #include <cstring>
@@ -170,17 +171,6 @@ __global__ __launch_bounds__(256) void k_temporal_atrous(const AtrousVarArgs P, 
 // ------------------------------------------------------------------------------------------------------------ host side
 using rtapi::fail;
 
-struct RtTemporal {
-    int device = 0;
-    int width = 0, height = 0;
-    rtapi::DevBuf<double> planes; // two histories of 12 doubles per pixel, the guides' 10, the frame's 3 and the output's 3
-    rtapi::DevBuf<int32_t> ids;   // the histories' and the guides' obj_id
-    double *host_length = nullptr; // pinned, W*H
-    bool has_prev = false;
-    int current = 0; // the history the next frame reads
-    RtCamera camera;
-};
-
 namespace {
 
 using rtapi::guides_complete;
@@ -224,7 +214,12 @@ hipError_t launch_variance(const RtRenderParams *p, const RtDenoiseParams *d, co
 constexpr double kAlpha = 0.2, kMaxHistory = 32.0;
 constexpr double kNormalTolerance = 0.25, kPlaneTolerance = 2.0, kSigmaLuminance = 4.0;
 
-bool history_complete(const RtHistory *h) {
+} // namespace
+
+// what rt_preview_temporal.hip shares (rt_temporal_state.h)
+namespace rtapi {
+
+static bool history_complete(const RtHistory *h) {
     return h && h->radiance && h->moments && h->length && h->normal && h->position && h->obj_id;
 }
 
@@ -240,10 +235,19 @@ int check_temporal(const RtTemporalParams *t) {
     return RT_OK;
 }
 
-int enqueue_accumulate(const RtRenderParams *p, const RtTemporalParams *t, const RtDenoiseParams *d, const double *rgb,
-                       const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out,
-                       hipStream_t stream) {
-    RT_HIP(launch_accumulate(p, t, (d->flags & RT_DENOISE_DEMODULATE) != 0, rgb, g, prev_camera, prev, out, stream));
+int check_accumulate_buffers(const double *rgb, const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev,
+                             const RtHistory *out) {
+    if (!rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device is NULL");
+    if (!guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
+    if (!history_complete(out)) return fail(RT_ERR_INVALID_ARGUMENT, "out_history or one of its planes is NULL");
+    if ((prev_camera == nullptr) != (prev == nullptr))
+        return fail(RT_ERR_INVALID_ARGUMENT, "prev_camera and prev_history are both NULL or neither is");
+    if (prev) {
+        if (!history_complete(prev)) return fail(RT_ERR_INVALID_ARGUMENT, "prev_history has a NULL plane");
+        if (prev->radiance == out->radiance || prev->moments == out->moments || prev->length == out->length ||
+            prev->normal == out->normal || prev->position == out->position || prev->obj_id == out->obj_id)
+            return fail(RT_ERR_INVALID_ARGUMENT, "out_history and prev_history must differ");
+    }
     return RT_OK;
 }
 
@@ -262,22 +266,30 @@ int enqueue_denoise_history(RtScene *s, const RtRenderParams *p, const RtDenoise
     return rtapi::enqueue_levels(s, p, d, var ? t->sigma_luminance : 0.0, h->radiance, var, *g, out, stream);
 }
 
+} // namespace rtapi
+
+namespace {
+
+using rtapi::check_temporal;
+using rtapi::enqueue_denoise_history;
+using rtapi::history_complete;
+using rtapi::kStateDoubles;
+using rtapi::state_guides;
+using rtapi::state_history;
+
+int enqueue_accumulate(const RtRenderParams *p, const RtTemporalParams *t, const RtDenoiseParams *d, const double *rgb,
+                       const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out,
+                       hipStream_t stream) {
+    RT_HIP(launch_accumulate(p, t, (d->flags & RT_DENOISE_DEMODULATE) != 0, rgb, g, prev_camera, prev, out, stream));
+    return RT_OK;
+}
+
 int accumulate_device(RtScene *s, const RtRenderParams *p, const RtTemporalParams *t, const RtDenoiseParams *d, const double *rgb,
                       const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out, void *stream) {
     int rc = rtapi::check_denoise(p, d);
     if (rc != RT_OK) return rc;
     if ((rc = check_temporal(t)) != RT_OK) return rc;
-    if (!rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device is NULL");
-    if (!guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
-    if (!history_complete(out)) return fail(RT_ERR_INVALID_ARGUMENT, "out_history or one of its planes is NULL");
-    if ((prev_camera == nullptr) != (prev == nullptr))
-        return fail(RT_ERR_INVALID_ARGUMENT, "prev_camera and prev_history are both NULL or neither is");
-    if (prev) {
-        if (!history_complete(prev)) return fail(RT_ERR_INVALID_ARGUMENT, "prev_history has a NULL plane");
-        if (prev->radiance == out->radiance || prev->moments == out->moments || prev->length == out->length ||
-            prev->normal == out->normal || prev->position == out->position || prev->obj_id == out->obj_id)
-            return fail(RT_ERR_INVALID_ARGUMENT, "out_history and prev_history must differ");
-    }
+    if ((rc = rtapi::check_accumulate_buffers(rgb, g, prev_camera, prev, out)) != RT_OK) return rc;
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     RT_HIP(hipSetDevice(s->device));
     return enqueue_accumulate(p, t, d, rgb, g, prev_camera, prev, out, (hipStream_t)stream);
@@ -295,34 +307,6 @@ int denoise_history_device(RtScene *s, const RtRenderParams *p, const RtDenoiseP
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     RT_HIP(hipSetDevice(s->device));
     return enqueue_denoise_history(s, p, d, t, h, g, out, (hipStream_t)stream);
-}
-
-// the planes of an RtTemporal: [history 0 | history 1 | guides | frame | output]
-constexpr size_t kHistoryDoubles = 12, kStateDoubles = 2 * kHistoryDoubles + 10 + 3 + 3;
-
-RtHistory state_history(RtTemporal *t, int k) {
-    const size_t pixels = (size_t)t->width * (size_t)t->height;
-    double *base = t->planes.ptr + (size_t)k * kHistoryDoubles * pixels;
-    RtHistory h;
-    h.radiance = base;
-    h.moments = base + 3 * pixels;
-    h.length = base + 5 * pixels;
-    h.normal = base + 6 * pixels;
-    h.position = base + 9 * pixels;
-    h.obj_id = t->ids.ptr + (size_t)k * pixels;
-    return h;
-}
-
-RtGuides state_guides(RtTemporal *t) {
-    const size_t pixels = (size_t)t->width * (size_t)t->height;
-    double *base = t->planes.ptr + 2 * kHistoryDoubles * pixels;
-    RtGuides g;
-    g.normal = base;
-    g.position = base + 3 * pixels;
-    g.albedo = base + 6 * pixels;
-    g.footprint = base + 9 * pixels;
-    g.obj_id = t->ids.ptr + 2 * pixels;
-    return g;
 }
 
 void temporal_free(RtTemporal *t) {
@@ -374,7 +358,7 @@ int render_temporal(RtScene *s, RtTemporal *t, const RtCamera *camera, const RtR
     RT_HIP(hipSetDevice(s->device));
     const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
     const hipStream_t stream = s->buf.stream;
-    double *frame = t->planes.ptr + (2 * kHistoryDoubles + 10) * pixels, *filtered = frame + n;
+    double *frame = rtapi::state_frame(t), *filtered = frame + n;
     const RtGuides g = state_guides(t);
     const RtHistory prev = state_history(t, t->current), next = state_history(t, t->current ^ 1);
     if ((rc = rtapi::enqueue_render(s, camera, p, frame, stream, 0, rtapi::Cancel())) != RT_OK) return rc;

@@ -78,7 +78,24 @@ __global__ __launch_bounds__(256) void k_upsample_preview(const UpsampleArgs P, 
 // ------------------------------------------------------------------------------------------------------------ host side
 using rtapi::fail;
 
+// (rt_scene.h) what both upsampling entry points, and rt_preview_temporal.hip's, refuse about params and denoise
+int rtapi::check_upsample(const RtRenderParams *p, const RtDenoiseParams *d, RtRenderParams &full) {
+    if (!p || !d) return fail(RT_ERR_INVALID_ARGUMENT, "params/denoise is NULL");
+    if (p->scale <= 1) return fail(RT_ERR_INVALID_ARGUMENT, "params->scale must be greater than 1: there is no preview to upsample");
+    if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "the preview is a whole frame: params->strip_count must be 0 or 1");
+    full = *p;
+    full.scale = 0;
+    int rc = rtapi::check_denoise(&full, d);
+    if (rc != RT_OK) return rc;
+    const rtapi::PreviewGrid g = rtapi::preview_grid(p);
+    if (p->width / g.step_x < 1 || p->height / g.step_y < 1) // (tiles_w > width: a block larger than the image)
+        return fail(RT_ERR_INVALID_ARGUMENT, "params->tiles_w / tiles_h leave the preview without an anchor pixel");
+    return RT_OK;
+}
+
 namespace {
+
+using rtapi::check_upsample;
 
 // What the three entry points refuse about params: NULL aside, rt_render_frame's rules for the fields the grid reads.
 int check_grid_params(const RtRenderParams *p) {
@@ -98,22 +115,6 @@ int preview_grid(const RtRenderParams *p, int32_t *step_x, int32_t *step_y, int3
     *step_y = g.step_y;
     *cover_w = g.cover_w;
     *cover_h = g.cover_h;
-    return RT_OK;
-}
-
-// What both upsampling entry points refuse about params and denoise; `full` becomes params at full resolution (scale 0),
-// what the guides and rt_denoise_device's levels take.
-int check_upsample(const RtRenderParams *p, const RtDenoiseParams *d, RtRenderParams &full) {
-    if (!p || !d) return fail(RT_ERR_INVALID_ARGUMENT, "params/denoise is NULL");
-    if (p->scale <= 1) return fail(RT_ERR_INVALID_ARGUMENT, "params->scale must be greater than 1: there is no preview to upsample");
-    if (p->strip_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, "the preview is a whole frame: params->strip_count must be 0 or 1");
-    full = *p;
-    full.scale = 0;
-    int rc = rtapi::check_denoise(&full, d);
-    if (rc != RT_OK) return rc;
-    const rtapi::PreviewGrid g = rtapi::preview_grid(p);
-    if (p->width / g.step_x < 1 || p->height / g.step_y < 1) // (tiles_w > width: a block larger than the image)
-        return fail(RT_ERR_INVALID_ARGUMENT, "params->tiles_w / tiles_h leave the preview without an anchor pixel");
     return RT_OK;
 }
 

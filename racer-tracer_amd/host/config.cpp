@@ -216,13 +216,13 @@ Args Args::parse(int argc, const char *const *argv) {
                 throw TracerError::ArgumentParsingError(s + " needs a positive threshold, not '" + v + "'");
             (s == "--adaptive" ? a.adaptive : a.nee_adaptive) = t;
         }
-        else if (s == "--temporal") {
+        else if (s == "--temporal" || s == "--preview-temporal") {
             const std::string v = val();
             char *end = nullptr;
             const long k = std::strtol(v.c_str(), &end, 10);
             if (v.empty() || end == nullptr || *end != '\0' || k < 1 || k > 1000000)
-                throw TracerError::ArgumentParsingError("--temporal needs a positive number of frames, not '" + v + "'");
-            a.temporal = (int)k;
+                throw TracerError::ArgumentParsingError(s + " needs a positive number of frames, not '" + v + "'");
+            (s == "--temporal" ? a.temporal : a.preview_temporal) = (int)k;
         }
         else if (s == "--nee-devices") {
             const std::string v = val();
@@ -274,6 +274,9 @@ Args Args::parse(int argc, const char *const *argv) {
     if (a.preview_upsample && (a.devices > 1 || a.nee || a.nee_stream || a.nee_devices > 0 || a.adaptive > 0.0 || a.nee_adaptive > 0.0 ||
                                a.temporal > 0 || a.denoise_variance))
         throw TracerError::ArgumentParsingError("--preview-upsample is a render mode of its own on one device: it combines with --denoise only");
+    if (a.preview_temporal > 0 && (a.devices > 1 || a.nee || a.nee_stream || a.nee_devices > 0 || a.adaptive > 0.0 || a.nee_adaptive > 0.0 ||
+                                   a.temporal > 0 || a.denoise_variance || a.preview_upsample))
+        throw TracerError::ArgumentParsingError("--preview-temporal is a render mode of its own on one device: it combines with --denoise only");
     if (a.nee_list_given && !(a.nee || a.nee_stream || a.nee_devices > 0 || a.nee_adaptive > 0.0))
         throw TracerError::ArgumentParsingError("--nee-lights and --nee-pick set the light list of next-event estimation: they need --nee, --nee-stream, --nee-devices or --nee-adaptive");
     return a;

@@ -77,6 +77,10 @@ struct Args { // config.rs:12-28
     // --preview-upsample: the config's `preview:` block through rt_render_preview_upsampled (include/rt_preview.h): the scaled
     // preview frame upsampled with full-resolution guides; --denoise adds the default a-trous levels; one device only
     bool preview_upsample = false;
+    // --preview-temporal K (K >= 1): K frames of the `preview:` block at seeds seed .. seed + K - 1 and the phases of frames
+    // 0 .. K - 1 through rt_render_preview_temporal (include/rt_preview_temporal.h) into one history, the last one written;
+    // --denoise gives the filter its levels; one device only
+    int preview_temporal = 0;
     bool help = false;
 
     static Args parse(int argc, const char *const *argv);

@@ -18,6 +18,9 @@
 // --nee-lights plain|all and --nee-pick uniform|power give every scene of an NEE run its light list (rt_scene_set_lights).
 // --preview-upsample renders the config's `preview:` block (scale > 1) through rt_render_preview_upsampled: the scaled preview
 // frame upsampled to full resolution with full-resolution guides; --denoise passes the default number of a-trous levels.
+// --preview-temporal K renders K frames of the `preview:` block at seeds seed .. seed + K - 1 through rt_render_preview_temporal
+// (include/rt_preview_temporal.h): each traces another pixel of its block, all go into one full-resolution history, the last
+// is written; --denoise gives the filter its levels.
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -27,7 +30,7 @@
 #include <string>
 #include <vector>
 #include "../../include/rt_host.h"
-#include "../../include/rt_preview.h"
+#include "../../include/rt_preview_temporal.h"
 #include "config.h"
 #include "error.h"
 
@@ -64,7 +67,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample] [--preview-temporal K]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -76,7 +79,7 @@ int main(int argc, char **argv) {
         return rc;
     }
     RtRenderParams params;
-    rth_session_params(session, args.preview_upsample ? 1 : 0, &params); // --preview-upsample: the `preview:` block
+    rth_session_params(session, args.preview_upsample || args.preview_temporal > 0 ? 1 : 0, &params); // ... the `preview:` block
     if (args.devices < 1) {
         fprintf(stderr, "--devices must be at least 1\n");
         rth_session_close(session);
@@ -116,7 +119,8 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Rendering image...\n"); // interactive.rs:229
     auto t0 = std::chrono::steady_clock::now();
     double traced = 1.0; // --adaptive: the fraction of the frame's samples traced
-    double mean_length = 0.0; // --temporal: the mean history length behind the last frame
+    double mean_length = 0.0; // --temporal, --preview-temporal: the mean history length behind the last frame
+    double filled = 0.0;      // --preview-temporal: the share of pixels with length 0 (filled from the last frame's anchors)
     double mean_sigma = 0.0;  // --denoise-variance: the mean of sqrt(var) over the frame
     if (args.preview_upsample) { // the preview frame, its guides, the upsample and (--denoise) the levels in one call
         RtDenoiseParams dp;
@@ -149,6 +153,28 @@ int main(int argc, char **argv) {
         for (double v : var) mean_sigma += std::sqrt(v);
         mean_sigma /= (double)var.size();
         if (rc == RT_OK) rth_tone_map(session, filtered.data(), sb.buffer.data(), n_rgb / 3);
+    } else if (args.preview_temporal > 0) { // K jittered preview frames into one full-resolution history; the last one is shown
+        RtTemporalParams tp;
+        rt_temporal_params_default(&tp);
+        RtDenoiseParams dp;
+        rt_denoise_params_default(&dp);
+        if (!args.denoise) dp.iterations = 0;
+        RtTemporal *history = nullptr;
+        rc = rt_temporal_create(args.device, params.width, params.height, &history);
+        std::vector<double> frame(n_rgb), length(n_rgb / 3);
+        RtRenderParams one = params;
+        for (int k = 0; rc == RT_OK && k < args.preview_temporal; ++k) {
+            one.seed = params.seed + (uint64_t)k; // equal seeds would trace equal samples
+            rc = rt_render_preview_temporal(scenes[0], history, rth_session_camera(session), &one, &tp, &dp, k, frame.data(), length.data());
+        }
+        rt_temporal_destroy(history);
+        for (double l : length) {
+            mean_length += l;
+            if (l == 0.0) filled += 1.0;
+        }
+        mean_length /= (double)length.size();
+        filled /= (double)length.size();
+        if (rc == RT_OK) rth_tone_map(session, frame.data(), sb.buffer.data(), n_rgb / 3);
     } else if (args.temporal > 0) { // K frames into one history; the last one, filtered inside the call, is tone-mapped here
         RtTemporalParams tp;
         rt_temporal_params_default(&tp);
@@ -212,7 +238,7 @@ int main(int argc, char **argv) {
     } else {
         rc = rt_render_multi(scenes.data(), (int)scenes.size(), rth_session_camera(session), &params, 0, on_tile, &sb, nullptr, nullptr);
     }
-    if (rc == RT_OK && args.denoise && args.temporal == 0 && !args.denoise_variance && !args.preview_upsample) { // the whole frame, filtered, then tone-mapped like the tiles were
+    if (rc == RT_OK && args.denoise && args.temporal == 0 && !args.denoise_variance && !args.preview_upsample && args.preview_temporal == 0) { // the whole frame, filtered, then tone-mapped like the tiles were
         RtDenoiseParams dp;
         rt_denoise_params_default(&dp);
         std::vector<double> filtered(n_rgb);
@@ -238,6 +264,9 @@ int main(int argc, char **argv) {
             fprintf(stderr, "Variance-guided filter: mean standard error of the luminance %.6f.\n", mean_sigma);
         if (args.temporal > 0)
             fprintf(stderr, "Temporal accumulation over %d frames: mean history length %.2f.\n", args.temporal, mean_length);
+        if (args.preview_temporal > 0)
+            fprintf(stderr, "Preview accumulation over %d frames: mean history length %.2f, %.1f %% of the pixels with length 0.\n",
+                    args.preview_temporal, mean_length, 100.0 * filled);
         fprintf(stderr, "It took %.3f seconds to render the image. (%.1f Msamples/s, %.2f segments/sample, kernel %.1f ms)\n",
                 secs, (double)st.samples / secs / 1e6, st.samples ? (double)st.segments / (double)st.samples : 0.0, st.kernel_ms);
         if (rth_session_image_action(session) == RTH_IMAGE_ACTION_SAVE_PNG) { // main.rs:153-156
