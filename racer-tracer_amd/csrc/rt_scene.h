@@ -12,6 +12,7 @@
 #include "rt_error.h"
 #include "rt_plan.h"
 #include "../../include/rt_abi.h"
+#include "../../include/rt_rays.h"
 
 // The trace kernels exist twice (rt_trace_common.h: ARITHMETIC): RT_ARITH_FAST, and RT_ARITH_REFERENCE behind *_exact.
 // Every launcher that has both flavours, ONCE: X(member of rtapi::Launchers, exported name, return type, parameters).  The
@@ -28,6 +29,8 @@
 //     runtime's occupancy query); the chunk length the flavour was compiled with.
 //   nee_lights* (rt_nee_lights_kernel.hip, rt_nee_lights_pass_kernel.hip, rt_nee_lights_stream_kernel.hip): nee, nee_pass,
 //     nee_stream and its blocks per CU with the extended light code (rt_nee_lights.h), which exist for PRIMS_ANY only.
+//   trace_rays (rt_rays_kernel.hip): n caller rays of device planes against args' scene, closest or any hit; `order` is
+//     the device copy of the table's description indices.
 #define RT_LAUNCHER_LIST(X)                                                                                                \
     X(trace, rtdev_launch_trace, hipError_t,                                                                               \
       (const rtdev::TraceArgs *args, int prims_class, int textured, int specular, hipStream_t stream))                     \
@@ -72,7 +75,10 @@
     X(nee_lights_stream, rtdev_launch_nee_lights_stream, hipError_t,                                                       \
       (const rtdev::TraceArgs *args, const rtdev::NeeArgs *nee, const rtdev::NeeLightArgs *lights, int textured,          \
        int specular, int bvh, unsigned blocks, hipStream_t stream))                                                        \
-    X(nee_lights_stream_blocks_per_cu, rtdev_nee_lights_stream_blocks_per_cu, int, (int textured, int specular, int bvh))
+    X(nee_lights_stream_blocks_per_cu, rtdev_nee_lights_stream_blocks_per_cu, int, (int textured, int specular, int bvh)) \
+    X(trace_rays, rtdev_launch_trace_rays, hipError_t,                                                                     \
+      (const rtdev::TraceArgs *args, const RtRays *rays, const RtRayHits *hits, const int32_t *order, int n, int any_hit, \
+       hipStream_t stream))
 #define RT_DECLARE_LAUNCHER(member, name, ret, params) \
     extern "C" ret name params;                        \
     extern "C" ret name##_exact params;
@@ -175,6 +181,10 @@ struct RenderBuffers {
     DevBuf<int32_t> guide_ids;
     // rt_render_adaptive_filtered (rt_variance_filter.hip), on first use: every pixel's samples and chunks, W*H each
     DevBuf<int32_t> batch_counts;
+    // rt_trace_rays (rt_rays.hip), on first use: one chunk of rays — planes [origin 3 | direction 3 | t_min | t_max | time]
+    // x RT_RAYS_HOST_CHUNK doubles — and of answers — [t | point 3 | normal 3 | uv 2] doubles, [prim | obj_id | front_face]
+    DevBuf<double> rays_in, rays_out;
+    DevBuf<int32_t> rays_ids;
 
     // what rt_scene_create makes when it takes no set over: only such a set is worth caching
     bool complete() const {
@@ -199,6 +209,9 @@ struct RenderBuffers {
         denoise_scratch.release();
         guide_ids.release();
         batch_counts.release();
+        rays_in.release();
+        rays_out.release();
+        rays_ids.release();
         tile_done.release();
         region_done.release();
         if (host_frame) (void)hipHostFree(host_frame);
@@ -305,6 +318,8 @@ struct RtScene {
     rtapi::DevBuf<double> nee_pick;
     std::vector<char> pick_uniform;
     std::vector<double> pick_weights; // p_k of the uncapped list (rt_scene_light_weights)
+    // ray queries (rt_rays.hip): table_order on the device, made by the scene's first query
+    rtapi::DevBuf<int32_t> rays_order;
 
     rtapi::RenderBuffers buf;
     bool has_stats = false;

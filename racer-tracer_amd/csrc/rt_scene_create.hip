@@ -325,6 +325,7 @@ void rt_scene_destroy(RtScene *s) {
     s->nee_slot.release();
     s->nee_prim.release();
     s->nee_pick.release();
+    s->rays_order.release();
     // what a render allocates — slices, frames, pinned memory, counters, streams, events — outlives the scene: the
     // reference rebuilds its scene on every object event (main.rs:174-189), and the next rt_scene_create on this
     // device takes these over instead of paying hipMalloc / hipHostMalloc again (render_cache_put); should the cache

@@ -216,6 +216,18 @@ Args Args::parse(int argc, const char *const *argv) {
                 throw TracerError::ArgumentParsingError(s + " needs a positive threshold, not '" + v + "'");
             (s == "--adaptive" ? a.adaptive : a.nee_adaptive) = t;
         }
+        else if (s == "--pick") {
+            const std::string v = val();
+            char *end = nullptr, *end2 = nullptr;
+            const long x = std::strtol(v.c_str(), &end, 10);
+            const bool comma = end != nullptr && end != v.c_str() && *end == ',' && end[1] != '\0';
+            const long y = comma ? std::strtol(end + 1, &end2, 10) : 0;
+            if (!comma || end2 == nullptr || *end2 != '\0' || x < 0 || y < 0 || x > 1000000 || y > 1000000)
+                throw TracerError::ArgumentParsingError(s + " needs a pixel as X,Y, not '" + v + "'");
+            a.pick = true;
+            a.pick_x = (int)x;
+            a.pick_y = (int)y;
+        }
         else if (s == "--temporal" || s == "--preview-temporal") {
             const std::string v = val();
             char *end = nullptr;

@@ -81,6 +81,10 @@ struct Args { // config.rs:12-28
     // 0 .. K - 1 through rt_render_preview_temporal (include/rt_preview_temporal.h) into one history, the last one written;
     // --denoise gives the filter its levels; one device only
     int preview_temporal = 0;
+    // --pick X,Y: after the run, the guides' ray of that pixel of the configured camera and image (its centre, pinhole, the
+    // middle of the shutter) through rt_trace_rays (include/rt_rays.h), one line on stdout; a pixel outside the image is refused
+    bool pick = false;
+    int pick_x = 0, pick_y = 0;
     bool help = false;
 
     static Args parse(int argc, const char *const *argv);

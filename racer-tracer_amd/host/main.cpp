@@ -21,6 +21,8 @@
 // --preview-temporal K renders K frames of the `preview:` block at seeds seed .. seed + K - 1 through rt_render_preview_temporal
 // (include/rt_preview_temporal.h): each traces another pixel of its block, all go into one full-resolution history, the last
 // is written; --denoise gives the filter its levels.
+// --pick X,Y asks the scene, after the run, what lies under pixel (X, Y) of the configured camera (include/rt_rays.h) and
+// prints the answer on stdout.
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -31,6 +33,7 @@
 #include <vector>
 #include "../../include/rt_host.h"
 #include "../../include/rt_preview_temporal.h"
+#include "../../include/rt_rays.h"
 #include "config.h"
 #include "error.h"
 
@@ -56,6 +59,35 @@ void on_tile(void *user, const double *rgb, int32_t r, int32_t c, int32_t w, int
                (size_t)w * 3 * sizeof(double));
 }
 
+// --pick X,Y: what lies under the pixel.  The ray is the guides' (rt_render_guides_device): through the pixel's centre, no
+// lens offset, at the middle of the shutter interval.  One line on stdout: `pick X Y prim obj_id t px py pz nx ny nz`, or
+// `pick X Y miss`.
+int pick_pixel(RtScene *scene, const RtCamera *cam, const RtRenderParams &params, int x, int y) {
+    const double u = ((double)x + 0.5) / (double)(params.width - 1), v = ((double)y + 0.5) / (double)(params.height - 1);
+    double o[3], d[3];
+    for (int k = 0; k < 3; ++k) {
+        o[k] = cam->origin[k];
+        d[k] = cam->upper_left_corner[k] + u * cam->horizontal[k] - v * cam->vertical[k] - o[k];
+    }
+    const double time = (cam->time_a + cam->time_b) * 0.5;
+    RtRays rays = {o, d, nullptr, nullptr, &time};
+    double t = 0.0, point[3] = {0, 0, 0}, normal[3] = {0, 0, 0};
+    int32_t prim = RT_RAY_MISS, obj_id = -1;
+    RtRayHits hits = {&t, point, normal, nullptr, &prim, &obj_id, nullptr};
+    RtRayQueryParams query;
+    rt_ray_query_params_default(&query);
+    const int rc = rt_trace_rays(scene, &rays, 1, &query, &hits);
+    if (rc != RT_OK) {
+        fprintf(stderr, "%s: %s\n", rt_strerror(rc), rt_last_error_message());
+        return rc;
+    }
+    if (prim < 0) printf("pick %d %d miss\n", x, y);
+    else
+        printf("pick %d %d %d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", x, y, (int)prim, (int)obj_id, t, point[0], point[1],
+               point[2], normal[0], normal[1], normal[2]);
+    return RT_OK;
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
@@ -67,7 +99,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample] [--preview-temporal K]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample] [--preview-temporal K] [--pick X,Y]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -82,6 +114,11 @@ int main(int argc, char **argv) {
     rth_session_params(session, args.preview_upsample || args.preview_temporal > 0 ? 1 : 0, &params); // ... the `preview:` block
     if (args.devices < 1) {
         fprintf(stderr, "--devices must be at least 1\n");
+        rth_session_close(session);
+        return RT_ERR_ARGUMENT_PARSING;
+    }
+    if (args.pick && (args.pick_x >= params.width || args.pick_y >= params.height)) {
+        fprintf(stderr, "--pick %d,%d lies outside the %d x %d image\n", args.pick_x, args.pick_y, params.width, params.height);
         rth_session_close(session);
         return RT_ERR_ARGUMENT_PARSING;
     }
@@ -278,6 +315,7 @@ int main(int argc, char **argv) {
             else fprintf(stderr, "No output directory for saving pngs. Skipping.\n");
         }
     }
+    if (rc == RT_OK && args.pick) rc = pick_pixel(scenes[0], rth_session_camera(session), params, args.pick_x, args.pick_y);
     destroy_scenes();
     rth_session_close(session);
     return rc;
