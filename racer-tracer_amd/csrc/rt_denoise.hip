@@ -271,8 +271,7 @@ int denoise_device(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d
     if (!rgb || !out) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device/out_device is NULL");
     if (rgb == out) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device and out_device must differ");
     if (!rtapi::guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
-    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    RT_HIP(hipSetDevice(s->device));
+    if ((rc = rtapi::use_scene_device(s)) != RT_OK) return rc;
     if ((rc = rtapi::reserve_denoise(s, (size_t)p->width * (size_t)p->height, false)) != RT_OK) return rc;
     return rtapi::enqueue_denoise(s, p, d, rgb, *g, out, (hipStream_t)stream);
 }

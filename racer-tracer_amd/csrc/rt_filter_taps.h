@@ -1,8 +1,9 @@
-// rt_filter_taps.h — the tap loops and weights that the three guide-aware filter units share: rt_denoise.hip (the a-trous
-// level), rt_temporal.hip (the variance-guided level, the variance of a history) and rt_variance_filter.hip (the variance
-// of a still frame).  DESIGN.md 4.6, 4.11 and 4.12 define them; tests hold the paths to each other bit for bit, which
-// they are because each is one function here.  Everything is f64, lane = pixel, 16x16 pixels per block, and every loop
-// adds in one fixed order (dy, then dx).
+// rt_filter_taps.h — the tap loops and weights that the five guide-aware filter units share: rt_denoise.hip (the a-trous
+// level), rt_temporal.hip (the variance-guided level, the variance of a history), rt_variance_filter.hip (the variance
+// of a still frame), and rt_upsample.hip and rt_preview_temporal.hip (the blend of a preview's four anchors, at phase
+// (0, 0) and at a frame's own).  DESIGN.md 4.6 and 4.11 to 4.14 define them; tests hold the paths to each other bit for
+// bit, which they are because each is one function here.  Everything is f64, lane = pixel, 16x16 pixels per block, and
+// every loop adds in one fixed order (dy, then dx; the anchors j, then i).
 //
 // The kernels that call these keep their names, arguments and launch shapes; against the hand-copied bodies they compile
 // to the same floating-point instructions in the same registers, with other integer address and branch glue (LABNOTES).
@@ -135,6 +136,56 @@ __device__ __forceinline__ double spatial_variance(int px, int py, int width, in
     }
     const double mean = s1 / s0; // the centre tap weighs 1, so a pixel alone in its window has none
     return fmax(0.0, s2 / s0 - __dmul_rn(mean, mean));
+}
+
+// (i0, i1, t) of one axis of the preview's grid shifted by the phase j: the anchors of column i sit at x = i step + j
+__device__ __forceinline__ void shifted_axis(int x, int j, int step, int count, int &i0, int &i1, double &t) {
+    const int xs = x - j;
+    i0 = xs < 0 ? 0 : min(xs / step, count - 1);
+    i1 = min(i0 + 1, count - 1);
+    t = (xs < 0 || i1 == i0) ? 0.0 : (double)(xs - i0 * step) / (double)step;
+}
+
+// the four anchors' weighted sum for one pixel; (i0, j0) is its first anchor
+struct AnchorBlend {
+    d3 acc;
+    double wsum;
+    int i0, j0;
+};
+
+// DESIGN.md 4.13's blend of the anchors (j0,i0) (j0,i1) (j1,i0) (j1,i1) around pixel p = (px, py) of the preview frame
+// `rgb`, on the grid of P (step_x, step_y, gx, gy) shifted by the phase (jx, jy) of 4.14: b = by bx, a tap with b == 0 or
+// another obj_id is skipped, w = b w_n w_x, the value demodulated.  An anchor's guides are read at the pixel it traced,
+// (i step_x + jx, j step_y + jy), its colour at its block's top-left pixel; at phase (0, 0) the two are one pixel.
+template <class Args>
+__device__ __forceinline__ AnchorBlend anchor_blend(const Args &P, int jx, int jy, const double *__restrict__ rgb,
+                                                    const RtGuides &G, int px, int py, size_t p, int id, d3 np, d3 xp) {
+    AnchorBlend r;
+    int i1, j1;
+    double tx, ty;
+    shifted_axis(px, jx, P.step_x, P.gx, r.i0, i1, tx);
+    shifted_axis(py, jy, P.step_y, P.gy, r.j0, j1, ty);
+    const int qi[2] = {r.i0, i1}, qj[2] = {r.j0, j1};
+    const double bx[2] = {1.0 - tx, tx}, by[2] = {1.0 - ty, ty};
+    const double inv_fx = P.inv_sx / G.footprint[p]; // a miss has footprint inf: 0
+    r.acc = mk(0.0, 0.0, 0.0);
+    r.wsum = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double b = by[k >> 1] * bx[k & 1];
+        if (b == 0.0) continue;
+        const int ay = qj[k >> 1] * P.step_y, ax = qi[k & 1] * P.step_x; // the block's top-left pixel: the colour
+        const size_t qc = (size_t)ay * (size_t)P.width + (size_t)ax;
+        const size_t q = (size_t)(ay + jy) * (size_t)P.width + (size_t)(ax + jx); // the pixel it traced: the guides
+        if (G.obj_id[q] != id) continue; // (-1 == -1: sky interpolates between sky anchors)
+        const double w = guide_stops(b, P.inv_sn2, P.inv_sx, inv_fx, np, xp, G, q);
+        const d3 v = mk(demodulated(rgb[3 * qc + 0], G.albedo[3 * q + 0], P.demodulate),
+                        demodulated(rgb[3 * qc + 1], G.albedo[3 * q + 1], P.demodulate),
+                        demodulated(rgb[3 * qc + 2], G.albedo[3 * q + 2], P.demodulate));
+        r.acc = r.acc + w * v;
+        r.wsum += w;
+    }
+    return r;
 }
 
 } // namespace RT_KNS

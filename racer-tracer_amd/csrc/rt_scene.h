@@ -341,6 +341,12 @@ inline void note_launches(RtScene *s, int launches) {
     s->last_launches = launches;
     s->summed_times = false;
 }
+// The last check of a device-side entry point and its first step: there is a scene, and its device is the current one
+inline int use_scene_device(const RtScene *s) {
+    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    RT_HIP(hipSetDevice(s->device));
+    return RT_OK;
+}
 } // namespace rtapi
 
 // Internal exports for the tests (not part of rt_abi.h; the ABI version does not cover them).
@@ -406,9 +412,6 @@ int enqueue_chunks(RtScene *s, PoolPasses &pp, int c0, int c1, hipStream_t strea
 // scene_guides: those planes as an RtGuides.  enqueue_guides / enqueue_denoise: the guide launch and the filter's
 // launches on `stream` (arguments checked by the caller).
 int check_denoise(const RtRenderParams *p, const RtDenoiseParams *d);
-// What the entry points that take a preview frame (rt_upsample.hip, rt_preview_temporal.hip) refuse about params and
-// denoise; `full` becomes params at full resolution (scale 0), what the guides and the filter's levels take.
-int check_upsample(const RtRenderParams *p, const RtDenoiseParams *d, RtRenderParams &full);
 // What the three filter units (rt_denoise.hip, rt_temporal.hip, rt_variance_filter.hip) share on the host.
 // guides_complete: no NULL among a caller's guide planes.  pixel_grid: 16x16 pixels per block of 256 lanes.
 // filter_stops: the inverse sigmas of a-trous level `level` (step 2^level) as the kernels take them, 0 where a stop is
@@ -421,6 +424,23 @@ struct FilterStops {
     double inv_sc2; // 1 / (sigma_c * 2^-level)^2
 };
 FilterStops filter_stops(const RtDenoiseParams *d, int level = 0);
+// What the entry points that take a preview frame (rt_upsample.hip, rt_preview_temporal.hip) refuse about params and
+// denoise; `full` becomes params at full resolution (scale 0), what the guides and the filter's levels take.
+int check_upsample(const RtRenderParams *p, const RtDenoiseParams *d, RtRenderParams &full);
+// ... and what their kernels' argument blocks (UpsampleArgs, PreviewAccumulateArgs) say about such a frame: the image, the
+// preview's grid with its anchors per row and column, and the blend's stops
+template <class Args> void fill_upsample_args(Args &a, const RtRenderParams *p, const RtDenoiseParams *d) {
+    const PreviewGrid pg = preview_grid(p);
+    a.width = p->width;
+    a.height = p->height;
+    a.step_x = pg.step_x;
+    a.step_y = pg.step_y;
+    a.gx = p->width / pg.step_x;
+    a.gy = p->height / pg.step_y;
+    a.demodulate = (d->flags & RT_DENOISE_DEMODULATE) != 0;
+    a.inv_sn2 = filter_stops(d).inv_sn2;
+    a.inv_sx = d->sigma_plane > 0.0 ? 1.0 / (d->sigma_plane * (double)(pg.step_x > pg.step_y ? pg.step_x : pg.step_y)) : 0.0;
+}
 // The levels of a demodulated frame and its re-modulation into `out`: plain levels (rt_denoise_device's) with
 // sigma_l <= 0, else variance-guided ones over `variance` (W*H).  The scene's scratch holds two colour buffers and, behind
 // them, two variance planes (8 W*H doubles, reserved here); `variance` may be the SECOND of those planes — level 0 reads

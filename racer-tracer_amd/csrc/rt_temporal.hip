@@ -11,13 +11,17 @@
 //               filtered alongside with the squared weights
 // With sigma_luminance <= 0 the levels are rt_denoise.hip's own launches, and the re-modulation always is.
 // The demodulation, the 7x7 window and the level are rt_filter_taps.h's demodulated, spatial_variance and
-// atrous_pixel<true>: the kernels here are its callers, as rt_denoise.hip's and rt_variance_filter.hip's are.
+// atrous_pixel<true>: the kernels here are its callers, as rt_denoise.hip's and rt_variance_filter.hip's are.  The
+// re-projection with its taps, the blend and the stores of a history pixel are rt_history_taps.h's, which
+// k_preview_accumulate (rt_preview_temporal.hip) calls too; the host side lends that unit its checks, the fill of the
+// argument block's history fields and the whole-frame sequence (rt_temporal_state.h).
 //
 // Compiled once, with the fast arithmetic, as rt_denoise.hip.  Lane = pixel, 16x16 pixels per block, taps straight from
 // global memory.  The launchers have internal linkage, but for rtdev_launch_atrous_var (rt_scene.h), through which
 // rtapi::enqueue_levels (rt_denoise.hip) runs the levels of a history here and of a still frame's batch variance.
 #include "rt_trace_common.h"
 #include "rt_filter_taps.h"
+#include "rt_history_taps.h"
 #include "rt_scene.h"
 #include "rt_temporal_state.h"
 
@@ -35,13 +39,7 @@ struct AccumulateArgs {
     double plane_tol;
 };
 
-__device__ __forceinline__ d3 cross3(d3 a, d3 b) {
-    return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-}
-
-// One pixel of the accumulation.  Whether a history tap exists is decided on doubles: no index is formed, and nothing
-// of the previous history is loaded, before the re-projected position is known to be finite and within one pixel of the
-// previous image, and every tap is bounds-checked on its own.
+// One pixel of the accumulation (rt_history_taps.h): the pixel's own sample first, then its history.
 __global__ __launch_bounds__(256) void k_temporal_accumulate(const AccumulateArgs P, const double *__restrict__ g,
                                                              const RtGuides G, const RtHistory prev, const RtHistory out) {
     const int px = blockIdx.x * 16 + (threadIdx.x & 15);
@@ -56,72 +54,10 @@ __global__ __launch_bounds__(256) void k_temporal_accumulate(const AccumulateArg
     const int id = G.obj_id[p];
     const d3 np = ld3(G.normal + 3 * p), xp = ld3(G.position + 3 * p);
 
-    d3 rad = cp;
-    double m1 = lp, m2 = lp * lp, len = 1.0;
-    if (P.has_prev && id >= 0) {
-        // ulc + u hor - v ver - o = s (x - o): columns hor, -ver, -(x - o) against o - ulc
-        const d3 o = ld3(P.o);
-        const d3 a = ld3(P.hor), b = -ld3(P.ver), cc = -(xp - o), r = o - ld3(P.ulc);
-        const d3 bxc = cross3(b, cc);
-        const double det = dot(a, bxc);
-        const double u = dot(r, bxc) / det;
-        const double v = dot(a, cross3(r, cc)) / det;
-        const double s = dot(a, cross3(b, r)) / det;
-        const double fx = u * (double)(P.width - 1) - 0.5;
-        const double fy = v * (double)(P.height - 1) - 0.5;
-        // (a NaN fails every comparison below)
-        const bool inside = det != 0.0 && s > 0.0 && fx >= -1.0 && fx <= (double)P.width && fy >= -1.0 && fy <= (double)P.height;
-        if (inside) {
-            const double flx = floor(fx), fly = floor(fy);
-            const int x0 = (int)flx, y0 = (int)fly; // in [-1, W] and [-1, H]
-            const double tx = fx - flx, ty = fy - fly;
-            const double fp = G.footprint[p];
-            d3 ch = mk(0.0, 0.0, 0.0);
-            double mh1 = 0.0, mh2 = 0.0, lh = 0.0, wsum = 0.0;
-            for (int j = 0; j < 2; ++j) {
-                const int qy = y0 + j;
-                if (qy < 0 || qy >= P.height) continue;
-                for (int i = 0; i < 2; ++i) {
-                    const int qx = x0 + i;
-                    if (qx < 0 || qx >= P.width) continue;
-                    const size_t q = (size_t)qy * (size_t)P.width + (size_t)qx;
-                    if (prev.obj_id[q] != id) continue;
-                    const d3 dn = np - ld3(prev.normal + 3 * q);
-                    if (!(len2(dn) <= P.normal_tol2)) continue;
-                    const double dist = dot(np, ld3(prev.position + 3 * q) - xp);
-                    if (!(fabs(dist) <= P.plane_tol * fp)) continue;
-                    const double w = (i ? tx : 1.0 - tx) * (j ? ty : 1.0 - ty);
-                    ch = ch + w * ld3(prev.radiance + 3 * q);
-                    mh1 += w * prev.moments[2 * q + 0];
-                    mh2 += w * prev.moments[2 * q + 1];
-                    lh += w * prev.length[q];
-                    wsum += w;
-                }
-            }
-            if (wsum >= 1e-3) {
-                const double inv = 1.0 / wsum;
-                const double N = lh * inv + 1.0;
-                const double al = fmax(1.0 / N, P.alpha), am = fmax(1.0 / N, P.alpha_moments);
-                rad = (1.0 - al) * (ch * inv) + al * cp;
-                m1 = (1.0 - am) * (mh1 * inv) + am * lp;
-                m2 = (1.0 - am) * (mh2 * inv) + am * (lp * lp);
-                len = fmin(N, P.max_history);
-            }
-        }
-    }
-    out.radiance[3 * p + 0] = rad.x;
-    out.radiance[3 * p + 1] = rad.y;
-    out.radiance[3 * p + 2] = rad.z;
-    out.moments[2 * p + 0] = m1;
-    out.moments[2 * p + 1] = m2;
-    out.length[p] = len;
-    out.normal[3 * p + 0] = np.x;
-    out.normal[3 * p + 1] = np.y;
-    out.normal[3 * p + 2] = np.z;
-    out.position[3 * p + 0] = xp.x;
-    out.position[3 * p + 1] = xp.y;
-    out.position[3 * p + 2] = xp.z;
-    out.obj_id[p] = id;
+    HistoryPixel v = fresh_pixel(cp, lp);
+    HistorySums h;
+    if (P.has_prev && id >= 0 && history_value<false>(P, G, prev, p, id, np, xp, h)) v = blended_pixel(P, h, cp, lp);
+    store_history(out, p, v, np, xp, id);
 }
 
 struct VarianceArgs {
@@ -176,29 +112,19 @@ namespace {
 using rtapi::guides_complete;
 using rtapi::pixel_grid;
 
-hipError_t launch_accumulate(const RtRenderParams *p, const RtTemporalParams *t, int demodulate, const double *rgb,
-                             const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out,
-                             hipStream_t stream) {
+int enqueue_accumulate(const RtRenderParams *p, const RtTemporalParams *t, const RtDenoiseParams *d, const double *rgb,
+                       const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out,
+                       hipStream_t stream) {
     RT_KNS::AccumulateArgs a;
     memset(&a, 0, sizeof a);
     a.width = p->width;
     a.height = p->height;
-    a.has_prev = prev != nullptr;
-    a.demodulate = demodulate;
-    if (prev_camera) {
-        memcpy(a.o, prev_camera->origin, sizeof a.o);
-        memcpy(a.ulc, prev_camera->upper_left_corner, sizeof a.ulc);
-        memcpy(a.hor, prev_camera->horizontal, sizeof a.hor);
-        memcpy(a.ver, prev_camera->vertical, sizeof a.ver);
-    }
-    a.alpha = t->alpha;
-    a.alpha_moments = t->alpha_moments;
-    a.max_history = t->max_history;
-    a.normal_tol2 = t->normal_tolerance * t->normal_tolerance;
-    a.plane_tol = t->plane_tolerance;
+    a.demodulate = (d->flags & RT_DENOISE_DEMODULATE) != 0;
+    rtapi::fill_history_args(a, t, prev_camera);
     hipLaunchKernelGGL(RT_KNS::k_temporal_accumulate, pixel_grid(p->width, p->height), dim3(256), 0, stream, a, rgb, *g,
                        prev ? *prev : *out, *out);
-    return hipGetLastError();
+    RT_HIP(hipGetLastError());
+    return RT_OK;
 }
 
 hipError_t launch_variance(const RtRenderParams *p, const RtDenoiseParams *d, const RtHistory *h, const RtGuides *g, double *var,
@@ -266,6 +192,38 @@ int enqueue_denoise_history(RtScene *s, const RtRenderParams *p, const RtDenoise
     return rtapi::enqueue_levels(s, p, d, var ? t->sigma_luminance : 0.0, h->radiance, var, *g, out, stream);
 }
 
+int render_into_state(RtScene *s, RtTemporal *t, const char *v1_message, const RtCamera *camera, const RtCamera *render_camera,
+                      const RtRenderParams *p, const RtRenderParams *full, const RtTemporalParams *tp, const RtDenoiseParams *d,
+                      const EnqueueAccumulate &accumulate, double *out_rgb, double *out_length) {
+    if (!out_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgb_host is NULL");
+    if (!t) return fail(RT_ERR_INVALID_ARGUMENT, "temporal_state is NULL");
+    if (p->width != t->width || p->height != t->height)
+        return fail(RT_ERR_INVALID_ARGUMENT, "params->width and height must be the RtTemporal's");
+    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (s->device != t->device) return fail(RT_ERR_INVALID_ARGUMENT, "the scene and the RtTemporal must be on the same device");
+    if (s->use_v1) return fail(RT_ERR_UNSUPPORTED, v1_message);
+    RT_HIP(hipSetDevice(s->device));
+    const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
+    const hipStream_t stream = s->buf.stream;
+    double *frame = state_frame(t), *filtered = frame + n;
+    const RtGuides g = state_guides(t);
+    const RtHistory prev = state_history(t, t->current), next = state_history(t, t->current ^ 1);
+    int rc = enqueue_render(s, render_camera, p, frame, stream, 0, Cancel());
+    if (rc != RT_OK) return rc;
+    if ((rc = enqueue_guides(s, camera, full, g, stream)) != RT_OK) return rc;
+    if ((rc = accumulate(frame, &g, t->has_prev ? &t->camera : nullptr, t->has_prev ? &prev : nullptr, &next, stream)) != RT_OK)
+        return rc;
+    if ((rc = enqueue_denoise_history(s, full, d, tp, &next, &g, filtered, stream)) != RT_OK) return rc;
+    RT_HIP(hipMemcpyAsync(out_rgb, filtered, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (out_length) RT_HIP(hipMemcpyAsync(t->host_length, next.length, pixels * sizeof(double), hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    if (out_length) memcpy(out_length, t->host_length, pixels * sizeof(double));
+    t->current ^= 1;
+    t->has_prev = true;
+    t->camera = *camera;
+    return RT_OK;
+}
+
 } // namespace rtapi
 
 namespace {
@@ -274,15 +232,6 @@ using rtapi::check_temporal;
 using rtapi::enqueue_denoise_history;
 using rtapi::history_complete;
 using rtapi::kStateDoubles;
-using rtapi::state_guides;
-using rtapi::state_history;
-
-int enqueue_accumulate(const RtRenderParams *p, const RtTemporalParams *t, const RtDenoiseParams *d, const double *rgb,
-                       const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out,
-                       hipStream_t stream) {
-    RT_HIP(launch_accumulate(p, t, (d->flags & RT_DENOISE_DEMODULATE) != 0, rgb, g, prev_camera, prev, out, stream));
-    return RT_OK;
-}
 
 int accumulate_device(RtScene *s, const RtRenderParams *p, const RtTemporalParams *t, const RtDenoiseParams *d, const double *rgb,
                       const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev, const RtHistory *out, void *stream) {
@@ -290,8 +239,7 @@ int accumulate_device(RtScene *s, const RtRenderParams *p, const RtTemporalParam
     if (rc != RT_OK) return rc;
     if ((rc = check_temporal(t)) != RT_OK) return rc;
     if ((rc = rtapi::check_accumulate_buffers(rgb, g, prev_camera, prev, out)) != RT_OK) return rc;
-    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    RT_HIP(hipSetDevice(s->device));
+    if ((rc = rtapi::use_scene_device(s)) != RT_OK) return rc;
     return enqueue_accumulate(p, t, d, rgb, g, prev_camera, prev, out, (hipStream_t)stream);
 }
 
@@ -304,8 +252,7 @@ int denoise_history_device(RtScene *s, const RtRenderParams *p, const RtDenoiseP
     if (!guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
     if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out_device is NULL");
     if (out == h->radiance) return fail(RT_ERR_INVALID_ARGUMENT, "out_device and the history's radiance must differ");
-    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    RT_HIP(hipSetDevice(s->device));
+    if ((rc = rtapi::use_scene_device(s)) != RT_OK) return rc;
     return enqueue_denoise_history(s, p, d, t, h, g, out, (hipStream_t)stream);
 }
 
@@ -348,33 +295,12 @@ int render_temporal(RtScene *s, RtTemporal *t, const RtCamera *camera, const RtR
     if (rc != RT_OK) return rc;
     if ((rc = check_temporal(tp)) != RT_OK) return rc;
     if ((rc = rtapi::check_params(camera, p)) != RT_OK) return rc;
-    if (!out_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgb_host is NULL");
-    if (!t) return fail(RT_ERR_INVALID_ARGUMENT, "temporal_state is NULL");
-    if (p->width != t->width || p->height != t->height)
-        return fail(RT_ERR_INVALID_ARGUMENT, "params->width and height must be the RtTemporal's");
-    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    if (s->device != t->device) return fail(RT_ERR_INVALID_ARGUMENT, "the scene and the RtTemporal must be on the same device");
-    if (s->use_v1) return fail(RT_ERR_UNSUPPORTED, "rt_render_temporal needs the pooled kernel");
-    RT_HIP(hipSetDevice(s->device));
-    const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
-    const hipStream_t stream = s->buf.stream;
-    double *frame = rtapi::state_frame(t), *filtered = frame + n;
-    const RtGuides g = state_guides(t);
-    const RtHistory prev = state_history(t, t->current), next = state_history(t, t->current ^ 1);
-    if ((rc = rtapi::enqueue_render(s, camera, p, frame, stream, 0, rtapi::Cancel())) != RT_OK) return rc;
-    if ((rc = rtapi::enqueue_guides(s, camera, p, g, stream)) != RT_OK) return rc;
-    if ((rc = enqueue_accumulate(p, tp, d, frame, &g, t->has_prev ? &t->camera : nullptr, t->has_prev ? &prev : nullptr, &next,
-                                 stream)) != RT_OK)
-        return rc;
-    if ((rc = enqueue_denoise_history(s, p, d, tp, &next, &g, filtered, stream)) != RT_OK) return rc;
-    RT_HIP(hipMemcpyAsync(out_rgb, filtered, n * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (out_length) RT_HIP(hipMemcpyAsync(t->host_length, next.length, pixels * sizeof(double), hipMemcpyDeviceToHost, stream));
-    RT_HIP(hipStreamSynchronize(stream));
-    if (out_length) memcpy(out_length, t->host_length, pixels * sizeof(double));
-    t->current ^= 1;
-    t->has_prev = true;
-    t->camera = *camera;
-    return RT_OK;
+    const auto accumulate = [&](const double *frame, const RtGuides *g, const RtCamera *prev_camera, const RtHistory *prev,
+                                const RtHistory *out, hipStream_t stream) {
+        return enqueue_accumulate(p, tp, d, frame, g, prev_camera, prev, out, stream);
+    };
+    return rtapi::render_into_state(s, t, "rt_render_temporal needs the pooled kernel", camera, camera, p, p, tp, d, accumulate,
+                                    out_rgb, out_length);
 }
 
 } // namespace

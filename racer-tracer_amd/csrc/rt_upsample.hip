@@ -8,7 +8,9 @@
 //            inv_sx = 1 / (sigma_plane max(step_x, step_y)); value g_q^2 (/ max(albedo_q, 1e-3));
 //   output   sqrt(max(acc / wsum (* albedo_p), 0)), or with wsum == 0 the input at anchor (j0, i0), bit for bit.
 // Everything is f64, lane = pixel, 16x16 pixels per block as the other filter kernels; the four taps (10 doubles each)
-// are read straight from global memory.  tests/upsample_model.py restates it in this order.
+// are read straight from global memory.  tests/upsample_model.py restates it in this order.  The taps' loop is
+// rt_filter_taps.h's anchor_blend at phase (0, 0); k_preview_accumulate's fill (rt_preview_temporal.hip) is the same
+// function at a frame's phase.
 //
 // Compiled once, with the fast arithmetic, like rt_denoise.hip.
 #include "rt_filter_taps.h"
@@ -33,40 +35,19 @@ __global__ __launch_bounds__(256) void k_upsample_preview(const UpsampleArgs P, 
     if (px >= P.width || py >= P.height) return;
     const size_t p = (size_t)py * (size_t)P.width + (size_t)px;
 
-    // the anchors around p: columns i0 <= i1 < gx, rows j0 <= j1 < gy, all of them pixels inside the covered area
-    const int i0 = min(px / P.step_x, P.gx - 1), i1 = min(i0 + 1, P.gx - 1);
-    const int j0 = min(py / P.step_y, P.gy - 1), j1 = min(j0 + 1, P.gy - 1);
-    const double tx = i1 == i0 ? 0.0 : (double)(px - i0 * P.step_x) / (double)P.step_x;
-    const double ty = j1 == j0 ? 0.0 : (double)(py - j0 * P.step_y) / (double)P.step_y;
-    const int qi[2] = {i0, i1}, qj[2] = {j0, j1};
-    const double bx[2] = {1.0 - tx, tx}, by[2] = {1.0 - ty, ty};
-
+    // the anchors around p on the unshifted grid: columns i0 <= i1 < gx, rows j0 <= j1 < gy, all of them pixels inside the
+    // covered area (rt_filter_taps.h)
     const int id = G.obj_id[p];
     const d3 np = ld3(G.normal + 3 * p), xp = ld3(G.position + 3 * p);
-    const double inv_fx = P.inv_sx / G.footprint[p]; // a miss has footprint inf: 0
-    d3 acc = mk(0.0, 0.0, 0.0);
-    double wsum = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double b = by[k >> 1] * bx[k & 1];
-        if (b == 0.0) continue;
-        const size_t q = (size_t)(qj[k >> 1] * P.step_y) * (size_t)P.width + (size_t)(qi[k & 1] * P.step_x);
-        if (G.obj_id[q] != id) continue; // (-1 == -1: sky interpolates between sky anchors)
-        const double w = guide_stops(b, P.inv_sn2, P.inv_sx, inv_fx, np, xp, G, q);
-        const d3 v = mk(demodulated(rgb[3 * q + 0], G.albedo[3 * q + 0], P.demodulate),
-                        demodulated(rgb[3 * q + 1], G.albedo[3 * q + 1], P.demodulate),
-                        demodulated(rgb[3 * q + 2], G.albedo[3 * q + 2], P.demodulate));
-        acc = acc + w * v;
-        wsum += w;
-    }
-    if (wsum > 0.0) {
-        d3 L = mk(acc.x / wsum, acc.y / wsum, acc.z / wsum);
+    const AnchorBlend a = anchor_blend(P, 0, 0, rgb, G, px, py, p, id, np, xp);
+    if (a.wsum > 0.0) {
+        d3 L = mk(a.acc.x / a.wsum, a.acc.y / a.wsum, a.acc.z / a.wsum);
         if (P.demodulate) L = mk(L.x * G.albedo[3 * p + 0], L.y * G.albedo[3 * p + 1], L.z * G.albedo[3 * p + 2]);
         out[3 * p + 0] = sqrt(fmax(L.x, 0.0));
         out[3 * p + 1] = sqrt(fmax(L.y, 0.0));
         out[3 * p + 2] = sqrt(fmax(L.z, 0.0));
     } else { // no anchor qualifies: the block's own anchor, as the replicated preview has it
-        const size_t q = (size_t)(j0 * P.step_y) * (size_t)P.width + (size_t)(i0 * P.step_x);
+        const size_t q = (size_t)(a.j0 * P.step_y) * (size_t)P.width + (size_t)(a.i0 * P.step_x);
         out[3 * p + 0] = rgb[3 * q + 0];
         out[3 * p + 1] = rgb[3 * q + 1];
         out[3 * p + 2] = rgb[3 * q + 2];
@@ -120,18 +101,8 @@ int preview_grid(const RtRenderParams *p, int32_t *step_x, int32_t *step_y, int3
 
 int enqueue_upsample(const RtRenderParams *p, const RtDenoiseParams *d, const double *rgb, const RtGuides &g, double *out,
                      hipStream_t stream) {
-    const rtapi::PreviewGrid pg = rtapi::preview_grid(p);
-    const rtapi::FilterStops st = rtapi::filter_stops(d);
     RT_KNS::UpsampleArgs a;
-    a.width = p->width;
-    a.height = p->height;
-    a.step_x = pg.step_x;
-    a.step_y = pg.step_y;
-    a.gx = p->width / pg.step_x;
-    a.gy = p->height / pg.step_y;
-    a.demodulate = (d->flags & RT_DENOISE_DEMODULATE) != 0;
-    a.inv_sn2 = st.inv_sn2;
-    a.inv_sx = d->sigma_plane > 0.0 ? 1.0 / (d->sigma_plane * (double)(pg.step_x > pg.step_y ? pg.step_x : pg.step_y)) : 0.0;
+    rtapi::fill_upsample_args(a, p, d);
     hipLaunchKernelGGL(RT_KNS::k_upsample_preview, rtapi::pixel_grid(p->width, p->height), dim3(256), 0, stream, a, rgb, g, out);
     RT_HIP(hipGetLastError());
     return RT_OK;
@@ -145,8 +116,7 @@ int upsample_preview_device(RtScene *s, const RtRenderParams *p, const RtDenoise
     if (!rgb || !out) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device/out_device is NULL");
     if (rgb == out) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_device and out_device must differ");
     if (!rtapi::guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
-    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    RT_HIP(hipSetDevice(s->device));
+    if ((rc = rtapi::use_scene_device(s)) != RT_OK) return rc;
     return enqueue_upsample(p, d, rgb, *g, out, (hipStream_t)stream);
 }
 

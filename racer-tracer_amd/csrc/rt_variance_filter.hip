@@ -134,8 +134,7 @@ int batch_variance_device(RtScene *s, const RtRenderParams *p, const RtDenoisePa
         return fail(RT_ERR_INVALID_ARGUMENT, "batch_planes or one of its planes is NULL");
     if (!guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
     if (!radiance || !var) return fail(RT_ERR_INVALID_ARGUMENT, "radiance_out_device/variance_out_device is NULL");
-    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    RT_HIP(hipSetDevice(s->device));
+    if ((rc = rtapi::use_scene_device(s)) != RT_OK) return rc;
     return enqueue_batch_variance(p, d, f, b, g, radiance, var, (hipStream_t)stream);
 }
 
@@ -148,8 +147,7 @@ int denoise_variance_device(RtScene *s, const RtRenderParams *p, const RtDenoise
     if (!guides_complete(g)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
     if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out_device is NULL");
     if (out == radiance) return fail(RT_ERR_INVALID_ARGUMENT, "out_device and radiance_device must differ");
-    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    RT_HIP(hipSetDevice(s->device));
+    if ((rc = rtapi::use_scene_device(s)) != RT_OK) return rc;
     return rtapi::enqueue_levels(s, p, d, f->sigma_luminance, radiance, var, *g, out, (hipStream_t)stream);
 }
 

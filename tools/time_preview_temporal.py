@@ -1,4 +1,5 @@
-"""Cost of the jittered preview accumulation on one MI355X -> profiles/preview_temporal.json.
+"""Cost of the jittered preview accumulation on one MI355X -> profiles/preview_temporal.json, or the
+file that --out names (a run of another library, RACER_TRACER_AMD_LIB, beside this tree's).
 
     python tools/time_preview_temporal.py --cost    # kernel times under a rocprofv3 kernel trace of its own
     python tools/time_preview_temporal.py --wall    # host clock of rt_render_preview_temporal beside the two calls it joins
@@ -38,11 +39,11 @@ KERNELS = r"k_(preview_accumulate|temporal_accumulate|upsample_preview)"
 LOOK_FROM, LOOK_AT = (278.0, 278.0, -800.0), (278.0, 278.0, 0.0)
 
 
-def save(section, rows):
-    results = json.load(open(OUT)) if os.path.exists(OUT) else {}
+def save(section, rows, out):
+    results = json.load(open(out)) if os.path.exists(out) else {}
     results[section] = rows
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    json.dump(results, open(OUT, "w"), indent=1)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    json.dump(results, open(out, "w"), indent=1)
 
 
 def _setup():
@@ -109,7 +110,7 @@ def trace_run(reps=6):
     scene.close()
 
 
-def cost():
+def cost(out):
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "trace", "--",
                sys.executable, os.path.abspath(__file__), "--trace-run"]
@@ -131,10 +132,10 @@ def cost():
     if "k_temporal_accumulate" in rows and "k_upsample_preview" in rows:
         rows["sum_of_the_two_it_joins_us"] = rows["k_temporal_accumulate"]["median_us"] + rows["k_upsample_preview"]["median_us"]
     print(json.dumps(rows), flush=True)
-    save("kernels_1920x1080_scale4", rows)
+    save("kernels_1920x1080_scale4", rows, out)
 
 
-def wall(reps=6):
+def wall(out, reps=6):
     rt, pv, pt, session, camera, p = _setup()
     scene = rt.Scene(session)
     full = _full(rt, p)
@@ -161,7 +162,7 @@ def wall(reps=6):
         t.close()
     scene.close()
     print(json.dumps(rows), flush=True)
-    save("wall_1920x1080_scale4", rows)
+    save("wall_1920x1080_scale4", rows, out)
 
 
 if __name__ == "__main__":
@@ -169,10 +170,11 @@ if __name__ == "__main__":
     ap.add_argument("--cost", action="store_true")
     ap.add_argument("--wall", action="store_true")
     ap.add_argument("--trace-run", action="store_true")
+    ap.add_argument("--out", default=OUT, help="the JSON file the results are merged into")
     args = ap.parse_args()
     if args.trace_run:
         trace_run()
     if args.cost:
-        cost()
+        cost(args.out)
     if args.wall:
-        wall()
+        wall(args.out)
