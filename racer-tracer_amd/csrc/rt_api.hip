@@ -113,14 +113,11 @@ int rtapi::fill_trace_args(const RtScene *s, const RtCamera *camera, const RtRen
 // The counters of a delivering launch over `n_tiles` item tiles (zero between launches: fresh ones must be cleared).
 int rtapi::reserve_delivery_counters(RtScene *s, size_t n_tiles) {
     rtapi::RenderBuffers &b = s->buf;
-    if (b.tile_done.count < n_tiles) {
-        RT_HIP(b.tile_done.alloc(n_tiles));
-        b.deliver_dirty = true;
-    }
-    if (b.region_done.count < (size_t)rtdev::RT_MAX_REGIONS) {
-        RT_HIP(b.region_done.alloc((size_t)rtdev::RT_MAX_REGIONS));
-        b.deliver_dirty = true;
-    }
+    bool grew = false;
+    RT_HIP(b.tile_done.reserve(n_tiles, &grew));
+    b.deliver_dirty = b.deliver_dirty || grew;
+    RT_HIP(b.region_done.reserve((size_t)rtdev::RT_MAX_REGIONS, &grew));
+    b.deliver_dirty = b.deliver_dirty || grew;
     return RT_OK;
 }
 using rtapi::reserve_delivery_counters;
@@ -136,8 +133,8 @@ int rtapi::reserve_render_buffers(RtScene *s, const RtRenderParams *p, bool deli
     const int owned = p->scale > 1 ? p->height : owned_rows_of(p); // (the preview's grid is smaller: an upper bound)
     const size_t slice_elems = (size_t)p->width * (size_t)owned * 3;
     const size_t chunks = (size_t)chunk_plan(p->samples).size() - 1;
-    if (s->buf.partial.count < slice_elems * chunks) RT_HIP(s->buf.partial.alloc(slice_elems * chunks));
-    if (s->buf.queue.count < 1) RT_HIP(s->buf.queue.alloc(1));
+    RT_HIP(s->buf.partial.reserve(slice_elems * chunks));
+    RT_HIP(s->buf.queue.reserve(1));
     if (delivering) return reserve_delivery_counters(s, rtapi::tile_count(p->width, owned));
     return RT_OK;
 }
@@ -149,7 +146,7 @@ namespace {
 int enqueue_v1(RtScene *s, rtdev::TraceArgs &a, const RtRenderParams *p, double *out_device, hipStream_t stream, int batch,
                const Cancel &cancel, int &launches) {
     const size_t n = (size_t)p->width * (size_t)p->height * 3;
-    if (s->buf.accum.count < n) RT_HIP(s->buf.accum.alloc(n));
+    RT_HIP(s->buf.accum.reserve(n));
     a.accum = s->buf.accum.ptr;
     RT_HIP(hipMemsetAsync(s->buf.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
     RT_HIP(hipEventRecord(s->buf.ev_begin, stream));
@@ -185,7 +182,7 @@ int rtapi::setup_delivery(RtScene *s, rtdev::TraceArgs &a, const Delivery &deliv
     a.deliver_out = delivery.out;
     a.tile_done = b.tile_done.ptr;
     a.region_done = b.region_done.ptr;
-    a.deliver_flags = b.host_flags;
+    a.deliver_flags = b.host_flags.ptr;
     a.deliver_serial = delivery.serial;
     a.deliver_col_step = delivery.col_step;
     a.deliver_cols = delivery.cols;
@@ -240,8 +237,8 @@ int pool_prologue(RtScene *s, rtdev::TraceArgs &a, const RtCamera *camera, const
     // slices hold the launch's owned rows only (the kernel compacts rows: owned_rows, tile_py0)
     a.slice_rows = a.owned_rows;
     const size_t slice_elems = (size_t)p->width * (size_t)a.slice_rows * 3;
-    if (b.partial.count < slice_elems * (size_t)a.total_chunks) RT_HIP(b.partial.alloc(slice_elems * (size_t)a.total_chunks));
-    if (b.queue.count < n_launches) RT_HIP(b.queue.alloc(n_launches));
+    RT_HIP(b.partial.reserve(slice_elems * (size_t)a.total_chunks));
+    RT_HIP(b.queue.reserve(n_launches));
     a.partial = b.partial.ptr;
     RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), stream));
 #ifdef RT_PROFILE_REGIONS
@@ -399,8 +396,8 @@ int rtapi::wait_event(hipEvent_t ev, const Cancel &cancel) {
 //   the v1 kernel's launches and anything not yet started.
 int rtapi::poison_queue_begin(RtScene *s) {
     // 1. the cancel word in pinned memory, which every wave reads with its next item: a CPU store, lands at once
-    if (s->buf.host_flags) {
-        reinterpret_cast<volatile unsigned int *>(s->buf.host_flags)[rtdev::RT_MAX_REGIONS] = 1u;
+    if (s->buf.host_flags.ptr) {
+        reinterpret_cast<volatile unsigned int *>(s->buf.host_flags.ptr)[rtdev::RT_MAX_REGIONS] = 1u;
         std::atomic_thread_fence(std::memory_order_seq_cst);
     }
     // 2. the item counters themselves, for a launch that has not started yet or a caller without the word (the v1
@@ -445,8 +442,8 @@ int render_frame_rgba8(RtScene *s, const RtCamera *camera, const RtRenderParams 
     RT_HIP(hipSetDevice(s->device));
     rtapi::RenderBuffers &b = s->buf;
     const size_t px = (size_t)p->width * (size_t)p->height;
-    if (b.frame.count < px * 3) RT_HIP(b.frame.alloc(px * 3));
-    if (b.rgba.count < px * 4) RT_HIP(b.rgba.alloc(px * 4));
+    RT_HIP(b.frame.reserve(px * 3));
+    RT_HIP(b.rgba.reserve(px * 4));
     rc = enqueue_render(s, camera, p, b.frame.ptr, b.stream, 0, Cancel());
     if (rc != RT_OK) return rc;
     rc = post_rgba8(s, tm, b.frame.ptr, px, b.rgba.ptr, nullptr, b.stream);

@@ -37,14 +37,9 @@ using rtapi::fail;
 
 // Pinned frame + flags of the call live on shares[0]'s scene.
 int rtapi::ensure_host_frame(RtScene *s, size_t doubles) {
-    if (s->buf.host_frame_count >= doubles) return RT_OK;
+    if (s->buf.host_frame.count >= doubles) return RT_OK; // (the device is made current only where the frame grows)
     RT_HIP(hipSetDevice(s->device));
-    if (s->buf.host_frame) (void)hipHostFree(s->buf.host_frame);
-    s->buf.host_frame = nullptr;
-    s->buf.host_frame_count = 0;
-    RT_HIP(hipHostMalloc((void **)&s->buf.host_frame, doubles * sizeof(double),
-                         hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
-    s->buf.host_frame_count = doubles;
+    RT_HIP(s->buf.host_frame.reserve(doubles, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
     return RT_OK;
 }
 
@@ -62,7 +57,7 @@ struct Share {
 // Blocks until region `r` of `sh` has been published.  RT_ERR_CANCEL_EVENT when the hook is raised first.
 int wait_region(Share &sh, int r, const Cancel &cancel) {
     RtScene *s = sh.scene;
-    const volatile unsigned int *flags = s->buf.host_flags;
+    const volatile unsigned int *flags = s->buf.host_flags.ptr;
     const uint32_t serial = sh.delivery.serial;
     for (unsigned spins = 1;; ++spins) {
         if (flags[r] == serial) {
@@ -172,7 +167,7 @@ int deliver_frame(RtScene *const *scenes, int n, const RtCamera *camera, const R
     for (Share &sh : shares) {
         sh.delivery.regions = rtapi::frame_bands(rtapi::tiles_across(rtapi::owned_rows_of(&sh.params)), rtapi::tiles_across(p->width),
                                                  nee ? rtdev::RT_MAX_REGIONS : rtapi::chunk_count(sh.params.samples));
-        sh.delivery.out = scenes[0]->buf.host_frame;
+        sh.delivery.out = scenes[0]->buf.host_frame.ptr;
         sh.delivery.col_step = p->width;
         sh.delivery.cols = 1;
         sh.delivery.nee = nee;
@@ -185,7 +180,7 @@ int deliver_frame(RtScene *const *scenes, int n, const RtCamera *camera, const R
             rc = wait_region(sh, (int)b, Cancel());
             if (rc != RT_OK) break;
             for (const rtapi::RowRun &run : rtapi::copy_runs(&sh.params, sh.delivery.regions[b], p->height))
-                memcpy(out_rgb + (size_t)run.image_row * row_doubles, scenes[0]->buf.host_frame + (size_t)run.image_row * row_doubles,
+                memcpy(out_rgb + (size_t)run.image_row * row_doubles, scenes[0]->buf.host_frame.ptr + (size_t)run.image_row * row_doubles,
                        (size_t)run.rows * row_doubles * sizeof(double));
         }
     if (rc != RT_OK) {
@@ -221,12 +216,12 @@ int deliver_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const R
     const rtapi::TileGrid grid(p->width, p->height, p->tiles_w, p->tiles_h);
     rc = ensure_host_frame(scenes[0], (size_t)p->width * (size_t)p->height * 3);
     if (rc != RT_OK) return rc;
-    const double *frame = scenes[0]->buf.host_frame;
+    const double *frame = scenes[0]->buf.host_frame.ptr;
     const std::vector<int> columns_after = rtapi::stream_windows(p->width, p->tiles_w, rtapi::tiles_across(p->height)).columns_after;
     if (columns_after.empty()) return fail(RT_ERR_INVALID_ARGUMENT, "empty frame");
     for (Share &sh : shares) {
         sh.delivery.regions = rtapi::stream_windows(p->width, p->tiles_w, rtapi::tiles_across(rtapi::owned_rows_of(&sh.params))).regions;
-        sh.delivery.out = scenes[0]->buf.host_frame;
+        sh.delivery.out = scenes[0]->buf.host_frame.ptr;
         sh.delivery.col_step = grid.width_step;
         sh.delivery.cols = p->tiles_w;
         sh.delivery.nee = nee;
@@ -266,7 +261,7 @@ int deliver_tiles(RtScene *const *scenes, int n, const RtCamera *camera, const R
 int tiles_from_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p, RtTileCallback callback, void *user,
                      const Cancel &cancel) {
     const size_t n = (size_t)p->width * (size_t)p->height * 3;
-    if (s->buf.frame.count < n) RT_HIP(s->buf.frame.alloc(n));
+    RT_HIP(s->buf.frame.reserve(n));
     int rc = ensure_host_frame(s, n);
     if (rc != RT_OK) return rc;
     int batch = 0;
@@ -281,7 +276,7 @@ int tiles_from_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p
                                column_layout ? p->tiles_w : 1);
     hipEvent_t copied = s->buf.ev_resolved; // re-recorded behind the copy: rt_scene_last_stats reads ev_traced -> ev_resolved (+ the copy)
     if (rc == RT_OK) {
-        hipError_t e = hipMemcpyAsync(s->buf.host_frame, s->buf.frame.ptr, n * sizeof(double), hipMemcpyDeviceToHost, s->buf.stream);
+        hipError_t e = hipMemcpyAsync(s->buf.host_frame.ptr, s->buf.frame.ptr, n * sizeof(double), hipMemcpyDeviceToHost, s->buf.stream);
         if (e == hipSuccess) e = hipEventRecord(copied, s->buf.stream);
         if (e != hipSuccess) { // the kernels are in flight on the scene's buffers: drain before the error goes up
             (void)hipStreamSynchronize(s->buf.stream);
@@ -304,13 +299,13 @@ int tiles_from_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p
         const int x = grid.column(ws).at, w = grid.column(ws).size;
         const double *col;
         if (column_layout) {
-            col = s->buf.host_frame + (size_t)p->height * (size_t)x * 3;
+            col = s->buf.host_frame.ptr + (size_t)p->height * (size_t)x * 3;
         } else if (w == p->width || w == 0) {
-            col = s->buf.host_frame; // (w == 0: an empty tile column — more tile columns than pixels — reads nothing)
+            col = s->buf.host_frame.ptr; // (w == 0: an empty tile column — more tile columns than pixels — reads nothing)
         } else {
             column.resize((size_t)w * (size_t)p->height * 3);
             for (int r = 0; r < p->height; ++r)
-                memcpy(&column[(size_t)r * w * 3], s->buf.host_frame + ((size_t)r * p->width + x) * 3, (size_t)w * 3 * sizeof(double));
+                memcpy(&column[(size_t)r * w * 3], s->buf.host_frame.ptr + ((size_t)r * p->width + x) * 3, (size_t)w * 3 * sizeof(double));
             col = column.data();
         }
         if (emit_column(grid, ws, col, callback, user, cancel)) return RT_OK;
@@ -321,7 +316,7 @@ int tiles_from_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p
 // rt_render_frame where the delivering launch does not apply (the v1 kernel, the preview scale): resolve kernel + one copy
 int frame_two_pass(RtScene *s, const RtCamera *camera, const RtRenderParams *p, double *out_rgb) {
     const size_t n = (size_t)p->width * (size_t)p->height * 3;
-    if (s->buf.frame.count < n) RT_HIP(s->buf.frame.alloc(n));
+    RT_HIP(s->buf.frame.reserve(n));
     int rc = rtapi::enqueue_render(s, camera, p, s->buf.frame.ptr, s->buf.stream, 0, Cancel());
     if (rc != RT_OK) {
         (void)hipStreamSynchronize(s->buf.stream);

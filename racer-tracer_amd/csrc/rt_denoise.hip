@@ -177,10 +177,10 @@ int rtapi::check_denoise(const RtRenderParams *p, const RtDenoiseParams *d) {
 int rtapi::reserve_denoise(RtScene *s, size_t pixels, bool own_guides, bool variance_planes) {
     RenderBuffers &b = s->buf;
     const size_t scratch = (variance_planes ? 8 : 6) * pixels;
-    if (b.denoise_scratch.count < scratch) RT_HIP(b.denoise_scratch.alloc(scratch));
+    RT_HIP(b.denoise_scratch.reserve(scratch));
     if (own_guides) {
-        if (b.guide_planes.count < 10 * pixels) RT_HIP(b.guide_planes.alloc(10 * pixels));
-        if (b.guide_ids.count < pixels) RT_HIP(b.guide_ids.alloc(pixels));
+        RT_HIP(b.guide_planes.reserve(10 * pixels));
+        RT_HIP(b.guide_ids.reserve(pixels));
     }
     return RT_OK;
 }
@@ -288,7 +288,7 @@ int denoise_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p, c
     const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
     rtapi::RenderBuffers &b = s->buf;
     if ((rc = rtapi::reserve_denoise(s, pixels, true)) != RT_OK) return rc;
-    if (b.frame.count < 2 * n) RT_HIP(b.frame.alloc(2 * n));
+    RT_HIP(b.frame.reserve(2 * n));
     const hipStream_t stream = b.stream;
     const RtGuides g = rtapi::scene_guides(s, pixels);
     if ((rc = rtapi::enqueue_guides(s, camera, p, g, stream)) != RT_OK) return rc;

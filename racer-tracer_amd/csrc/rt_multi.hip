@@ -66,7 +66,7 @@ int render_multi(RtScene *const *scenes, int n, const RtRenderParams *p, int str
         sh.params = params[(size_t)i];
         RT_HIP(hipSetDevice(sh.scene->device));
         sh.in_place = sh.scene->device == dst_device && !sh.scene->gather_staged;
-        if (!sh.in_place && sh.scene->buf.frame.count < n_elems) RT_HIP(sh.scene->buf.frame.alloc(n_elems));
+        if (!sh.in_place) RT_HIP(sh.scene->buf.frame.reserve(n_elems));
         rc = render.reserve(sh.scene, &sh.params);
         if (rc != RT_OK) return rc;
     }

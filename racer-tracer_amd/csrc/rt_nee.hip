@@ -102,10 +102,10 @@ int rtapi::reserve_nee_buffers(RtScene *s, const RtRenderParams *p, bool deliver
     rtapi::RenderBuffers &b = s->buf;
     if (!delivering) {
         const size_t n = (size_t)p->width * (size_t)p->height * 3;
-        if (b.accum.count < n) RT_HIP(b.accum.alloc(n));
+        RT_HIP(b.accum.reserve(n));
         return RT_OK;
     }
-    if (b.queue.count < 1) RT_HIP(b.queue.alloc(1));
+    RT_HIP(b.queue.reserve(1));
     return rtapi::reserve_delivery_counters(s, rtapi::tile_count(p->width, rtapi::owned_rows_of(p)));
 }
 
@@ -208,7 +208,7 @@ int rtapi::nee_frame_to_host(RtScene *s, const RtCamera *camera, const RtRenderP
     RT_HIP(hipSetDevice(s->device));
     rtapi::RenderBuffers &b = s->buf;
     const size_t n = (size_t)p->width * (size_t)p->height * 3;
-    if (b.frame.count < n) RT_HIP(b.frame.alloc(n));
+    RT_HIP(b.frame.reserve(n));
     const int rc = enqueue_nee(s, camera, p, ls, b.frame.ptr, b.stream);
     if (rc != RT_OK) return rc;
     RT_HIP(hipStreamSynchronize(b.stream));
@@ -289,28 +289,22 @@ int rtapi::set_light_list(RtScene *s, const RtLightListParams &lp) {
     }
     std::vector<double> weights = rtapi::light_pick(s->light_facts, lights, (int)count, lp.pick).p;
 
-    struct Tables { // freed on every way out: after the exchange below they hold the scene's OLD tables
-        rtapi::DevBuf<int32_t> slot, prim;
-        rtapi::DevBuf<double> pick;
-        ~Tables() {
-            slot.release();
-            prim.release();
-            pick.release();
-        }
-    } fresh;
+    // freed on every way out: after the exchange below they hold the scene's OLD tables
+    rtapi::DevBuf<int32_t> fresh_slot, fresh_prim;
+    rtapi::DevBuf<double> fresh_pick;
     auto fill = [](auto &buf, const auto &host) -> hipError_t {
         hipError_t e = buf.alloc(host.size());
         if (e == hipSuccess && !host.empty())
             e = hipMemcpy(buf.ptr, host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice);
         return e;
     };
-    RT_HIP(fill(fresh.slot, t.slot));
-    RT_HIP(fill(fresh.prim, t.prim));
-    RT_HIP(fill(fresh.pick, rows));
+    RT_HIP(fill(fresh_slot, t.slot));
+    RT_HIP(fill(fresh_prim, t.prim));
+    RT_HIP(fill(fresh_pick, rows));
     // nothing below can fail
-    std::swap(s->nee_slot, fresh.slot);
-    std::swap(s->nee_prim, fresh.prim);
-    std::swap(s->nee_pick, fresh.pick);
+    std::swap(s->nee_slot, fresh_slot);
+    std::swap(s->nee_prim, fresh_prim);
+    std::swap(s->nee_pick, fresh_pick);
     s->lights = t.lights;
     s->light_params = lp;
     s->lights_extended = extended;

@@ -70,27 +70,27 @@ int reserve_passes(RtScene *s, const RtRenderParams *p, int passes, size_t n, in
     int rc = nee ? RT_OK : rtapi::reserve_render_buffers(s, p, false);
     if (rc != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
-    if (!nee && b.queue.count < (size_t)passes) RT_HIP(b.queue.alloc((size_t)passes));
-    if (nee && b.partial.count < n) RT_HIP(b.partial.alloc(n)); // (here: the running sums at the last chunk boundary)
-    if (b.accum.count < n) RT_HIP(b.accum.alloc(n));
-    if (b.frame.count < (size_t)slots * n) RT_HIP(b.frame.alloc((size_t)slots * n));
+    if (!nee) RT_HIP(b.queue.reserve((size_t)passes));
+    if (nee) RT_HIP(b.partial.reserve(n)); // (here: the running sums at the last chunk boundary)
+    RT_HIP(b.accum.reserve(n));
+    RT_HIP(b.frame.reserve((size_t)slots * n));
     if ((rc = rtapi::ensure_host_frame(s, (size_t)slots * n)) != RT_OK) return rc;
-    if (!b.stream_copy) RT_HIP(hipStreamCreateWithFlags(&b.stream_copy, hipStreamNonBlocking));
-    for (int k = 0; k < slots; ++k) {
-        if (!b.ev_pass_begin[k]) RT_HIP(hipEventCreate(&b.ev_pass_begin[k]));
-        if (!b.ev_pass_traced[k]) RT_HIP(hipEventCreate(&b.ev_pass_traced[k]));
-        if (!b.ev_folded[k]) RT_HIP(hipEventCreate(&b.ev_folded[k]));
-        if (!b.ev_copied[k]) RT_HIP(hipEventCreateWithFlags(&b.ev_copied[k], hipEventDisableTiming));
-        if (n_tiles && !b.ev_counted[k]) RT_HIP(hipEventCreateWithFlags(&b.ev_counted[k], hipEventDisableTiming));
+    RT_HIP(b.stream_copy.ensure(hipStreamNonBlocking));
+    for (int k = 0; k < slots; ++k) { // (the spans are read with hipEventElapsedTime: timing events)
+        RT_HIP(b.ev_pass_begin[k].ensure());
+        RT_HIP(b.ev_pass_traced[k].ensure());
+        RT_HIP(b.ev_folded[k].ensure());
+        RT_HIP(b.ev_copied[k].ensure(hipEventDisableTiming));
+        if (n_tiles) RT_HIP(b.ev_counted[k].ensure(hipEventDisableTiming));
     }
     if (n_tiles) {
-        if (b.squares.count < n) RT_HIP(b.squares.alloc(n));
-        if (b.tile_stop.count < n_tiles) RT_HIP(b.tile_stop.alloc(n_tiles));
-        if (b.tile_scale.count < n_tiles) RT_HIP(b.tile_scale.alloc(n_tiles));
-        if (b.tile_err.count < 3 * n_tiles) RT_HIP(b.tile_err.alloc(3 * n_tiles));
-        if (b.tile_lists.count < 2 * n_tiles) RT_HIP(b.tile_lists.alloc(2 * n_tiles));
-        if (b.tile_counts.count < (size_t)passes) RT_HIP(b.tile_counts.alloc((size_t)passes));
-        if (!b.host_counts) RT_HIP(hipHostMalloc((void **)&b.host_counts, sizeof(uint32_t) * rtdev::RT_MAX_CHUNKS, hipHostMallocDefault));
+        RT_HIP(b.squares.reserve(n));
+        RT_HIP(b.tile_stop.reserve(n_tiles));
+        RT_HIP(b.tile_scale.reserve(n_tiles));
+        RT_HIP(b.tile_err.reserve(3 * n_tiles));
+        RT_HIP(b.tile_lists.reserve(2 * n_tiles));
+        RT_HIP(b.tile_counts.reserve((size_t)passes));
+        RT_HIP(b.host_counts.reserve(rtdev::RT_MAX_CHUNKS, hipHostMallocDefault));
     }
     return RT_OK;
 }
@@ -126,7 +126,7 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     rtapi::RenderBuffers &b = s->buf;
     // denoised: the guides, the filter's scratch and a third device frame slot, the filter's output
     if (dn && (rc = rtapi::reserve_denoise(s, n / 3, true)) != RT_OK) return rc;
-    if (dn && b.frame.count < 3 * n) RT_HIP(b.frame.alloc(3 * n));
+    if (dn) RT_HIP(b.frame.reserve(3 * n));
     const RtGuides guides = dn ? rtapi::scene_guides(s, n / 3) : RtGuides();
     const hipStream_t stream = b.stream, copy = b.stream_copy;
     rtapi::PoolPasses pp;
@@ -195,10 +195,10 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
         RT_HIP(hipEventRecord(b.ev_folded[slot], stream));
         RT_HIP(hipStreamWaitEvent(copy, b.ev_folded[slot], 0));
         if (ad) { // the count first: the calling thread enqueues the next pass on it, not on the frame
-            RT_HIP(hipMemcpyAsync(b.host_counts + k, b.tile_counts.ptr + k, sizeof(uint32_t), hipMemcpyDeviceToHost, copy));
+            RT_HIP(hipMemcpyAsync(b.host_counts.ptr + k, b.tile_counts.ptr + k, sizeof(uint32_t), hipMemcpyDeviceToHost, copy));
             RT_HIP(hipEventRecord(b.ev_counted[slot], copy));
         }
-        RT_HIP(hipMemcpyAsync(b.host_frame + (size_t)slot * n, dev, n * sizeof(double), hipMemcpyDeviceToHost, copy));
+        RT_HIP(hipMemcpyAsync(b.host_frame.ptr + (size_t)slot * n, dev, n * sizeof(double), hipMemcpyDeviceToHost, copy));
         RT_HIP(hipEventRecord(b.ev_copied[slot], copy));
         return RT_OK;
     };
@@ -226,7 +226,7 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
             const int slot = k % slots;
             if (ad) { // pass k + 1 goes out as soon as it is known to trace something
                 if ((rc2 = rtapi::wait_event(b.ev_counted[slot], cancel)) != RT_OK) return rc2;
-                running = b.host_counts[k];
+                running = b.host_counts.ptr[k];
                 if (running > 0 && enqueued < passes) {
                     if (cancel.raised()) return RT_ERR_CANCEL_EVENT;
                     if ((rc2 = enqueue_pass(enqueued++)) != RT_OK) return rc2;
@@ -240,7 +240,7 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
             RT_HIP(hipEventElapsedTime(&ms, b.ev_pass_traced[slot], b.ev_folded[slot]));
             fold_ms += ms;
             if (cancel.raised()) return RT_ERR_CANCEL_EVENT;
-            if (callback) callback(user, b.host_frame + (size_t)slot * n, starts[(size_t)ends[(size_t)k]], p->samples);
+            if (callback) callback(user, b.host_frame.ptr + (size_t)slot * n, starts[(size_t)ends[(size_t)k]], p->samples);
             delivered = k;
             if (ad) {
                 if (running == 0) break; // every tile has stopped
@@ -271,7 +271,7 @@ int render_progressive(RtScene *s, const RtCamera *camera, const RtRenderParams 
     // adaptive: the outputs are the state of the last callback.  Its frame and tile errors are in slot `delivered` % 3,
     // which no later pass has written (at most two passes run beyond it); a tile stopped after it ran on to its boundary.
     const int slot = delivered % slots, done = starts[(size_t)ends[(size_t)delivered]];
-    memcpy(ad->out_rgb, b.host_frame + (size_t)slot * n, n * sizeof(double));
+    memcpy(ad->out_rgb, b.host_frame.ptr + (size_t)slot * n, n * sizeof(double));
     if (ad->out_tile_error)
         RT_HIP(hipMemcpy(ad->out_tile_error, b.tile_err.ptr + (size_t)slot * n_tiles, n_tiles * sizeof(double), hipMemcpyDeviceToHost));
     if (ad->out_samples) {

@@ -76,9 +76,9 @@ int trace_rays_host(RtScene *s, const RtRays *rays, int64_t n, const RtRayQueryP
     if ((rc = ensure_order(s)) != RT_OK) return rc;
     rtapi::RenderBuffers &b = s->buf;
     const size_t chunk = (size_t)RT_RAYS_HOST_CHUNK;
-    if (b.rays_in.count < 9 * chunk) RT_HIP(b.rays_in.alloc(9 * chunk));
-    if (b.rays_out.count < 9 * chunk) RT_HIP(b.rays_out.alloc(9 * chunk));
-    if (b.rays_ids.count < 3 * chunk) RT_HIP(b.rays_ids.alloc(3 * chunk));
+    RT_HIP(b.rays_in.reserve(9 * chunk));
+    RT_HIP(b.rays_out.reserve(9 * chunk));
+    RT_HIP(b.rays_ids.reserve(3 * chunk));
     const hipStream_t stream = b.stream;
     // the chunk's planes on the device; a plane the caller leaves out is left out there too
     double *in = b.rays_in.ptr, *out = b.rays_out.ptr;

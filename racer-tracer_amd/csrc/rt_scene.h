@@ -1,16 +1,20 @@
 // rt_scene.h — what the host-side translation units of the library share: the RtScene object
 // behind include/rt_abi.h's opaque handle, the RT_HIP check of a runtime call and the one function
-// that enqueues a render (rt_api.hip).  The error helpers are rt_error.h's, the rules that need no
-// device rt_plan.h's.  Private to the library.
+// that enqueues a render (rt_api.hip), with the render buffers a scene carries (RenderBuffers).  The
+// error helpers are rt_error.h's, the rules that need no device rt_plan.h's, the types that own device
+// memory, pinned memory, streams and events rt_resources.h's: nothing here frees by hand.  Holds no
+// kernel and compiles with a plain host compiler (tests/resources_driver.cpp).  Private to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <new>
 #include <string>
 #include <vector>
 #include "rt_device_types.h"
 #include "rt_bvh.h"
 #include "rt_error.h"
 #include "rt_plan.h"
+#include "rt_resources.h"
 #include "../../include/rt_abi.h"
 #include "../../include/rt_rays.h"
 
@@ -101,23 +105,6 @@ struct Launchers {
             return rtapi::fail(RT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));  \
     } while (0)
 
-template <class T> struct DevBuf {
-    T *ptr = nullptr;
-    size_t count = 0;
-    hipError_t alloc(size_t n) {
-        release();
-        if (n == 0) return hipSuccess;
-        hipError_t e = hipMalloc((void **)&ptr, n * sizeof(T));
-        if (e == hipSuccess) count = n;
-        return e;
-    }
-    void release() {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        count = 0;
-    }
-};
-
 // How a caller asks for cancellation: the flag of rt_render, the callback of rt_render_ex, or neither.
 // Polled by the calling thread only.
 struct Cancel {
@@ -140,9 +127,23 @@ struct Delivery {
 };
 
 // Everything a render allocates on first use — slices, the v1 accumulator, frames, the packed RGBA, counters, the pinned
-// frame and flags, streams, events — kept per device across rt_scene_destroy / rt_scene_create (rt_scene_create.hip:
-// render_cache_put / render_cache_take), which move the whole set.
+// frame and flags, streams, events — kept per device across rt_scene_destroy / rt_scene_create (rt_render_cache.h), which
+// move the whole set.  Every resource is an owner of rt_resources.h: the set frees itself, on its own device, and a member
+// added here needs no other line anywhere.  The members are declared streams, events, memory, so that they go in the
+// reverse order: memory, then events, then streams.
 struct RenderBuffers {
+    OwnersDevice device;                // the scene's; made current (and left current) before the members are freed
+    Stream stream;                      // used by the host-output entry points
+    // cancel: the stream whose command processor overwrites the launches' item counters (rt_api.hip: poison_queue)
+    Stream stream_ctl;
+    // rt_render_progressive (rt_progressive.hip), made on its first call: the stream that copies a pass's frame to the host
+    // and, per frame slot (two; three for rt_render_adaptive), the pass's trace span, the end of its fold, the end of the
+    // copy of its running-tile count (adaptive) and the end of its frame's copy
+    Stream stream_copy;
+    Event ev_begin, ev_traced, ev_resolved;
+    Event ev_pass_begin[3], ev_pass_traced[3];
+    Event ev_folded[3], ev_counted[3], ev_copied[3];
+
     DevBuf<double> partial;             // [chunks][owned rows][W][3] per-chunk sums (pooled kernel)
     DevBuf<unsigned int> queue;         // one item counter per launch of a render call
     DevBuf<double> accum;               // running sums, W*H*3 (v1 kernel; the passes of rt_render_progressive)
@@ -152,28 +153,17 @@ struct RenderBuffers {
     DevBuf<double> squares, tile_scale, tile_err;
     DevBuf<int32_t> tile_stop;
     DevBuf<uint32_t> tile_lists, tile_counts;
-    uint32_t *host_counts = nullptr;    // [RT_MAX_CHUNKS] pinned
+    PinnedBuf<uint32_t> host_counts;    // [RT_MAX_CHUNKS]
     DevBuf<uint8_t> rgba;               // packed frame of rt_render_frame_rgba8
     DevBuf<unsigned long long> segments; // rt_device_types.h: RT_STAT_*
-    hipStream_t stream = nullptr;       // used by the host-output entry points
-    hipEvent_t ev_begin = nullptr, ev_traced = nullptr, ev_resolved = nullptr;
     // Delivery (rt_deliver.hip): the launch writes finished pixels straight into `host_frame` — pinned, portable host
     // memory mapped into every device, so several scenes (devices) can fill one frame — and publishes finished regions
     // in `host_flags`; tile_done / region_done are the device counters behind that (zero between launches).
-    double *host_frame = nullptr;
-    size_t host_frame_count = 0;
-    unsigned int *host_flags = nullptr; // [RT_MAX_REGIONS] published regions + [1] the cancel word the waves read (TraceArgs.cancel_flag)
+    PinnedBuf<double> host_frame;
+    PinnedBuf<unsigned int> host_flags; // [RT_MAX_REGIONS] published regions + [1] the cancel word the waves read (TraceArgs.cancel_flag)
     DevBuf<unsigned int> tile_done, region_done;
     uint32_t deliver_serial = 0; // the flags still hold the serials this set published: the counter moves on with the set
     bool deliver_dirty = false;  // a delivering launch was cut short: the counters must be cleared before the next one
-    // cancel: the stream whose command processor overwrites the launches' item counters (rt_api.hip: poison_queue)
-    hipStream_t stream_ctl = nullptr;
-    // rt_render_progressive (rt_progressive.hip), made on its first call: the stream that copies a pass's frame to the host
-    // and, per frame slot (two; three for rt_render_adaptive), the pass's trace span, the end of its fold, the end of the
-    // copy of its running-tile count (adaptive) and the end of its frame's copy
-    hipStream_t stream_copy = nullptr;
-    hipEvent_t ev_pass_begin[3] = {}, ev_pass_traced[3] = {};
-    hipEvent_t ev_folded[3] = {}, ev_counted[3] = {}, ev_copied[3] = {};
     // denoising (rt_denoise.hip), made on first use: the guides of rt_denoise_frame and rt_render_progressive_denoised —
     // planes [normal 3 | position 3 | albedo 3 | footprint 1] x W*H doubles and obj_id x W*H — and the filter's two
     // ping-pong buffers of W*H*3 doubles each
@@ -186,46 +176,21 @@ struct RenderBuffers {
     DevBuf<double> rays_in, rays_out;
     DevBuf<int32_t> rays_ids;
 
+    RenderBuffers() = default;
+    RenderBuffers(RenderBuffers &&) = default;
+    // what the target held is freed as a whole set — on ITS device, in the order above — before it takes the other over
+    RenderBuffers &operator=(RenderBuffers &&o) noexcept {
+        if (this != &o) {
+            this->~RenderBuffers();
+            new (this) RenderBuffers(std::move(o));
+        }
+        return *this;
+    }
+    ~RenderBuffers() { device.make_current(); }
+
     // what rt_scene_create makes when it takes no set over: only such a set is worth caching
     bool complete() const {
-        return stream && stream_ctl && ev_begin && ev_traced && ev_resolved && host_flags && segments.ptr;
-    }
-    void free_all(int device) {
-        (void)hipSetDevice(device);
-        partial.release();
-        queue.release();
-        accum.release();
-        frame.release();
-        squares.release();
-        tile_scale.release();
-        tile_err.release();
-        tile_stop.release();
-        tile_lists.release();
-        tile_counts.release();
-        if (host_counts) (void)hipHostFree(host_counts);
-        rgba.release();
-        segments.release();
-        guide_planes.release();
-        denoise_scratch.release();
-        guide_ids.release();
-        batch_counts.release();
-        rays_in.release();
-        rays_out.release();
-        rays_ids.release();
-        tile_done.release();
-        region_done.release();
-        if (host_frame) (void)hipHostFree(host_frame);
-        if (host_flags) (void)hipHostFree(host_flags);
-        if (ev_begin) (void)hipEventDestroy(ev_begin);
-        if (ev_traced) (void)hipEventDestroy(ev_traced);
-        if (ev_resolved) (void)hipEventDestroy(ev_resolved);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (stream_ctl) (void)hipStreamDestroy(stream_ctl);
-        for (hipEvent_t *evs : {ev_pass_begin, ev_pass_traced, ev_folded, ev_counted, ev_copied})
-            for (int k = 0; k < 3; ++k)
-                if (evs[k]) (void)hipEventDestroy(evs[k]);
-        if (stream_copy) (void)hipStreamDestroy(stream_copy);
-        *this = RenderBuffers();
+        return stream && stream_ctl && ev_begin && ev_traced && ev_resolved && host_flags.ptr && segments.ptr;
     }
 };
 
@@ -250,7 +215,7 @@ struct RtScene {
     rtapi::DevBuf<rtdev::Texture> textures;
     rtapi::DevBuf<rtdev::Image> images;
     rtapi::DevBuf<rtdev::Perlin> perlins;
-    std::vector<uint8_t *> image_pixels; // device copies of the RGBA8 texels
+    std::vector<rtapi::DevBuf<uint8_t>> image_pixels; // device copies of the RGBA8 texels
     int n_prims = 0, n_materials = 0, n_textures = 0, n_images = 0, n_perlins = 0;
     int perlin_identity = 1; // all permutation tables are the identity (noise.rs:121-130 never shuffles them)
     rtdev::Background bg;
@@ -332,8 +297,8 @@ struct RtScene {
 namespace rtapi {
 // A launch whose waves read the scene's cancel word (the slot behind the region flags): lowered, and named in its arguments
 inline void arm_cancel_word(RtScene *s, rtdev::TraceArgs &a) {
-    s->buf.host_flags[rtdev::RT_MAX_REGIONS] = 0u;
-    a.cancel_flag = s->buf.host_flags + rtdev::RT_MAX_REGIONS;
+    s->buf.host_flags.ptr[rtdev::RT_MAX_REGIONS] = 0u;
+    a.cancel_flag = s->buf.host_flags.ptr + rtdev::RT_MAX_REGIONS;
 }
 // A call has enqueued its (first) launches: rt_scene_last_stats reads the counters and the event spans of this call
 inline void note_launches(RtScene *s, int launches) {

@@ -1,5 +1,5 @@
-// rt_scene_create.hip — scenes on the device: rt_scene_create / rt_scene_create_ex, rt_scene_destroy and the render-buffer
-// cache between them (include/rt_abi.h), plus the scene-level exports for the tests.  scene_create reads top to bottom:
+// rt_scene_create.hip — scenes on the device: rt_scene_create / rt_scene_create_ex, rt_scene_destroy (include/rt_abi.h; the
+// render-buffer cache between them is rt_render_cache.h's), plus the scene-level exports for the tests.  scene_create reads top to bottom:
 // validate, plan (rt_plan.h: values only), choose the tree, upload, size the pooled kernel, take render buffers.
 //
 // Host code only (HIP runtime calls).  Nothing here falls back to a CPU renderer: without a usable HIP device
@@ -8,59 +8,16 @@
 #include <stdint.h>
 #include <string.h>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <vector>
 #include "rt_rect_pairs.h"
+#include "rt_render_cache.h"
 #include "rt_scene.h"
 
 using rtapi::DevBuf;
 using rtapi::fail;
 
-// ---------------------------------------------------------------------------------------------- render-buffer cache
-// Everything a render call allocates on first use (RenderBuffers), kept per device across rt_scene_destroy /
-// rt_scene_create.  Measured on 1 x MI355X at 1080p (tools/time_scene_create.py, profiles/r04_scene_create.txt):
-// rt_scene_create itself is 0.3 - 1.4 ms, but the first render of a new scene paid 3 ms of hipMalloc / hipHostMalloc
-// (50 MB pinned frame, slices, counters) and the destroy before it 1 - 4 ms of hipFree / hipHostFree — on every object
-// event of the reference's interactive loop.  At most two sets per device are kept (two scenes alive at a time is the
-// pattern of `rebuild, then drop the old one`); rt_release_cached_buffers gives the memory back.
 namespace {
-struct CachedSet {
-    int device;
-    rtapi::RenderBuffers buf;
-};
-std::mutex g_cache_mutex;
-std::vector<CachedSet> g_cache;
-const size_t kCachedSetsPerDevice = 2;
-
-// rt_scene_destroy: the scene's render buffers go to the cache, or are freed when the device's slots are taken or the
-// scene never got as far as creating its streams.  Should the cache throw, they are still the scene's.
-void render_cache_put(RtScene *s) {
-    if (s->buf.complete()) {
-        std::lock_guard<std::mutex> lock(g_cache_mutex);
-        size_t held = 0;
-        for (const CachedSet &c : g_cache) held += c.device == s->device;
-        if (held < kCachedSetsPerDevice) {
-            g_cache.push_back(CachedSet{s->device, s->buf});
-            s->buf = rtapi::RenderBuffers();
-            return;
-        }
-    }
-    s->buf.free_all(s->device);
-}
-// rt_scene_create: take over a cached set of this device (the one with the largest slices), if there is one
-bool render_cache_take(RtScene *s) {
-    std::lock_guard<std::mutex> lock(g_cache_mutex);
-    int best = -1;
-    for (size_t i = 0; i < g_cache.size(); ++i)
-        if (g_cache[i].device == s->device && (best < 0 || g_cache[i].buf.partial.count > g_cache[(size_t)best].buf.partial.count))
-            best = (int)i;
-    if (best < 0) return false;
-    s->buf = g_cache[(size_t)best].buf;
-    g_cache.erase(g_cache.begin() + best);
-    return true;
-}
-
 // ------------------------------------------------------------------------------------------------ scene creation
 #define RT_FAST_LAUNCHER(member, name, ret, params) name,
 #define RT_EXACT_LAUNCHER(member, name, ret, params) name##_exact,
@@ -78,12 +35,13 @@ template <class T> int upload(DevBuf<T> &buf, const std::vector<T> &host) {
 // The images' texels on the device (RtScene.image_pixels) and their device records.
 int upload_images(const RtSceneDesc *d, RtScene *s, std::vector<rtdev::Image> &images) {
     images.assign((size_t)d->n_images, rtdev::Image());
-    s->image_pixels.assign((size_t)d->n_images, nullptr);
+    s->image_pixels = std::vector<DevBuf<uint8_t>>((size_t)d->n_images);
     for (int i = 0; i < d->n_images; ++i) {
         size_t bytes = (size_t)d->images[i].width * (size_t)d->images[i].height * 4;
-        RT_HIP(hipMalloc((void **)&s->image_pixels[(size_t)i], bytes));
-        RT_HIP(hipMemcpy(s->image_pixels[(size_t)i], d->images[i].rgba, bytes, hipMemcpyHostToDevice));
-        images[(size_t)i].rgba = s->image_pixels[(size_t)i];
+        DevBuf<uint8_t> &texels = s->image_pixels[(size_t)i];
+        RT_HIP(texels.alloc(bytes));
+        RT_HIP(hipMemcpy(texels.ptr, d->images[i].rgba, bytes, hipMemcpyHostToDevice));
+        images[(size_t)i].rgba = texels.ptr;
         images[(size_t)i].width = d->images[i].width;
         images[(size_t)i].height = d->images[i].height;
     }
@@ -180,16 +138,16 @@ int size_pool(RtScene *s) {
 // The scene's render buffers: a cached set of this device's, or a fresh one of what every render needs.
 int acquire_render_buffers(RtScene *s) {
     rtapi::RenderBuffers &b = s->buf;
-    if (!render_cache_take(s)) { // nothing of this device's to take over: the first scene, or more than the cache holds
+    if (!rtapi::render_cache_take(s->device, b)) { // nothing of this device's to take over: the first scene, or more than the cache holds
+        b.device = s->device;
         RT_HIP(b.segments.alloc(rtdev::RT_STAT_SLOTS)); // rt_device_types.h: RT_STAT_*
-        RT_HIP(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&b.ev_begin));
-        RT_HIP(hipEventCreate(&b.ev_traced));
-        RT_HIP(hipEventCreate(&b.ev_resolved));
-        RT_HIP(hipHostMalloc((void **)&b.host_flags, (rtdev::RT_MAX_REGIONS + 1) * sizeof(unsigned int),
-                             hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
-        memset(b.host_flags, 0, (rtdev::RT_MAX_REGIONS + 1) * sizeof(unsigned int));
-        RT_HIP(hipStreamCreateWithFlags(&b.stream_ctl, hipStreamNonBlocking));
+        RT_HIP(b.stream.ensure(hipStreamNonBlocking));
+        RT_HIP(b.ev_begin.ensure()); // (timing events: rt_scene_last_stats reads their spans)
+        RT_HIP(b.ev_traced.ensure());
+        RT_HIP(b.ev_resolved.ensure());
+        RT_HIP(b.host_flags.alloc(rtdev::RT_MAX_REGIONS + 1, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
+        memset(b.host_flags.ptr, 0, (rtdev::RT_MAX_REGIONS + 1) * sizeof(unsigned int));
+        RT_HIP(b.stream_ctl.ensure(hipStreamNonBlocking));
     }
     RT_HIP(hipMemsetAsync(b.segments.ptr, 0, rtdev::RT_STAT_SLOTS * sizeof(unsigned long long), b.stream));
     return RT_OK;
@@ -308,42 +266,11 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
 extern "C" {
 
 void rt_scene_destroy(RtScene *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->buf.stream) (void)hipStreamSynchronize(s->buf.stream);
-    if (s->buf.stream_ctl) (void)hipStreamSynchronize(s->buf.stream_ctl);
-    for (uint8_t *p : s->image_pixels)
-        if (p) (void)hipFree(p);
-    s->prims.release();
-    s->textures.release();
-    s->images.release();
-    s->perlins.release();
-    s->bvh_nodes.release();
-    s->bvh_nodes_ordered.release();
-    s->bvh_prim_index.release();
-    s->leaf_geo.release();
-    s->nee_slot.release();
-    s->nee_prim.release();
-    s->nee_pick.release();
-    s->rays_order.release();
-    // what a render allocates — slices, frames, pinned memory, counters, streams, events — outlives the scene: the
-    // reference rebuilds its scene on every object event (main.rs:174-189), and the next rt_scene_create on this
-    // device takes these over instead of paying hipMalloc / hipHostMalloc again (render_cache_put); should the cache
-    // throw, they are freed here
-    if (rtapi::guarded("rt_scene_destroy", [&] { render_cache_put(s); return RT_OK; }) != RT_OK) s->buf.free_all(s->device);
-    delete s;
+    if (s) rtapi::scene_destroy(s); // rt_render_cache.h
 }
 
 void rt_release_cached_buffers(void) {
-    (void)rtapi::guarded("rt_release_cached_buffers", [] {
-        std::vector<CachedSet> all;
-        {
-            std::lock_guard<std::mutex> lock(g_cache_mutex);
-            all.swap(g_cache);
-        }
-        for (CachedSet &c : all) c.buf.free_all(c.device);
-        return RT_OK;
-    });
+    (void)rtapi::guarded("rt_release_cached_buffers", [] { rtapi::render_cache_release_all(); return RT_OK; });
 }
 
 int rt_scene_create(const RtSceneDesc *d, int device, RtScene **out) {

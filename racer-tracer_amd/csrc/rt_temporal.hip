@@ -27,6 +27,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 
 namespace RT_KNS {
 
@@ -215,9 +216,9 @@ int render_into_state(RtScene *s, RtTemporal *t, const char *v1_message, const R
         return rc;
     if ((rc = enqueue_denoise_history(s, full, d, tp, &next, &g, filtered, stream)) != RT_OK) return rc;
     RT_HIP(hipMemcpyAsync(out_rgb, filtered, n * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (out_length) RT_HIP(hipMemcpyAsync(t->host_length, next.length, pixels * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (out_length) RT_HIP(hipMemcpyAsync(t->host_length.ptr, next.length, pixels * sizeof(double), hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
-    if (out_length) memcpy(out_length, t->host_length, pixels * sizeof(double));
+    if (out_length) memcpy(out_length, t->host_length.ptr, pixels * sizeof(double));
     t->current ^= 1;
     t->has_prev = true;
     t->camera = *camera;
@@ -256,14 +257,6 @@ int denoise_history_device(RtScene *s, const RtRenderParams *p, const RtDenoiseP
     return enqueue_denoise_history(s, p, d, t, h, g, out, (hipStream_t)stream);
 }
 
-void temporal_free(RtTemporal *t) {
-    (void)hipSetDevice(t->device);
-    t->planes.release();
-    t->ids.release();
-    if (t->host_length) (void)hipHostFree(t->host_length);
-    delete t;
-}
-
 int temporal_create(int device, int32_t width, int32_t height, RtTemporal **out) {
     if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
@@ -273,19 +266,17 @@ int temporal_create(int device, int32_t width, int32_t height, RtTemporal **out)
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(RT_ERR_NO_DEVICE, "no HIP device");
     if (device < 0 || device >= count) return fail(RT_ERR_INVALID_ARGUMENT, "device out of range");
     RT_HIP(hipSetDevice(device));
-    RtTemporal *t = new RtTemporal();
+    std::unique_ptr<RtTemporal> t(new RtTemporal()); // (a state half made frees what it got on the way out)
     t->device = device;
     t->width = width;
     t->height = height;
     const size_t pixels = (size_t)width * (size_t)height;
     hipError_t e = t->planes.alloc(kStateDoubles * pixels);
     if (e == hipSuccess) e = t->ids.alloc(3 * pixels);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&t->host_length, pixels * sizeof(double), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        temporal_free(t);
+    if (e == hipSuccess) e = t->host_length.alloc(pixels, hipHostMallocDefault);
+    if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_HIP, std::string("rt_temporal_create: ") + hipGetErrorString(e));
-    }
-    *out = t;
+    *out = t.release();
     return RT_OK;
 }
 
@@ -347,8 +338,7 @@ int rt_temporal_create(int device, int32_t width, int32_t height, RtTemporal **o
 }
 
 void rt_temporal_destroy(RtTemporal *t) {
-    if (!t) return;
-    (void)rtapi::guarded("rt_temporal_destroy", [&] { temporal_free(t); return RT_OK; });
+    delete t; // (~RtTemporal: on its own device)
 }
 
 int rt_temporal_reset(RtTemporal *t) {

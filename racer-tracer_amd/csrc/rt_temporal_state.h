@@ -13,10 +13,11 @@ struct RtTemporal {
     int width = 0, height = 0;
     rtapi::DevBuf<double> planes; // two histories of 12 doubles per pixel, the guides' 10, the frame's 3 and the output's 3
     rtapi::DevBuf<int32_t> ids;   // the histories' and the guides' obj_id
-    double *host_length = nullptr; // pinned, W*H
+    rtapi::PinnedBuf<double> host_length; // W*H
     bool has_prev = false;
     int current = 0; // the history the next frame reads
     RtCamera camera;
+    ~RtTemporal() { (void)hipSetDevice(device); } // the owners above free themselves behind this, on their device
 };
 
 namespace rtapi {

@@ -134,7 +134,7 @@ int render_preview_upsampled(RtScene *s, const RtCamera *camera, const RtRenderP
     const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
     rtapi::RenderBuffers &b = s->buf;
     if ((rc = rtapi::reserve_denoise(s, pixels, true)) != RT_OK) return rc;
-    if (b.frame.count < 3 * n) RT_HIP(b.frame.alloc(3 * n));
+    RT_HIP(b.frame.reserve(3 * n));
     const hipStream_t stream = b.stream;
     double *preview = b.frame.ptr, *upsampled = preview + n, *result = upsampled;
     const RtGuides g = rtapi::scene_guides(s, pixels);

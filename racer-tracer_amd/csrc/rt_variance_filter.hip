@@ -199,9 +199,9 @@ int render_adaptive_filtered(RtScene *s, const RtCamera *camera, const RtRenderP
     RT_HIP(hipSetDevice(s->device));
     rtapi::RenderBuffers &b = s->buf;
     if ((rc = rtapi::reserve_denoise(s, pixels, true)) != RT_OK) return rc;
-    if (b.batch_counts.count < 2 * pixels) RT_HIP(b.batch_counts.alloc(2 * pixels));
+    RT_HIP(b.batch_counts.reserve(2 * pixels));
     // the adaptive call has drained its streams: its frame slots (three of W*H*3) now hold C, var and the filtered frame
-    if (b.frame.count < 7 * pixels) RT_HIP(b.frame.alloc(7 * pixels));
+    RT_HIP(b.frame.reserve(7 * pixels));
     double *radiance = b.frame.ptr, *var = radiance + n, *filtered = var + pixels;
     const hipStream_t stream = b.stream;
     const RtGuides g = rtapi::scene_guides(s, pixels);
