@@ -24,9 +24,12 @@ int check_query(const RtScene *s, const RtRays *rays, int64_t n, const RtRayQuer
     return RT_OK;
 }
 
+} // namespace
+
 // The scene part of the render's argument block: fill_trace_args with a zeroed camera and 2 x 2 one-sample params, as
-// enqueue_guides fills it with the caller's (the camera and the pixel grid are read by nothing in k_trace_rays_f64).
-int query_args(const RtScene *s, rtdev::TraceArgs &a) {
+// enqueue_guides fills it with the caller's (the camera and the pixel grid are read by nothing in k_trace_rays_f64, nor
+// in rt_occlusion.hip's kernel, which takes the same block).
+int rtapi::query_args(const RtScene *s, rtdev::TraceArgs &a) {
     RtCamera none;
     memset(&none, 0, sizeof none);
     RtRenderParams one;
@@ -39,6 +42,10 @@ int query_args(const RtScene *s, rtdev::TraceArgs &a) {
     if (!s->use_bvh) a.n_bvh_nodes = 0;
     return RT_OK;
 }
+
+namespace {
+
+using rtapi::query_args;
 
 // The device copy of RtScene.table_order, made by the scene's first query.  A plain (synchronous) copy, once: a later
 // query on another stream must not overtake it.

@@ -17,6 +17,7 @@
 #include "rt_resources.h"
 #include "../../include/rt_abi.h"
 #include "../../include/rt_rays.h"
+#include "../../include/rt_occlusion.h"
 
 // The trace kernels exist twice (rt_trace_common.h: ARITHMETIC): RT_ARITH_FAST, and RT_ARITH_REFERENCE behind *_exact.
 // Every launcher that has both flavours, ONCE: X(member of rtapi::Launchers, exported name, return type, parameters).  The
@@ -35,6 +36,8 @@
 //     nee_stream and its blocks per CU with the extended light code (rt_nee_lights.h), which exist for PRIMS_ANY only.
 //   trace_rays (rt_rays_kernel.hip): n caller rays of device planes against args' scene, closest or any hit; `order` is
 //     the device copy of the table's description indices.
+//   occlusion (rt_occlusion_kernel.hip): n caller rays of device planes against args' scene, one int32 per ray: is there
+//     a hit inside the ray's window (include/rt_occlusion.h).
 #define RT_LAUNCHER_LIST(X)                                                                                                \
     X(trace, rtdev_launch_trace, hipError_t,                                                                               \
       (const rtdev::TraceArgs *args, int prims_class, int textured, int specular, hipStream_t stream))                     \
@@ -82,7 +85,9 @@
     X(nee_lights_stream_blocks_per_cu, rtdev_nee_lights_stream_blocks_per_cu, int, (int textured, int specular, int bvh)) \
     X(trace_rays, rtdev_launch_trace_rays, hipError_t,                                                                     \
       (const rtdev::TraceArgs *args, const RtRays *rays, const RtRayHits *hits, const int32_t *order, int n, int any_hit, \
-       hipStream_t stream))
+       hipStream_t stream))                                                                                                \
+    X(occlusion, rtdev_launch_occlusion, hipError_t,                                                                       \
+      (const rtdev::TraceArgs *args, const RtRays *rays, int32_t *occluded, int n, hipStream_t stream))
 #define RT_DECLARE_LAUNCHER(member, name, ret, params) \
     extern "C" ret name params;                        \
     extern "C" ret name##_exact params;
@@ -173,6 +178,7 @@ struct RenderBuffers {
     DevBuf<int32_t> batch_counts;
     // rt_trace_rays (rt_rays.hip), on first use: one chunk of rays — planes [origin 3 | direction 3 | t_min | t_max | time]
     // x RT_RAYS_HOST_CHUNK doubles — and of answers — [t | point 3 | normal 3 | uv 2] doubles, [prim | obj_id | front_face]
+    // (rt_trace_occlusion, rt_occlusion.hip, stages through rays_in and the first plane of rays_ids)
     DevBuf<double> rays_in, rays_out;
     DevBuf<int32_t> rays_ids;
 
@@ -414,6 +420,9 @@ int enqueue_levels(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d
                    const double *variance, const RtGuides &g, double *out, hipStream_t stream);
 // The trace kernels' argument block of a render (rt_api.hip: fill_args), for launches of other kernels that trace rays.
 int fill_trace_args(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, rtdev::TraceArgs &a);
+// ... its scene part alone, for the kernels that take caller rays (rt_rays.hip; rt_occlusion.hip): the tree when the scene
+// walks one (use_bvh), and of a tree that renders keep in LDS its global copy.
+int query_args(const RtScene *s, rtdev::TraceArgs &a);
 int reserve_denoise(RtScene *s, size_t pixels, bool own_guides, bool variance_planes = false);
 RtGuides scene_guides(RtScene *s, size_t pixels);
 int enqueue_guides(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtGuides &g, hipStream_t stream);

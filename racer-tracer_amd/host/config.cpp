@@ -228,6 +228,19 @@ Args Args::parse(int argc, const char *const *argv) {
             a.pick_x = (int)x;
             a.pick_y = (int)y;
         }
+        else if (s == "--visible") {
+            const std::string v = val();
+            const char *at = v.c_str();
+            bool ok = !v.empty();
+            for (int k = 0; k < 6 && ok; ++k) {
+                char *end = nullptr;
+                a.visible_ab[k] = std::strtod(at, &end);
+                ok = end != nullptr && end != at && std::isfinite(a.visible_ab[k]) && *end == (k < 5 ? ',' : '\0');
+                at = end + 1;
+            }
+            if (!ok) throw TracerError::ArgumentParsingError(s + " needs two points as AX,AY,AZ,BX,BY,BZ, not '" + v + "'");
+            a.visible = true;
+        }
         else if (s == "--temporal" || s == "--preview-temporal") {
             const std::string v = val();
             char *end = nullptr;

@@ -85,6 +85,10 @@ struct Args { // config.rs:12-28
     // middle of the shutter) through rt_trace_rays (include/rt_rays.h), one line on stdout; a pixel outside the image is refused
     bool pick = false;
     int pick_x = 0, pick_y = 0;
+    // --visible AX,AY,AZ,BX,BY,BZ: after the run, whether the segment from a to b is free of the scene, through
+    // rt_trace_occlusion (include/rt_occlusion.h) with the window [1e-3, 1 - 1e-3], one line on stdout; six finite numbers
+    bool visible = false;
+    double visible_ab[6] = {0, 0, 0, 0, 0, 0};
     bool help = false;
 
     static Args parse(int argc, const char *const *argv);

@@ -23,6 +23,8 @@
 // is written; --denoise gives the filter its levels.
 // --pick X,Y asks the scene, after the run, what lies under pixel (X, Y) of the configured camera (include/rt_rays.h) and
 // prints the answer on stdout.
+// --visible AX,AY,AZ,BX,BY,BZ asks the scene, after the run, whether the segment between the two points is free
+// (include/rt_occlusion.h) and prints yes or no on stdout.
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -33,6 +35,7 @@
 #include <vector>
 #include "../../include/rt_host.h"
 #include "../../include/rt_preview_temporal.h"
+#include "../../include/rt_occlusion.h"
 #include "../../include/rt_rays.h"
 #include "config.h"
 #include "error.h"
@@ -88,6 +91,26 @@ int pick_pixel(RtScene *scene, const RtCamera *cam, const RtRenderParams &params
     return RT_OK;
 }
 
+// --visible AX,AY,AZ,BX,BY,BZ: is the segment from a to b free of the scene?  The ray (a, b - a) over the window
+// [1e-3, 1 - 1e-3], at time 0.  One line on stdout: `visible ax ay az bx by bz yes` or `... no`.
+int visible_between(RtScene *scene, const double ab[6]) {
+    const double d[3] = {ab[3] - ab[0], ab[4] - ab[1], ab[5] - ab[2]};
+    const double t_min = 1e-3, t_max = 1.0 - 1e-3;
+    RtRays rays = {ab, d, &t_min, &t_max, nullptr};
+    int32_t occluded = 0;
+    const int rc = rt_trace_occlusion(scene, &rays, 1, &occluded);
+    if (rc != RT_OK) {
+        fprintf(stderr, "%s: %s\n", rt_strerror(rc), rt_last_error_message());
+        return rc;
+    }
+    if (occluded == RT_RAY_INVALID) { // (a == b: the direction is all zeros)
+        fprintf(stderr, "--visible: the two points do not span a segment\n");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    printf("visible %.17g %.17g %.17g %.17g %.17g %.17g %s\n", ab[0], ab[1], ab[2], ab[3], ab[4], ab[5], occluded ? "no" : "yes");
+    return RT_OK;
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
@@ -99,7 +122,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample] [--preview-temporal K] [--pick X,Y]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample] [--preview-temporal K] [--pick X,Y] [--visible AX,AY,AZ,BX,BY,BZ]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -316,6 +339,7 @@ int main(int argc, char **argv) {
         }
     }
     if (rc == RT_OK && args.pick) rc = pick_pixel(scenes[0], rth_session_camera(session), params, args.pick_x, args.pick_y);
+    if (rc == RT_OK && args.visible) rc = visible_between(scenes[0], args.visible_ab);
     destroy_scenes();
     rth_session_close(session);
     return rc;
