@@ -43,18 +43,19 @@ int rtapi::query_args(const RtScene *s, rtdev::TraceArgs &a) {
     return RT_OK;
 }
 
-namespace {
-
-using rtapi::query_args;
-
-// The device copy of RtScene.table_order, made by the scene's first query.  A plain (synchronous) copy, once: a later
-// query on another stream must not overtake it.
-int ensure_order(RtScene *s) {
+// The device copy of RtScene.table_order, made by the scene's first query (this one's or rt_multihit.hip's).  A plain
+// (synchronous) copy, once: a later query on another stream must not overtake it.
+int rtapi::ensure_order(RtScene *s) {
     if (s->rays_order.count == s->table_order.size()) return RT_OK;
     RT_HIP(s->rays_order.alloc(s->table_order.size()));
     RT_HIP(hipMemcpy(s->rays_order.ptr, s->table_order.data(), s->table_order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     return RT_OK;
 }
+
+namespace {
+
+using rtapi::ensure_order;
+using rtapi::query_args;
 
 int enqueue_rays(RtScene *s, const rtdev::TraceArgs &a, const RtRays &rays, int n, const RtRayQueryParams *q, const RtRayHits &hits,
                  hipStream_t stream) {

@@ -18,6 +18,7 @@
 #include "../../include/rt_abi.h"
 #include "../../include/rt_rays.h"
 #include "../../include/rt_occlusion.h"
+#include "../../include/rt_multihit.h"
 
 // The trace kernels exist twice (rt_trace_common.h: ARITHMETIC): RT_ARITH_FAST, and RT_ARITH_REFERENCE behind *_exact.
 // Every launcher that has both flavours, ONCE: X(member of rtapi::Launchers, exported name, return type, parameters).  The
@@ -38,6 +39,8 @@
 //     the device copy of the table's description indices.
 //   occlusion (rt_occlusion_kernel.hip): n caller rays of device planes against args' scene, one int32 per ray: is there
 //     a hit inside the ray's window (include/rt_occlusion.h).
+//   multihit (rt_multihit_kernel.hip): n caller rays of device planes against args' scene, the first k primitives
+//     along each ray into slot-major planes and a count per ray (include/rt_multihit.h); `order` as for trace_rays.
 #define RT_LAUNCHER_LIST(X)                                                                                                \
     X(trace, rtdev_launch_trace, hipError_t,                                                                               \
       (const rtdev::TraceArgs *args, int prims_class, int textured, int specular, hipStream_t stream))                     \
@@ -87,7 +90,10 @@
       (const rtdev::TraceArgs *args, const RtRays *rays, const RtRayHits *hits, const int32_t *order, int n, int any_hit, \
        hipStream_t stream))                                                                                                \
     X(occlusion, rtdev_launch_occlusion, hipError_t,                                                                       \
-      (const rtdev::TraceArgs *args, const RtRays *rays, int32_t *occluded, int n, hipStream_t stream))
+      (const rtdev::TraceArgs *args, const RtRays *rays, int32_t *occluded, int n, hipStream_t stream))                    \
+    X(multihit, rtdev_launch_multihit, hipError_t,                                                                         \
+      (const rtdev::TraceArgs *args, const RtRays *rays, const RtRayHits *hits, int32_t *count, const int32_t *order,     \
+       int n, int k, hipStream_t stream))
 #define RT_DECLARE_LAUNCHER(member, name, ret, params) \
     extern "C" ret name params;                        \
     extern "C" ret name##_exact params;
@@ -178,7 +184,8 @@ struct RenderBuffers {
     DevBuf<int32_t> batch_counts;
     // rt_trace_rays (rt_rays.hip), on first use: one chunk of rays — planes [origin 3 | direction 3 | t_min | t_max | time]
     // x RT_RAYS_HOST_CHUNK doubles — and of answers — [t | point 3 | normal 3 | uv 2] doubles, [prim | obj_id | front_face]
-    // (rt_trace_occlusion, rt_occlusion.hip, stages through rays_in and the first plane of rays_ids)
+    // (rt_trace_occlusion, rt_occlusion.hip, stages through rays_in and the first plane of rays_ids; rt_trace_rays_multi,
+    // rt_multihit.hip, through all three, an eighth of a chunk's rays at a time with up to eight slots each)
     DevBuf<double> rays_in, rays_out;
     DevBuf<int32_t> rays_ids;
 
@@ -420,9 +427,12 @@ int enqueue_levels(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d
                    const double *variance, const RtGuides &g, double *out, hipStream_t stream);
 // The trace kernels' argument block of a render (rt_api.hip: fill_args), for launches of other kernels that trace rays.
 int fill_trace_args(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, rtdev::TraceArgs &a);
-// ... its scene part alone, for the kernels that take caller rays (rt_rays.hip; rt_occlusion.hip): the tree when the scene
+// ... its scene part alone, for the kernels that take caller rays (rt_rays.hip; rt_occlusion.hip; rt_multihit.hip): the tree when the scene
 // walks one (use_bvh), and of a tree that renders keep in LDS its global copy.
 int query_args(const RtScene *s, rtdev::TraceArgs &a);
+// The device copy of RtScene.table_order in s->rays_order, made by the scene's first query that names primitives
+// (rt_rays.hip), with one synchronous copy.
+int ensure_order(RtScene *s);
 int reserve_denoise(RtScene *s, size_t pixels, bool own_guides, bool variance_planes = false);
 RtGuides scene_guides(RtScene *s, size_t pixels);
 int enqueue_guides(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtGuides &g, hipStream_t stream);

@@ -228,6 +228,27 @@ Args Args::parse(int argc, const char *const *argv) {
             a.pick_x = (int)x;
             a.pick_y = (int)y;
         }
+        else if (s == "--pick-through") {
+            const std::string v = val();
+            long xyk[3] = {0, 0, 4};
+            const char *at = v.c_str();
+            int got = 0;
+            bool ok = !v.empty();
+            while (ok && got < 3) {
+                char *end = nullptr;
+                xyk[got] = std::strtol(at, &end, 10);
+                ok = end != nullptr && end != at && (*end == '\0' || (*end == ',' && got < 2));
+                ++got;
+                if (!ok || *end == '\0') break;
+                at = end + 1;
+            }
+            if (!ok || got < 2 || xyk[0] < 0 || xyk[1] < 0 || xyk[0] > 1000000 || xyk[1] > 1000000 || xyk[2] < 1 || xyk[2] > 8)
+                throw TracerError::ArgumentParsingError(s + " needs a pixel and a count of 1..8 as X,Y[,K], not '" + v + "'");
+            a.pick_through = true;
+            a.through_x = (int)xyk[0];
+            a.through_y = (int)xyk[1];
+            a.through_k = (int)xyk[2];
+        }
         else if (s == "--visible") {
             const std::string v = val();
             const char *at = v.c_str();

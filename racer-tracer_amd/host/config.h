@@ -85,6 +85,10 @@ struct Args { // config.rs:12-28
     // middle of the shutter) through rt_trace_rays (include/rt_rays.h), one line on stdout; a pixel outside the image is refused
     bool pick = false;
     int pick_x = 0, pick_y = 0;
+    // --pick-through X,Y[,K]: after the run, the first K (1..RT_MULTIHIT_MAX = 8, default 4) primitives along that same ray
+    // through rt_trace_rays_multi (include/rt_multihit.h), one line per hit on stdout; refused like --pick
+    bool pick_through = false;
+    int through_x = 0, through_y = 0, through_k = 4;
     // --visible AX,AY,AZ,BX,BY,BZ: after the run, whether the segment from a to b is free of the scene, through
     // rt_trace_occlusion (include/rt_occlusion.h) with the window [1e-3, 1 - 1e-3], one line on stdout; six finite numbers
     bool visible = false;

@@ -23,6 +23,7 @@
 // is written; --denoise gives the filter its levels.
 // --pick X,Y asks the scene, after the run, what lies under pixel (X, Y) of the configured camera (include/rt_rays.h) and
 // prints the answer on stdout.
+// --pick-through X,Y[,K] asks for the first K primitives under that pixel, in order (include/rt_multihit.h), one line each.
 // --visible AX,AY,AZ,BX,BY,BZ asks the scene, after the run, whether the segment between the two points is free
 // (include/rt_occlusion.h) and prints yes or no on stdout.
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
@@ -35,6 +36,7 @@
 #include <vector>
 #include "../../include/rt_host.h"
 #include "../../include/rt_preview_temporal.h"
+#include "../../include/rt_multihit.h"
 #include "../../include/rt_occlusion.h"
 #include "../../include/rt_rays.h"
 #include "config.h"
@@ -65,14 +67,18 @@ void on_tile(void *user, const double *rgb, int32_t r, int32_t c, int32_t w, int
 // --pick X,Y: what lies under the pixel.  The ray is the guides' (rt_render_guides_device): through the pixel's centre, no
 // lens offset, at the middle of the shutter interval.  One line on stdout: `pick X Y prim obj_id t px py pz nx ny nz`, or
 // `pick X Y miss`.
-int pick_pixel(RtScene *scene, const RtCamera *cam, const RtRenderParams &params, int x, int y) {
+void pixel_ray(const RtCamera *cam, const RtRenderParams &params, int x, int y, double o[3], double d[3], double &time) {
     const double u = ((double)x + 0.5) / (double)(params.width - 1), v = ((double)y + 0.5) / (double)(params.height - 1);
-    double o[3], d[3];
     for (int k = 0; k < 3; ++k) {
         o[k] = cam->origin[k];
         d[k] = cam->upper_left_corner[k] + u * cam->horizontal[k] - v * cam->vertical[k] - o[k];
     }
-    const double time = (cam->time_a + cam->time_b) * 0.5;
+    time = (cam->time_a + cam->time_b) * 0.5;
+}
+
+int pick_pixel(RtScene *scene, const RtCamera *cam, const RtRenderParams &params, int x, int y) {
+    double o[3], d[3], time;
+    pixel_ray(cam, params, x, y, o, d, time);
     RtRays rays = {o, d, nullptr, nullptr, &time};
     double t = 0.0, point[3] = {0, 0, 0}, normal[3] = {0, 0, 0};
     int32_t prim = RT_RAY_MISS, obj_id = -1;
@@ -88,6 +94,30 @@ int pick_pixel(RtScene *scene, const RtCamera *cam, const RtRenderParams &params
     else
         printf("pick %d %d %d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", x, y, (int)prim, (int)obj_id, t, point[0], point[1],
                point[2], normal[0], normal[1], normal[2]);
+    return RT_OK;
+}
+
+// --pick-through X,Y[,K]: the first K primitives under the pixel, along --pick's ray.  One line on stdout per filled slot j:
+// `pick-through X Y j prim obj_id t px py pz nx ny nz`, or `pick-through X Y miss` when there is none.
+int pick_through(RtScene *scene, const RtCamera *cam, const RtRenderParams &params, int x, int y, int k) {
+    double o[3], d[3], time;
+    pixel_ray(cam, params, x, y, o, d, time);
+    RtRays rays = {o, d, nullptr, nullptr, &time};
+    double t[RT_MULTIHIT_MAX], point[3 * RT_MULTIHIT_MAX], normal[3 * RT_MULTIHIT_MAX];
+    int32_t prim[RT_MULTIHIT_MAX], obj_id[RT_MULTIHIT_MAX], count = 0;
+    RtRayHits hits = {t, point, normal, nullptr, prim, obj_id, nullptr}; // (n = 1: slot j of a plane is its entry j)
+    RtMultiHitParams mp;
+    rt_multihit_params_default(&mp);
+    mp.k = k;
+    const int rc = rt_trace_rays_multi(scene, &rays, 1, &mp, &hits, &count);
+    if (rc != RT_OK) {
+        fprintf(stderr, "%s: %s\n", rt_strerror(rc), rt_last_error_message());
+        return rc;
+    }
+    if (count <= 0) printf("pick-through %d %d miss\n", x, y);
+    for (int j = 0; j < count; ++j)
+        printf("pick-through %d %d %d %d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", x, y, j, (int)prim[j], (int)obj_id[j], t[j],
+               point[3 * j], point[3 * j + 1], point[3 * j + 2], normal[3 * j], normal[3 * j + 1], normal[3 * j + 2]);
     return RT_OK;
 }
 
@@ -122,7 +152,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample] [--preview-temporal K] [--pick X,Y] [--visible AX,AY,AZ,BX,BY,BZ]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample] [--preview-temporal K] [--pick X,Y] [--pick-through X,Y[,K]] [--visible AX,AY,AZ,BX,BY,BZ]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -142,6 +172,11 @@ int main(int argc, char **argv) {
     }
     if (args.pick && (args.pick_x >= params.width || args.pick_y >= params.height)) {
         fprintf(stderr, "--pick %d,%d lies outside the %d x %d image\n", args.pick_x, args.pick_y, params.width, params.height);
+        rth_session_close(session);
+        return RT_ERR_ARGUMENT_PARSING;
+    }
+    if (args.pick_through && (args.through_x >= params.width || args.through_y >= params.height)) {
+        fprintf(stderr, "--pick-through %d,%d lies outside the %d x %d image\n", args.through_x, args.through_y, params.width, params.height);
         rth_session_close(session);
         return RT_ERR_ARGUMENT_PARSING;
     }
@@ -339,6 +374,8 @@ int main(int argc, char **argv) {
         }
     }
     if (rc == RT_OK && args.pick) rc = pick_pixel(scenes[0], rth_session_camera(session), params, args.pick_x, args.pick_y);
+    if (rc == RT_OK && args.pick_through)
+        rc = pick_through(scenes[0], rth_session_camera(session), params, args.through_x, args.through_y, args.through_k);
     if (rc == RT_OK && args.visible) rc = visible_between(scenes[0], args.visible_ab);
     destroy_scenes();
     rth_session_close(session);
