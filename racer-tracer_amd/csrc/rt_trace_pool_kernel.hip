@@ -85,6 +85,7 @@
 #include "rt_pool_profile.h"
 #include "rt_pool_lds.h"
 #include "rt_pool_coop.h"
+#include "rt_ring_level.h"
 #include "rt_pool_deliver.h"
 
 #ifndef RT_OCC_TEX
@@ -257,6 +258,10 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
     // ahead of the hand-out), or ~0 when the item's batches are all drawn: ONE scalar compare per iteration decides
     uint32_t batch_due = ~0u;
     uint32_t ring_head = 0; // PRETRACE: slot of the ring's oldest entry
+    // PRETRACE: the entries that wait in the ring, kept as a counter, and the level below which a camera batch is due
+    // (rt_ring_level.h; 0 once the item's batches are all drawn).  `next` is not kept up inside that variant's path loop:
+    // it is the pool's index in front of the loop (0) and behind it (total).
+    uint32_t ring_level = 0, batch_below = 0;
     uint32_t my_pixel = 0; // image index of this lane's pixel of the current item's tile
 
     RT_REGION_DECL
@@ -431,6 +436,8 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         batches_done = 0;
         batch_due = n_batches > 0u ? 0u : ~0u;
         ring_head = 0;
+        ring_level = 0;
+        batch_below = rt_ring::batch_below_of(0u, total, RING_SLOTS);
         return true;
     };
     // The item of slot `s` has no path left: its sums go to its own slice of `partial` (or the launch finishes the tile's
@@ -544,7 +551,9 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
         }
         }
     };
-    auto pretrace_batch = [&](uint32_t b) {
+    // (Returns the count of the entries it queued.  The caller adds it to the level: with the level updated in here, on
+    // one of the two ways out, the path loop carried a copy of it and a vector move more per iteration, C3 +0.09 ms.)
+    auto pretrace_batch = [&](uint32_t b) -> uint32_t {
         if constexpr (PRETRACE) {
         int lane = lane_of_wave; // (opaque, like start_item's)
         asm volatile("" : "+v"(lane));
@@ -564,13 +573,12 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 atomicAdd(&L.sum[pix_b][2], one);
             }
             if (lane == 0) L.n_started += (uint32_t)__popcll(in_pool);
-            next += (uint32_t)__popcll(in_pool);
-            return;
+            return 0u; // (nothing queues up: the level stays 0)
         }
         const u4 bc = philox4x32(pixel_b, sample_b, RT_RNG_CAMERA, 0u, A.seed_lo, A.seed_hi);
         // (the 64 slots behind the ring's entries are free — the path loop sees to that: at most RING_SLOTS - 64 entries
         // wait when a batch runs)
-        const uint32_t in_ring = min(b << 6, total) - next;
+        const uint32_t in_ring = ring_level;
         d3 bo, bd;
         {
             const double v = div_by((double)py_b + u53(bc.a, bc.b), (double)(A.height - 1), K->inv_height_m1); // cpu.rs:39-40
@@ -639,8 +647,9 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
             L.ring_best[slot] = (uint16_t)((uint32_t)best | sign_of(bd.x) << RING_BEST_BITS | sign_of(bd.y) << (RING_BEST_BITS + 1u) |
                                            sign_of(bd.z) << (RING_BEST_BITS + 2u));
         }
-        next += (uint32_t)__popcll(ends); // `next` counts the entries that have left the pool: ended here, or handed out
+        return (uint32_t)__popcll(lives); // (the entries that ended here have left the pool)
         }
+        return 0u;
     };
 
     // ---- path state of this lane (it outlives the items: a lane's path may belong to either slot)
@@ -707,10 +716,14 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 // ---- camera batches: keep more than RING_SLOTS - 64 entries in the ring while the pool has any (a batch
                 // needs 64 free slots, and nothing else does; the hand-out goes short only where more lanes are idle than
                 // entries wait — at an item's start, and in the iteration that follows a batch most of whose entries ended)
-                while (batches_done < n_batches && min(batches_done << 6, total) - next <= RING_SLOTS - 64u) pretrace_batch(batches_done++);
+                // ("a batch is left" and "64 slots are free" as one comparison: the last batch puts batch_below out of reach)
+                while (rt_ring::batch_is_due(ring_level, batch_below)) {
+                    ring_level = rt_ring::after_batch(ring_level, pretrace_batch(batches_done++));
+                    batch_below = rt_ring::batch_below_of(batches_done << 6, total, RING_SLOTS);
+                }
                 RT_REGION(1); // batches
                 // ---- hand ring entries to the lanes without a path (ballot + prefix count)
-                const uint32_t in_ring = min(batches_done << 6, total) - next;
+                const uint32_t in_ring = ring_level;
                 if (in_ring != 0u) {
                     const uint64_t idle = ~alive_m;
                     const uint32_t r = (uint32_t)lane_rank(idle);
@@ -727,10 +740,9 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                     }
                     const uint32_t pixel_new = (uint32_t)shfl_i((int)my_pixel, pix_new);
                     const uint64_t taking = idle & ballot(r < in_ring);
-                    const uint32_t n_take = min((uint32_t)__popcll(idle), in_ring);
-                    next += n_take;
-                    ring_head += n_take;
-                    if (ring_head >= RING_SLOTS) ring_head -= RING_SLOTS;
+                    const uint32_t n_take = rt_ring::taken((uint32_t)__popcll(idle), in_ring);
+                    ring_level = rt_ring::after_hand_out(in_ring, n_take);
+                    ring_head = rt_ring::slot_at(ring_head, n_take, RING_SLOTS);
                     if (__builtin_amdgcn_inverse_ballot_w64(taking)) { // the hit the batch found: loads, and no arithmetic on doubles
                         asm volatile("; hand_out_begin");
                         spix = pix_new;
@@ -851,7 +863,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 ended_m |= deep_m;
                 // ---- the next segment of every lane that has its new ray
                 const uint64_t shooting = finish_m & ~deep_m;
-                RT_LANES(__popcll(shooting), next >= total);
+                RT_LANES(__popcll(shooting), rt_ring::pool_is_dry(ring_level, batch_below)); // (what `next >= total` says)
                 // (the pending hit is dead here — a lane that does not shoot is `waiting`, ended or idle, and none of those reads
                 // it before it is set again — and saying so costs no instruction: set to "no hit" out here, for every lane,
                 // the move was issued twice, here and again in front of the closest-hit loop)
@@ -901,6 +913,7 @@ __global__ __launch_bounds__(256, TEXTURED ? (PRIMS == PRIMS_ANY ? (BVH ? RT_OCC
                 alive_m &= ~ended_m;
                 RT_REGION(6); // scatter + accumulate
             }
+            next = total; // every batch is drawn and the ring is empty: the pool's index, for the item code above
         } else
         // ---- the path loop: until the pool runs dry or the draining item's last path ends
         for (;;) {
