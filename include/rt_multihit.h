@@ -8,7 +8,9 @@
  * RT_RAYS_CLOSEST reports, slot j what RT_RAYS_CLOSEST would report with the primitives of slots 0..j-1 removed from the
  * scene, and one primitive never fills two slots.  Among hits with exactly equal t the order is unspecified; if such a
  * tie straddles slot k-1 and the first hit left out, which of the two is kept is unspecified.  Both window ends are
- * inclusive, and the fast flavour's open box edges are rt_rays.h's.
+ * inclusive, and the fast flavour's open box edges are rt_rays.h's.  So is the direction's scale (rt_rays.h: THE
+ * DIRECTION'S SCALE): the direction is normalised by a power of two before the walk and every slot's t handed back in the
+ * caller's units; tested for a largest component within 2^+-300.
  *
  * count is the number of filled slots, 0..k.  There is no "more than k" flag: computing one would forbid the shrinking far
  * end that makes the walk cheap (once k hits are held, nothing beyond the k-th is looked at).  Unfilled slots hold a miss's

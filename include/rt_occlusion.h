@@ -3,7 +3,8 @@
  *
  * A ray is occluded iff RT_RAYS_CLOSEST (rt_rays.h) over the same window would report a hit.  Both window ends are
  * inclusive, the defaults are [0.001, inf), and t is in units of the direction.  A segment from a to b is the ray
- * (a, b - a) with a window inside [0, 1].
+ * (a, b - a) with a window inside [0, 1] — however close a and b lie: the direction's scale is rt_rays.h's (THE
+ * DIRECTION'S SCALE: normalised by a power of two before the walk, tested for a largest component within 2^+-300).
  *
  * The answer is one int32_t per ray: 1 occluded, 0 not, RT_RAY_INVALID for an invalid ray (rt_rays.h's rule: a non-finite
  * origin, direction, time or t_min, t_min < 0, a t_max that is NaN or below t_min, a direction of all zeros), which is

@@ -2,12 +2,27 @@
  * types are rt_abi.h's.  DESIGN.md section 4.15 has the definition, tests/ray_query_model.py restates it with the oracle.
  *
  * A ray is (origin, direction, [t_min, t_max], time).  The direction has any length: t is in units of it (ray.rs:30-32).
+ * THE DIRECTION'S SCALE.  A direction whose largest component lies outside 2^-32 .. 2^33 in magnitude is walked as
+ * d 2^-E over the window [t_min, t_max] 2^E, E the binary exponent of that component, and t is handed back times 2^-E
+ * (csrc/rt_query_ray.h): exact products, so the answer does not depend on the unit the direction is measured in — bit
+ * for bit in the RT_ARITH_REFERENCE flavour, and one answer for every scale outside that band in the fast one.  Held by
+ * the tests for a largest component within 2^-300 .. 2^300.  The same code serves every largest component that is a
+ * normal double, untested beyond that range; what then limits a ray is the range of a double alone: a window end whose
+ * scaled value overflows or underflows acts as +inf or 0, and a t that leaves the range in the caller's units is reported
+ * as it rounds there.  The record is formed from the caller's own o and d and the reported t (point = o + t d).
+ * Directions of subnormal components are scaled by 2^1022 and no further.
  * RT_RAYS_CLOSEST answers with the scene's own closest-hit rule over the ray's window — the rule a render applies over
  * [0.001, inf): both ends inclusive, in the linear loop a later primitive wins an exact tie, through the tree only exact
  * ties may differ, and a box's side on an edge is open.  The record is the render's hit record: point, the face normal
  * (against the ray), u / v in f64, front_face, with every wrapper quirk the render has (translate.rs:36).
  * RT_RAYS_ANY answers with SOME primitive that has a hit inside the window (which one is unspecified), and the record of
  * that hit.
+ *
+ * A ray that lies EXACTLY in the plane of a rect or of a box's side meets the reference's own 0 / 0 there: as in the
+ * reference that primitive then answers with t = NaN, and which primitive the query names is unspecified.
+ *
+ * The planes of RtRays must not be written to while a query that reads them is in flight: a kernel may read a ray's
+ * entries more than once.
  *
  * A miss is t = +inf, prim = obj_id = RT_RAY_MISS and zeros elsewhere.  An INVALID ray — a non-finite origin, direction,
  * time or t_min, t_min < 0, a t_max that is NaN or below t_min, a direction of all zeros — is answered in its lane with

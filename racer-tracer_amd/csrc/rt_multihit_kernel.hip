@@ -7,6 +7,7 @@
 // No LDS, no scratch (the list is a compile-time recursion over scalars, never an array), no inline assembly of its own.
 #include "rt_bvh_kbest.h"
 #include "rt_scene.h"
+#include "rt_query_ray.h"
 
 namespace RT_KNS {
 
@@ -22,30 +23,26 @@ __global__ __launch_bounds__(256) void k_trace_rays_multi_f64(const TraceArgs A,
     if (ray >= (unsigned)n) return;
     const size_t r = (size_t)ray;
 
-    const d3 o = ld3(R.origin + 3 * r), d = ld3(R.direction + 3 * r);
-    const double t_min = R.t_min ? R.t_min[r] : 0.001; // renderer.rs:58
-    const double t_max = R.t_max ? R.t_max[r] : __builtin_inf();
-    const double time = R.time ? R.time[r] : 0.0;
-
-    // k_trace_rays_f64's rule, decided here, before any hit code runs (every comparison is false on a NaN)
+    // judged and normalised before any hit code runs (rt_query_ray.h): the walk sees dn and [lo, hi], the record o, d and t
+    const QueryRay q = load_query_ray(R, r);
+    const d3 o = q.o, dn = q.dn;
+    const double time = q.time, t_min = q.lo, t_max = q.hi;
+    const bool valid = q.valid;
     const double INF = __builtin_inf();
-    const bool valid = fabs(o.x) < INF && fabs(o.y) < INF && fabs(o.z) < INF && fabs(d.x) < INF && fabs(d.y) < INF &&
-                       fabs(d.z) < INF && fabs(time) < INF && t_min >= 0.0 && t_min < INF && t_max >= t_min &&
-                       (d.x != 0.0 || d.y != 0.0 || d.z != 0.0);
 
     KBest<CAP> L;
     kbest_clear(L);
     if (valid) {
-        const d3 inv_d = rcp3(d);
-        const double inv_a = rcp_f64(len2(d));
+        const d3 inv_d = rcp3(dn);
+        const double inv_a = rcp_f64(len2(dn));
         if (BVH) {
-            kbest_hit_bvh<PRIMS_ANY, CAP>(A, bvh_nodes_for(A, d), o, d, inv_d, inv_a, time, t_min, t_max, k, L);
+            kbest_hit_bvh<PRIMS_ANY, CAP>(A, bvh_nodes_for(A, dn), o, dn, inv_d, inv_a, time, t_min, t_max, k, L);
         } else {
             double far = t_max;
             for (int i = 0; i < A.n_prims; ++i) { // the render's loop, with the k-th hit where it has the best one
                 double t;
                 int aux;
-                if (prim_t<PRIMS_ANY>(load_prim_uniform(A.prims, i), o, d, inv_d, inv_a, time, t_min, far, t, aux)) {
+                if (prim_t<PRIMS_ANY>(load_prim_uniform(A.prims, i), o, dn, inv_d, inv_a, time, t_min, far, t, aux)) {
                     kbest_insert(L, t, i, aux);
                     far = kbest_far(L, k, t_max);
                 }
@@ -55,6 +52,7 @@ __global__ __launch_bounds__(256) void k_trace_rays_multi_f64(const TraceArgs A,
 
     // the slots in order: each turn takes the list's first entry (no subscript, one copy of the record code)
     int filled = 0;
+    const d3 d = caller_direction(R, r);
     for (int j = 0; j < k; ++j) {
         double best_t;
         int best, best_aux;
@@ -65,8 +63,8 @@ __global__ __launch_bounds__(256) void k_trace_rays_multi_f64(const TraceArgs A,
         if (best >= 0) {
             const Prim &P = A.prims[best];
             // the f64 sphere_uv (FAST_UV = false), as in k_trace_rays_f64
-            const Hit h = prim_hit_record<PRIMS_ANY, true, false>(P, o, d, time, best_t, best_aux, H.uv != nullptr);
-            t = best_t;
+            t = caller_t(d, best_t); // in units of the caller's d, as in k_trace_rays_f64
+            const Hit h = prim_hit_record<PRIMS_ANY, true, false>(P, o, d, time, t, best_aux, H.uv != nullptr);
             x = h.point;
             nrm = h.normal;
             u = h.u;

@@ -6,6 +6,7 @@
 // No hit record, no `order` table, no LDS, no scratch, no inline assembly of its own.
 #include "rt_bvh_any.h"
 #include "rt_scene.h"
+#include "rt_query_ray.h"
 
 namespace RT_KNS {
 
@@ -17,29 +18,24 @@ __global__ __launch_bounds__(256) void k_occluded_f64(const TraceArgs A, const R
     if (ray >= (unsigned)n) return;
     const size_t r = (size_t)ray;
 
-    const d3 o = ld3(R.origin + 3 * r), d = ld3(R.direction + 3 * r);
-    const double t_min = R.t_min ? R.t_min[r] : 0.001; // renderer.rs:58
-    const double t_max = R.t_max ? R.t_max[r] : __builtin_inf();
-    const double time = R.time ? R.time[r] : 0.0;
-
-    // k_trace_rays_f64's rule, decided here, before any hit code runs (every comparison is false on a NaN)
-    const double INF = __builtin_inf();
-    const bool valid = fabs(o.x) < INF && fabs(o.y) < INF && fabs(o.z) < INF && fabs(d.x) < INF && fabs(d.y) < INF &&
-                       fabs(d.z) < INF && fabs(time) < INF && t_min >= 0.0 && t_min < INF && t_max >= t_min &&
-                       (d.x != 0.0 || d.y != 0.0 || d.z != 0.0);
+    // judged and normalised before any hit code runs (rt_query_ray.h): the walk sees dn and [lo, hi]
+    const QueryRay q = load_query_ray(R, r);
+    const d3 o = q.o, dn = q.dn;
+    const double time = q.time, t_min = q.lo, t_max = q.hi;
+    const bool valid = q.valid;
 
     bool found = false;
     if (valid) {
-        const d3 inv_d = rcp3(d);
-        const double inv_a = rcp_f64(len2(d));
+        const d3 inv_d = rcp3(dn);
+        const double inv_a = rcp_f64(len2(dn));
         if (BVH) {
-            found = any_hit_bvh<PRIMS_ANY>(A, bvh_nodes_for(A, d), o, d, inv_d, inv_a, time, t_min, t_max);
+            found = any_hit_bvh<PRIMS_ANY>(A, bvh_nodes_for(A, dn), o, dn, inv_d, inv_a, time, t_min, t_max);
         } else {
             // a lane stops at its first accepted primitive; the wave leaves when all its lanes have stopped
             for (int i = 0; i < A.n_prims; ++i) {
                 double t;
                 int aux;
-                if (!found && prim_t<PRIMS_ANY>(load_prim_uniform(A.prims, i), o, d, inv_d, inv_a, time, t_min, t_max, t, aux)) found = true;
+                if (!found && prim_t<PRIMS_ANY>(load_prim_uniform(A.prims, i), o, dn, inv_d, inv_a, time, t_min, t_max, t, aux)) found = true;
                 if (ballot(!found) == 0) break;
             }
         }

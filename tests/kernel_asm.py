@@ -9,7 +9,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
-SOURCES = {"pool": "rt_trace_pool_kernel.hip", "v1": "rt_trace_kernel.hip"}
+SOURCES = {"pool": "rt_trace_pool_kernel.hip", "v1": "rt_trace_kernel.hip", "multihit": "rt_multihit_kernel.hip"}
 # the Makefile's EXACT_FLAGS: the RT_ARITH_REFERENCE copy of the trace kernels
 FLAVOURS = {"fast": [], "exact": ["-DRT_EXACT_DIV", "-ffp-contract=off"]}
 
