@@ -2,7 +2,10 @@
 // section 4.16; include/rt_occlusion.h.)
 //
 // A SECOND COPY of closest_hit_bvh (rt_trace_common.h), on purpose: that function's descent step is 58 % of the BVH
-// variant's vector instructions, and a helper shared with it would move instructions in the pooled kernel.  Whoever
+// variant's vector instructions, and a helper shared with it would move instructions in the pooled kernel.  (That was
+// compiled once, a shared prologue plus a shared `bvh_descend`, all __forceinline__, for this walk, the closest one and
+// kbest_hit_bvh: tools/device_asm_digests.py --counts showed 16 of 84 functions moved, all eight PRETRACE variants of
+// k_trace_pool_f64 among them, and one exact variant gained scratch loads and stores.)  Whoever
 // changes one of the two reads the other.  Copied from it, line for line: the f64 clip to the root box through
 // kernargs_here(), the f32 SlabRay, the window ends rounded outward, the sentinel-terminated descent with its
 // v_pk_fma_f32 step, and the leaf test that runs sphere_t on the LeafGeo record before the tag is asked.

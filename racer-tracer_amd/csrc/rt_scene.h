@@ -182,10 +182,10 @@ struct RenderBuffers {
     DevBuf<int32_t> guide_ids;
     // rt_render_adaptive_filtered (rt_variance_filter.hip), on first use: every pixel's samples and chunks, W*H each
     DevBuf<int32_t> batch_counts;
-    // rt_trace_rays (rt_rays.hip), on first use: one chunk of rays — planes [origin 3 | direction 3 | t_min | t_max | time]
-    // x RT_RAYS_HOST_CHUNK doubles — and of answers — [t | point 3 | normal 3 | uv 2] doubles, [prim | obj_id | front_face]
-    // (rt_trace_occlusion, rt_occlusion.hip, stages through rays_in and the first plane of rays_ids; rt_trace_rays_multi,
-    // rt_multihit.hip, through all three, an eighth of a chunk's rays at a time with up to eight slots each)
+    // the host forms of the ray queries (rt_query_stage.h), on first use: one chunk of rays — planes [origin 3 | direction 3 |
+    // t_min | t_max | time] x RT_RAYS_HOST_CHUNK doubles — and of answers — [t | point 3 | normal 3 | uv 2] doubles, [prim |
+    // obj_id | front_face] (rt_trace_occlusion stages through rays_in and the first plane of rays_ids; rt_trace_rays_multi
+    // through all three, an eighth of a chunk's rays at a time with up to eight slots each)
     DevBuf<double> rays_in, rays_out;
     DevBuf<int32_t> rays_ids;
 
@@ -296,7 +296,7 @@ struct RtScene {
     rtapi::DevBuf<double> nee_pick;
     std::vector<char> pick_uniform;
     std::vector<double> pick_weights; // p_k of the uncapped list (rt_scene_light_weights)
-    // ray queries (rt_rays.hip): table_order on the device, made by the scene's first query
+    // ray queries (rt_query.hip): table_order on the device, made by the scene's first query that names primitives
     rtapi::DevBuf<int32_t> rays_order;
 
     rtapi::RenderBuffers buf;
@@ -427,11 +427,11 @@ int enqueue_levels(RtScene *s, const RtRenderParams *p, const RtDenoiseParams *d
                    const double *variance, const RtGuides &g, double *out, hipStream_t stream);
 // The trace kernels' argument block of a render (rt_api.hip: fill_args), for launches of other kernels that trace rays.
 int fill_trace_args(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, rtdev::TraceArgs &a);
-// ... its scene part alone, for the kernels that take caller rays (rt_rays.hip; rt_occlusion.hip; rt_multihit.hip): the tree when the scene
+// ... its scene part alone, for the kernels that take caller rays (rt_query.hip): the tree when the scene
 // walks one (use_bvh), and of a tree that renders keep in LDS its global copy.
 int query_args(const RtScene *s, rtdev::TraceArgs &a);
 // The device copy of RtScene.table_order in s->rays_order, made by the scene's first query that names primitives
-// (rt_rays.hip), with one synchronous copy.
+// (rt_query.hip), with one synchronous copy.
 int ensure_order(RtScene *s);
 int reserve_denoise(RtScene *s, size_t pixels, bool own_guides, bool variance_planes = false);
 RtGuides scene_guides(RtScene *s, size_t pixels);

@@ -14,9 +14,10 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi, check, lib
+from . import abi, check, lib  # noqa: F401  (importable from here as before)
 from .rays import (HIT_PLANES, RAY_PLANES, RT_RAY_INVALID, RT_RAY_MISS, RT_RAYS_HOST_CHUNK, RtRayHits, RtRays,  # noqa: F401
                    _shape)
+from .rays import binder, ray_planes, ray_planes_torch, result_tensor
 
 RT_MULTIHIT_MAX = 8
 RT_MULTIHIT_HOST_CHUNK = RT_RAYS_HOST_CHUNK // RT_MULTIHIT_MAX      # rays per staging chunk of rt_trace_rays_multi
@@ -34,16 +35,7 @@ PROTOTYPES = {
                                       C.POINTER(RtRayHits), C.c_void_p]),
 }
 
-_bound = []  # the library objects that carry PROTOTYPES (kept alive here: identity is what is compared)
-
-
-def bound(library=None):
-    """`library` (None: the default one) with PROTOTYPES attached; raises AttributeError where it lacks an entry point."""
-    library = library if library is not None else lib()
-    if not any(b is library for b in _bound):
-        abi.bind(library, PROTOTYPES)
-        _bound.append(library)
-    return library
+bound = binder(PROTOTYPES)
 
 
 def multihit_params(k=None, library=None):
@@ -65,17 +57,7 @@ def trace_rays_multi(scene, origin, direction, k, t_min=None, t_max=None, time=N
     front_face int32 — plus "count", int32 [n]."""
     library = bound(scene._lib)
     k = int(k)
-    given = {"origin": origin, "direction": direction, "t_min": t_min, "t_max": t_max, "time": time}
-    n = len(origin)
-    rays, keep = RtRays(), []
-    for name, width in RAY_PLANES.items():
-        if given[name] is None:
-            continue
-        a = np.ascontiguousarray(given[name], dtype=np.float64)
-        if a.shape != _shape(width, n):
-            raise ValueError("%s must have shape %s" % (name, _shape(width, n)))
-        keep.append(a)
-        setattr(rays, name, a.ctypes.data)
+    rays, n, _keep = ray_planes(origin, direction, t_min, t_max, time)
     p = multihit_params(k, library)
     rows = min(max(k, 0), RT_MULTIHIT_MAX)      # (a k the C call refuses allocates nothing of its size)
     out, hits = {}, RtRayHits()
@@ -100,17 +82,7 @@ def trace_rays_multi_torch(scene, origin, direction, k, t_min=None, t_max=None, 
     import torch
     library = bound(scene._lib)
     k = int(k)
-    dev = torch.device("cuda", scene.device)
-    given = {"origin": origin, "direction": direction, "t_min": t_min, "t_max": t_max, "time": time}
-    n = int(origin.shape[0])
-    rays = RtRays()
-    for name, width in RAY_PLANES.items():
-        a = given[name]
-        if a is None:
-            continue
-        if a.dtype != torch.float64 or not a.is_contiguous() or a.device != dev or tuple(a.shape) != _shape(width, n):
-            raise ValueError("%s must be a contiguous float64 tensor of shape %s on %s" % (name, _shape(width, n), dev))
-        setattr(rays, name, a.data_ptr())
+    rays, n, dev = ray_planes_torch(scene, origin, direction, t_min, t_max, time)
     p = multihit_params(k, library)
     rows = min(max(k, 0), RT_MULTIHIT_MAX)
     result, hits = {}, RtRayHits()
@@ -118,12 +90,9 @@ def trace_rays_multi_torch(scene, origin, direction, k, t_min=None, t_max=None, 
     for name, width, is_double in wanted:
         dtype = torch.float64 if is_double else torch.int32
         need = n if name == "count" else rows * n * width
-        if out is not None and name in out:
-            a = out[name]
-            if a.dtype != dtype or not a.is_contiguous() or a.device != dev or a.numel() < need:
-                raise ValueError("out[%r] must be a contiguous %s tensor of at least %d elements on %s" % (name, dtype, need, dev))
-        else:
-            a = torch.empty((n,) if name == "count" else _slots(width, rows, n), dtype=dtype, device=dev)
+        a = result_tensor(out.get(name) if out is not None else None, (n,) if name == "count" else _slots(width, rows, n), dtype,
+                          dev, lambda a: a.numel() >= need,
+                          "out[%r] must be a contiguous %s tensor of at least %d elements on %s" % (name, dtype, need, dev))
         result[name] = a
         if name != "count":
             setattr(hits, name, a.data_ptr() if need else None)

@@ -12,41 +12,23 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi, check, lib
+from . import abi, check, lib  # noqa: F401  (importable from here as before)
 from .rays import RAY_PLANES, RT_RAY_INVALID, RT_RAYS_HOST_CHUNK, RtRays, _shape  # noqa: F401  (re-exported)
+from .rays import binder, ray_planes, ray_planes_torch, result_tensor
 
 PROTOTYPES = {
     "rt_trace_occlusion_device": (C.c_int, [C.c_void_p, C.POINTER(RtRays), C.c_int64, C.c_void_p, C.c_void_p]),
     "rt_trace_occlusion": (C.c_int, [C.c_void_p, C.POINTER(RtRays), C.c_int64, C.c_void_p]),
 }
 
-_bound = []  # the library objects that carry PROTOTYPES (kept alive here: identity is what is compared)
-
-
-def bound(library=None):
-    """`library` (None: the default one) with PROTOTYPES attached; raises AttributeError where it lacks an entry point."""
-    library = library if library is not None else lib()
-    if not any(b is library for b in _bound):
-        abi.bind(library, PROTOTYPES)
-        _bound.append(library)
-    return library
+bound = binder(PROTOTYPES)
 
 
 def occluded(scene, origins, directions, t_min=None, t_max=None, time=None):
     """rt_trace_occlusion on numpy arrays: origins, directions [n, 3]; t_min, t_max, time [n] or None (0.001, +inf, 0).
     -> int32 [n]: 1 occluded, 0 not, RT_RAY_INVALID for an invalid ray."""
     library = bound(scene._lib)
-    given = {"origin": origins, "direction": directions, "t_min": t_min, "t_max": t_max, "time": time}
-    n = len(origins)
-    rays, keep = RtRays(), []
-    for name, width in RAY_PLANES.items():
-        if given[name] is None:
-            continue
-        a = np.ascontiguousarray(given[name], dtype=np.float64)
-        if a.shape != _shape(width, n):
-            raise ValueError("%s must have shape %s" % (name, _shape(width, n)))
-        keep.append(a)
-        setattr(rays, name, a.ctypes.data)
+    rays, n, _keep = ray_planes(origins, directions, t_min, t_max, time)
     out = np.zeros(max(n, 1), dtype=np.int32)      # (never a NULL address, an empty batch included)
     check(library.rt_trace_occlusion(scene._h, C.byref(rays), n, out.ctypes.data), "rt_trace_occlusion", library)
     return out[:n]
@@ -59,22 +41,9 @@ def occluded_torch(scene, origins, directions, t_min=None, t_max=None, time=None
     whole)."""
     import torch
     library = bound(scene._lib)
-    dev = torch.device("cuda", scene.device)
-    given = {"origin": origins, "direction": directions, "t_min": t_min, "t_max": t_max, "time": time}
-    n = int(origins.shape[0])
-    rays = RtRays()
-    for name, width in RAY_PLANES.items():
-        a = given[name]
-        if a is None:
-            continue
-        if a.dtype != torch.float64 or not a.is_contiguous() or a.device != dev or tuple(a.shape) != _shape(width, n):
-            raise ValueError("%s must be a contiguous float64 tensor of shape %s on %s" % (name, _shape(width, n), dev))
-        setattr(rays, name, a.data_ptr())
-    if out is not None:
-        if out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev or out.dim() != 1 or out.shape[0] < n:
-            raise ValueError("out must be a contiguous int32 tensor of at least %d elements on %s" % (n, dev))
-    else:
-        out = torch.empty(n, dtype=torch.int32, device=dev)
+    rays, n, dev = ray_planes_torch(scene, origins, directions, t_min, t_max, time)
+    out = result_tensor(out, n, torch.int32, dev, lambda a: a.dim() == 1 and a.shape[0] >= n,
+                        "out must be a contiguous int32 tensor of at least %d elements on %s" % (n, dev))
     if n == 0:      # (an empty tensor has no address to pass, and rt_trace_occlusion_device would enqueue nothing)
         return out
     with torch.cuda.device(dev):

@@ -43,16 +43,21 @@ HIT_PLANES = {"t": (1, True), "point": (3, True), "normal": (3, True), "uv": (2,
               "obj_id": (1, False), "front_face": (1, False)}
 RAY_PLANES = {"origin": 3, "direction": 3, "t_min": 1, "t_max": 1, "time": 1}
 
-_bound = []  # the library objects that carry PROTOTYPES (kept alive here: identity is what is compared)
+def binder(prototypes):
+    """-> bound(library=None) over one module's `prototypes`: `library` (None: the default one) with them attached, once per
+    library object; raises AttributeError where the library lacks an entry point."""
+    attached = []  # the library objects that carry the prototypes (kept alive here: identity is what is compared)
+
+    def bound(library=None):
+        library = library if library is not None else lib()
+        if not any(b is library for b in attached):
+            abi.bind(library, prototypes)
+            attached.append(library)
+        return library
+    return bound
 
 
-def bound(library=None):
-    """`library` (None: the default one) with PROTOTYPES attached; raises AttributeError where it lacks an entry point."""
-    library = library if library is not None else lib()
-    if not any(b is library for b in _bound):
-        abi.bind(library, PROTOTYPES)
-        _bound.append(library)
-    return library
+bound = binder(PROTOTYPES)
 
 
 def query_params(mode=RT_RAYS_CLOSEST, library=None):
@@ -67,13 +72,11 @@ def _shape(width, n):
     return (n,) if width == 1 else (n, width)
 
 
-def trace_rays(scene, origins, directions, t_min=None, t_max=None, time=None, mode=RT_RAYS_CLOSEST, planes=tuple(HIT_PLANES)):
-    """rt_trace_rays on numpy arrays: origins, directions [n, 3]; t_min, t_max, time [n] or None (0.001, +inf, 0).
-    -> dict of numpy planes (`planes`: which; all by default): t [n], point, normal [n, 3], uv [n, 2] f64; prim, obj_id,
-    front_face [n] int32.  A miss has t = inf and prim = RT_RAY_MISS, an invalid ray prim = RT_RAY_INVALID."""
-    library = bound(scene._lib)
-    given = {"origin": origins, "direction": directions, "t_min": t_min, "t_max": t_max, "time": time}
-    n = len(origins)
+def ray_planes(origin, direction, t_min, t_max, time):
+    """The caller's ray planes as numpy converts them -> (RtRays, n, the converted arrays: keep them until the call is over).
+    ValueError for a plane whose shape is not [n, 3] / [n]."""
+    given = {"origin": origin, "direction": direction, "t_min": t_min, "t_max": t_max, "time": time}
+    n = len(origin)
     rays, keep = RtRays(), []
     for name, width in RAY_PLANES.items():
         if given[name] is None:
@@ -83,6 +86,44 @@ def trace_rays(scene, origins, directions, t_min=None, t_max=None, time=None, mo
             raise ValueError("%s must have shape %s" % (name, _shape(width, n)))
         keep.append(a)
         setattr(rays, name, a.ctypes.data)
+    return rays, n, keep
+
+
+def ray_planes_torch(scene, origin, direction, t_min, t_max, time):
+    """The caller's ray planes as tensors of the scene's device -> (RtRays, n, that device).  ValueError for a plane that is
+    not contiguous f64 of shape [n, 3] / [n] there."""
+    import torch
+    dev = torch.device("cuda", scene.device)
+    given = {"origin": origin, "direction": direction, "t_min": t_min, "t_max": t_max, "time": time}
+    n = int(origin.shape[0])
+    rays = RtRays()
+    for name, width in RAY_PLANES.items():
+        a = given[name]
+        if a is None:
+            continue
+        if a.dtype != torch.float64 or not a.is_contiguous() or a.device != dev or tuple(a.shape) != _shape(width, n):
+            raise ValueError("%s must be a contiguous float64 tensor of shape %s on %s" % (name, _shape(width, n), dev))
+        setattr(rays, name, a.data_ptr())
+    return rays, n, dev
+
+
+def result_tensor(own, shape, dtype, dev, fits, refusal):
+    """A fresh result tensor of `shape`, or the caller's `own` where there is one: ValueError(refusal) unless it is
+    contiguous, of `dtype`, on `dev` and fits(own)."""
+    import torch
+    if own is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if own.dtype != dtype or not own.is_contiguous() or own.device != dev or not fits(own):
+        raise ValueError(refusal)
+    return own
+
+
+def trace_rays(scene, origins, directions, t_min=None, t_max=None, time=None, mode=RT_RAYS_CLOSEST, planes=tuple(HIT_PLANES)):
+    """rt_trace_rays on numpy arrays: origins, directions [n, 3]; t_min, t_max, time [n] or None (0.001, +inf, 0).
+    -> dict of numpy planes (`planes`: which; all by default): t [n], point, normal [n, 3], uv [n, 2] f64; prim, obj_id,
+    front_face [n] int32.  A miss has t = inf and prim = RT_RAY_MISS, an invalid ray prim = RT_RAY_INVALID."""
+    library = bound(scene._lib)
+    rays, n, _keep = ray_planes(origins, directions, t_min, t_max, time)
     out, hits = {}, RtRayHits()
     for name in planes:
         width, is_double = HIT_PLANES[name]
@@ -101,30 +142,15 @@ def trace_rays_torch(scene, origins, directions, t_min=None, t_max=None, time=No
     place of fresh ones."""
     import torch
     library = bound(scene._lib)
-    dev = torch.device("cuda", scene.device)
-    given = {"origin": origins, "direction": directions, "t_min": t_min, "t_max": t_max, "time": time}
-    n = int(origins.shape[0])
-    rays = RtRays()
-    for name, width in RAY_PLANES.items():
-        a = given[name]
-        if a is None:
-            continue
-        if a.dtype != torch.float64 or not a.is_contiguous() or a.device != dev or tuple(a.shape) != _shape(width, n):
-            raise ValueError("%s must be a contiguous float64 tensor of shape %s on %s" % (name, _shape(width, n), dev))
-        setattr(rays, name, a.data_ptr())
+    rays, n, dev = ray_planes_torch(scene, origins, directions, t_min, t_max, time)
     result, hits = {}, RtRayHits()
     for name in planes:
         width, is_double = HIT_PLANES[name]
-        dtype = torch.float64 if is_double else torch.int32
-        if out is not None:
-            a = out[name]
-            if (a.dtype != dtype or not a.is_contiguous() or a.device != dev or a.shape[0] < n
-                    or tuple(a.shape[1:]) != _shape(width, n)[1:]):
-                raise ValueError("out[%r] must be a contiguous %s tensor of at least %d rows on %s" % (name, dtype, n, dev))
-        else:
-            a = torch.empty(_shape(width, n), dtype=dtype, device=dev)
-        result[name] = a
-        setattr(hits, name, a.data_ptr())
+        dtype, shape = torch.float64 if is_double else torch.int32, _shape(width, n)
+        result[name] = result_tensor(out[name] if out is not None else None, shape, dtype, dev,
+                                     lambda a: a.shape[0] >= n and tuple(a.shape[1:]) == shape[1:],
+                                     "out[%r] must be a contiguous %s tensor of at least %d rows on %s" % (name, dtype, n, dev))
+        setattr(hits, name, result[name].data_ptr())
     q = query_params(mode, library)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
