@@ -1,6 +1,7 @@
 // rt_query.hip — the host side of every query on caller rays: closest / any hit (include/rt_rays.h),
-// occlusion (include/rt_occlusion.h; 4.16) and multi-hit (include/rt_multihit.h; 4.17).  Each entry point states its own
-// refusals and its launch (rt_rays_kernel.hip, rt_occlusion_kernel.hip, rt_multihit_kernel.hip); the refusals they share,
+// occlusion (include/rt_occlusion.h; 4.16), multi-hit (include/rt_multihit.h; 4.17) and, on caller points, ambient
+// occlusion with its frame (include/rt_ambient.h; 4.18).  Each entry point states its own refusals and its launch
+// (rt_rays_kernel.hip, rt_occlusion_kernel.hip, rt_multihit_kernel.hip, rt_ambient_kernel.hip); the refusals they share,
 // the steps before a launch and the chunked host form (rt_query_stage.h) are stated once.
 //
 // Host code only (HIP runtime calls).  A query takes every scene rt_render_guides_device takes and follows its rules: the
@@ -8,6 +9,7 @@
 // in whichever child order the last camera left it (a walk is correct in any order: rt_bvh_any.h, rt_bvh_kbest.h).
 #include "rt_query_stage.h"
 
+#include <cmath>
 #include <cstring>
 
 using rtapi::fail;
@@ -71,6 +73,47 @@ int check_multi(const RtScene *s, const RtRays *rays, int64_t n, const RtMultiHi
     if (p->k < 1 || p->k > RT_MULTIHIT_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "params->k must be in 1..RT_MULTIHIT_MAX");
     if (p->_reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, "params->_reserved must be 0");
     return check_batch(s, rays, n);
+}
+
+// The ambient query's params, and the batch against them (index_base + n): every cause with its own message.
+int check_ambient_params(const RtAmbientParams *p, int64_t n) {
+    if (!p) return fail(RT_ERR_INVALID_ARGUMENT, "the ambient params are NULL");
+    if (p->samples < 1 || p->samples > RT_AMBIENT_MAX_SAMPLES || (p->samples & (p->samples - 1)) != 0)
+        return fail(RT_ERR_INVALID_ARGUMENT, "params->samples must be a power of two in 1..RT_AMBIENT_MAX_SAMPLES");
+    if (p->_reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, "params->_reserved must be 0");
+    if (!(p->bias >= 0.0) || !std::isfinite(p->bias)) return fail(RT_ERR_INVALID_ARGUMENT, "params->bias must be finite and not negative");
+    if (!(p->radius >= p->bias)) return fail(RT_ERR_INVALID_ARGUMENT, "params->radius must not be NaN or below params->bias");
+    if (p->index_base < 0 || p->index_base > ((int64_t)1 << 32) || (n > 0 && p->index_base + n > ((int64_t)1 << 32)))
+        return fail(RT_ERR_INVALID_ARGUMENT, "params->index_base must be at least 0 and index_base + n at most 2^32");
+    return RT_OK;
+}
+
+int check_ambient(const RtScene *s, const RtRays *points, int64_t n, const RtAmbientParams *p, const int32_t *open) {
+    if (!points) return fail(RT_ERR_INVALID_ARGUMENT, "points is NULL");
+    if (!open) return fail(RT_ERR_INVALID_ARGUMENT, "open is NULL");
+    if (n < 0 || n > (int64_t)INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "n must be in 0..INT32_MAX");
+    const int rc = check_ambient_params(p, n);
+    if (rc != RT_OK) return rc;
+    if (n > 0 && !points->origin) return fail(RT_ERR_INVALID_ARGUMENT, "points->origin is NULL");
+    if (n > 0 && !points->direction) return fail(RT_ERR_INVALID_ARGUMENT, "points->direction (the normals) is NULL");
+    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    return RT_OK;
+}
+
+// The frame forms: rt_render_guides_device's refusals (rt_denoise.hip), the ambient params for W * H points from index 0,
+// the scene last.  `guides`: the caller's, or NULL for the host-output form, which brings the scene's own.
+int check_ambient_frame(const RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtAmbientParams *ap, const RtGuides *guides,
+                        bool own_guides, const double *out) {
+    RtDenoiseParams none;
+    rt_denoise_params_default(&none);
+    int rc = rtapi::check_denoise(p, &none);
+    if (rc != RT_OK) return rc;
+    if (!own_guides && !rtapi::guides_complete(guides)) return fail(RT_ERR_INVALID_ARGUMENT, "guides_device or one of its planes is NULL");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    if ((rc = check_ambient_params(ap, (int64_t)p->width * (int64_t)p->height)) != RT_OK) return rc;
+    if (ap->index_base != 0) return fail(RT_ERR_INVALID_ARGUMENT, "ambient->index_base must be 0 for a frame: pixel p is point p");
+    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    return rtapi::check_params(camera, p);
 }
 
 // Behind an entry point's checks (`checked`: what they said) and before its launches: nothing for a refused or an empty
@@ -141,6 +184,66 @@ int multi_host(RtScene *s, const RtRays *rays, int64_t n, const RtMultiHitParams
                               });
 }
 
+// `walked`: the header's rays_out_device (here a ray plane by that name is the staging buffer's, rt_query_stage.h)
+int ambient_device(RtScene *s, const RtRays *points, int64_t n, const RtAmbientParams *p, int32_t *open, const RtAmbientRays *walked,
+                   void *stream) {
+    rtdev::TraceArgs a;
+    const int rc = begin_query(s, check_ambient(s, points, n, p, open), n, false, a);
+    if (rc != RT_OK || n == 0) return rc;
+    RT_HIP(s->kernels->ambient(&a, points, (int)n, p, 0.0, open, nullptr, nullptr, walked, (hipStream_t)stream));
+    return RT_OK;
+}
+
+int ambient_host(RtScene *s, const RtRays *points, int64_t n, const RtAmbientParams *p, int32_t *open) {
+    rtdev::TraceArgs a;
+    const int rc = begin_query(s, check_ambient(s, points, n, p, open), n, false, a);
+    if (rc != RT_OK || n == 0) return rc;
+    RtAmbientParams chunk = *p; // every chunk's launch names the index of its first point: the answer is the whole batch's
+    return rtapi::stage_query(s->buf, kPlane, points, (size_t)n, nullptr, 1, 1, open, [&](const RtRays &dp, const RtRayHits &, int32_t *answers, int m) {
+        const hipError_t e = s->kernels->ambient(&a, &dp, m, &chunk, 0.0, answers, nullptr, nullptr, nullptr, s->buf.stream);
+        chunk.index_base += m;
+        return e;
+    });
+}
+
+// The guides of (camera, p) into g, then the query at every pixel into `out` (both device memory), on `stream`.
+int enqueue_ambient_frame(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtAmbientParams *ap, const RtGuides &g, double *out,
+                          hipStream_t stream) {
+    int rc = rtapi::enqueue_guides(s, camera, p, g, stream);
+    if (rc != RT_OK) return rc;
+    rtdev::TraceArgs a;
+    if ((rc = rtapi::query_args(s, a)) != RT_OK) return rc;
+    RtRays points;
+    points.origin = g.position;
+    points.direction = g.normal;
+    points.t_min = points.t_max = points.time = nullptr;
+    const double mid = (camera->time_a + camera->time_b) * 0.5; // the guides' own time (rt_abi.h)
+    RT_HIP(s->kernels->ambient(&a, &points, p->width * p->height, ap, mid, nullptr, out, g.obj_id, nullptr, stream));
+    return RT_OK;
+}
+
+int ambient_frame_device(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtAmbientParams *ap, const RtGuides *g, double *out,
+                         void *stream) {
+    const int rc = check_ambient_frame(s, camera, p, ap, g, false, out);
+    if (rc != RT_OK) return rc;
+    RT_HIP(hipSetDevice(s->device));
+    return enqueue_ambient_frame(s, camera, p, ap, *g, out, (hipStream_t)stream);
+}
+
+int ambient_frame_host(RtScene *s, const RtCamera *camera, const RtRenderParams *p, const RtAmbientParams *ap, double *out) {
+    int rc = check_ambient_frame(s, camera, p, ap, nullptr, true, out);
+    if (rc != RT_OK) return rc;
+    RT_HIP(hipSetDevice(s->device));
+    const size_t pixels = (size_t)p->width * (size_t)p->height, n = 3 * pixels;
+    rtapi::RenderBuffers &b = s->buf;
+    if ((rc = rtapi::reserve_denoise(s, pixels, true)) != RT_OK) return rc;
+    RT_HIP(b.frame.reserve(n));
+    if ((rc = enqueue_ambient_frame(s, camera, p, ap, rtapi::scene_guides(s, pixels), b.frame.ptr, b.stream)) != RT_OK) return rc;
+    RT_HIP(hipStreamSynchronize(b.stream));
+    RT_HIP(hipMemcpy(out, b.frame.ptr, n * sizeof(double), hipMemcpyDeviceToHost)); // (a frame, not ray planes: those are rt_query_stage.h's)
+    return RT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -183,6 +286,34 @@ int rt_trace_rays_multi_device(RtScene *s, const RtRays *rays_device, int64_t n,
 int rt_trace_rays_multi(RtScene *s, const RtRays *rays_host, int64_t n, const RtMultiHitParams *params, const RtRayHits *hits_host,
                         int32_t *count_host) {
     return rtapi::guarded("rt_trace_rays_multi", [&] { return multi_host(s, rays_host, n, params, hits_host, count_host); });
+}
+
+void rt_ambient_params_default(RtAmbientParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof *out);
+    out->samples = 16;
+    out->bias = 1e-3;
+    out->radius = __builtin_inf();
+}
+
+int rt_trace_ambient_device(RtScene *s, const RtRays *points_device, int64_t n, const RtAmbientParams *params, int32_t *open_device,
+                            const RtAmbientRays *walked_device, void *hip_stream) {
+    return rtapi::guarded("rt_trace_ambient_device",
+                          [&] { return ambient_device(s, points_device, n, params, open_device, walked_device, hip_stream); });
+}
+
+int rt_trace_ambient(RtScene *s, const RtRays *points_host, int64_t n, const RtAmbientParams *params, int32_t *open_host) {
+    return rtapi::guarded("rt_trace_ambient", [&] { return ambient_host(s, points_host, n, params, open_host); });
+}
+
+int rt_render_ambient_device(RtScene *s, const RtCamera *camera, const RtRenderParams *params, const RtAmbientParams *ambient,
+                             const RtGuides *guides_device, double *out_device, void *hip_stream) {
+    return rtapi::guarded("rt_render_ambient_device",
+                          [&] { return ambient_frame_device(s, camera, params, ambient, guides_device, out_device, hip_stream); });
+}
+
+int rt_render_ambient(RtScene *s, const RtCamera *camera, const RtRenderParams *params, const RtAmbientParams *ambient, double *out_host) {
+    return rtapi::guarded("rt_render_ambient", [&] { return ambient_frame_host(s, camera, params, ambient, out_host); });
 }
 
 } // extern "C"

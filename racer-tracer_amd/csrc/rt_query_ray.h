@@ -1,6 +1,6 @@
 // rt_query_ray.h — what the three ray queries (rt_rays_kernel.hip, rt_occlusion_kernel.hip, rt_multihit_kernel.hip) do
 // with a ray the caller brings before any hit code sees it: the validity rule, once, and a power-of-two normalisation of
-// the direction.
+// the direction.  (rt_ambient_kernel.hip judges its points by the same rule and scales their normals by the same factor.)
 //
 // Why the direction is normalised.  "The direction has any length and t is in units of it" (include/rt_rays.h), but the
 // tree walks cull in single precision with 1 / d clamped to +-2^64 (rt_bvh_slab.h: slab_finite — the clamp is there for

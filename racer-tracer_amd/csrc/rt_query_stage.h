@@ -1,5 +1,5 @@
 // rt_query_stage.h — the chunked host form of every query on caller rays (rt_query.hip: rt_trace_rays, rt_trace_occlusion,
-// rt_trace_rays_multi), ONCE: the caller's host planes go through the scene's three staging buffers a chunk at a time, a
+// rt_trace_rays_multi; rt_trace_ambient's points are staged as rays are), ONCE: the caller's host planes go through the scene's three staging buffers a chunk at a time, a
 // launch per chunk, the answers back behind it.  Runtime calls only (reserve, hipMemcpyAsync, hipStreamSynchronize), no
 // kernel and no launcher of its own: it compiles with a plain host compiler against a fake runtime
 // (tests/query_stage_driver.cpp).  Private to the library.

@@ -19,6 +19,7 @@
 #include "../../include/rt_rays.h"
 #include "../../include/rt_occlusion.h"
 #include "../../include/rt_multihit.h"
+#include "../../include/rt_ambient.h"
 
 // The trace kernels exist twice (rt_trace_common.h: ARITHMETIC): RT_ARITH_FAST, and RT_ARITH_REFERENCE behind *_exact.
 // Every launcher that has both flavours, ONCE: X(member of rtapi::Launchers, exported name, return type, parameters).  The
@@ -41,6 +42,9 @@
 //     a hit inside the ray's window (include/rt_occlusion.h).
 //   multihit (rt_multihit_kernel.hip): n caller rays of device planes against args' scene, the first k primitives
 //     along each ray into slot-major planes and a count per ray (include/rt_multihit.h); `order` as for trace_rays.
+//   ambient (rt_ambient_kernel.hip): n caller points of device planes against args' scene, params' hemisphere samples of
+//     each formed, walked and counted (include/rt_ambient.h): the count into `open`, or its frame value into `frame` beside
+//     the guides' obj_id; the rays it walked into `walked`'s planes where there are some.
 #define RT_LAUNCHER_LIST(X)                                                                                                \
     X(trace, rtdev_launch_trace, hipError_t,                                                                               \
       (const rtdev::TraceArgs *args, int prims_class, int textured, int specular, hipStream_t stream))                     \
@@ -93,7 +97,10 @@
       (const rtdev::TraceArgs *args, const RtRays *rays, int32_t *occluded, int n, hipStream_t stream))                    \
     X(multihit, rtdev_launch_multihit, hipError_t,                                                                         \
       (const rtdev::TraceArgs *args, const RtRays *rays, const RtRayHits *hits, int32_t *count, const int32_t *order,     \
-       int n, int k, hipStream_t stream))
+       int n, int k, hipStream_t stream))                                                                                  \
+    X(ambient, rtdev_launch_ambient, hipError_t,                                                                           \
+      (const rtdev::TraceArgs *args, const RtRays *points, int n, const RtAmbientParams *params, double default_time,      \
+       int32_t *open, double *frame, const int32_t *obj_id, const RtAmbientRays *walked, hipStream_t stream))
 #define RT_DECLARE_LAUNCHER(member, name, ret, params) \
     extern "C" ret name params;                        \
     extern "C" ret name##_exact params;

@@ -262,6 +262,19 @@ Args Args::parse(int argc, const char *const *argv) {
             if (!ok) throw TracerError::ArgumentParsingError(s + " needs two points as AX,AY,AZ,BX,BY,BZ, not '" + v + "'");
             a.visible = true;
         }
+        else if (s == "--ao") {
+            const std::string v = val();
+            char *end = nullptr, *end2 = nullptr;
+            const long n = std::strtol(v.c_str(), &end, 10);
+            bool ok = !v.empty() && end != v.c_str() && n >= 1 && n <= 1024 && (n & (n - 1)) == 0 && (*end == '\0' || *end == ',');
+            if (ok && *end == ',') {
+                a.ao_radius = std::strtod(end + 1, &end2);
+                ok = end2 != end + 1 && *end2 == '\0' && a.ao_radius > 0.0 && !std::isnan(a.ao_radius);
+            }
+            if (!ok)
+                throw TracerError::ArgumentParsingError(s + " needs a sample count, a power of two in 1..1024, and optionally a radius > 0 as S[,RADIUS], not '" + v + "'");
+            a.ao = (int)n;
+        }
         else if (s == "--temporal" || s == "--preview-temporal") {
             const std::string v = val();
             char *end = nullptr;
@@ -323,6 +336,9 @@ Args Args::parse(int argc, const char *const *argv) {
     if (a.preview_temporal > 0 && (a.devices > 1 || a.nee || a.nee_stream || a.nee_devices > 0 || a.adaptive > 0.0 || a.nee_adaptive > 0.0 ||
                                    a.temporal > 0 || a.denoise_variance || a.preview_upsample))
         throw TracerError::ArgumentParsingError("--preview-temporal is a render mode of its own on one device: it combines with --denoise only");
+    if (a.ao > 0 && (a.devices > 1 || a.nee_devices > 0 || a.nee || a.nee_stream || a.adaptive > 0.0 || a.nee_adaptive > 0.0 || a.temporal > 0 ||
+                     a.denoise || a.denoise_variance || a.preview_upsample || a.preview_temporal > 0))
+        throw TracerError::ArgumentParsingError("--ao is a render mode of its own on one device: it combines with no other render mode or filter");
     if (a.nee_list_given && !(a.nee || a.nee_stream || a.nee_devices > 0 || a.nee_adaptive > 0.0))
         throw TracerError::ArgumentParsingError("--nee-lights and --nee-pick set the light list of next-event estimation: they need --nee, --nee-stream, --nee-devices or --nee-adaptive");
     return a;

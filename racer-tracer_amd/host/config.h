@@ -93,6 +93,10 @@ struct Args { // config.rs:12-28
     // rt_trace_occlusion (include/rt_occlusion.h) with the window [1e-3, 1 - 1e-3], one line on stdout; six finite numbers
     bool visible = false;
     double visible_ab[6] = {0, 0, 0, 0, 0, 0};
+    // --ao S[,RADIUS]: the ambient-occlusion frame of the configured camera (rt_render_ambient, include/rt_ambient.h) in
+    // place of the path-traced one: S samples per pixel, a power of two in 1..1024, and a radius > 0 (default: none)
+    int ao = 0;
+    double ao_radius = 0.0; // 0: the default, +inf
     bool help = false;
 
     static Args parse(int argc, const char *const *argv);

@@ -26,6 +26,8 @@
 // --pick-through X,Y[,K] asks for the first K primitives under that pixel, in order (include/rt_multihit.h), one line each.
 // --visible AX,AY,AZ,BX,BY,BZ asks the scene, after the run, whether the segment between the two points is free
 // (include/rt_occlusion.h) and prints yes or no on stdout.
+// --ao S[,RADIUS] renders the ambient-occlusion frame of the configured camera (include/rt_ambient.h: rt_render_ambient, S
+// hemisphere samples per pixel within RADIUS) in place of the path-traced one; it goes through the tone map and the image action.
 // The reference opens a window and renders when R is released (scene_controller/interactive.rs:83-86); this renders the final
 // image once and exits, which is what `--image-action png` is for.
 #include <chrono>
@@ -36,6 +38,7 @@
 #include <vector>
 #include "../../include/rt_host.h"
 #include "../../include/rt_preview_temporal.h"
+#include "../../include/rt_ambient.h"
 #include "../../include/rt_multihit.h"
 #include "../../include/rt_occlusion.h"
 #include "../../include/rt_rays.h"
@@ -152,7 +155,7 @@ int main(int argc, char **argv) {
         return e.code();
     }
     if (args.help) {
-        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample] [--preview-temporal K] [--pick X,Y] [--pick-through X,Y[,K]] [--visible AX,AY,AZ,BX,BY,BZ]\n");
+        printf("racer-tracer-amd [-c config.yml] [-s scene.yml|sandbox] [--image-action png|none] [--seed N] [--device N] [--devices N] [--denoise] [--denoise-variance] [--adaptive T] [--nee] [--nee-stream] [--nee-devices N] [--nee-adaptive T] [--nee-lights plain|all] [--nee-pick uniform|power] [--temporal K] [--preview-upsample] [--preview-temporal K] [--pick X,Y] [--pick-through X,Y[,K]] [--visible AX,AY,AZ,BX,BY,BZ] [--ao S[,RADIUS]]\n");
         return 0;
     }
     RthSession *session = nullptr;
@@ -217,7 +220,16 @@ int main(int argc, char **argv) {
     double mean_length = 0.0; // --temporal, --preview-temporal: the mean history length behind the last frame
     double filled = 0.0;      // --preview-temporal: the share of pixels with length 0 (filled from the last frame's anchors)
     double mean_sigma = 0.0;  // --denoise-variance: the mean of sqrt(var) over the frame
-    if (args.preview_upsample) { // the preview frame, its guides, the upsample and (--denoise) the levels in one call
+    if (args.ao > 0) { // the ambient-occlusion frame in the path-traced one's place
+        RtAmbientParams ao;
+        rt_ambient_params_default(&ao);
+        ao.samples = args.ao;
+        if (args.ao_radius > 0.0) ao.radius = args.ao_radius;
+        ao.seed = params.seed;
+        std::vector<double> frame(n_rgb);
+        rc = rt_render_ambient(scenes[0], rth_session_camera(session), &params, &ao, frame.data());
+        if (rc == RT_OK) rth_tone_map(session, frame.data(), sb.buffer.data(), n_rgb / 3);
+    } else if (args.preview_upsample) { // the preview frame, its guides, the upsample and (--denoise) the levels in one call
         RtDenoiseParams dp;
         rt_denoise_params_default(&dp);
         if (!args.denoise) dp.iterations = 0;
