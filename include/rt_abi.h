@@ -296,12 +296,21 @@ enum RtGather {
     RT_GATHER_AUTO = 0,
     RT_GATHER_STAGED = 1
 };
+/* launch_blocks: a cap on the grid of this scene's persistent launches — the pooled trace kernel (whole frames, strips,
+ * the preview scale, the delivering launch, the passes of rt_render_progressive / rt_render_adaptive with their tile
+ * lists) and both NEE stream kernels.  Like RT_GATHER_STAGED a switch for tests: a launch has min(resident blocks,
+ * (items + 3) / 4) blocks, so on a large card a wave takes a second work item only in frames of many thousands of items;
+ * with launch_blocks = c > 0 a launch has min(that, c) blocks, and a SMALL frame executes the item-after-item code that
+ * a full-size frame runs.  It changes no pixel: every sum is either per item (f64 slices) or fixed-point.  0 (default):
+ * no cap.  Negative: RT_ERR_INVALID_ARGUMENT.  The v1 kernel and the lane-per-pixel NEE kernels are not persistent and
+ * ignore it. */
 typedef struct RtSceneOptions {
     int32_t closest_hit; /* RtClosestHit  */
     int32_t kernel;      /* RtTraceKernel */
     int32_t arithmetic;  /* RtArithmetic  */
     int32_t gather;      /* RtGather      */
-    int32_t _reserved[4]; /* must be 0 */
+    int32_t launch_blocks; /* 0: no cap; c > 0: at most c blocks per persistent launch */
+    int32_t _reserved[3]; /* must be 0 */
 } RtSceneOptions;
 
 /* Statistics of the last render on a scene (path segments = ray_color

@@ -109,7 +109,7 @@ RT_GATHER_AUTO, RT_GATHER_STAGED = 0, 1
 
 class RtSceneOptions(C.Structure):
     _fields_ = [("closest_hit", C.c_int32), ("kernel", C.c_int32), ("arithmetic", C.c_int32), ("gather", C.c_int32),
-                ("_reserved", C.c_int32 * 4)]
+                ("launch_blocks", C.c_int32), ("_reserved", C.c_int32 * 3)]
 
 
 RT_DENOISE_DEMODULATE = 1
@@ -281,7 +281,8 @@ PROTOTYPES = {
 
 # Internal exports of the library for the tests (csrc/rt_scene.h; not in rt_abi.h, not covered by ABI_VERSION)
 VARIANT_FIELDS = ("kernel", "prims_class", "textured", "specular", "use_bvh", "exact", "bvh_nodes_in_lds", "has_moving",
-                  "perlin_in_lds", "static_lds", "dyn_lds", "dyn_lds_lens", "blocks_per_cu", "blocks_per_cu_lens")
+                  "perlin_in_lds", "static_lds", "dyn_lds", "dyn_lds_lens", "blocks_per_cu", "blocks_per_cu_lens",
+                  "last_launch_blocks", "last_launch_items")
 CLASSIFY_FIELDS = ("prims_class", "textured", "specular", "has_moving")
 DEV_PROTOTYPES = {
     "rtdev_scene_variant": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),

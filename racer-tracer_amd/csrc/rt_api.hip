@@ -212,7 +212,8 @@ int order_bvh_for_camera(RtScene *s, const RtCamera *camera, hipStream_t stream)
 // The item grid and chunk table of a pooled render, after checking that a block fits one CU's LDS: the primitive table
 // of the linear loop, the textures, the Perlin gradients, the lens samples and the ray times all come on top of the
 // kernel's static LDS (rt_device_types.h: pool_lds_layout).  A launch that does not fit is refused here, before anything
-// is enqueued; the lens part depends on the camera.  max_blocks: the variant's resident blocks on the device.
+// is enqueued; the lens part depends on the camera.  max_blocks: the variant's resident blocks on the device, or the
+// scene's launch_blocks where that is less.
 int setup_pool_grid(const RtScene *s, rtdev::TraceArgs &a, const RtRenderParams *p, std::vector<int> &starts,
                      unsigned &max_blocks) {
     const size_t lds = (size_t)s->pool_static_lds + (a.lens_lds ? s->pool_dyn_lds_lens : s->pool_dyn_lds);
@@ -220,7 +221,7 @@ int setup_pool_grid(const RtScene *s, rtdev::TraceArgs &a, const RtRenderParams 
     if (lds > rtdev::kLdsPerCu || blocks_per_cu < 1)
         return fail(RT_ERR_UNSUPPORTED, a.lens_lds ? "the trace kernel's LDS (static + tables + lens samples) exceeds a CU's 160 KiB"
                                                    : "the trace kernel's LDS (static + tables) exceeds a CU's 160 KiB");
-    max_blocks = (unsigned)(s->num_cus * blocks_per_cu);
+    max_blocks = rtapi::cap_blocks(s, (unsigned)(s->num_cus * blocks_per_cu));
     rtapi::set_tile_grid(a, a.cover_w / a.step_x, a.owned_rows); // grid cells per row x grid rows
     starts = chunk_plan(p->samples);
     rtapi::set_chunk_table(a, starts);
@@ -270,6 +271,7 @@ int launch_pool(RtScene *s, rtdev::TraceArgs &a, const std::vector<int> &starts,
         return fail(RT_ERR_UNSUPPORTED, "more than 2^30 work items in one launch");
     a.queue = s->buf.queue.ptr + index;
     const unsigned blocks = std::min(max_blocks, (a.n_items + 3) / 4);
+    rtapi::note_grid(s, blocks, a.n_items);
     // the pixel rectangle of every rect record (rt_primary_bounds.h), from this call's camera like the scene's own, which
     // fill_args has put into `a`: the kernel's second argument (tests/test_background_flag_cpu.py holds TraceArgs to
     // ending at bg_black).  A few dozen 3x3 determinants per launch; nothing is kept between calls.

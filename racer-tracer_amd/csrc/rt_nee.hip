@@ -193,8 +193,9 @@ int rtapi::enqueue_nee_stream(RtScene *s, const RtCamera *camera, const RtRender
     if (delivery.cancellable) rtapi::arm_cancel_word(s, a); // the waves read it at every hand-out and chunk boundary
     const int per_cu = s->lights_extended ? s->kernels->nee_lights_stream_blocks_per_cu(s->textured, s->specular, s->use_bvh)
                                           : s->kernels->nee_stream_blocks_per_cu(s->prims_class, s->textured, s->specular, s->use_bvh);
-    const unsigned resident = (unsigned)(s->num_cus > 0 ? s->num_cus : 1) * (unsigned)per_cu;
+    const unsigned resident = rtapi::cap_blocks(s, (unsigned)(s->num_cus > 0 ? s->num_cus : 1) * (unsigned)per_cu);
     const unsigned blocks = std::min(resident, (a.n_items + 3u) / 4u);
+    rtapi::note_grid(s, blocks, a.n_items);
     if ((rc = open_launches(s, stream, /*clear_queue=*/true)) != RT_OK) return rc;
     if (s->lights_extended) RT_HIP(s->kernels->nee_lights_stream(&a, &nee, &lx, s->textured, s->specular, s->use_bvh, blocks, stream));
     else RT_HIP(s->kernels->nee_stream(&a, &nee, s->prims_class, s->textured, s->specular, s->use_bvh, blocks, stream));

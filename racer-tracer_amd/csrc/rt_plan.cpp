@@ -72,6 +72,7 @@ int check_options(const RtSceneOptions *options, RtSceneOptions &opt) {
     if (opt.kernel < RT_KERNEL_POOL || opt.kernel > RT_KERNEL_V1) return fail(RT_ERR_INVALID_ARGUMENT, "unknown kernel option");
     if (opt.arithmetic < RT_ARITH_FAST || opt.arithmetic > RT_ARITH_REFERENCE) return fail(RT_ERR_INVALID_ARGUMENT, "unknown arithmetic option");
     if (opt.gather < RT_GATHER_AUTO || opt.gather > RT_GATHER_STAGED) return fail(RT_ERR_INVALID_ARGUMENT, "unknown gather option");
+    if (opt.launch_blocks < 0) return fail(RT_ERR_INVALID_ARGUMENT, "launch_blocks must not be negative (0: no cap)");
     for (int32_t r : opt._reserved)
         if (r != 0) return fail(RT_ERR_INVALID_ARGUMENT, "reserved option fields must be 0");
     return RT_OK;

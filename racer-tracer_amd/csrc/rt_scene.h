@@ -281,6 +281,10 @@ struct RtScene {
     bool exact = false;    // RtSceneOptions.arithmetic == RT_ARITH_REFERENCE: the *_exact copy of the trace kernels
     const rtapi::Launchers *kernels = nullptr; // ... and their launchers (rt_scene_create.hip: scene_create)
     bool gather_staged = false; // RtSceneOptions.gather == RT_GATHER_STAGED (rt_multi.hip)
+    // RtSceneOptions.launch_blocks: 0, or the most blocks a persistent launch of this scene gets (cap_blocks below), and
+    // what the most recent such launch got: its blocks and its items (rtdev_scene_variant)
+    int launch_blocks = 0;
+    int last_launch_blocks = 0, last_launch_items = 0;
     int num_cus = 0, pool_blocks_per_cu = 1;
     int pool_blocks_per_cu_lens = 1; // ... when the camera has an aperture (its lens samples take dynamic LDS)
     int pool_static_lds = 0;         // static LDS of the variant's kernel (hipFuncGetAttributes)
@@ -320,6 +324,16 @@ inline void arm_cancel_word(RtScene *s, rtdev::TraceArgs &a) {
     s->buf.host_flags.ptr[rtdev::RT_MAX_REGIONS] = 0u;
     a.cancel_flag = s->buf.host_flags.ptr + rtdev::RT_MAX_REGIONS;
 }
+// The resident blocks of a persistent kernel on the device, under the scene's launch_blocks cap (0: none).  A cap only
+// lowers the count: every block of the launch stays co-resident.
+inline unsigned cap_blocks(const RtScene *s, unsigned resident) {
+    return s->launch_blocks > 0 && (unsigned)s->launch_blocks < resident ? (unsigned)s->launch_blocks : resident;
+}
+// The grid of a persistent launch, where it is computed: kept for rtdev_scene_variant
+inline void note_grid(RtScene *s, unsigned blocks, uint32_t n_items) {
+    s->last_launch_blocks = (int)blocks;
+    s->last_launch_items = (int)n_items;
+}
 // A call has enqueued its (first) launches: rt_scene_last_stats reads the counters and the event spans of this call
 inline void note_launches(RtScene *s, int launches) {
     s->has_stats = true;
@@ -340,7 +354,10 @@ inline int use_scene_device(const RtScene *s) {
 //   rtdev_scene_variant: what rt_scene_create_ex chose for a scene, RTDEV_VARIANT_FIELDS values in this order:
 //     kernel (0 pool, 1 v1), prims_class (rtdev::PRIMS_*), textured, specular, use_bvh, exact (RT_ARITH_REFERENCE kernels),
 //     bvh_nodes_in_lds, has_moving, perlin_in_lds, static LDS of the pool variant, its dynamic LDS without and with lens
-//     samples (bytes; 0 for v1), resident blocks per CU without and with lens samples.  Writes min(n_out, fields) values.
+//     samples (bytes; 0 for v1), resident blocks per CU without and with lens samples, last_launch_blocks and
+//     last_launch_items: the block count and n_items of the scene's most recent persistent launch (pooled kernel, NEE
+//     stream kernels; 0 before the first), which is how a test sees that RtSceneOptions.launch_blocks took effect.
+//     Writes min(n_out, fields) values.
 //   rtdev_scene_classify: the selection rule of rt_scene_create_ex on a description alone (no device): prims_class, textured,
 //     specular, has_moving.  Returns the description's validation error, if any.
 //   rtdev_scene_radiance_bound: the bound on a finished sample's radiance that rt_scene_create_ex gives a description
@@ -348,7 +365,7 @@ inline int use_scene_device(const RtScene *s) {
 //   rtdev_sum_exponent: the exponent e of the fixed-point sums (TraceArgs.sum_scale = 2^(52-e)) that a render of `samples`
 //     samples per pixel gets from a radiance bound, or e = 0: f64 sums; RT_ERR_UNSUPPORTED where the render is refused
 //     (rt_plan.cpp: sum_exponent).
-#define RTDEV_VARIANT_FIELDS 14
+#define RTDEV_VARIANT_FIELDS 16
 extern "C" int rtdev_scene_variant(const RtScene *s, int32_t *out, int32_t n_out);
 extern "C" int rtdev_scene_classify(const RtSceneDesc *d, int32_t out[4]);
 extern "C" int rtdev_scene_radiance_bound(const RtSceneDesc *d, double *bound);

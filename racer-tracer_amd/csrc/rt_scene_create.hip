@@ -171,6 +171,7 @@ int scene_create(const RtSceneDesc *d, int device, const RtSceneOptions *options
     s->exact = opt.arithmetic == RT_ARITH_REFERENCE;
     s->gather_staged = opt.gather == RT_GATHER_STAGED;
     s->use_v1 = opt.kernel == RT_KERNEL_V1;
+    s->launch_blocks = opt.launch_blocks;
 
     // ---- plan: what the description alone decides (rt_plan.h)
     std::vector<rtdev::Prim> prims = rtapi::pack_prims(d);
@@ -312,7 +313,7 @@ int rtdev_scene_variant(const RtScene *s, int32_t *out, int32_t n_out) {
             s->use_v1 ? 1 : 0, s->prims_class, s->textured, s->specular, s->use_bvh, (int32_t)s->exact, s->bvh_nodes_in_lds ? 1 : 0,
             s->has_moving, (s->textured && s->n_perlins > 0 && s->perlin_identity) ? 1 : 0,
             s->use_v1 ? 0 : s->pool_static_lds, s->use_v1 ? 0 : (int32_t)s->pool_dyn_lds, s->use_v1 ? 0 : (int32_t)s->pool_dyn_lds_lens,
-            s->pool_blocks_per_cu, s->pool_blocks_per_cu_lens};
+            s->pool_blocks_per_cu, s->pool_blocks_per_cu_lens, s->last_launch_blocks, s->last_launch_items};
         for (int32_t k = 0; k < n_out && k < RTDEV_VARIANT_FIELDS; ++k) out[k] = v[k];
         return RT_OK;
     });

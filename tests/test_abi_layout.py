@@ -186,6 +186,45 @@ def test_scene_options_are_validated(rt, abi):
     assert rt.lib().rt_scene_create_ex(C.byref(bundle.desc), 0, C.byref(bad), C.byref(h)) == abi.RT_ERR_INVALID_ARGUMENT
 
 
+def test_launch_blocks_option_and_the_variant_fields(rt, abi):
+    """RtSceneOptions.launch_blocks took the first reserved word: same size, 0 the default, a negative value refused with
+    a message of its own, the three words left still refused when set; a positive value passes the option check (what
+    comes back then is the device's answer).  rtdev_scene_variant's fields: the binding's tuple has the header's count
+    and ends on the grid of the last persistent launch."""
+    import scenes_py as S
+    bundle, _, _ = S.cornell_box()
+    assert C.sizeof(abi.RtSceneOptions) == 32 and abi.RtSceneOptions.launch_blocks.offset == 16
+    assert abi.RtSceneOptions._reserved.offset == 20 and len(abi.RtSceneOptions()._reserved) == 3
+    assert abi.RtSceneOptions().launch_blocks == 0
+
+    def create(opt):
+        h = C.c_void_p()
+        rc = rt.lib().rt_scene_create_ex(C.byref(bundle.desc), 0, C.byref(opt), C.byref(h))
+        message = rt.lib().rt_last_error_message()
+        if rc == abi.RT_OK:
+            rt.lib().rt_scene_destroy(h)
+        return rc, message
+
+    for value in (-1, -2 ** 31):
+        rc, message = create(abi.RtSceneOptions(0, 0, 0, 0, value))
+        assert rc == abi.RT_ERR_INVALID_ARGUMENT and b"launch_blocks" in message, (value, message)
+    for word in range(3):
+        bad = abi.RtSceneOptions(0, 0, 0, 0, 4)
+        bad._reserved[word] = 1
+        rc, message = create(bad)
+        assert rc == abi.RT_ERR_INVALID_ARGUMENT and b"reserved" in message and b"launch_blocks" not in message, word
+    for value in (0, 1, 3, 2 ** 31 - 1):
+        rc, _ = create(abi.RtSceneOptions(0, 0, 0, 0, value))
+        assert rc in (abi.RT_OK, abi.RT_ERR_NO_DEVICE), (value, rc)
+    header = open(os.path.join(ROOT, "racer-tracer_amd", "csrc", "rt_scene.h")).read()
+    assert int(re.search(r"#define RTDEV_VARIANT_FIELDS (\d+)", header).group(1)) == len(abi.VARIANT_FIELDS) == 16
+    assert abi.VARIANT_FIELDS[-2:] == ("last_launch_blocks", "last_launch_items")
+    assert ABI_VERSION_UNCHANGED == abi.ABI_VERSION
+
+
+ABI_VERSION_UNCHANGED = 5   # a reserved word got a name: size, offsets and the meaning of 0 are what they were
+
+
 def test_no_device_is_an_error_not_a_fallback(rt):
     if rt.device_count() > 0:
         pytest.skip("a GPU is visible")

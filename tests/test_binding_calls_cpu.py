@@ -187,10 +187,11 @@ def test_every_wrapper_reaches_the_symbol_its_docstring_names_and_every_symbol_i
 
     bundle = abi.SceneBundle([], [], [], abi.sky())
     scene = rt.Scene(bundle, device=2, closest_hit=abi.RT_HIT_BVH, kernel=abi.RT_KERNEL_V1, arithmetic=abi.RT_ARITH_REFERENCE,
-                     gather=abi.RT_GATHER_STAGED)
+                     gather=abi.RT_GATHER_STAGED, launch_blocks=3)
     desc, device, opt, handle = stub.last("rt_scene_create_ex")
     assert C.addressof(desc._obj) == C.addressof(bundle.desc) and device == 2 and handle._obj is scene._h
     assert (opt._obj.closest_hit, opt._obj.kernel, opt._obj.arithmetic, opt._obj.gather) == (2, 1, 1, 1)
+    assert opt._obj.launch_blocks == 3 and list(opt._obj._reserved) == [0, 0, 0]
     assert scene._h.value == 1 and scene._lib is stub and scene._desc_owner is bundle and scene.device == 2
     assert "rt_scene_create_ex" in rt.Scene.__init__.__doc__
     for name, (call, symbol) in SITES.items():
@@ -255,6 +256,8 @@ def test_a_description_goes_in_bare_or_in_a_bundle(rt, stub):
         assert C.addressof(stub.last("rtdev_scene_radiance_bound")[0]._obj) == C.addressof(desc)
         scene = rt.Scene(given)
         assert C.addressof(stub.last("rt_scene_create_ex")[0]._obj) == C.addressof(desc)
+        opt = stub.last("rt_scene_create_ex")[2]._obj    # the defaults are rt_scene_create's own: no cap on the grid
+        assert (opt.closest_hit, opt.kernel, opt.arithmetic, opt.gather, opt.launch_blocks, list(opt._reserved)) == (0, 0, 0, 0, 0, [0, 0, 0])
         scene.close()
 
 
@@ -292,7 +295,9 @@ def test_the_small_helpers_hand_over_and_return_what_they_say(rt, stub):
 
     stub.during["rtdev_scene_variant"] = lambda args: args[1].__setitem__(slice(0, len(args[1])), range(len(args[1])))
     assert scene.variant() == dict(zip(abi.VARIANT_FIELDS, range(len(abi.VARIANT_FIELDS))))
-    assert stub.last("rtdev_scene_variant")[2] == len(abi.VARIANT_FIELDS)
+    assert stub.last("rtdev_scene_variant")[2] == len(abi.VARIANT_FIELDS) == 16
+    # the grid of the scene's last persistent launch follows the 14 fields of the kernel choice, in this order
+    assert abi.VARIANT_FIELDS[12:] == ("blocks_per_cu", "blocks_per_cu_lens", "last_launch_blocks", "last_launch_items")
     stub.during["rt_scene_last_stats"] = lambda args: setattr(args[1]._obj, "segments", 123)
     assert scene.last_stats().segments == 123
     # the streams and optional addresses: None is NULL / stream 0

@@ -26,9 +26,12 @@ def strips(scene, camera, w, h, spp, rows, count):
 
 
 def test_frames_do_not_depend_on_strips_that_cut_tiles(rt, gpu):
-    """Strips of 5 or 3 rows cut the 8x8 item tiles: every item then holds other pixels, starts and ends beside other
-    items — and, with integer sums, the frame is the same to the last bit (the one-item-at-a-time variants, whose f64
-    sums depend on the order their samples finish in, agree to 1e-12 here: tests/test_gpu_parity_proofs.py)."""
+    """Strips of 5 or 3 rows cut the 8x8 item tiles: every item then holds other pixels — and, with integer sums, the
+    frame is the same to the last bit (the one-item-at-a-time variants, whose f64 sums depend on the order their samples
+    finish in, agree to 1e-12 here: tests/test_gpu_parity_proofs.py).  These launches have at most 720 items, fewer than
+    a large card has resident waves, so there every wave takes ONE item from a freshly started state: no item starts
+    while another of its wave drains.  Items beside other items are tests/test_gpu_item_succession.py's, which caps the
+    grid (RtSceneOptions.launch_blocks)."""
     bundle, cam, _ = S.cornell_box_boxes()
     w, h, spp = 160, 90, 24
     camera = S.camera_for(cam, w, h)
